@@ -7,7 +7,9 @@ Workload at N=1 (config.workload): BASELINE configs[1] = C2 of SURVEY.md §8:
   Default E=24 as S=24 / hierarchical off (SURVEY §8 "primary"); --hier gives S=12 + 12 resampled.
 One step = G(zs, ...) forward on fresh latents + imgs.backward(G0) populating every generator
 parameter gradient the reference populates (+ gradient all-reduce when N > 1).
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the roofline / cpu_baseline legs.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; --full adds the
+secondary legs (exact-fp32 timings, full GAN step, other geometries, roofline / power, cpu_baseline).
+--dump-outputs DIR writes what the last timed step computed (images, parameter gradients) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -41,6 +43,11 @@ def parse():
     ap.add_argument("--num-steps", type=int, default=None, help="coarse samples per ray")
     ap.add_argument("--hier", action="store_true", help="hierarchical sampling (S coarse + S fine)")
     ap.add_argument("--freeze", action="store_true", help="GeneratorNerfINR_freeze_NeRF (the r256 stages: gradients for the INR head only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary legs (exact-fp32 timings, full GAN step, other geometries, "
+                         "roofline / power, cpu_baseline); the --no-* options below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (imgs, every parameter gradient) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="skip the extra exact-fp32-MFMA timing")
@@ -483,6 +490,29 @@ def other_configs(dev, mode):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """name -> tensor: each written as out_dir/<name>.npy in float32.  Over DUMP_CAP_BYTES in all, every array of more than
+    64 Ki elements is replaced by the same fixed fraction of its flattened elements (sorted indices drawn with seed 0, so two
+    runs of the same configuration sample the same positions); smaller arrays are always written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    big = [k for k, x in host.items() if x.size > 65536]
+    total = sum(x.nbytes for x in host.values())
+    keep = 1.0
+    if total > DUMP_CAP_BYTES:
+        small = total - sum(host[k].nbytes for k in big)
+        keep = (DUMP_CAP_BYTES - small) / (total - small)
+    for k, x in host.items():
+        if keep < 1.0 and k in big:
+            idx = np.random.RandomState(0).choice(x.size, max(1, int(x.size * keep)), replace=False)
+            x = x.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
 def _free_port():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
@@ -551,6 +581,10 @@ def main():
     if overlap:
         a.no_graph = True                      # hooks run in eager autograd only
     reduce_grads = GradAllReducer(params, bucket_mb=8.0 if overlap else 64.0, overlap=overlap, single_rank_exchange=pg and world == 1)
+    # the images of the latest step, for --dump-outputs: an eager call keeps its own; in graph mode only the captured call's
+    # (the graph's static output, rewritten by every replay) — nothing kept from a warm-up call is released inside the capture
+    last = {}
+    keep_eager = [True]
 
     def fwd_bwd():
         zs = G.get_zs(b)
@@ -559,11 +593,14 @@ def main():
         imgs, _ = G(zs, img_size=img, num_steps=S, hierarchical_sample=a.hier, nerf_noise=0.,
                     return_aux_img=False, grad_points=None, forward_points=None, **G_KW)
         imgs.backward(G0)
+        if keep_eager[0] or torch.cuda.is_current_stream_capturing():
+            last["imgs"] = imgs
 
     graph = None
     if not a.no_graph:
         # ~570 kernel launches per step: capture latents (graph-safe Philox RNG: fresh draws per replay) + forward +
         # backward once, replay per step; the gradient all-reduce stays outside the graph.  Eager on any capture error.
+        keep_eager[0] = False
         try:
             # the product's capture helper (cips3d_amd/graph.py): two eager warm-up calls on a side stream, then the capture;
             # with a process group up, RCCL's watchdog thread may touch the HIP runtime while this thread captures, so only
@@ -574,6 +611,7 @@ def main():
             print(f"[bench] hipGraph capture failed ({type(e).__name__}: {e}); running eagerly", file=sys.stderr)
             graph = None
             torch.cuda.synchronize()
+        keep_eager[0] = True
     use_graph = [graph is not None]
 
     ar_events, ar_bytes = [], [0]
@@ -626,9 +664,14 @@ def main():
     dt = timed(a.steps, a.warmup, record=True)
     ms = dt / a.steps * 1e3
     value = world * b * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        # before any secondary leg runs the generator again: the images and the (all-reduced) gradients of the last timed step
+        outs = {"imgs": last["imgs"]}
+        outs.update({"grad." + k: p.grad for k, p in G.named_parameters() if p.grad is not None})
+        dump_outputs(a.dump_outputs, outs)
     exact = None
     f32_all = None
-    if mode == "bf16x3" and not a.no_exact:
+    if a.full and mode == "bf16x3" and not a.no_exact:
         # two extra legs, timed like the headline (same launch mode, step count and warm-up):
         #  * f32_mfma_head_and_siren_forward: head GEMMs (forward and backward) and the SIREN forward on exact fp32 MFMA
         #    (v_mfma_f32_32x32x2_f32); the SIREN backward stays the fused split-bf16 kernel — the key says so;
@@ -719,15 +762,15 @@ def main():
                              # both terms from this rank's own stream events (median all-reduce / median step)
                              "step_ms_median_events": round(per_step.get("median", ms), 4),
                              "frac_of_step": round(med / max(per_step.get("median", ms), 1e-9), 4)}
-    if rank == 0 and world == 1 and not a.no_full_step:
+    if a.full and rank == 0 and world == 1 and not a.no_full_step:
         try:
             line["full_step"] = full_gan_step(dev, b, img, 12, steps=4, warmup=2)
         except Exception as e:                      # noqa: BLE001 — the secondary number must never cost the headline line
             line["full_step"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not a.no_other_configs and mode == "bf16x3":
+    if a.full and rank == 0 and world == 1 and not a.no_other_configs and mode == "bf16x3":
         line["other_configs"] = other_configs(dev, mode)
     if rank == 0:
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             r = gemm_roofline(dev, b, img * img, mode)
             if mode == "bf16x3" and world == 1:
                 try:
@@ -768,12 +811,12 @@ def main():
             except Exception:                       # noqa: BLE001
                 pass
             line["roofline"] = r
-        if world == 1 and not a.no_roofline:
+        if a.full and world == 1 and not a.no_roofline:
             try:
                 line["power"] = power_sample(step)
             except Exception as e:                      # noqa: BLE001
                 line["power"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(img, S, a.hier)
             try:
                 # the UNMODIFIED reference's CPU path: it exists only in the build container (/root/reference does not travel),

@@ -427,6 +427,21 @@ def make_op_cases():
     print("upfirdn2d ->", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def make_reference_layout():
+    """The reference's own configuration (ffhq_exp.yaml: G_cfg_3D2D, D_cfg) and the state_dict layout (key order, shapes,
+    dtypes) of the models it builds from it: what tests/test_compat_cpu.py checks the drop-in classes and the checkpoint
+    directory format against where the reference itself is absent."""
+    from tl2.proj.fvcore import build_model
+    torch.manual_seed(0)
+    G = build_model(CFG["G_cfg_3D2D"], device="cpu")
+    D = build_model(CFG["D_cfg"], kwargs_priority=True, diffaug=False)
+    layout = lambda m: [(k, tuple(v.shape), str(v.dtype).replace("torch.", "")) for k, v in m.state_dict().items()]
+    out = {"G_cfg_3D2D": dict(CFG["G_cfg_3D2D"]), "D_cfg": dict(CFG["D_cfg"]), "G_state": layout(G), "D_state": layout(D)}
+    path = os.path.join(OUT, "reference_layout.pt")
+    torch.save(out, path)
+    print("reference layout ->", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def main(mint):
     """mint = "fixture": everything; "gates": only tests/golden/gates_<tag>.pt (the LeakyReLU gates of the reference's
     run of every training-path case; each rerun is checked bit for bit against the committed fixture)."""
@@ -459,11 +474,15 @@ def make_rest():
     make_camera_cases()
     make_op_cases()
     make_pigan_cases()
+    make_reference_layout()
 
 
 if __name__ == "__main__":
     if "pigan" in sys.argv[1:]:
         os.makedirs(OUT, exist_ok=True)
         make_pigan_cases()
+    elif "layout" in sys.argv[1:]:
+        os.makedirs(OUT, exist_ok=True)
+        make_reference_layout()
     else:
         main("gates" if "gates" in sys.argv[1:] else "fixture")

@@ -4,9 +4,11 @@
     `fused` / `upfirdn2d_op` stand-ins (their module-level `load(...)` calls receive the stand-ins), and the pybind call
     signatures match what those files call (fused_bias_act.cpp:11-21, upfirdn2d.cpp:12-23);
   * the registry module registers the drop-in classes under tl2's MODEL_REGISTRY contract, and `build_model` with the
-    reference's own YAML config (ffhq_exp.yaml) constructs them with the reference's parameter count and key order.
+    reference's own YAML config (ffhq_exp.yaml) constructs them with the reference's parameter count and key order;
+  * checkpoint directories round-trip between the drop-in classes and the reference's state_dict layout.
 No compute: there is no GPU here (the ops raise the reference's "must be a CUDA tensor" error on CPU tensors).
-/root/reference only exists in the build container; on the GPU box these tests skip."""
+The first test runs the reference's own files and skips where the reference checkout is absent; the registry and checkpoint
+tests read the reference's configuration and state_dict layout from tests/golden/reference_layout.pt (oracle/make_golden.py)."""
 import importlib.util
 import inspect
 import os
@@ -14,6 +16,8 @@ import sys
 
 import pytest
 import torch
+
+from conftest import load_golden
 
 REF = "/root/reference"
 needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
@@ -24,6 +28,24 @@ def _load_ref_file(name, rel):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def _reference_layout_module(entries):
+    """A module whose state_dict has exactly the reference's keys, order, shapes and dtypes (`entries` from
+    reference_layout.pt), filled from torch's current seed: what the reference's own classes write to and read from a
+    checkpoint directory"""
+    root = torch.nn.Module()
+    for key, shape, dtype in entries:
+        *path, leaf = key.split(".")
+        m = root
+        for name in path:
+            if name not in m._modules:
+                m.add_module(name, torch.nn.Module())
+            m = m._modules[name]
+        t = torch.randn(shape).to(getattr(torch, dtype))
+        m.register_parameter(leaf, torch.nn.Parameter(t, requires_grad=t.is_floating_point()))
+    assert [(k, tuple(v.shape)) for k, v in root.state_dict().items()] == [(k, tuple(s_)) for k, s_, _ in entries]
+    return root
 
 
 @needs_ref
@@ -56,18 +78,26 @@ def test_unmodified_reference_op_files_bind_to_the_hip_standins():
         compat.load("something_else")
 
 
-@needs_ref
-def test_registry_builds_the_drop_in_models_from_the_reference_yaml():
-    import yaml
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, ROOT)
-    from oracle import ref_shim
-    ref_shim.install()                                   # tl2 is not installed here: its registry contract, stubbed
+@pytest.fixture()
+def own_tl2(monkeypatch):
+    """tl2 is not installed here: the package's own stand-in (cips3d_amd/compat/shims) provides its registry contract; tl2
+    modules another test installed are set aside for the test, the stand-in's dropped again afterwards"""
+    before = set(sys.modules)
+    for name in [m for m in sys.modules if m.split(".")[0] == "tl2"]:
+        monkeypatch.delitem(sys.modules, name)
+    monkeypatch.syspath_prepend(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cips3d_amd", "compat", "shims"))
+    yield
+    for name in set(sys.modules) - before:
+        if name.split(".")[0] == "tl2":
+            sys.modules.pop(name, None)
+
+
+def test_registry_builds_the_drop_in_models_from_the_reference_yaml(own_tl2):
     from tl2.proj.fvcore import MODEL_REGISTRY, build_model
     import cips3d_amd.compat.registry as reg
     names = reg.register(MODEL_REGISTRY)
     assert "cips3d_amd.compat.registry.GeneratorNerfINR" in names
-    cfg = yaml.safe_load(open(os.path.join(REF, "exp/cips3d/configs/ffhq_exp.yaml")))
+    cfg = load_golden("reference_layout")               # ffhq_exp.yaml's G_cfg_3D2D / D_cfg and the reference models' layout
     g_cfg = dict(cfg["G_cfg_3D2D"], register_modules=["cips3d_amd.compat.registry"],
                  name="cips3d_amd.compat.registry.GeneratorNerfINR")
     d_cfg = dict(cfg["D_cfg"], register_modules=["cips3d_amd.compat.registry"],
@@ -79,37 +109,25 @@ def test_registry_builds_the_drop_in_models_from_the_reference_yaml():
     assert type(G) is GeneratorNerfINR and type(D) is Discriminator_MultiScale_Aux
     assert sum(p.numel() for p in G.parameters()) == 11287743 and len(G.state_dict()) == 172
     assert sum(p.numel() for p in D.parameters()) == 37518914 and len(D.state_dict()) == 160
-    # same key order as the reference's own classes built from the same YAML
-    from exp.cips3d.models import generator as ref_gen, discriminator as ref_disc    # noqa: F401  (registers them)
-    Gr = build_model(cfg["G_cfg_3D2D"], device="cpu")
-    Dr = build_model(cfg["D_cfg"], kwargs_priority=True, diffaug=False)
-    assert list(G.state_dict().keys()) == list(Gr.state_dict().keys())
-    assert list(D.state_dict().keys()) == list(Dr.state_dict().keys())
-    assert all(a.shape == b.shape for a, b in zip(G.state_dict().values(), Gr.state_dict().values()))
-    assert all(a.shape == b.shape for a, b in zip(D.state_dict().values(), Dr.state_dict().values()))
+    # same key order, shapes and dtypes as the reference's own classes built from the same YAML
+    for net, ref in ((G, cfg["G_state"]), (D, cfg["D_state"])):
+        assert [(k, tuple(v.shape), str(v.dtype).replace("torch.", "")) for k, v in net.state_dict().items()] == list(ref)
 
 
-@needs_ref
 def test_checkpoint_directory_round_trips_with_the_reference_classes(tmp_path):
     """tl2-layout checkpoint directory ({generator, G_ema, discriminator, state_dict}.pth; train.py:249-256): a directory
-    written from the REFERENCE's modules loads into the drop-in classes (strict) and a directory written from the
-    drop-in classes loads into the reference's modules (strict), values bit for bit; `Checkpointer(...)
+    written from modules with the REFERENCE's state_dict layout (keys, order, shapes, dtypes of its classes built from
+    ffhq_exp.yaml, tests/golden/reference_layout.pt) loads into the drop-in classes (strict) and a directory written from the
+    drop-in classes loads into such modules (strict), values bit for bit; `Checkpointer(...)
     .load_state_dict_from_file(G_ema.pth)` (gen_images.py:102) reads the single-network file."""
     import copy
-    import yaml
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, ROOT)
-    from oracle import ref_shim
-    ref_shim.install()
-    from tl2.proj.fvcore import build_model
-    from exp.cips3d.models import generator as ref_gen, discriminator as ref_disc    # noqa: F401
     from cips3d_amd import GeneratorNerfINR, Discriminator_MultiScale_Aux
     from cips3d_amd.checkpoint import save_models, load_models, Checkpointer
     from conftest import G_CFG, D_CFG
-    cfg = yaml.safe_load(open(os.path.join(REF, "exp/cips3d/configs/ffhq_exp.yaml")))
+    lay = load_golden("reference_layout")
     torch.manual_seed(5)
-    Gr = build_model(cfg["G_cfg_3D2D"], device="cpu")
-    Dr = build_model(cfg["D_cfg"], kwargs_priority=True, diffaug=False)
+    Gr = _reference_layout_module(lay["G_state"])
+    Dr = _reference_layout_module(lay["D_state"])
     Gr_ema = copy.deepcopy(Gr)
     with torch.no_grad():
         for p in Gr_ema.parameters():
@@ -133,7 +151,7 @@ def test_checkpoint_directory_round_trips_with_the_reference_classes(tmp_path):
             p.add_(1.0)
     save_models(d2, {"generator": G, "G_ema": G_ema, "discriminator": D, "state_dict": st})
     torch.manual_seed(7)
-    Gr2 = build_model(cfg["G_cfg_3D2D"], device="cpu")
+    Gr2 = _reference_layout_module(lay["G_state"])
     Checkpointer(Gr2).load_state_dict_from_file(os.path.join(d2, "G_ema.pth"))
     assert all(torch.equal(v, G_ema.state_dict()[k]) for k, v in Gr2.state_dict().items())
     # freeze variant: load_nerf_ema (generator.py:1957-1961) copies the NeRF side of G_ema
