@@ -1,7 +1,7 @@
 // disc_ops.hip — the discriminator's native ops for gfx950 (H5): the two ops the reference
 // ships as CUDA extensions, with identical contracts, plus the im2col / col2im pair that
 // feeds EqualConv2d to the fp32 MFMA GEMM.  All HBM-bandwidth bound streaming kernels.
-#include "common.h"
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
 
 // A readable zero outside any tensor: out-of-range taps of the register-tiled upfirdn2d kernels are redirected here by
@@ -998,11 +998,6 @@ extern "C" int cips_upfirdn2d(const float* input, const float* kernel, float* ou
 // those launches' bit for bit (fp32 multiply, round-to-nearest-even splits).
 // Workgroup = 32 output x 32 input channels of one job: per tap the tile is read with the lanes along c (the forward bank's
 // contiguous dimension) and written back through LDS with the lanes along o (the alternate forms' contiguous dimension).
-__device__ __forceinline__ unsigned short wp_f2bf(float v) {
-  unsigned u = __float_as_uint(v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 struct WPrepArgs { cips_wprep_job job[CIPS_WPREP_MAX_JOBS]; };
 __global__ __launch_bounds__(256) void conv_weight_prep_kernel(WPrepArgs a) {
   __shared__ unsigned short th[32][33], tl[32][33];
@@ -1021,8 +1016,8 @@ __global__ __launch_bounds__(256) void conv_weight_prep_kernel(WPrepArgs a) {
       if (o < j.O && c < j.C) {
         float v = j.w[((long long)o * j.C + c) * T + t] * j.scale;
         asm volatile("" : "+v"(v));           // the ROUNDED product: without the barrier hipcc contracts `w * scale - hi` into one fma (lo planes 1-2 ulp off in 1.6 % of the elements)
-        h = wp_f2bf(v);
-        l = wp_f2bf(v - __uint_as_float(((unsigned)h) << 16));
+        h = f2bf(v);
+        l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
         if (fh) { const long long q = (long long)o * T * j.C + (long long)t * j.C + c; fh[q] = h; fl[q] = l; }
       }
       th[rr][tx] = h; tl[rr][tx] = l;

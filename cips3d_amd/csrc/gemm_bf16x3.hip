@@ -27,61 +27,40 @@
 // flight across raw s_barriers with counted s_waitcnt vmcnt(N); one barrier per k-tile.  Workgroups are
 // persistent (one per CU) and walk the tile list XCD-contiguously.  The epilogue stages every auxiliary
 // input and every output through a per-wave LDS scratch so that HBM only sees 16-byte accesses.
-// A 128x128 / 4-wave / 2-stage form (two workgroups per CU) is selectable with CIPS_X3_TILE=128
-// (measured equal within noise).
-#include "common.h"
+// (A 128x128 / 4-wave / 2-stage form with two workgroups per CU measured equal within noise.)
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
-#include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int BN = 128, BK = 32;
 constexpr int ROWB = 64;                     // LDS row pitch in bytes: 32 bf16, no padding; the four 16-byte k-chunks
                                              // of a row are XOR-swizzled by (row>>2)&3 so that both the DMA image
                                              // (lane-linear) and the ds_read_b128 fragment reads are conflict-free
-// Workgroup tile (64*WM) x 128: WM = 4 -> 256x128, 8 waves, 1 workgroup per CU (120 KB LDS);
-//                               WM = 2 -> 128x128, 4 waves, 2 workgroups per CU (80 KB LDS each), so one
-// workgroup's barriers / prologue / epilogue overlap the other's MFMA phase.
-template <int WM> struct Cfg {
-  static constexpr int BM = 64 * WM;
-  static constexpr int THREADS = WM * 2 * 64;
-  static constexpr int NB = 8 / (2 * WM);               // B row groups (16 rows) per wave per plane
+// Workgroup tile 256 x 128: 8 waves, 1 workgroup per CU
+struct Cfg {
+  static constexpr int BM = 256;
+  static constexpr int NW = 8;                          // waves
+  static constexpr int THREADS = NW * 64;
+  static constexpr int NB = 1;                          // B row groups (16 rows) per wave per plane
   static constexpr int OFF_AHI = 0;
   static constexpr int OFF_ALO = OFF_AHI + BM * ROWB;
   static constexpr int OFF_BHI = OFF_ALO + BM * ROWB;
   static constexpr int OFF_BLO = OFF_BHI + BN * ROWB;
   static constexpr int STAGE = OFF_BLO + BN * ROWB;
-  static constexpr int NSTAGE = (WM == 4) ? 3 : 2;      // LDS ring depth: 256-row form 3 stages (1 WG / CU); 128-row form 2 stages, 72 KB -> 2 WGs / CU
+  static constexpr int NSTAGE = 3;                      // LDS ring depth
   static constexpr int PIECES = 4 + 2 * NB;             // LDS-DMA instructions per wave per k-tile
-  static constexpr int SMEM_EPI = WM * 2 * 2 * 64 * 72 * 2;   // per-wave epilogue scratch
+  static constexpr int SMEM_EPI = NW * 2 * 64 * 72 * 2;   // per-wave epilogue scratch
   static constexpr int SMEM_BYTES = (NSTAGE * STAGE > SMEM_EPI) ? NSTAGE * STAGE : SMEM_EPI;
 };
 
 struct Args {
   cips_gemm_x3_desc d;
   int tiles_m, tiles_n, total;
-  int stagger_cycles;   // start-phase quantum (shader cycles), 0 = no staggering
-  int ncu;
-  int dbg;              // tuning only (env CIPS_X3_GDBG): bit0 skip fragment reads + MFMA, bit1 skip the LDS-DMA loads, bit2 skip the main loop
 };
 
-__device__ __forceinline__ u16 f2bf(float v) {
-  unsigned u = __float_as_uint(v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ void split2(float v, u16& hi, u16& lo) {
-  hi = f2bf(v);
-  lo = f2bf(v - bf2f(hi));
-}
-
-template <int WM>
-__global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
-  using CF = Cfg<WM>;
+__global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
+  using CF = Cfg;
   constexpr int BM = CF::BM, OFF_AHI = CF::OFF_AHI, OFF_ALO = CF::OFF_ALO, OFF_BHI = CF::OFF_BHI, OFF_BLO = CF::OFF_BLO,
                 STAGE = CF::STAGE, NB = CF::NB;
   (void)BM;
@@ -91,26 +70,11 @@ __global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g
   // Persistent workgroups: the grid is one workgroup per CU (or fewer); each walks the tile list with a
   // stride of gridDim.x, which keeps it on its XCD (gridDim.x % 8 == 0) and saves the per-tile workgroup
   // launch / LDS (re)allocation latency (~3 us against ~25 us of main loop at K = 512).
-  // Optional de-phasing of the persistent workgroups (CIPS_X3_STAGGER=1): four start phases, so that not every
-  // CU reaches its store-heavy epilogue at the same moment.  Measured neutral on MI355X: the epilogue traffic adds
+  // De-phasing the workgroups' start (four phases across CUs) was measured neutral on MI355X: the epilogue traffic adds
   // to the main loop's time whatever the phase relation (268 MB of fp32 C cost ~75 us on top of a 205 us main
   // loop), i.e. the kernel is bound by the memory system, not by MFMA issue.
-  if (CIPS_TUNE(g.stagger_cycles) > 0) {
-    // 256-row form: four phases across CUs.  128-row form (two workgroups per CU): the second half of the grid
-    // (the co-resident partner of workgroup b is b + #CUs) starts half a tile later, so that one workgroup's
-    // store drain overlaps its partner's MFMA phase.
-    const int phase = (WM == 4) ? ((blockIdx.x >> 3) & 3) : (blockIdx.x >= g.ncu ? 2 : 0);
-    for (int i = 0; i < phase * g.stagger_cycles; i += 64 * 100) __builtin_amdgcn_s_sleep(100);
-  }
   for (int tseq = blockIdx.x; tseq < g.total; tseq += gridDim.x) {
-  int bid = tseq;
-  {
-    const int nx = 8;
-    int q = g.total / nx, r = g.total % nx;
-    int xcd = bid % nx, idx = bid / nx;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
+  const int bid = xcd_tile(tseq, g.total);
   const int tn = bid % g.tiles_n;
   const int tm = (bid / g.tiles_n) % g.tiles_m;
   const int bz = bid / (g.tiles_n * g.tiles_m);
@@ -140,15 +104,12 @@ __global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g
   // chunk kc = slot ^ ((row>>2)&3) — the swizzle lives in the SOURCE address, the reads apply the same XOR.
   // Rows past M / N are clamped (their products only reach outputs that are never stored); K % 32 == 0.
   // Two LDS stages: the DMA for tile t+1 runs while tile t is multiplied; one barrier per k-tile.
-  // The DMA is issued in the SGPR-base form (asm, see gemm_bf16x3_wide.hip): uniform plane pointer of the k-tile + one
+  // The DMA is issued in the SGPR-base form (lds_dma16, gemm_x3_common.h): uniform plane pointer of the k-tile + one
   // 32-bit byte offset per lane and row group, computed once per output tile.
   const int drow = lane >> 2, dslot = lane & 3;
   const int uw = __builtin_amdgcn_readfirstlane(wave);
-  constexpr int NW = 2 * WM;
+  constexpr int NW = CF::NW;
   const unsigned sbase_nt = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
-  auto dma_s = [&](const u16* p, unsigned off, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(p), "s"(lds_addr) : "memory");
-  };
   auto row_off = [&](int ld, int rows_total, int row_base) -> unsigned {
     const int row = row_base + drow;                                  // row inside the workgroup tile
     const int kcsw = dslot ^ ((row >> 2) & 3);
@@ -167,14 +128,14 @@ __global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g
 #pragma unroll
     for (int i = 0; i < 2; ++i) {            // A: BM/16 row groups per plane, 2 per wave
       const int gidx = uw + NW * i;
-      dma_s(ah, offA_nt[i], s + OFF_AHI + gidx * 16 * ROWB);
-      dma_s(al, offA_nt[i], s + OFF_ALO + gidx * 16 * ROWB);
+      lds_dma16(ah, offA_nt[i], s + OFF_AHI + gidx * 16 * ROWB);
+      lds_dma16(al, offA_nt[i], s + OFF_ALO + gidx * 16 * ROWB);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {           // B: 8 row groups per plane
       const int gidx = uw + NW * i;
-      dma_s(bh, offB_nt[i], s + OFF_BHI + gidx * 16 * ROWB);
-      dma_s(bl, offB_nt[i], s + OFF_BLO + gidx * 16 * ROWB);
+      lds_dma16(bh, offB_nt[i], s + OFF_BHI + gidx * 16 * ROWB);
+      lds_dma16(bl, offB_nt[i], s + OFF_BLO + gidx * 16 * ROWB);
     }
   };
   auto compute = [&](int stage) {
@@ -211,10 +172,10 @@ __global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g
   // front of tile kt is a COUNTED vmcnt that leaves the younger tiles' pieces outstanding
   // (cdna_hip_programming.md T3/T4: never drain to 0 in the main loop).
   constexpr int NSTAGE = CF::NSTAGE, PIECES = CF::PIECES, DIST = NSTAGE - 1;
-  const int nk = CIPS_TUNE(g.dbg & 4) ? 0 : K / BK;               // bit2: epilogue only
+  const int nk = K / BK;
 #pragma unroll
   for (int t = 0; t < DIST; ++t)
-    if (t < nk && !CIPS_TUNE(g.dbg & 2)) issue_tile(t, t * BK);
+    if (t < nk) issue_tile(t, t * BK);
   for (int kt = 0; kt < nk; ++kt) {
     const int younger = min(DIST - 1, nk - 1 - kt);      // tiles issued after kt that may stay in flight
     if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PIECES) : "memory");
@@ -222,8 +183,8 @@ __global__ __launch_bounds__(Cfg<WM>::THREADS, 2) void gemm_bf16x3_kernel(Args g
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                         // every wave's pieces of tile kt have landed;
                                                           // every wave is done reading stage (kt-1) % NSTAGE
-    if (kt + DIST < nk && !CIPS_TUNE(g.dbg & 2)) issue_tile((kt + DIST) % NSTAGE, (kt + DIST) * BK);
-    if (!CIPS_TUNE(g.dbg & 1)) compute(kt % NSTAGE);
+    if (kt + DIST < nk) issue_tile((kt + DIST) % NSTAGE, (kt + DIST) * BK);
+    compute(kt % NSTAGE);
   }
   __builtin_amdgcn_s_barrier();
 
@@ -510,14 +471,7 @@ __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(A
   const int uw = __builtin_amdgcn_readfirstlane(wave);
 
   for (int tseq = blockIdx.x; tseq < g.total; tseq += gridDim.x) {
-  int bid = tseq;
-  {
-    const int nx = 8;
-    int q = g.total / nx, r = g.total % nx;
-    int xcd = bid % nx, idx = bid / nx;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
+  const int bid = xcd_tile(tseq, g.total);
   const int tn = bid % g.tiles_n;
   const int tm = (bid / g.tiles_n) % g.tiles_m;
   const int bz = bid / (g.tiles_n * g.tiles_m);
@@ -536,12 +490,9 @@ __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(A
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // LDS-DMA in the SGPR-base form (asm, see gemm_bf16x3_wide.hip): uniform row pointer of the k-tile + one 32-bit
+  // LDS-DMA in the SGPR-base form (lds_dma16, gemm_x3_common.h): uniform row pointer of the k-tile + one 32-bit
   // byte offset per lane and piece, computed once per output tile
   const unsigned sbase_km = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
-  auto dma_s = [&](const u16* p, unsigned off, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(p), "s"(lds_addr) : "memory");
-  };
   unsigned offA_km[KC::A_PER_WAVE], offB_km[KC::B_PER_WAVE];
 #pragma unroll
   for (int i = 0; i < KC::A_PER_WAVE; ++i) {             // A: A_PIECES 1-KiB pieces per plane
@@ -569,14 +520,14 @@ __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(A
 #pragma unroll
     for (int i = 0; i < KC::A_PER_WAVE; ++i) {
       const int idx = uw + NW * i;
-      dma_s(ah, offA_km[i], s + OFF_AHI + idx * 1024);
-      dma_s(al, offA_km[i], s + OFF_ALO + idx * 1024);
+      lds_dma16(ah, offA_km[i], s + OFF_AHI + idx * 1024);
+      lds_dma16(al, offA_km[i], s + OFF_ALO + idx * 1024);
     }
 #pragma unroll
     for (int i = 0; i < KC::B_PER_WAVE; ++i) {
       const int idx = uw + NW * i;
-      dma_s(bh, offB_km[i], s + OFF_BHI + idx * 1024);
-      dma_s(bl, offB_km[i], s + OFF_BLO + idx * 1024);
+      lds_dma16(bh, offB_km[i], s + OFF_BHI + idx * 1024);
+      lds_dma16(bl, offB_km[i], s + OFF_BLO + idx * 1024);
     }
   };
   // transpose-read one 32(m) x 16(k) fragment: two ds_read_b64_tr_b16 (rows kb.. and kb+4..)
@@ -856,7 +807,7 @@ extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    hipFuncSetAttribute((const void*)gemm_bf16x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<4>::SMEM_BYTES);
+    hipFuncSetAttribute((const void*)gemm_bf16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES);
     attr = true;
   }
   Args g;
@@ -866,22 +817,9 @@ extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream
   long long total = (long long)g.tiles_m * g.tiles_n * d->batch;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {   // persistent grid: one workgroup per CU
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
-  }
+  const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
-  g.stagger_cycles = 0; g.ncu = ncu; g.dbg = 0;
-#ifdef CIPS_TUNING
-  // stagger quantum = a quarter of one tile's main-loop time (~3500 cycles per k-tile); measured: no effect
-  g.stagger_cycles = (cips_tune_env("CIPS_X3_STAGGER", 0) == 1 && g.total >= 2 * grid) ? (d->K / BK) * 3500 / 4 : 0;
-  g.dbg = cips_tune_env("CIPS_X3_GDBG", 0);
-#endif
-  hipLaunchKernelGGL(gemm_bf16x3_kernel<4>, dim3(grid), dim3(512), Cfg<4>::SMEM_BYTES, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(gemm_bf16x3_kernel, dim3(grid), dim3(512), Cfg::SMEM_BYTES, (hipStream_t)stream, g);
   return CIPS_CHECK_LAUNCH();
 }
 
@@ -921,17 +859,14 @@ extern "C" int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t str
   long long total = (long long)g.tiles_m * g.tiles_n * d->batch;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  g.stagger_cycles = 0; g.ncu = 0; g.dbg = 0;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
+  static bool attr = false;
+  CIPS_PER_DEVICE(attr, false);
+  if (!attr) {
     hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<4>::SMEM_BYTES);
     hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<2>::SMEM_BYTES);
+    attr = true;
   }
+  const int ncu = cips_persistent_cus();
   if (bm == 256) {
     const int grid = g.total < ncu ? g.total : ncu;
     hipLaunchKernelGGL(gemm_bf16x3_km_kernel<4>, dim3(grid), dim3(512), KmCfg<4>::SMEM_BYTES, (hipStream_t)stream, g);

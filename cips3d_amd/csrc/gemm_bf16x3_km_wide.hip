@@ -12,22 +12,20 @@
 //     block (dWb2 = a1^T g, dWb1 = x^T g1) together, 256 tiles.  (Splitting K instead and meeting in C through
 //     fp32 atomics was measured at 2x the time of the whole GEMM: 16.7 M scalar atomics.)
 //   * two 64 KiB LDS stages, the eight pieces of k-tile t+1 issued one per three MFMAs under k-tile t.
-#include "common.h"
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
-#include <stdlib.h>
 #include <utility>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef short short8v __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int BM = 256, BN = 256, BK = 32;
 constexpr int ROW = 512;                         // bytes per k-row of an operand image (256 bf16)
 constexpr int OFF_AHI = 0, OFF_ALO = 32 * ROW, OFF_BHI = 2 * 32 * ROW, OFF_BLO = 3 * 32 * ROW;
 constexpr int STAGE = 4 * 32 * ROW;              // 65536
+static_assert(OFF_ALO == X3_PLANE_BYTES && OFF_BHI == 2 * X3_PLANE_BYTES && OFF_BLO == 3 * X3_PLANE_BYTES, "stage layout of gemm_x3_common.h");
 constexpr int NSTAGE = 2;
 constexpr int PF = 36;                           // epilogue scratch pitch (fp32 [32][36] per wave, aliases stage 1)
 constexpr int SMEM_BYTES = NSTAGE * STAGE;
@@ -66,14 +64,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_wide_kernel(KArgs g) {
     int lane = lane0;
     asm volatile("" : "+v"(lane));               // keep per-lane address math inside the persistent loop
     const int l31 = lane & 31, hf = lane >> 5, s16 = lane & 15, mhalf = (lane >> 4) & 1;
-    int bid = tseq;
-    {
-      const int nx = 8;
-      int q = g.total / nx, r = g.total % nx;
-      int xcd = bid % nx, idx = bid / nx;
-      int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-      bid = base + idx;
-    }
+    const int bid = xcd_tile(tseq, g.total);
     const int tn = bid % g.tiles_n;
     const int tm = (bid / g.tiles_n) % g.tiles_m;
     const int bz = (bid / (g.tiles_n * g.tiles_m)) % d.batch;
@@ -114,11 +105,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_wide_kernel(KArgs g) {
       offA[par] = (unsigned)(lh * d.lda + m) * 2u;
       offB[par] = (unsigned)(lh * d.ldb + n) * 2u;
     }
-    // SGPR-base form through asm (see gemm_bf16x3_wide.hip): uniform row pointer + one 32-bit offset per lane
-    auto dma = [&](const u16* p, unsigned off, unsigned char* lds_base) {
-      const unsigned la = sbase + (unsigned)(lds_base - smem);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(p), "s"(la) : "memory");
-    };
+    // SGPR-base form (lds_dma16): uniform row pointer + one 32-bit offset per lane
+    auto dma = [&](const u16* p, unsigned off, unsigned char* lds_base) { lds_dma16(p, off, sbase + (unsigned)(lds_base - smem)); };
     // CONV: byte offset of this lane's B row for contraction row q (a global output-pixel index) — its column part
     // comes from offB[] with the lane's k-row term removed (computed below with lh = 0 semantics)
     unsigned colB[2];
@@ -253,14 +241,6 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_wide_kernel(KArgs g) {
 //   * ONE barrier per k-tile, four MFMAs into its second k-step: it publishes k-tile t+1 (DMA'd a whole k-tile period
 //     earlier, not half of one) and frees the current stage for k-tile t+2, whose eight pieces follow one per two MFMAs.
 // Same MFMA order per accumulator as the kernel above: results are bit-identical.
-template <typename F, int... I>
-__device__ __forceinline__ void kstatic_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-// fragment order of a k-step: 0 a_lo[0], 1..4 b_hi[0..3], 5 a_lo[1], 6 a_hi[0], 7..10 b_lo[0..3], 11 a_hi[1]
-__device__ __forceinline__ constexpr bool kf_is_a(int q) { return q == 0 || q == 5 || q == 6 || q == 11; }
-__device__ __forceinline__ constexpr int kf_idx(int q) { return q == 0 || q == 6 ? 0 : q == 5 || q == 11 ? 1 : q <= 4 ? q - 1 : q - 7; }
-__device__ __forceinline__ constexpr int kf_plane(int q) { return q == 0 || q == 5 ? OFF_ALO : q == 6 || q == 11 ? OFF_AHI : q <= 4 ? OFF_BHI : OFF_BLO; }
-__device__ __forceinline__ constexpr int km_a(int m) { return (m >> 3) == 0 ? (((m >> 2) & 1) ? 5 : 0) : (((m >> 2) & 1) ? 11 : 6); }
-__device__ __forceinline__ constexpr int km_b(int m) { return (m >> 3) == 1 ? 7 + (m & 3) : 1 + (m & 3); }
 
 template <bool CONV>
 __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
@@ -278,14 +258,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const int l31 = lane & 31, hf = lane >> 5, s16 = lane & 15, mhalf = (lane >> 4) & 1;
-    int bid = tseq;
-    {
-      const int nx = 8;
-      int q = g.total / nx, r = g.total % nx;
-      int xcd = bid % nx, idx = bid / nx;
-      int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-      bid = base + idx;
-    }
+    const int bid = xcd_tile(tseq, g.total);
     const int tn = bid % g.tiles_n;
     const int tm = (bid / g.tiles_n) % g.tiles_m;
     const int bz = (bid / (g.tiles_n * g.tiles_m)) % d.batch;
@@ -321,9 +294,6 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       offA[par] = (unsigned)(lh * d.lda + m) * 2u;
       offB[par] = (unsigned)(lh * d.ldb + n) * 2u;
     }
-    auto dma = [&](const u16* p, unsigned off, unsigned la) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(p), "s"(la) : "memory");
-    };
     unsigned colB[2];
 #pragma unroll
     for (int par = 0; par < 2; ++par) colB[par] = offB[par] - (unsigned)(lh * d.ldb) * 2u;
@@ -348,11 +318,11 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       const int idx = uw + 8 * (pc >> 2), which = pc & 3;
       const long long rowoff = (long long)(k0 + 2 * idx);
       const unsigned la = sbase + st + (unsigned)idx * 1024u;
-      if (which == 0) dma(Ahi + rowoff * d.lda, offA[idx & 1], la + OFF_AHI);
-      else if (which == 1) dma(Alo + rowoff * d.lda, offA[idx & 1], la + OFF_ALO);
-      else if constexpr (CONV) dma(which == 2 ? Bhi : Blo, cvoff[pc >> 2], la + (which == 2 ? OFF_BHI : OFF_BLO));
-      else if (which == 2) dma(Bhi + rowoff * d.ldb, offB[idx & 1], la + OFF_BHI);
-      else dma(Blo + rowoff * d.ldb, offB[idx & 1], la + OFF_BLO);
+      if (which == 0) lds_dma16(Ahi + rowoff * d.lda, offA[idx & 1], la + OFF_AHI);
+      else if (which == 1) lds_dma16(Alo + rowoff * d.lda, offA[idx & 1], la + OFF_ALO);
+      else if constexpr (CONV) lds_dma16(which == 2 ? Bhi : Blo, cvoff[pc >> 2], la + (which == 2 ? OFF_BHI : OFF_BLO));
+      else if (which == 2) lds_dma16(Bhi + rowoff * d.ldb, offB[idx & 1], la + OFF_BHI);
+      else lds_dma16(Blo + rowoff * d.ldb, offB[idx & 1], la + OFF_BLO);
     };
     auto fbase = [&](int colw, int ks) -> unsigned {
       const int kb = 16 * ks + 8 * hf + (s16 >> 2);
@@ -377,8 +347,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
     bf16x8 F0[12], F1[12];
     auto rd = [&](auto Q_, const unsigned (&A)[2], const unsigned (&B)[4]) -> bf16x8 {
       constexpr int q = decltype(Q_)::value;
-      if constexpr (kf_is_a(q)) return frag(A[kf_idx(q)], kf_plane(q));
-      else return frag(B[kf_idx(q)], kf_plane(q));
+      if constexpr (x3_frag_is_a(q)) return frag(A[x3_frag_tile(q)], x3_frag_plane(q));
+      else return frag(B[x3_frag_tile(q)], x3_frag_plane(q));
     };
 
     // one k-tile.  MODE 0: steady state (DMA of k-tile kt+2, fragments of k-tile kt+1); 1: next-to-last (fragments only);
@@ -393,9 +363,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       if constexpr (MODE == 0) conv_prep((kt + 2) * BK);
       __builtin_amdgcn_sched_barrier(0);
       // k-step a: MFMAs on set 0, the twelve fragments of k-step b into set 1 (one per two MFMAs)
-      kstatic_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
+      static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[km_a(m)], F0[km_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[x3_mfma_a(m)], F0[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr ((m & 1) == 0) {
           constexpr int q = m >> 1;
           F1[q] = rd(std::integral_constant<int, q>{}, a1, b1);
@@ -403,9 +373,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
         __builtin_amdgcn_sched_barrier(0);
       });
       // k-step b
-      kstatic_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
+      static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[km_a(m)], F1[km_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[x3_mfma_a(m)], F1[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr (m == 3) {
           // every read of stage `cur` has returned, this wave's pieces of k-tile kt+1 have landed (issued a k-tile period
           // ago): behind the barrier stage `nxt` is readable and `cur` writable
@@ -433,7 +403,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, BK, STAGE);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    kstatic_for(std::make_integer_sequence<int, 12>{}, [&](auto Q_) { F0[decltype(Q_)::value] = rd(Q_, fa[0], fb[0]); });
+    static_for(std::make_integer_sequence<int, 12>{}, [&](auto Q_) { F0[decltype(Q_)::value] = rd(Q_, fa[0], fb[0]); });
     __builtin_amdgcn_sched_barrier(0);
     for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
     ktile(std::integral_constant<int, 1>{}, nk - 2);
@@ -501,16 +471,14 @@ extern "C" int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int n
   long long total = (long long)g.tiles_m * g.tiles_n * d->batch * ngroups;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
+  static bool attr = false;
+  CIPS_PER_DEVICE(attr, false);
+  if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    attr = true;
   }
+  const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
   if (d->K >= 2 * BK)                         // else: the one-k-tile form
     hipLaunchKernelGGL(gemm_bf16x3_km_v3_kernel<false>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
@@ -545,16 +513,14 @@ extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t
   const long long total = (long long)g.tiles_m * g.tiles_n * d.batch * g.ngroups;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
+  static bool attr = false;
+  CIPS_PER_DEVICE(attr, false);
+  if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    attr = true;
   }
+  const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
   if (g.cv.ktiles / g.cv.nchunks >= 2)          // every chunk has at least two k-tiles (else: the one-k-tile form)
     hipLaunchKernelGGL(gemm_bf16x3_km_v3_kernel<true>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);

@@ -21,16 +21,14 @@
 //
 // Restrictions (else hipErrorNotSupported and the caller falls back to gemm_bf16x3_wide): M, N multiples of 256,
 // K a multiple of 64, no transposed planes, gate planes as bit planes, 16-byte aligned rows of every tensor.
-#include "common.h"
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
 #include <utility>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 256, BN = 256, BK = 32, ROWB = 64;
@@ -40,29 +38,12 @@ constexpr int SCR_OFF = 2 * STAGE;              // the epilogue scratch starts b
 constexpr int SCR_WAVE = 4096;                  // per wave: two fp32 [16][32] halves (ping-pong)
 constexpr int SMEM_BYTES = SCR_OFF + 8 * SCR_WAVE;
 static_assert(SMEM_BYTES == 163840, "the kernel owns the whole LDS of the CU");
+static_assert(OFF_ALO == X3_PLANE_BYTES && OFF_BHI == 2 * X3_PLANE_BYTES && OFF_BLO == 3 * X3_PLANE_BYTES && ROWB == 64, "stage layout of gemm_x3_common.h");
 
 struct VArgs {
   cips_gemm_x3_desc d;
   int tiles_m, tiles_n, total;
-  // tuning aids (env CIPS_X3_V3DBG / CIPS_X3_V3SKEW / CIPS_X3_V3PHASES; results are WRONG with dbg != 0):
-  // dbg bit 0: epilogue arithmetic without any global store; bit 1: every store of a workgroup lands in one 256 KiB
-  // window (L2-resident); bit 2: non-temporal stores; bit 3: skip the epilogue
-  int dbg;
-  int skew, phases;     // workgroups of XCD x start (x % phases) * skew shader cycles late
 };
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
-// fragment q of a k-step, in the order the pass-major MFMA stream first needs them:
-//   0: a_lo[0]   1..4: b_hi[0..3]   5: a_lo[1]   6: a_hi[0]   7..10: b_lo[0..3]   11: a_hi[1]
-__device__ __forceinline__ constexpr int frag_is_a(int q) { return q == 0 || q == 5 || q == 6 || q == 11; }
-__device__ __forceinline__ constexpr int frag_off(int q) {
-  return q == 0 ? OFF_ALO : q == 5 ? OFF_ALO + 32 * ROWB : q == 6 ? OFF_AHI : q == 11 ? OFF_AHI + 32 * ROWB
-       : q <= 4 ? OFF_BHI + (q - 1) * 32 * ROWB : OFF_BLO + (q - 7) * 32 * ROWB;
-}
-__device__ __forceinline__ constexpr int mfma_a(int m) { return (m >> 3) == 0 ? (((m >> 2) & 1) ? 5 : 0) : (((m >> 2) & 1) ? 11 : 6); }
-__device__ __forceinline__ constexpr int mfma_b(int m) { return (m >> 3) == 1 ? 7 + (m & 3) : 1 + (m & 3); }
 
 #define LDS_B128(a) (*((__attribute__((address_space(3))) const bf16x8*)(uintptr_t)(a)))
 #define LDS_F4(a) (*((__attribute__((address_space(3))) const f32x4*)(uintptr_t)(a)))
@@ -78,7 +59,7 @@ __device__ __forceinline__ constexpr int mfma_b(int m) { return (m >> 3) == 1 ? 
 // ADDP: the addend (HAS_ADD) arrives as the split planes of a gated tensor plus the bit plane of that gate (descriptor fields
 // addp_*): value = (hi + lo) * (bit ? 1 : addp_gain), same bytes in as the fp32 addend, and no C_unmasked copy is needed by
 // the next layer.
-template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool DBG = false, bool RGBF = false, bool ADDP = false>
+template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool RGBF = false, bool ADDP = false>
 __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
@@ -89,12 +70,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
   const int nk = d.K / BK;                                 // even, >= 2
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
 
-  auto decode = [&](int t, int& tm, int& tn, int& bz) {    // XCD-contiguous tile ranges (gemm_bf16x3.hip)
-    const int nx = 8;
-    const int q = g.total / nx, r = g.total % nx;
-    const int xcd = t % nx, idx = t / nx;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int bid = base + idx;
+  auto decode = [&](int t, int& tm, int& tn, int& bz) {
+    const int bid = xcd_tile(t, g.total);
     tn = bid % g.tiles_n;
     tm = (bid / g.tiles_n) % g.tiles_m;
     bz = bid / (g.tiles_n * g.tiles_m);
@@ -117,24 +94,16 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       sr.offB[p] = (unsigned)(row * d.ldb + kcsw * 8) * 2u;
     }
   };
-  auto dma = [&](const u16* plane_k, unsigned off, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(plane_k), "s"(lds_addr) : "memory");
-  };
   // piece pc = 0..7 of the k-tile starting at contraction index k0, into the stage at LDS byte offset `st`
   auto dma_piece = [&](const Src& sr, int pc, int k0, unsigned st) {
     const int pp = pc >> 2, which = pc & 3;
     const unsigned la = sbase + st + (unsigned)((uw + 8 * pp) * 16 * ROWB);
-    if (which == 0) dma(sr.Ahi + k0, sr.offA[pp], la + OFF_AHI);
-    else if (which == 1) dma(sr.Alo + k0, sr.offA[pp], la + OFF_ALO);
-    else if (which == 2) dma(sr.Bhi + k0, sr.offB[pp], la + OFF_BHI);
-    else dma(sr.Blo + k0, sr.offB[pp], la + OFF_BLO);
+    if (which == 0) lds_dma16(sr.Ahi + k0, sr.offA[pp], la + OFF_AHI);
+    else if (which == 1) lds_dma16(sr.Alo + k0, sr.offA[pp], la + OFF_ALO);
+    else if (which == 2) lds_dma16(sr.Bhi + k0, sr.offB[pp], la + OFF_BHI);
+    else lds_dma16(sr.Blo + k0, sr.offB[pp], la + OFF_BLO);
   };
 
-  if (CIPS_TUNE(g.skew) > 0) {
-    const int ph = (int)(blockIdx.x & 7) % (g.phases > 0 ? g.phases : 1);
-    const long long t0 = __builtin_readcyclecounter();
-    while (__builtin_readcyclecounter() - t0 < (long long)ph * g.skew) __builtin_amdgcn_s_sleep(32);
-  }
   // ---- kernel prologue: the first tile's k-tiles 0 and 1
   bool have = (int)blockIdx.x < g.total;
   if (have) {
@@ -178,17 +147,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     bf16x8 F0[12], F1[12];
 
     // ---- epilogue plumbing declared here: the first inputs are requested inside the last k-tile
-    const bool win = DBG && (g.dbg & 2);             // tuning: every tile's outputs land in rows 0..255 of image 0
-    const long long cbase = win ? n0 : (long long)bz * d.strideC + (long long)m0 * d.ldc + n0;      // fp32 tensors (ld = ldc)
-    const long long pbase = win ? n0 : (long long)bz * d.strideP + (long long)m0 * d.ldp + n0;      // planes / gate planes (ld = ldp)
-    auto st16 = [&](void* ubase, unsigned off, u32x4 v) {
-      u32x4* q = (u32x4*)((char*)ubase + off);
-      if constexpr (DBG) {
-        if (g.dbg & 1) return;
-        if (g.dbg & 4) { __builtin_nontemporal_store(v, q); return; }
-      }
-      *q = v;
-    };
+    const long long cbase = (long long)bz * d.strideC + (long long)m0 * d.ldc + n0;      // fp32 tensors (ld = ldc)
+    const long long pbase = (long long)bz * d.strideP + (long long)m0 * d.ldp + n0;      // planes / gate planes (ld = ldp)
+    auto st16 = [&](void* ubase, unsigned off, u32x4 v) { *(u32x4*)((char*)ubase + off) = v; };
     auto st16f = [&](void* ubase, unsigned off, float a, float b, float c, float e) {
       u32x4 v = {__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(e)};
       st16(ubase, off, v);
@@ -253,10 +214,10 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       // k-step a: MFMAs on set 0, the twelve reads of k-step b into set 1 (one per two MFMAs)
       static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[mfma_a(m)], F0[mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[x3_mfma_a(m)], F0[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr ((m & 1) == 0) {
           constexpr int q = m >> 1;
-          F1[q] = LDS_B128((frag_is_a(q) ? a1 : b1) + frag_off(q));
+          F1[q] = LDS_B128((x3_frag_is_a(q) ? a1 : b1) + x3_frag_off_nt(q));
         }
         SB();
       });
@@ -271,7 +232,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       }
       static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[mfma_a(m)], F1[mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[x3_mfma_a(m)], F1[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr (m == 3) {
           // every fragment read of stage `cur` has returned (lgkmcnt), this wave's pieces of k-tile kt+1 have landed
           // (vmcnt; they were issued a k-tile period ago): behind the barrier stage `nxt` is readable, `cur` writable
@@ -283,8 +244,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         if constexpr (MODE <= 1) {
           if constexpr (m >= 5 && m <= 15 && (m & 1) == 1) {
             constexpr int q = m - 5;
-            F0[q] = LDS_B128((frag_is_a(q) ? a0n : b0n) + frag_off(q));
-            F0[q + 1] = LDS_B128((frag_is_a(q + 1) ? a0n : b0n) + frag_off(q + 1));
+            F0[q] = LDS_B128((x3_frag_is_a(q) ? a0n : b0n) + x3_frag_off_nt(q));
+            F0[q + 1] = LDS_B128((x3_frag_is_a(q + 1) ? a0n : b0n) + x3_frag_off_nt(q + 1));
           }
         }
         if constexpr (MODE == 2) {
@@ -302,7 +263,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
 #pragma unroll
-    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((frag_is_a(q) ? fa0 : fb0) + frag_off(q));
+    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
     SB();
     for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
     ktile(std::integral_constant<int, 1>{}, nk - 2);
@@ -330,7 +291,6 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     };
     float rw[3][8];                           // rgb_w columns of the current column block
     float tacc[3] = {0.f, 0.f, 0.f};          // RGBF: the current row set's ToRGB sums
-    if (DBG && (g.dbg & 8)) { asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[1][3][15])); continue; }
     put(std::integral_constant<int, 0>{});
     static_for(std::make_integer_sequence<int, 16>{}, [&](auto HS_) {
       constexpr int hs = decltype(HS_)::value;
@@ -412,7 +372,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         unsigned v = bits << (8 * q2);
         v |= (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
         v |= (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);     // quad_perm [2,3,0,1]
-        if (q2 == 0 && !(DBG && (g.dbg & 1))) {
+        if (q2 == 0) {
           unsigned char* q = (unsigned char*)d.mask_out + ((pbase + up) >> 3);
           *reinterpret_cast<unsigned*>(q + (eP >> 3)) = v;
         }
@@ -446,7 +406,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
             t += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x4E, 0xF, 0xF, true));
             v[c] = t;
           }
-          if (q2 == 0 && !(DBG && (g.dbg & 1))) {
+          if (q2 == 0) {
             const long long row = (long long)bz * d.M + m0 + wm * 64 + (rs >> 1) * 32 + (rs & 1) * 16 + h_rr;
             float* q = d.torgb_part + ((long long)(tn * 2 + wn) * d.batch * d.M + row) * 4;
             *reinterpret_cast<float4*>(q) = make_float4(v[0], v[1], v[2], 0.f);
@@ -478,15 +438,15 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
 
 }  // namespace
 
-template <bool A, bool Mk, bool R, bool FAST, bool DBG = false, bool RGBF = false, bool ADDP = false>
+template <bool A, bool Mk, bool R, bool FAST, bool RGBF = false, bool ADDP = false>
 static void launch_v3f(const VArgs& g, int grid, hipStream_t stream) {
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, DBG, RGBF, ADDP>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, DBG, RGBF, ADDP>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
+  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
 }
 template <bool A, bool Mk, bool R>
 static void launch_v3(const VArgs& g, int grid, hipStream_t stream) {
@@ -495,14 +455,11 @@ static void launch_v3(const VArgs& g, int grid, hipStream_t stream) {
   const bool fwd = !Mk && d.act == 1 && d.mask_out != nullptr, bwd = Mk && d.act == 0 && d.mask_out == nullptr;
   const bool fast = d.P_hi != nullptr && d.C == nullptr && (fwd || bwd) && (A || d.C_unmasked == nullptr);
   if constexpr (!A && !Mk) {
-    if (d.torgb_w) { launch_v3f<A, Mk, R, true, false, true>(g, grid, stream); return; }     // the entry point checked `fast`
+    if (d.torgb_w) { launch_v3f<A, Mk, R, true, true>(g, grid, stream); return; }     // the entry point checked `fast`
   }
   if constexpr (A && Mk && !R) {
-    if (d.addp_hi) { launch_v3f<A, Mk, R, true, false, false, true>(g, grid, stream); return; }   // likewise
+    if (d.addp_hi) { launch_v3f<A, Mk, R, true, false, true>(g, grid, stream); return; }   // likewise
   }
-#ifdef CIPS_TUNING
-  if (fast && g.dbg) { launch_v3f<A, Mk, R, true, true>(g, grid, stream); return; }
-#endif
   if (fast) launch_v3f<A, Mk, R, true>(g, grid, stream);
   else launch_v3f<A, Mk, R, false>(g, grid, stream);
 }
@@ -545,25 +502,8 @@ extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_v3(const cips_gemm_x3_desc* d, cip
   const long long total = (long long)g.tiles_m * g.tiles_n * d->batch;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
-  }
-  int grid = g.total < ncu ? g.total : ncu;
-#ifdef CIPS_TUNING
-  {
-    // tuning aids (probe builds only), read on every call: see VArgs
-    g.dbg = cips_tune_env("CIPS_X3_V3DBG", 0);
-    g.skew = cips_tune_env("CIPS_X3_V3SKEW", 0);
-    g.phases = cips_tune_env("CIPS_X3_V3PHASES", 2);
-    const int eg = cips_tune_env("CIPS_X3_V3GRID", 0);
-    if (eg > 0 && eg < grid) grid = (eg / 8) * 8 > 0 ? (eg / 8) * 8 : grid;
-  }
-#endif
+  const int ncu = cips_persistent_cus();
+  const int grid = g.total < ncu ? g.total : ncu;
   hipStream_t st = (hipStream_t)stream;
   if (a) launch_v3<true, true, false>(g, grid, st);
   else if (m) launch_v3<false, true, false>(g, grid, st);

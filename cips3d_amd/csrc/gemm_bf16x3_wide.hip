@@ -23,15 +23,11 @@
 //     epilogue's stores in flight (vmcnt retires in order: the DMA pieces are older than every store).
 // Restrictions (else the caller falls back to the 256x128 kernel): no transposed planes (T_hi), 16-byte aligned
 // rows of every auxiliary tensor (N, ldc, ldp multiples of 8).
-#include "common.h"
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
-#include <stdlib.h>
 #include <utility>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int BM = 256, BN = 256, BK = 32, ROWB = 64;
 constexpr int OFF_AHI = 0, OFF_ALO = BM * ROWB, OFF_BHI = 2 * BM * ROWB, OFF_BLO = OFF_BHI + BN * ROWB;
@@ -43,12 +39,9 @@ constexpr int SCR_WAVE = 32 * PF * 4;           // 4608 B per wave
 constexpr int SMEM_BYTES = NSTAGE * STAGE;      // 131072; the epilogue scratch (36 KiB) aliases stage 1 only, so that
                                                 // the next tile's first k-tile can stream into stage 0 meanwhile
 static_assert(8 * SCR_WAVE <= STAGE, "scratch");
+static_assert(OFF_ALO == X3_PLANE_BYTES && OFF_BHI == 2 * X3_PLANE_BYTES && OFF_BLO == 3 * X3_PLANE_BYTES && ROWB == 64, "stage layout of gemm_x3_common.h");
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// compile-time loop: the sub-tile index must be a constant, or acc[][] is indexed dynamically and lands in scratch
-template <typename F, int... I>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 // Implicit-GEMM convolution (CONV instantiation): the B operand's rows are output pixels of image `bz`, its
 // contraction index is (tap, channel); row r of k-tile (tap, c0) is the 32-channel slice at input pixel
@@ -78,20 +71,14 @@ struct ConvPart {
 };
 struct WArgs {
   cips_gemm_x3_desc d;
-  int tiles_m, tiles_n, total, dbg;
+  int tiles_m, tiles_n, total;
+  int nparts;                  // conv2d_x3_v3_kernel only: 0 = one range described by d / cv / tiles_n (plain convolution),
+                               // else the ranges part[0 .. nparts)
   int ksplit;                  // > 1: the contraction is cut into ksplit ranges of k-tiles (chunk c takes k-tiles
                                // [c*T/ksplit, (c+1)*T/ksplit)); chunk c of batch entry b writes C + (c*batch + b)*strideC
   ConvGeom cv;
-  int nparts;                  // conv2d_x3_v3_kernel only: 0 = one range described by d / cv / tiles_n (plain convolution)
   ConvPart part[4];
 };
-
-__device__ __forceinline__ u16 f2bf(float v) {
-  unsigned u = __float_as_uint(v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
 
 // HAS_ADD / HAS_MASK / HAS_RES: which global inputs the epilogue reads (fp32 addend, gate plane, residual planes);
 // compile-time so that only their prefetch registers exist.
@@ -104,18 +91,14 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
   const int uw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wave = uw, wm = wave >> 1, wn = wave & 1;       // 4 x 2 waves
   const int M = d.M, N = d.N, K = d.K;
-  const int nk_all = CIPS_TUNE(g.dbg & 4) ? 0 : K / BK;
+  const int nk_all = K / BK;
   const int ksplit = g.ksplit > 1 ? g.ksplit : 1;
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
 #define LDS_B128(a) (*((__attribute__((address_space(3))) const bf16x8*)(uintptr_t)(a)))
 
   // tile coordinates of sequence number t (XCD-contiguous tile ranges, see gemm_bf16x3.hip)
   auto decode = [&](int t, int& tm, int& tn, int& bz, int& kc) {
-    const int nx = 8;
-    int q = g.total / nx, r = g.total % nx;
-    int xcd = t % nx, idx = t / nx;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int bid = base + idx;
+    const int bid = xcd_tile(t, g.total);
     tn = bid % g.tiles_n;
     tm = (bid / g.tiles_n) % g.tiles_m;
     const int bk = bid / (g.tiles_n * g.tiles_m);
@@ -176,13 +159,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
       return k0;
     }
   };
-  // Written as asm to get the SGPR-base form (uniform plane pointer in s[..], one 32-bit offset per lane): the builtin
-  // takes a flat 64-bit pointer and hipcc then builds 64-bit per-lane addresses with two v_lshl_add_u64 per piece
-  // (A/B on one box: main loop 207 -> 197 us, 20 fewer VGPRs).
-  // M0 (LDS destination of the wave's 1 KiB) is not used by anything else in this kernel.
-  auto dma = [&](const u16* plane_k, unsigned off, unsigned char* lds_base) {
-    const unsigned la = sbase + (unsigned)(lds_base - smem);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(plane_k), "s"(la) : "memory");
+  auto dma = [&](const u16* plane_k, unsigned off, unsigned char* lds_base) {    // SGPR-base form (lds_dma16)
+    lds_dma16(plane_k, off, sbase + (unsigned)(lds_base - smem));
   };
   auto dma_piece = [&](const Src& sr, int pc, int k0, int kb, unsigned char* s) {      // pc = 0..7; kb = prep_b(sr, k0)
     const int pp = pc >> 2, which = pc & 3;
@@ -297,7 +275,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
 
     // ---------------- main loop: two stages, DMA of k-tile kt+1 in flight under the MFMAs of k-tile kt
     Pre pre[2];
-    if (nk > 0 && !first_issued && !CIPS_TUNE(g.dbg & 2)) {
+    if (nk > 0 && !first_issued) {
       const int kb0 = prep_b(src, 0);
 #pragma unroll
       for (int pc = 0; pc < 8; ++pc) dma_piece(src, pc, 0, kb0, smem);
@@ -318,19 +296,14 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
       __builtin_amdgcn_s_barrier();              // k-tile kt has landed everywhere; stage (kt+1)&1 is free again
       const bool more = kt + 1 < nk;
       if (!more) prefetch(0, pre[0]);            // last k-tile: the first sub-tile's epilogue inputs ride under its MFMAs
-      if (!CIPS_TUNE(g.dbg & 1)) compute(kt & 1, more && !CIPS_TUNE(g.dbg & 2), (kt + 1) & 1, (kt + 1) * BK);
-      else if (more && !CIPS_TUNE(g.dbg & 2)) {
-        const int kb1 = prep_b(src, (kt + 1) * BK);
-#pragma unroll
-        for (int pc = 0; pc < 8; ++pc) dma_piece(src, pc, (kt + 1) * BK, kb1, smem + ((kt + 1) & 1) * STAGE);
-      }
+      compute(kt & 1, more, (kt + 1) & 1, (kt + 1) * BK);
     }
     if (nk == 0) prefetch(0, pre[0]);
     __syncthreads();   // main-loop LDS reads are done everywhere; the scratch regions alias stage 1
 
     // ---------------- the next output tile's first k-tile streams into stage 0 while this tile's epilogue runs
     first_issued = false;
-    if (nk > 0 && (nk & 1) == 0 && tseq + (int)gridDim.x < g.total && !CIPS_TUNE(g.dbg & 2)) {
+    if (nk > 0 && (nk & 1) == 0 && tseq + (int)gridDim.x < g.total) {
       int tm2, tn2, bz2, kc2;
       decode(tseq + gridDim.x, tm2, tn2, bz2, kc2);
       Src nsrc;
@@ -492,14 +465,6 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
 // k-tile t+2 follows that barrier).  Same tile, LDS image, gather addressing (make_src / prep_b above) and MFMA order per
 // accumulator as the CONV instantiation of the kernel above: bit-identical outputs.  A convolution's contraction is long
 // (9 C / 32 k-tiles), so tiles do not overlap here: k-tiles 0 and 1 are requested at the tile start.
-__device__ __forceinline__ constexpr bool cq_is_a(int q) { return q == 0 || q == 5 || q == 6 || q == 11; }
-__device__ __forceinline__ constexpr int cq_off(int q) {
-  return q == 0 ? OFF_ALO : q == 5 ? OFF_ALO + 32 * ROWB : q == 6 ? OFF_AHI : q == 11 ? OFF_AHI + 32 * ROWB
-       : q <= 4 ? OFF_BHI + (q - 1) * 32 * ROWB : OFF_BLO + (q - 7) * 32 * ROWB;
-}
-__device__ __forceinline__ constexpr int cm_a(int m) { return (m >> 3) == 0 ? (((m >> 2) & 1) ? 5 : 0) : (((m >> 2) & 1) ? 11 : 6); }
-__device__ __forceinline__ constexpr int cm_b(int m) { return (m >> 3) == 1 ? 7 + (m & 3) : 1 + (m & 3); }
-
 __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
@@ -521,13 +486,10 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
     int nimg = g.cv.nimg;
     long long a_off = 0, c_off = 0, strideC = d.strideC;
     {
-      const int nx = 8;
-      int q = g.total / nx, r = g.total % nx;
-      int xcd = tseq % nx, idx = tseq / nx;
-      int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-      int bid = base + idx;
+      int bid = xcd_tile(tseq, g.total);
       int tiles_n = g.tiles_n;
       if (g.nparts > 0) {
+        const int nx = 8, xcd = tseq % nx, idx = tseq / nx;
         // several ranges with different contraction lengths: every XCD takes ITS eighth of EVERY range (contiguous inside
         // the range, for L2 reuse of the operands), longest range first — one contiguous eighth of the whole sequence would
         // hand XCD 0 only the long tiles and XCD 7 only the short ones.  g.total = 8 x the longest per-XCD sequence; a slot
@@ -601,16 +563,13 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
         offB[p] = (ok ? (unsigned)(((iy * g.cv.W + ix) * g.cv.C + c0) * 2) + imgoff[p] : zero_rel) + chunk[p];
       }
     };
-    auto dma = [&](const u16* plane_k, unsigned off, unsigned la) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(plane_k), "s"(la) : "memory");
-    };
     auto dma_piece = [&](int pc, int k0, unsigned st) {        // uses offB of the last prep_b
       const int pp = pc >> 2, which = pc & 3;
       const unsigned la = sbase + st + (unsigned)((uw + 8 * pp) * 16 * ROWB);
-      if (which == 0) dma(Ahi + k0, offA[pp], la + OFF_AHI);
-      else if (which == 1) dma(Alo + k0, offA[pp], la + OFF_ALO);
-      else if (which == 2) dma(Bhi, offB[pp], la + OFF_BHI);
-      else dma(Blo, offB[pp], la + OFF_BLO);
+      if (which == 0) lds_dma16(Ahi + k0, offA[pp], la + OFF_AHI);
+      else if (which == 1) lds_dma16(Alo + k0, offA[pp], la + OFF_ALO);
+      else if (which == 2) lds_dma16(Bhi, offB[pp], la + OFF_BHI);
+      else lds_dma16(Blo, offB[pp], la + OFF_BLO);
     };
 
     f32x16 acc[2][4];
@@ -634,16 +593,16 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
       __builtin_amdgcn_sched_barrier(0);
       static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[cm_a(m)], F0[cm_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[x3_mfma_a(m)], F0[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr ((m & 1) == 0) {
           constexpr int q = m >> 1;
-          F1[q] = LDS_B128((cq_is_a(q) ? a1 : b1) + cq_off(q));
+          F1[q] = LDS_B128((x3_frag_is_a(q) ? a1 : b1) + x3_frag_off_nt(q));
         }
         __builtin_amdgcn_sched_barrier(0);
       });
       static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
-        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[cm_a(m)], F1[cm_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
+        acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F1[x3_mfma_a(m)], F1[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr (m == 3) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if constexpr (MODE == 0) {
           if constexpr (m >= 4 && m <= 18 && (m & 1) == 0) dma_piece((m - 4) >> 1, (kt + 2) * BK, cur);
@@ -651,8 +610,8 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
         if constexpr (MODE <= 1) {
           if constexpr (m >= 5 && m <= 15 && (m & 1) == 1) {
             constexpr int q = m - 5;
-            F0[q] = LDS_B128((cq_is_a(q) ? a0n : b0n) + cq_off(q));
-            F0[q + 1] = LDS_B128((cq_is_a(q + 1) ? a0n : b0n) + cq_off(q + 1));
+            F0[q] = LDS_B128((x3_frag_is_a(q) ? a0n : b0n) + x3_frag_off_nt(q));
+            F0[q + 1] = LDS_B128((x3_frag_is_a(q + 1) ? a0n : b0n) + x3_frag_off_nt(q + 1));
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -667,7 +626,7 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, BK, STAGE);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
 #pragma unroll
-    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((cq_is_a(q) ? fa0 : fb0) + cq_off(q));
+    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
     __builtin_amdgcn_sched_barrier(0);
     for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
     ktile(std::integral_constant<int, 1>{}, nk - 2);
@@ -743,14 +702,7 @@ static void launch_wide(const WArgs& g, int grid, hipStream_t stream) {
 }
 
 static int wide_grid(int total) {
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
-  }
+  const int ncu = cips_persistent_cus();
   return total < ncu ? total : ncu;
 }
 
@@ -814,7 +766,6 @@ extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) 
   const long long total = (long long)g.tiles_m * g.tiles_n * d.batch * ks;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  g.dbg = 0;
   const bool v3 = (K / 32) / ks >= 2;           // every chunk has at least two k-tiles (else: the one-k-tile form of the wide kernel)
   if (v3) {
     static bool attr = false;
@@ -931,19 +882,7 @@ extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_wide(const cips_gemm_x3_desc* d, c
   long long total = (long long)g.tiles_m * g.tiles_n * d->batch;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  static int ncu = 0;
-  CIPS_PER_DEVICE(ncu, 0);
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    ncu = (ncu / 8) * 8;
-  }
-  g.dbg = 0;
-#ifdef CIPS_TUNING
-  g.dbg = cips_tune_env("CIPS_X3_GDBG", 0);
-#endif
-  const int grid = g.total < ncu ? g.total : ncu;
+  const int grid = wide_grid(g.total);
   hipStream_t st = (hipStream_t)stream;
   if (a) launch_wide<true, true, false>(g, grid, st);
   else if (m) launch_wide<false, true, false>(g, grid, st);

@@ -16,7 +16,7 @@
 // per MFMA is ~3% of LDS bandwidth: staging is never the limiter, MFMA issue is.
 // Workgroup ids are remapped so that each XCD (block id % 8) walks a contiguous run of
 // tiles with the N index fastest: the N-tiles that share an A panel hit the same L2.
-#include "common.h"
+#include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
 
 namespace {
@@ -41,15 +41,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(Args g) {
   float* Bs = smem + SMEM_A;
   const cips_gemm_desc& d = g.d;
 
-  // ---- XCD-aware bijective remap of the workgroup id (block b runs on XCD b % 8) ----
-  int bid = blockIdx.x;
-  {
-    const int nx = 8;
-    int q = g.total / nx, r = g.total % nx;
-    int xcd = bid % nx, idx = bid / nx;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
+  const int bid = xcd_tile(blockIdx.x, g.total);
   const int tn = bid % g.tiles_n;
   const int tm = (bid / g.tiles_n) % g.tiles_m;
   const int bz = bid / (g.tiles_n * g.tiles_m);

@@ -6,7 +6,7 @@
 // once per layer — B x 1 MB, L2/MALL resident — and the bmm itself is cips_gemm_f32 with the
 // LeakyReLU / skip epilogue fused.  ToRGB (generator.py:983-1006) is a 512 -> 3 projection:
 // pure HBM streaming, one wave per pixel row.
-#include "common.h"
+#include "gemm_x3_common.h"
 #include <cstdlib>
 #include "../../include/cips3d_hip.h"
 
@@ -60,11 +60,6 @@ __global__ __launch_bounds__(256) void modfc_prep_kernel(const float* __restrict
 //   (1) demod[b][n] = rsqrt(sum_k (W[k][n] (s[b][k]+1))^2 + eps)          grid (out/32, B)
 //   (2) 32x32 tiles of v = W (s+1) demod, split to hi/lo, written row-major and (through LDS) transposed,
 //       both with coalesced accesses                                            grid (out/32, in/32, B)
-__device__ __forceinline__ unsigned short f2bf_rne(float v) {
-  unsigned u = __float_as_uint(v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 __global__ __launch_bounds__(256) void modfc_demod_kernel(const float* __restrict__ W, const float* __restrict__ s,
                                                           float* __restrict__ demod, int in_dim, int out_dim, float eps) {
   __shared__ float red[8][33];
@@ -102,8 +97,8 @@ __global__ __launch_bounds__(256) void modfc_planes_kernel(const float* __restri
     unsigned short h = 0, l = 0;
     if (k < in_dim && n < out_dim) {
       const float v = W[(long long)k * out_dim + n] * (s[(long long)b * in_dim + k] + 1.f) * demod[(long long)b * out_dim + n];
-      h = f2bf_rne(v);
-      l = f2bf_rne(v - __uint_as_float(((unsigned)h) << 16));
+      h = f2bf(v);
+      l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
       wbh[base + (long long)k * out_dim + n] = h;
       wbl[base + (long long)k * out_dim + n] = l;
     }
@@ -190,8 +185,6 @@ __global__ __launch_bounds__(256) void modfc_prep_bwd_s_kernel(const float* __re
 }
 
 // ---- ToRGB --------------------------------------------------------------------------
-typedef unsigned short u16;
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
 // load 4 consecutive activations either from fp32 or from bf16 hi/lo planes
 template <bool X3>
 __device__ __forceinline__ float4 ldx4(const void* xa, const void* xb, long long e) {
@@ -518,8 +511,8 @@ __global__ __launch_bounds__(256) void torgb_bwd_x_x3_kernel(const float* __rest
     unsigned hw[4], lw[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const u16 h0 = f2bf_rne(v[2 * q]), h1 = f2bf_rne(v[2 * q + 1]);
-      const u16 l0 = f2bf_rne(v[2 * q] - __uint_as_float(((unsigned)h0) << 16)), l1 = f2bf_rne(v[2 * q + 1] - __uint_as_float(((unsigned)h1) << 16));
+      const u16 h0 = f2bf(v[2 * q]), h1 = f2bf(v[2 * q + 1]);
+      const u16 l0 = f2bf(v[2 * q] - __uint_as_float(((unsigned)h0) << 16)), l1 = f2bf(v[2 * q + 1] - __uint_as_float(((unsigned)h1) << 16));
       hw[q] = (unsigned)h0 | ((unsigned)h1 << 16);
       lw[q] = (unsigned)l0 | ((unsigned)l1 << 16);
     }
@@ -580,8 +573,8 @@ __global__ __launch_bounds__(256) void modfc_planes_batch_kernel(PrepJobs J, int
     unsigned short h = 0, l = 0;
     if (k < in_dim && n < out_dim) {
       const float v = W[(long long)k * out_dim + n] * (s[(long long)b * in_dim + k] + 1.f) * demod[(long long)b * out_dim + n];
-      h = f2bf_rne(v);
-      l = f2bf_rne(v - __uint_as_float(((unsigned)h) << 16));
+      h = f2bf(v);
+      l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
       wbh[base + (long long)k * out_dim + n] = h;
       wbl[base + (long long)k * out_dim + n] = l;
     }
@@ -628,8 +621,8 @@ __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, i
         const float v[4] = {w.x * sc * dm.x, w.y * sc * dm.y, w.z * sc * dm.z, w.w * sc * dm.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          h[j] = f2bf_rne(v[j]);
-          l[j] = f2bf_rne(v[j] - __uint_as_float(((unsigned)h[j]) << 16));
+          h[j] = f2bf(v[j]);
+          l[j] = f2bf(v[j] - __uint_as_float(((unsigned)h[j]) << 16));
         }
         const long long o = base + (long long)k * out_dim + n;
         *reinterpret_cast<uint2*>(wbh + o) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
