@@ -392,17 +392,17 @@ class CIPSNet(nn.Module):
         if join:
             main.wait_stream(side)
         # (not ok: the modulation Linears are kept all the same — forward() takes its parameters from here)
-        self._tail = dict(key=(B, n, in0, len(names), id(style_dict)), params=params, ports=ports)
+        self._tail = dict(key=(B, n, in0, len(names)), styles=style_dict, params=params, ports=ports)
         return True
 
     def forward(self, input, style_dict, img_size=1024, **kwargs):
         names = self._names(img_size)
         tail, self._tail = getattr(self, "_tail", None), None
-        key = (input.shape[0], input.shape[1], input.shape[2], len(names), id(style_dict))
+        key = (input.shape[0], input.shape[1], input.shape[2], len(names))
         if (tail is None and torch.is_grad_enabled() and input.is_cuda and input.requires_grad
                 and self.open_tail_ports(style_dict, *key[:3], img_size=img_size)):
             tail, self._tail = self._tail, None          # not opened ahead (a direct call): open them now
-        if tail is not None and tail["key"] == key and torch.is_grad_enabled():
+        if tail is not None and tail["key"] == key and tail["styles"] is style_dict and torch.is_grad_enabled():
             if tail["ports"] is not None:
                 rgb = ops.inr_head_with_ports(len(names), input, tail["params"], tail["ports"])
             else:
@@ -658,7 +658,7 @@ class GeneratorNerfINR(nn.Module):
             # (CIPSNet.open_tail_ports); they sit on the INR mapping network's side stream, joined right before the head.
             # Only where a NeRF backward follows the head's: with a frozen NeRF there is nothing to run beside, and the
             # side-stream form measured 0.4 ms slower than the plain one at the r256 stages (profiles/r6_tail_ab.txt)
-            if self.inr_net.open_tail_ports(style_dict, b, n, 32, join=False):
+            if self.inr_net.open_tail_ports(style_dict, b, n, self.siren.rgb_dim, join=False):
                 self._pending_side = _side_stream(device)
 
         # ---------------- random draws in reference order ----------------
@@ -889,8 +889,10 @@ class GeneratorNerfINR(nn.Module):
         finally:
             # a deferred INR-mapping side stream is joined on EVERY exit (no-op after _render's own join): an exception
             # before the INR head must not leave the fork open — the main stream would never wait for it, and a
-            # hipGraph capture would end with an unjoined stream
+            # hipGraph capture would end with an unjoined stream.  Nor may it leave the gradient ports _render opened
+            # for the head pending: they hold the modulation graph, and the next forward() must not find them
             self._join_side()
+            self.inr_net._tail = None
 
     def forward_camera_pos_and_lookup(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                       h_mean, v_mean, hierarchical_sample, camera_pos, camera_lookup, psi=1,

@@ -9,6 +9,7 @@ import ctypes as C
 import ctypes as _ct
 import math
 import os as _os
+import weakref
 
 import torch
 
@@ -853,11 +854,13 @@ class InrHeadFunction(torch.autograd.Function):
     args: x0 (B,n,in0); then per block k (nblocks of them): W1 (in,out), s1 (B,in), W2 (out,out),
     s2 (B,out); then per block with a ToRGB (k >= 3): T (3,out), tau (3).
     s* = SinStyleMod.modulation(style) (mod_conv_fc.py:474) computed on the host side.
-    Blocks k >= 4 use the skip connection (generator.py:1128, 971-973)."""
+    Blocks k >= 4 use the skip connection (generator.py:1128, 971-973).
+    grad_mode, ports: as InrHeadX3Function; this form keeps what a backward needs either way and has no gradient ports."""
 
     @staticmethod
-    def forward(ctx, nblocks, x0, *params):
-        nblocks, _grad_mode = nblocks if isinstance(nblocks, tuple) else (nblocks, True)
+    def forward(ctx, nblocks, grad_mode, ports, x0, *params):
+        if ports is not None:
+            raise RuntimeError("the exact-fp32 INR head has no gradient ports")
         x0 = _c(x0.detach())
         B, n, _ = x0.shape
         dev = x0.device
@@ -958,7 +961,7 @@ class InrHeadFunction(torch.autograd.Function):
                     epi["rgb_w"] = rgbp[2 * (k - 1 - 3)]
                 g2 = bmm_nn(g1, wbt1, out=torch.empty(B, n, width, device=dev), **epi)
                 Dout = newD
-        flat = [None, dx0]
+        flat = [None, None, None, dx0]
         for gb in grads_blocks:
             flat.extend(gb)
         flat.extend(grads_rgb)
@@ -971,13 +974,11 @@ class InrHeadFunction(torch.autograd.Function):
 import os as _os
 INR_MODE = _os.environ.get("CIPS_INR_MODE", "bf16x3")   # "bf16x3" (default, ~1e-5 rel. per layer) or "f32" (exact fp32 MFMA)
 BF = torch.bfloat16
-INR_W_KMAJOR = True   # dW GEMMs read the row-major planes through LDS transpose reads (no transposed copies in HBM)
 # The head's weight-gradient tail (style / modulated-weight gradients of all layers, ToRGB weight gradients: ~0.75 ms of streaming
 # kernels at C2) depends on nothing that follows the head in the backward pass.  "side": it hangs off the head through two
 # gradient ports whose autograd nodes live on the generator's side stream, so it runs next to the compositing / SIREN backward
 # instead of in front of it (CIPSNet.forward; profiles/r6_cores_tail_probe.txt).  "main": everything inside InrHeadX3Function.
 INR_TAIL = _os.environ.get("CIPS_INR_TAIL", "side")
-                                                                 # transpose reads: no transposed planes in HBM
 
 
 class Planes:
@@ -1418,11 +1419,6 @@ def torgb_bwd_w_x3_batch(xps, drgb2d, cores=False):
     return [(dw[i], db[i]) for i in range(n)]
 
 
-# LeakyReLU gates of the head kept as bit planes (1 bit per activation, written by the forward GEMMs' epilogues) instead
-# of bf16 planes: 2.5 GB less HBM traffic per C2 step (layer widths that are not multiples of 32 keep the bf16 form).
-INR_GATE_BITS = True
-
-
 # ToRGB forward folded into the epilogue of the block's second GEMM wherever the 256x256-tile kernel takes the shape
 # (else the separate ToRGB kernel).  Backward: the skip gradient is re-read from the previous layer's GATED planes (un-gated
 # on the fly with that gate's bit plane) instead of from a separate fp32 copy the previous GEMM would have to write, and the
@@ -1430,307 +1426,268 @@ INR_GATE_BITS = True
 # interior tiles); the fp32 copy / the K = 32 zero-padded GEMM remain as the ragged-shape forms.
 
 
-def _bsl(t, b0, b1):
-    """images b0..b1 of a (B, ...) tensor / Planes (a contiguous view)"""
-    if t is None:
-        return None
-    if isinstance(t, Planes):
-        return Planes(t.hi[b0:b1], t.lo[b0:b1])
-    return t[b0:b1]
+class _HeadLayer:
+    """One SinBlock of the split-bf16 head: what the forward plans and writes, and what the backward reads.  gate1 / gate2:
+    the LeakyReLU gates of a1 and of the block output as the backward's `mask` operand takes them — bit planes (`bits`;
+    written by the forward's epilogues unless pinned), else the bf16 sign form: a1's own hi plane, and the output's hi
+    plane or, behind a skip connection, a copy of a2's sign the forward writes."""
+    __slots__ = ("cin", "cout", "skip", "bits", "pinned1", "pinned2", "xP", "a1P", "gate1", "oP", "gate2", "wb1", "d1", "wb2",
+                 "d2")
 
 
-def _chunk_ranges(B):
-    """image ranges the head's launch chain is cut into: one (two chains on two streams measured slower, profiles/HISTORY.md section 3)"""
-    return [(0, B)]
+def _pixel_split(n, ksp, more):
+    """pixel-split factor of a per-image weight gradient over n pixels: `ksp`, doubled while `more(ksp)` holds and the
+    halves stay whole 32-row k-tiles of at least 512 rows"""
+    while more(ksp) and n % (2 * ksp * 32) == 0 and n // (2 * ksp) >= 512:
+        ksp *= 2
+    return ksp
 
 
-def _run_chunks(ranges, fn, dev):
-    for r in ranges:
-        fn(*r)
+def _split_parts(out, ksp):
+    """what a weight-gradient GEMM split in `ksp` pixel parts writes: `out` (nb, M, N) itself, or (nb*ksp, M, N) partials"""
+    return out if ksp == 1 else torch.empty(out.shape[0] * ksp, *out.shape[1:], device=out.device)
+
+
+def _sum_split(part, out):
+    """out (nb, M, N) = the sum of the pixel-split partials `part` (nb*ksp, M, N); nothing to do when part is out"""
+    if part is not out:
+        torch.sum(part.view(out.shape[0], -1, *out.shape[1:]), dim=1, out=out)
+
+
+def _wgrad_km(A, G, out, n, ksp, defer=False):
+    """out[b] (M, N) = A[b]^T G[b] over the n pixels of image b (A (nb, n, M), G (nb, n, N) row-major Planes) on the K-major
+    GEMM, the pixel range split in `ksp` parts — a pure view, (nb, n, C) -> (nb*ksp, n/ksp, C).  The partial products are
+    summed into `out` here, or with `defer` by the caller's _sum_split of what this returns."""
+    nb, M, N = out.shape
+    part = _split_parts(out, ksp)
+    nk = n // ksp
+    gemm_x3_km(A, G, M, N, nk, M, N, nb * ksp, nk * M, nk * N, part)
+    if defer:
+        return part
+    _sum_split(part, out)
+    return out
+
+
+def _head_wgrad(L, gP, g1P, gwb1, gwb2, n):
+    """the per-image weight gradients of one block: dWb2 = a1^T g, dWb1 = x^T g1.  Each contracts over the n pixels of one
+    image; with few images per GPU a 512x512 output is too few tiles for the chip, so the pixel range is split in parts and
+    the partial products are summed."""
+    nb, cin, cout = gwb1.shape
+    ksp = _pixel_split(n, 1, lambda s: nb * s < 32)
+    if cin == cout:
+        part2, part1 = _split_parts(gwb2, ksp), _split_parts(gwb1, ksp)
+        nk = n // ksp
+        gemm_x3_km_grouped([(L.a1P, gP, part2), (L.xP, g1P, part1)], cout, cout, nk, cout, cout, nb * ksp, nk * cout, nk * cout)
+    else:
+        # the block's square problem alone is half a chip of 256 x 256 tiles: two pixel halves fill it
+        tiles = (cout + 255) // 256
+        ksp2 = _pixel_split(n, ksp, lambda s: nb * s * tiles * tiles < 192)
+        part2 = _wgrad_km(L.a1P, gP, gwb2, n, ksp2, defer=ksp2 == ksp)
+        # a narrow first layer (cin = 32: one row tile, 2 column tiles per image = 64 workgroups) streams the whole gradient
+        # plane through a quarter of the chip: split its pixel range further
+        ksp1 = _pixel_split(n, ksp, lambda s: cin <= 128 and nb * s * tiles < 192)
+        part1 = _wgrad_km(L.xP, g1P, gwb1, n, ksp1, defer=ksp1 == ksp)
+    # partials of the common split `ksp` are summed here, dWb2 first (those of a split of its own right after their GEMM)
+    _sum_split(part2, gwb2)
+    _sum_split(part1, gwb1)
 
 
 class InrHeadX3Function(torch.autograd.Function):
-    """Same contract as InrHeadFunction, on the bf16x3 GEMM.  Every activation / gradient lives in HBM
-    as bf16 hi/lo planes in both orientations (row-major for the forward / dX operand, transposed for
-    the dW operand), written by the producing GEMM's epilogue."""
+    """Same contract as InrHeadFunction, on the bf16x3 GEMM.  Every activation / gradient lives in HBM as row-major bf16
+    hi/lo planes written by the producing GEMM's epilogue: the A operand of the next forward GEMM and of the dX GEMM, read
+    k-major by the weight-gradient GEMMs.
+
+    ports: None, or the TailPorts of inr_head_open_ports — the parameters then come detached and are followed by the ports'
+    handles, which the backward answers with dL/dWb of every layer and drgb (the weight-gradient tail runs in the ports'
+    backward nodes)."""
 
     @staticmethod
-    def forward(ctx, nblocks, x0, *params):
-        ports = None
-        if isinstance(nblocks, tuple) and len(nblocks) == 3:
-            # (nblocks, grad mode, state of the two gradient ports): params carries, after the usual tensors (passed detached),
-            # one handle per modulated layer and the ToRGB handle; their "gradients" are dL/dWb and drgb (see _ModPrepGradPort)
-            nblocks, grad_mode, ports = nblocks
-            params = params[:len(params) - 2 * nblocks - 1]
-        else:
-            nblocks, grad_mode = nblocks if isinstance(nblocks, tuple) else (nblocks, True)
+    def forward(ctx, nblocks, grad_mode, ports, x0, *params):
         x0 = _c(x0.detach())
         B, n, in0 = x0.shape
         if n % 32 or in0 % 32:
             raise RuntimeError("bf16x3 INR path needs pixels per image and feature width to be multiples of 32")
         dev = x0.device
-        blocks = []
-        for k in range(nblocks):
-            blocks.append(tuple(_c(p.detach()) for p in params[4 * k:4 * k + 4]))
-        rgbp = [_c(p.detach()) for p in params[4 * nblocks:]]
+        blocks = [tuple(_c(p.detach()) for p in params[4 * k:4 * k + 4]) for k in range(nblocks)]
+        # (T, tau) of the ToRGB tap of every block k >= 3; what follows them are the ports' handles
+        rgbp = [_c(p.detach()) for p in params[4 * nblocks:4 * nblocks + 2 * max(nblocks - 3, 0)]]
         _chk(x0, *[t for blk in blocks for t in blk], *rgbp)
-        train = grad_mode and any(ctx.needs_input_grad)       # no-grad / inference: no transposed planes, nothing kept
-        want_t = train and not INR_W_KMAJOR     # K-major dW form reads the row-major planes: no transposed copies
-        x0P, x0T = split_planes(x0, want_t=want_t)
+        train = grad_mode and any(ctx.needs_input_grad)       # no-grad / inference: nothing kept
+        x0P, _ = split_planes(x0, want_t=False)
         rgb = torch.empty(B, n, 3, device=dev)
         # modulate / demodulate / split every layer's weights up front, in one batch
         prepped = modfc_prep_x3_batch([(W, s_) for (W1, s1, W2, s2) in blocks for (W, s_) in ((W1, s1), (W2, s2))])
         dbg = GATE_PIN is not None or GATE_REC is not None          # gate instrumentation (tests): bit planes always
-        # every full-batch buffer is allocated here, on the caller's stream, before the chains fork
-        plan = []
+        # every buffer is allocated here, before the first GEMM
+        layers = []
+        xP = x0P
         for k, (W1, s1, W2, s2) in enumerate(blocks):
+            L = _HeadLayer()
             cin, cout = W1.shape
-            bits = (train or dbg) and (INR_GATE_BITS or dbg) and cout % 32 == 0
+            # LeakyReLU gates as bit planes (1 bit per activation, written by the forward GEMMs' epilogues) instead of bf16
+            # planes: 2.5 GB less HBM traffic per C2 step (layer widths that are not multiples of 32 keep the bf16 form)
+            bits = (train or dbg) and cout % 32 == 0
             pin1 = _next_pin(B, n, cout, dev)
             pin2 = _next_pin(B, n, cout, dev)
             if (pin1 is not None or GATE_REC is not None) and not bits:
                 raise RuntimeError("gate instrumentation needs layer widths that are multiples of 32")
-            skip = (k >= 4) and (cin == cout)
-            e = dict(cin=cin, cout=cout, bits=bits, pin1=pin1, pin2=pin2, skip=skip)
-            e["a1P"] = Planes.empty(B, n, cout, device=dev)
-            e["a1T"] = Planes.empty(B, cout, n, device=dev) if want_t else None
-            e["a1g"] = pin1 if pin1 is not None else (torch.empty(B, n, cout // 8, device=dev, dtype=torch.uint8) if bits else None)
-            e["oP"] = Planes.empty(B, n, cout, device=dev)
-            e["oT"] = Planes.empty(B, cout, n, device=dev) if want_t else None
+            L.cin, L.cout, L.bits, L.skip = cin, cout, bits, (k >= 4) and (cin == cout)
+            L.pinned1, L.pinned2 = pin1 is not None, pin2 is not None
+            L.xP = xP
+            L.a1P = Planes.empty(B, n, cout, device=dev)
+            L.gate1 = pin1 if pin1 is not None else (torch.empty(B, n, cout // 8, device=dev, dtype=torch.uint8) if bits else L.a1P.hi)
+            L.oP = Planes.empty(B, n, cout, device=dev)
             if pin2 is not None:
-                e["m2"] = pin2
+                L.gate2 = pin2
             elif bits:
-                e["m2"] = torch.empty(B, n, cout // 8, device=dev, dtype=torch.uint8)
-            elif skip:
-                e["m2"] = torch.empty(B, n, cout, device=dev, dtype=BF) if train else None
+                L.gate2 = torch.empty(B, n, cout // 8, device=dev, dtype=torch.uint8)
+            elif L.skip:
+                L.gate2 = torch.empty(B, n, cout, device=dev, dtype=BF) if train else None
             else:
-                e["m2"] = e["oP"].hi
-            plan.append(e)
-        any_rgb = nblocks > 3
-
-        def run(b0, b1):
-            nb = b1 - b0
-            xP = _bsl(x0P, b0, b1)
-            first_rgb = True
-            for k, e in enumerate(plan):
-                cin, cout, bits, skip = e["cin"], e["cout"], e["bits"], e["skip"]
-                wb1, wbt1, d1 = prepped[2 * k]
-                wb2, wbt2, d2 = prepped[2 * k + 1]
-                wbt1, wbt2 = _bsl(wbt1, b0, b1), _bsl(wbt2, b0, b1)
-                a1P, a1T, a1g = _bsl(e["a1P"], b0, b1), _bsl(e["a1T"], b0, b1), _bsl(e["a1g"], b0, b1)
-                oP, oT, m2 = _bsl(e["oP"], b0, b1), _bsl(e["oT"], b0, b1), _bsl(e["m2"], b0, b1)
-                if e["pin1"] is not None:
-                    # pinned: `gate ? 1 : slope` from the supplied plane in place of the LeakyReLU on the computed sign
-                    gemm_x3(xP, wbt1, n, cout, cin, cin, cin, nb, n * cin, cout * cin, P=a1P, T=a1T, ldt=n, strideT=cout * n,
-                            mask=a1g, gate_bits=1)
-                else:
-                    gemm_x3(xP, wbt1, n, cout, cin, cin, cin, nb, n * cin, cout * cin, P=a1P, T=a1T, ldt=n, strideT=cout * n,
-                            act=1, mask_out=a1g, gate_bits=2 if bits else 0)
-                if e["pin2"] is not None:
-                    gemm_x3(a1P, wbt2, n, cout, cout, cout, cout, nb, n * cout, cout * cout, P=oP, T=oT, ldt=n,
-                            strideT=cout * n, res=xP if skip else None, mask=m2, gate_bits=1)
-                elif bits and k >= 3 and oT is None:
-                    gemm_x3_torgb(a1P, wbt2, n, cout, cout, cout, cout, nb, n * cout, cout * cout, oP, rgbp[2 * (k - 3)],
-                                  rgbp[2 * (k - 3) + 1], rgb[b0:b1].view(nb * n, 3), not first_rgb,
-                                  act=1, res=xP if skip else None, mask_out=m2, gate_bits=2)
-                    first_rgb = False
-                    xP = oP
-                    continue
-                elif bits:
-                    gemm_x3(a1P, wbt2, n, cout, cout, cout, cout, nb, n * cout, cout * cout, P=oP, T=oT, ldt=n,
-                            strideT=cout * n, act=1, res=xP if skip else None, mask_out=m2, gate_bits=2)
-                elif skip:
-                    gemm_x3(a1P, wbt2, n, cout, cout, cout, cout, nb, n * cout, cout * cout, P=oP, T=oT, ldt=n,
-                            strideT=cout * n, act=1, res=xP, mask_out=m2)
-                else:
-                    gemm_x3(a1P, wbt2, n, cout, cout, cout, cout, nb, n * cout, cout * cout, P=oP, T=oT, ldt=n,
-                            strideT=cout * n, act=1)
-                if k >= 3:
-                    torgb_fwd_x3(oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb[b0:b1].view(nb * n, 3), accumulate=not first_rgb)
-                    first_rgb = False
-                xP = oP
-
-        _run_chunks(_chunk_ranges(B), run, dev)
-        saved = []
-        xP, xT = x0P, x0T
-        for k, e in enumerate(plan):
-            if GATE_REC is not None:
-                GATE_REC.append(e["a1g"])
-                GATE_REC.append(e["m2"])
-            if train:
-                # keep for backward: xT (dW1), a1 gate + a1T (dW2), out planes (ToRGB grad), m2 gate, weights
-                wb1, _, d1 = prepped[2 * k]
-                wb2, _, d2 = prepped[2 * k + 1]
-                saved.append(dict(xT=xT, xP=xP, a1P=e["a1P"], a1m=e["a1g"] if e["bits"] else e["a1P"].hi, a1T=e["a1T"], oP=e["oP"],
-                                  m2=e["m2"], wb1=wb1, d1=d1, wb2=wb2, d2=d2, skip=e["skip"], bits=e["bits"]))
-            xP, xT = e["oP"], e["oT"]
-        if not any_rgb:
+                L.gate2 = L.oP.hi
+            L.wb1, _, L.d1 = prepped[2 * k]
+            L.wb2, _, L.d2 = prepped[2 * k + 1]
+            layers.append(L)
+            xP = L.oP
+        first_rgb = True
+        for k, L in enumerate(layers):
+            cin, cout = L.cin, L.cout
+            wbt1, wbt2 = prepped[2 * k][1], prepped[2 * k + 1][1]
+            res = L.xP if L.skip else None
+            if L.pinned1:
+                # pinned: `gate ? 1 : slope` from the supplied plane in place of the LeakyReLU on the computed sign
+                gemm_x3(L.xP, wbt1, n, cout, cin, cin, cin, B, n * cin, cout * cin, P=L.a1P, mask=L.gate1, gate_bits=1)
+            else:
+                gemm_x3(L.xP, wbt1, n, cout, cin, cin, cin, B, n * cin, cout * cin, P=L.a1P, act=1,
+                        mask_out=L.gate1 if L.bits else None, gate_bits=2 if L.bits else 0)
+            mod2 = (L.a1P, wbt2, n, cout, cout, cout, cout, B, n * cout, cout * cout)
+            if L.pinned2:
+                gemm_x3(*mod2, P=L.oP, res=res, mask=L.gate2, gate_bits=1)
+            elif L.bits and k >= 3:
+                gemm_x3_torgb(*mod2, L.oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb.view(B * n, 3), not first_rgb,
+                              act=1, res=res, mask_out=L.gate2, gate_bits=2)
+                first_rgb = False
+                continue
+            elif L.bits:
+                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2, gate_bits=2)
+            elif L.skip:
+                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2)
+            else:
+                gemm_x3(*mod2, P=L.oP, act=1)
+            if k >= 3:
+                torgb_fwd_x3(L.oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb.view(B * n, 3), accumulate=not first_rgb)
+                first_rgb = False
+        if GATE_REC is not None:
+            for L in layers:
+                GATE_REC.append(L.gate1)
+                GATE_REC.append(L.gate2)
+        if nblocks <= 3:
             rgb.zero_()
-        ctx.nblocks, ctx.blocks, ctx.rgbp, ctx.saved = nblocks, blocks, rgbp, saved
+        # kept for backward: every layer's input / a1 / output planes, both gates and the prepped weights
+        ctx.layers, ctx.blocks, ctx.rgbp = (layers if train else []), blocks, rgbp
         ctx.dims = (B, n)
-        ctx.kmajor = INR_W_KMAJOR
         ctx.ports = ports if train else None
-        if ports is not None and train:
-            ports["demod"] = [d for k in range(nblocks) for d in (saved[k]["d1"], saved[k]["d2"])]
-            ports["taps"] = [saved[k]["oP"] for k in range(3, nblocks)]
+        if ctx.ports is not None:
+            ports.demod = [d for L in layers for d in (L.d1, L.d2)]
+            ports.taps = [L.oP for L in layers[3:]]
         return rgb
 
     @staticmethod
     def backward(ctx, drgb):
-        nblocks, blocks, rgbp, saved = ctx.nblocks, ctx.blocks, ctx.rgbp, ctx.saved
+        layers, blocks, rgbp, ports = ctx.layers, ctx.blocks, ctx.rgbp, ctx.ports
+        nblocks = len(layers)
         B, n = ctx.dims
         drgb = _c(drgb)
         dev = drgb.device
-        width = blocks[-1][2].shape[1]
-        km = ctx.kmajor
-        # full-batch outputs of the chains: per-image dL/dWb of every layer, dx0, and the ToRGB weight-gradient partials
-        gwb = []
-        for k in range(nblocks):
-            cin, cout = blocks[k][0].shape
-            gwb.append((torch.empty(B, cin, cout, device=dev), torch.empty(B, cout, cout, device=dev)))       # (gwb1, gwb2)
-        cin0 = blocks[0][0].shape[0]
-        dx0 = torch.empty(B, n, cin0, device=dev)
-        ranges = _chunk_ranges(B)
-        rgb_parts = [[None] * len(ranges) for _ in range(nblocks)]
-        def run(b0, b1):
-            nb = b1 - b0
-            ci = [r[0] for r in ranges].index(b0)
-            drgb_c = drgb[b0:b1]
-            drgb2 = drgb_c.reshape(nb * n, 3)
-            PT = (lambda c: None) if km else (lambda c: Planes.empty(nb, c, n, device=dev))
-            k = nblocks - 1
-            gP, gT = Planes.empty(nb, n, width, device=dev), PT(width)
-            Dout = None
-            # the skip gradient D (un-gated) is either kept as an fp32 copy next to the gated planes every GEMM writes
-            # for its successors, or — when every layer has bit-plane gates and the 256x256-tile kernel takes the shapes —
-            # recovered from those planes by the consumer (INR_ADDP): no copy written, same bytes read
-            addp = km and all(saved[j]["bits"] for j in range(nblocks))
-            if addp:
-                for j in range(1, nblocks):
-                    if saved[j]["skip"]:
-                        cj_in, cj_out = blocks[j][0].shape
-                        addp = addp and _addp_shape_ok(n, cj_in, cj_out, nb, dev)
-            if k >= 3 and km and saved[k]["bits"] and width % 8 == 0:
-                # grad wrt out_k = drgb @ T_k (rank 3), gate of a2_k fused: one streaming kernel writing the planes
-                Dout = torch.empty(nb, n, width, device=dev) if saved[k]["skip"] and not addp else None
-                torgb_bwd_x_x3(drgb2, rgbp[2 * (k - 3)], _bsl(saved[k]["m2"], b0, b1), Dout, gP)
-            elif k >= 3:
-                # ... as a K=32 zero-padded bf16x3 GEMM where the transposed planes are wanted too
-                tpad = torch.zeros(1, width, 32, device=dev); tpad[0, :, :3] = rgbp[2 * (k - 3)].t()
-                tP, _ = split_planes(tpad, want_t=False)
-                dpad = torch.zeros(nb, n, 32, device=dev); dpad[..., :3] = drgb_c
-                dP, _ = split_planes(dpad, want_t=False)
-                Dout = torch.empty(nb, n, width, device=dev) if saved[k]["skip"] and not addp else None
-                gemm_x3(dP, tP, n, width, 32, 32, 32, nb, n * 32, 0, P=gP, T=gT, ldt=n, strideT=width * n,
-                        C_unmasked=Dout, mask=_bsl(saved[k]["m2"], b0, b1), gate_bits=1 if saved[k]["bits"] else 0)
+        drgb2 = drgb.reshape(B * n, 3)
+        width = layers[-1].cout
+        # per-image dL/dWb of every layer (gwb1, gwb2) and dx0
+        gwb = [(torch.empty(B, L.cin, L.cout, device=dev), torch.empty(B, L.cout, L.cout, device=dev)) for L in layers]
+        dx0 = torch.empty(B, n, layers[0].cin, device=dev)
+        gP = Planes.empty(B, n, width, device=dev)
+        # the skip gradient D (un-gated) is either kept as an fp32 copy next to the gated planes every GEMM writes
+        # for its successors, or — when every layer has bit-plane gates and the 256x256-tile kernel takes the shapes —
+        # recovered from those planes by the consumer: no copy written, same bytes read
+        addp = all(L.bits for L in layers) and all(_addp_shape_ok(n, L.cin, L.cout, B, dev) for L in layers[1:] if L.skip)
+        k, L = nblocks - 1, layers[-1]
+        Dout = None
+        if k >= 3 and L.bits and width % 8 == 0:
+            # grad wrt out_k = drgb @ T_k (rank 3), gate of a2_k fused: one streaming kernel writing the planes
+            Dout = torch.empty(B, n, width, device=dev) if L.skip and not addp else None
+            torgb_bwd_x_x3(drgb2, rgbp[2 * (k - 3)], L.gate2, Dout, gP)
+        elif k >= 3:
+            # ... else as a K=32 zero-padded bf16x3 GEMM
+            tpad = torch.zeros(1, width, 32, device=dev); tpad[0, :, :3] = rgbp[2 * (k - 3)].t()
+            tP, _ = split_planes(tpad, want_t=False)
+            dpad = torch.zeros(B, n, 32, device=dev); dpad[..., :3] = drgb
+            dP, _ = split_planes(dpad, want_t=False)
+            Dout = torch.empty(B, n, width, device=dev) if L.skip and not addp else None
+            gemm_x3(dP, tP, n, width, 32, 32, 32, B, n * 32, 0, P=gP, C_unmasked=Dout, mask=L.gate2,
+                    gate_bits=1 if L.bits else 0)
+        else:
+            gP.hi.zero_(); gP.lo.zero_()
+            Dout = torch.zeros(B, n, width, device=dev) if L.skip and not addp else None
+        # ToRGB weight / bias gradients of all taps: they need only the saved block outputs and drgb
+        grads_rgb = []
+        if ports is None and nblocks > 3:
+            for dT, dtau in torgb_bwd_w_x3_batch([L.oP for L in layers[3:]], drgb2):
+                grads_rgb += [dT, dtau]
+        for k in range(nblocks - 1, -1, -1):
+            L = layers[k]
+            cin, cout = L.cin, L.cout
+            gP_in = gP              # D_{k+1} gated by a2_k's gate: the planes form of the skip gradient
+            # ---- mod2: gradient through the gate of a1 ----
+            g1P = Planes.empty(B, n, cout, device=dev)
+            gemm_x3(gP, L.wb2, n, cout, cout, cout, cout, B, n * cout, cout * cout, P=g1P, mask=L.gate1,
+                    gate_bits=1 if L.bits else 0)
+            _head_wgrad(L, gP, g1P, *gwb[k], n)
+            if k == 0:
+                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, C=dx0)
             else:
-                gP.hi.zero_(); gP.lo.zero_()
-                if gT is not None:
-                    gT.hi.zero_(); gT.lo.zero_()
-                Dout = torch.zeros(nb, n, width, device=dev) if saved[k]["skip"] and not addp else None
-            # ToRGB weight / bias gradients of all taps: they need only the saved block outputs and drgb
-            taps = list(range(3, nblocks)) if ctx.ports is None else []
-            if taps:
-                for k_, res_ in zip(taps, torgb_bwd_w_x3_batch([_bsl(saved[k_]["oP"], b0, b1) for k_ in taps], drgb2)):
-                    rgb_parts[k_][ci] = res_
-            for k in range(nblocks - 1, -1, -1):
-                sv = saved[k]
-                W1, s1, W2, s2 = blocks[k]
-                cin, cout = W1.shape
-                gP_in = gP              # D_{k+1} gated by a2_k's gate: the planes form of the skip gradient
-                # ---- mod2: gradient through the gate of a1 ----
-                g1P, g1T = Planes.empty(nb, n, cout, device=dev), PT(cout)
-                gemm_x3(gP, _bsl(sv["wb2"], b0, b1), n, cout, cout, cout, cout, nb, n * cout, cout * cout, P=g1P, T=g1T, ldt=n,
-                        strideT=cout * n, mask=_bsl(sv["a1m"], b0, b1), gate_bits=1 if sv["bits"] else 0)
-                # ---- weight gradients of both layers: dWb2 = a1^T g, dWb1 = x^T g1 ----
-                gwb1, gwb2 = gwb[k][0][b0:b1], gwb[k][1][b0:b1]
-                a1P, xP = _bsl(sv["a1P"], b0, b1), _bsl(sv["xP"], b0, b1)
-                if km:
-                    # dWb[b] = X[b]^T G[b] contracts over the n pixels of image b.  With few images per GPU a 512x512
-                    # output is too few tiles for the chip, so the pixel range is split in `ksp` parts — a pure view of
-                    # the row-major planes, (B, n, C) -> (B*ksp, n/ksp, C) — and the partial products are summed.
-                    ksp = 1
-                    while nb * ksp < 32 and n % (2 * ksp * 32) == 0 and n // (2 * ksp) >= 512:
-                        ksp *= 2
-                    nk_ = n // ksp
-                    part2 = gwb2 if ksp == 1 else torch.empty(nb * ksp, cout, cout, device=dev)
-                    part1 = gwb1 if ksp == 1 else torch.empty(nb * ksp, cin, cout, device=dev)
-                    if cin == cout:
-                        gemm_x3_km_grouped([(a1P, gP, part2), (xP, g1P, part1)], cout, cout, nk_, cout, cout,
-                                           nb * ksp, nk_ * cout, nk_ * cout)
-                    else:
-                        # the block's square problem alone is half a chip of 256 x 256 tiles: two pixel halves fill it
-                        ksp2 = ksp
-                        while nb * ksp2 * ((cout + 255) // 256) ** 2 < 192 and n % (2 * ksp2 * 32) == 0 and n // (2 * ksp2) >= 512:
-                            ksp2 *= 2
-                        if ksp2 != ksp:
-                            part2 = torch.empty(nb * ksp2, cout, cout, device=dev)
-                        nk2 = n // ksp2
-                        gemm_x3_km(a1P, gP, cout, cout, nk2, cout, cout, nb * ksp2, nk2 * cout, nk2 * cout, part2)
-                        if ksp2 != ksp:
-                            torch.sum(part2.view(nb, ksp2, cout, cout), dim=1, out=gwb2)
-                            part2 = gwb2
-                        # a narrow first layer (cin = 32: one row tile, 2 column tiles per image = 64 workgroups) streams
-                        # the whole gradient plane through a quarter of the chip: split its pixel range further
-                        ksp1 = ksp
-                        while cin <= 128 and nb * ksp1 * ((cout + 255) // 256) < 192 and n % (2 * ksp1 * 32) == 0 and n // (2 * ksp1) >= 512:
-                            ksp1 *= 2
-                        if ksp1 != ksp:
-                            part1 = torch.empty(nb * ksp1, cin, cout, device=dev)
-                        nk1 = n // ksp1
-                        gemm_x3_km(xP, g1P, cin, cout, nk1, cin, cout, nb * ksp1, nk1 * cin, nk1 * cout, part1)
-                        if ksp1 != ksp:
-                            torch.sum(part1.view(nb, ksp1, cin, cout), dim=1, out=gwb1)
-                            part1 = gwb1
-                    if ksp > 1:
-                        if part2 is not gwb2:
-                            torch.sum(part2.view(nb, ksp, cout, cout), dim=1, out=gwb2)
-                        if part1 is not gwb1:
-                            torch.sum(part1.view(nb, ksp, cin, cout), dim=1, out=gwb1)
-                else:
-                    gemm_x3(_bsl(sv["a1T"], b0, b1), gT, cout, cout, n, n, n, nb, cout * n, cout * n, C=gwb2)
-                    gemm_x3(_bsl(sv["xT"], b0, b1), g1T, cin, cout, n, n, n, nb, cin * n, cout * n, C=gwb1)
-                if k == 0:
-                    gemm_x3(g1P, _bsl(sv["wb1"], b0, b1), n, cin, cout, cout, cout, nb, n * cout, cin * cout, C=dx0[b0:b1])
-                else:
-                    pv = saved[k - 1]
-                    newD = torch.empty(nb, n, cin, device=dev) if pv["skip"] and not addp else None
-                    gP, gT = Planes.empty(nb, n, cin, device=dev), PT(cin)
-                    gemm_x3(g1P, _bsl(sv["wb1"], b0, b1), n, cin, cout, cout, cout, nb, n * cout, cin * cout, P=gP, T=gT, ldt=n,
-                            strideT=cin * n, add=Dout if sv["skip"] and not addp else None,
-                            addp=(gP_in, _bsl(sv["m2"], b0, b1)) if sv["skip"] and addp else None,
-                            rgb_g=drgb2 if k - 1 >= 3 else None, rgb_w=rgbp[2 * (k - 1 - 3)] if k - 1 >= 3 else None,
-                            C_unmasked=newD, mask=_bsl(pv["m2"], b0, b1), gate_bits=1 if pv["bits"] else 0)
-                    Dout = newD
-
-        _run_chunks(ranges, run, dev)
-        if ctx.ports is not None:
-            _tail_gate_clear(dev)
+                prev = layers[k - 1]
+                newD = torch.empty(B, n, cin, device=dev) if prev.skip and not addp else None
+                gP = Planes.empty(B, n, cin, device=dev)
+                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, P=gP,
+                        add=Dout if L.skip and not addp else None, addp=(gP_in, L.gate2) if L.skip and addp else None,
+                        rgb_g=drgb2 if k - 1 >= 3 else None, rgb_w=rgbp[2 * (k - 1 - 3)] if k - 1 >= 3 else None,
+                        C_unmasked=newD, mask=prev.gate2, gate_bits=1 if prev.bits else 0)
+                Dout = newD
+        if ports is not None:
+            _TAIL_GATE[dev.index] = ports        # armed: the next compositing backward publishes its event to the ports
             # the tail runs in the ports' backward nodes (side stream): hand them dL/dWb of every layer and drgb
-            return (None, dx0) + (None,) * (4 * nblocks + len(rgbp)) + tuple(g for k in range(nblocks) for g in gwb[k]) + (drgb,)
-        grads_blocks = [None] * nblocks
-        grads_rgb = [None] * len(rgbp)
-        for k in range(3, nblocks):
-            parts = rgb_parts[k]
-            dT, dtau = parts[0]
-            for q in parts[1:]:
-                dT = dT + q[0]; dtau = dtau + q[1]
-            grads_rgb[2 * (k - 3)], grads_rgb[2 * (k - 3) + 1] = dT, dtau
+            return (None, None, None, dx0) + (None,) * (4 * nblocks + len(rgbp)) + tuple(g for pair in gwb for g in pair) + (drgb,)
         pending = []      # (W, s, demod, dL/dWb) of every layer: their prep backward runs as one batch
         for k in range(nblocks - 1, -1, -1):
-            sv = saved[k]
             W1, s1, W2, s2 = blocks[k]
-            pending.append((W2, s2, sv["d2"], gwb[k][1]))
-            pending.append((W1, s1, sv["d1"], gwb[k][0]))
+            pending.append((W2, s2, layers[k].d2, gwb[k][1]))
+            pending.append((W1, s1, layers[k].d1, gwb[k][0]))
         res = modfc_prep_bwd_batch(pending)          # pending order: block nblocks-1 (mod2, mod1), ..., block 0
+        grads_blocks = [None] * nblocks
         for i, k in enumerate(range(nblocks - 1, -1, -1)):
             (dW2, ds2), (dW1, ds1) = res[2 * i], res[2 * i + 1]
             grads_blocks[k] = (dW1, ds1, dW2, ds2)
-        flat = [None, dx0]
-        for gb in grads_blocks:
-            flat.extend(gb)
-        flat.extend(grads_rgb)
-        return tuple(flat)
+        return (None, None, None, dx0) + tuple(g for gb in grads_blocks for g in gb) + tuple(grads_rgb)
+
+
+class TailPorts:
+    """The gradient ports of one head evaluation (see INR_TAIL), from inr_head_open_ports.  `handles`: their outputs, the
+    trailing inputs of InrHeadX3Function — one per modulated layer, then the ToRGB one.  The head's forward fills in `demod`
+    and `taps`; `gate` is the event of the compositing backward (see _TAIL_GATE), and `waited` records that the ports'
+    backward waited for one.  The ports' nodes hold it by weak reference — it holds their outputs, and a strong reference
+    back would close a cycle through the autograd graph that Python's collector cannot free; the head's node keeps it
+    alive until they have run."""
+    __slots__ = ("handles", "demod", "taps", "gate", "waited", "__weakref__")
+
+    def __init__(self):
+        self.handles, self.demod, self.taps, self.gate, self.waited = (), None, None, None, False
+
+    def wait(self, dev):
+        """in a port's backward, on its stream: disarm the gate, then wait for the event published while it was armed"""
+        if _TAIL_GATE.get(dev.index) is self:
+            del _TAIL_GATE[dev.index]
+        if self.gate is not None:
+            torch.cuda.current_stream(dev).wait_event(self.gate)
+            self.waited = True
 
 
 class _ModPrepGradPort(torch.autograd.Function):
@@ -1740,37 +1697,37 @@ class _ModPrepGradPort(torch.autograd.Function):
     stream that is current when apply() is called: CIPSNet.forward calls it under the generator's side stream."""
 
     @staticmethod
-    def forward(ctx, state, B, *ws):
-        ctx.state = state
+    def forward(ctx, ports, B, *ws):
+        ctx.ports = weakref.ref(ports)
         ctx.ws = tuple(_c(t.detach()) for t in ws)
         z = _zero_handle(ws[0].device)
         return tuple(z.expand(B, ws[2 * i].shape[0], ws[2 * i].shape[1]) for i in range(len(ws) // 2))
 
     @staticmethod
     def backward(ctx, *gwb):
-        _tail_gate_wait(gwb[0].device)
-        demod = ctx.state["demod"]
-        layers = [(ctx.ws[2 * i], ctx.ws[2 * i + 1], demod[i], _c(gwb[i])) for i in range(len(gwb))]
+        ports = ctx.ports()
+        ports.wait(gwb[0].device)
+        layers = [(ctx.ws[2 * i], ctx.ws[2 * i + 1], ports.demod[i], _c(gwb[i])) for i in range(len(gwb))]
         res = modfc_prep_bwd_batch(layers, cores=True)
         return (None, None) + tuple(t for pair in res for t in pair)
 
 
 class _ToRGBGradPort(torch.autograd.Function):
     """Gradient port of the ToRGB taps: forward returns a stride-0 zero shaped like the head's output (its gradient IS drgb),
-    backward computes every tap's weight / bias gradient from the block outputs the head kept (state["taps"])."""
+    backward computes every tap's weight / bias gradient from the block outputs the head kept (TailPorts.taps)."""
 
     @staticmethod
-    def forward(ctx, state, shape, *rgbp):
-        ctx.state, ctx.n = state, len(rgbp)
+    def forward(ctx, ports, shape, *rgbp):
+        ctx.ports = weakref.ref(ports)
         return _zero_handle(rgbp[0].device).expand(shape)
 
     @staticmethod
     def backward(ctx, drgb):
-        _tail_gate_wait(drgb.device)
-        taps = ctx.state["taps"]
+        ports = ctx.ports()
+        ports.wait(drgb.device)
         drgb2 = _c(drgb).reshape(-1, 3)
         out = []
-        for dT, dtau in torgb_bwd_w_x3_batch(taps, drgb2, cores=True):
+        for dT, dtau in torgb_bwd_w_x3_batch(ports.taps, drgb2, cores=True):
             out += [dT, dtau]
         return (None, None) + tuple(out)
 
@@ -1790,28 +1747,19 @@ def _zero_handle(dev):
 
 
 # The ports' tail must not start while the compositing backward (HBM-bound, on the critical path) is running: it would share the
-# bandwidth and delay it by as much as the tail gains.  The NeRF path's backward publishes an event right after that launch; the
-# ports' backward nodes — which the engine runs AFTER it when the ports were opened before the ray march in the forward pass
-# (lower sequence numbers; GeneratorNerfINR._render does that) — make their stream wait for it.  No event (frozen NeRF, ports
-# opened late): the tail starts as soon as the head's backward is done.
-_TAIL_GATE = {}
-
-
-def _tail_gate_clear(dev):
-    _TAIL_GATE.pop(torch.device(dev).index, None)
+# bandwidth and delay it by as much as the tail gains.  The head's backward arms the gate of its device with its TailPorts; a
+# compositing backward that runs while a gate is armed records an event right after its launch into them (the last one wins).
+# The ports' backward nodes — which the engine runs AFTER it when the ports were opened before the ray march in the forward pass
+# (lower sequence numbers; GeneratorNerfINR._render does that) — disarm the gate and make their stream wait for that event.  No
+# event (no compositing backward, ports opened late): the tail starts as soon as the head's backward is done.
+_TAIL_GATE = {}        # device index -> the armed TailPorts
 
 
 def _tail_gate_publish(dev):
-    if INR_TAIL == "side" and torch.device(dev).type == "cuda":
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        _TAIL_GATE[torch.device(dev).index] = ev
-
-
-def _tail_gate_wait(dev):
-    ev = _TAIL_GATE.get(torch.device(dev).index)
-    if ev is not None:
-        torch.cuda.current_stream(dev).wait_event(ev)
+    ports = _TAIL_GATE.get(dev.index)
+    if ports is not None:
+        ports.gate = torch.cuda.Event()
+        ports.gate.record(torch.cuda.current_stream(dev))
 
 
 def inr_head_ports_ok(nblocks, B, n, in0, params, dev):
@@ -1821,22 +1769,21 @@ def inr_head_ports_ok(nblocks, B, n, in0, params, dev):
 
 
 def inr_head_open_ports(nblocks, B, n, params, side):
-    """the two gradient ports of one head evaluation (see INR_TAIL), their autograd nodes on `side` -> (state, handles, H)"""
-    state = {}
+    """the two gradient ports of one head evaluation (see INR_TAIL), their autograd nodes on `side` -> TailPorts"""
+    ports = TailPorts()
     ws, rgbp = params[:4 * nblocks], params[4 * nblocks:]
     dev = params[0].device
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
-        handles = _ModPrepGradPort.apply(state, B, *ws)
-        H = _ToRGBGradPort.apply(state, (B, n, 3), *rgbp)
-    return state, handles, H
+        handles = _ModPrepGradPort.apply(ports, B, *ws)
+        ports.handles = handles + (_ToRGBGradPort.apply(ports, (B, n, 3), *rgbp),)
+    return ports
 
 
 def inr_head_with_ports(nblocks, x0, params, ports):
     """inr_head with the weight-gradient tail behind the gradient ports `ports` = inr_head_open_ports(...)"""
-    state, handles, H = ports
     det = [t.detach() for t in params]
-    return InrHeadX3Function.apply((nblocks, True, state), x0, *det, *handles, H)
+    return InrHeadX3Function.apply(nblocks, True, ports, x0, *det, *ports.handles)
 
 
 def inr_head(nblocks, x0, *params):
@@ -1844,8 +1791,8 @@ def inr_head(nblocks, x0, *params):
     # grad_points, generator.py:1591-1593) runs on the exact fp32 MFMA path, which has no such granule
     x3 = INR_MODE == "bf16x3" and x0.shape[1] % 32 == 0 and x0.shape[2] % 32 == 0
     fn = InrHeadX3Function if x3 else InrHeadFunction
-    # (nblocks, caller's grad mode): under torch.no_grad() nothing is kept for a backward
-    return fn.apply((nblocks, torch.is_grad_enabled()), x0, *params)
+    # the caller's grad mode: under torch.no_grad() nothing is kept for a backward
+    return fn.apply(nblocks, torch.is_grad_enabled(), None, x0, *params)
 
 
 # --------------------------------------------------------------------------------------

@@ -478,7 +478,8 @@ def test_weight_gradient_tail_on_the_side_stream_gives_the_same_gradients(tag):
     """ops.INR_TAIL: the head's weight-gradient tail behind two gradient ports on the side stream (opened before the ray march,
     gated behind the compositing backward, co-resident kernel forms) against everything inside InrHeadX3Function on the caller's
     stream: the same images bit for bit, every parameter gradient present in both and equal up to the tail kernels' summation
-    order; the ported form is the one that ran (except with a frozen NeRF, where nothing follows the head's backward)."""
+    order; the ported form is the one that ran (except with a frozen NeRF, where nothing follows the head's backward), its
+    ports waited for the event the compositing backward published, and no tail gate is left armed in either form."""
     from cips3d_amd import ops
     if ops.INR_MODE != "bf16x3":
         pytest.skip("the ports belong to the split-bf16 head")
@@ -489,7 +490,7 @@ def test_weight_gradient_tail_on_the_side_stream_gives_the_same_gradients(tag):
     rand = {k: v.to(d) for k, v in fix["rand"].items()}
     calls = []
     orig = ops.inr_head_with_ports
-    ops.inr_head_with_ports = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+    ops.inr_head_with_ports = lambda *a, **k: (calls.append(a[3]), orig(*a, **k))[1]      # a[3]: the TailPorts
     out = {}
     keep = ops.INR_TAIL
     try:
@@ -504,6 +505,9 @@ def test_weight_gradient_tail_on_the_side_stream_gives_the_same_gradients(tag):
             torch.cuda.synchronize()
             # (a frozen NeRF has no backward to run beside: the generator keeps the plain form there)
             assert (len(calls) - n0 == 1) == (mode == "side" and not fix["freeze"])
+            # opened by _render before the ray march, the ports ran behind the compositing backward and waited for its event
+            assert all(ports.waited for ports in calls[n0:])
+            assert not ops._TAIL_GATE
             out.setdefault(mode, []).append((imgs.detach().clone(), {n: p.grad.clone() for n, p in G.named_parameters() if p.grad is not None}))
     finally:
         ops.INR_TAIL = keep
