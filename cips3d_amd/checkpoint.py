@@ -10,7 +10,8 @@ strict=False, rank=rank)` (:262, :272); gen_images.py:102 and eval_fid.py load o
 the reference; the layout it produces — one `torch.save`d `state_dict()` per entry, `<save_dir>/<name>.pth`, plain dicts
 saved as they are — is what the released checkpoints (`G_ema.pth`, README.md:96-100) look like and what these functions
 read and write, so a checkpoint directory written by the reference loads into the MI355X classes and vice versa (the
-172 / 160 state_dict keys and shapes are identical, tests/test_compat_cpu.py)."""
+172 / 160 state_dict keys and shapes are identical, tests/test_compat_cpu.py; the generator_v1 models' 174,
+tests/test_generator_v1_cpu.py)."""
 import os
 
 import torch

@@ -582,7 +582,7 @@ class GeneratorNerfINR(nn.Module):
             side = _side_stream(z_inr.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                inr = self.mapping_network_inr(z_inr)
+                inr = self._map_inr(z_inr)
             z_inr.record_stream(side)
             style_dict.update(self.mapping_network_nerf(z_nerf))
             for t in inr.values():
@@ -593,8 +593,12 @@ class GeneratorNerfINR(nn.Module):
                 self._join_side()
             return style_dict
         style_dict.update(self.mapping_network_nerf(z_nerf))
-        style_dict.update(self.mapping_network_inr(z_inr))
+        style_dict.update(self._map_inr(z_inr))
         return style_dict
+
+    def _map_inr(self, z_inr):
+        """z_inr -> the INR-side styles: the chain mapping_network() runs on the side stream"""
+        return self.mapping_network_inr(z_inr)
 
     def _join_side(self):
         """the caller's stream waits for the INR mapping MLP (no-op when nothing is pending)"""
@@ -929,7 +933,7 @@ class GeneratorNerfINR_freeze_NeRF(GeneratorNerfINR):
             side = _side_stream(z_inr.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                inr = self.mapping_network_inr(z_inr)
+                inr = self._map_inr(z_inr)
             z_inr.record_stream(side)
             with torch.no_grad():
                 style_dict.update(self.mapping_network_nerf(z_nerf))
@@ -942,7 +946,7 @@ class GeneratorNerfINR_freeze_NeRF(GeneratorNerfINR):
             return style_dict
         with torch.no_grad():
             style_dict.update(self.mapping_network_nerf(z_nerf))
-        style_dict.update(self.mapping_network_inr(z_inr))
+        style_dict.update(self._map_inr(z_inr))
         return style_dict
 
     def _render(self, *args, **kwargs):
