@@ -632,3 +632,115 @@ def test_gated_gradient_as_planes_only(cfg, monkeypatch):
         dm._dense(ph)
     with pytest.raises(RuntimeError):
         dm._conv_bwd_data(ph, torch.randn(O, 3, 1, 1, device=d), (B, 3, 16, 16), 1, 0)
+
+
+def _shipped_conv_cases():
+    """(C, O, k, stride, pad, H_in) of every EqualConv2d the two shipped discriminators run on planes of 4 .. 33 pixels a
+    side (the ResBlocks of resolutions 32, 16 and 8 and the final 4 x 4 convolution), read from the built module: 3 x 3
+    stride 1 pad 1, 3 x 3 stride 2 pad 0 behind the Blur (its input is the blurred plane), the 1 x 1 stride 2 skip."""
+    from cips3d_amd.discriminator import Discriminator_MultiScale_Aux
+    D = Discriminator_MultiScale_Aux(**D_CFG)
+    seen = {}
+
+    def layer(l, h, name):
+        blur, conv = getattr(l, "down_blur", None), l.equal_conv
+        hin = h if blur is None else h + blur.pad[0] + blur.pad[1] - 3
+        O, C, k, _ = conv.weight.shape
+        seen.setdefault((C, O, k, conv.stride, conv.padding, hin), name)
+        return (hin + 2 * conv.padding - k) // conv.stride + 1
+
+    for tag, net in (("main", D.main_disc), ("aux", D.aux_disc)):
+        for r in (32, 16, 8):
+            blk = net.convs[str(r)]
+            h = layer(blk.conv2, layer(blk.conv1, r, f"{tag}.convs.{r}.conv1"), f"{tag}.convs.{r}.conv2")
+            assert h == r // 2 and layer(blk.skip, r, f"{tag}.convs.{r}.skip") == r // 2
+        assert layer(net.final_conv, 4, f"{tag}.final_conv") == 4
+    assert {(c[0], c[1]) for c in seen} == {(256, 256), (512, 512)} and {c[2:5] for c in seen} == {(3, 1, 1), (3, 2, 0), (1, 2, 0)}
+    assert {c[5] for c in seen if c[3] == 1} == {4, 8, 16, 32}
+    return [pytest.param(c + (B,), id=f"{name}-{c[5]}x{c[5]}-B{B}") for c, name in seen.items() for B in (1, 4, 8)]
+
+
+@pytest.mark.parametrize("cfg", _shipped_conv_cases())
+def test_conv_ops_at_the_shipped_channel_table_and_training_batches(cfg):
+    """The convolution ops at the shapes the shipped discriminators contain (256 and 512 channels, planes 4 .. 33) and the
+    per-GPU batches of training, B = 1, 4 and 8, against torch in fp64 on the CPU.  The launcher's fold of the batch into the
+    pixel dimension, its contraction split, the weight gradient's chunk count and the parity data gradient's fold all follow
+    B; at O = 512 the folded problem has two row tiles and (B * N = 128, 512) a ragged or several column tiles — every other
+    folded test shape has O <= 96.
+      forward:          dm.conv2d; ops.conv2d_x3 with bias + LeakyReLU in the epilogue at the launcher's ksplit (the
+                        activation then runs in sum_chunks when it splits) and at ksplit = 1 (in the GEMM epilogue);
+      data gradient:    dm.conv2d's autograd; stride 1 the flipped-weight convolution, stride 2 conv2d_x3_dgrad_s2;
+      weight gradient:  dm.conv2d's autograd; conv2d_x3_wgrad with its own chunk count, dm._conv_bwd_weight where that is None;
+      B = 8 as one launch against eight B = 1 launches on the same planes: fp32 summation order (2e-6).
+    Bars: 3e-5 rel_err, the split-bf16 class (test_implicit_conv_split_contraction, test_conv_weight_gradient_ragged_chunks).
+    Activated outputs whose fp64 pre-activation is within the kernel's rounding of 0 (|pre| < 3e-5 x rms) are left out and
+    counted; at most 1e-3 of the outputs may be (Gaussian inputs: 2.4e-5 expected)."""
+    import math
+    from cips3d_amd import ops, _lib, discriminator as dm
+    F = torch.nn.functional
+    C, O, k, stride, pad, H, B = cfg
+    lib = _lib.load()
+    d = torch.device("cuda:0")
+    tol = 3e-5
+    g = torch.Generator().manual_seed(C + 3 * O + 7 * k + 11 * stride + 13 * H + 17 * B)
+    x = torch.randn(B, C, H, H, generator=g, dtype=torch.float64, requires_grad=True)
+    w = (torch.randn(O, C, k, k, generator=g, dtype=torch.float64) / (C * k * k) ** 0.5).requires_grad_(True)
+    bias = torch.randn(O, generator=g, dtype=torch.float64) * 0.3
+    y = F.conv2d(x, w, stride=stride, padding=pad)
+    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    gx, gw = torch.autograd.grad((y * dy).sum(), (x, w))
+    y = y.detach()
+    Ho = y.shape[2]
+    N, K = Ho * Ho, k * k * C
+    x32, w32, dy32 = x.detach().float().to(d), w.detach().float().to(d), dy.float().to(d)
+    # ---- the module-level op and its autograd (the dispatch the networks take)
+    xd, wd = x32.clone().requires_grad_(True), w32.clone().requires_grad_(True)
+    yd = dm.conv2d(xd, wd, stride=stride, padding=pad)
+    gxd, gwd = torch.autograd.grad((yd * dy32).sum(), (xd, wd))
+    e_mod = (rel_err(yd, y), rel_err(gxd, gx), rel_err(gwd, gw))
+    # ---- the ops
+    def planes(m):              # (M, c, k, k) -> Planes (M, k*k*c), contraction index (tap, channel)
+        return ops.split_planes(m.permute(0, 2, 3, 1).reshape(1, m.shape[0], -1).contiguous(), want_p=True, want_t=False)[0]
+    wP, xP, dyP = planes(w32), ops.split_planes_nhwc(x32), ops.split_planes_nhwc(dy32)
+    ks = lib.cips_conv2d_x3_ksplit(B, O, N, K)
+    pre = y + bias.view(1, -1, 1, 1)
+    want = F.leaky_relu(pre, 0.2) * math.sqrt(2)
+    keep = pre.abs() >= 3e-5 * pre.pow(2).mean().sqrt()
+    n_amb = int((~keep).sum())
+    assert n_amb <= 1e-3 * keep.numel(), (n_amb, keep.numel())
+    e_act = []
+    for ksplit in (None, 1):
+        ya = ops.conv2d_x3(wP, xP, B, C, H, H, O, k, k, stride, pad, ksplit=ksplit, bias=bias.float().to(d), act=True,
+                           act_scale=math.sqrt(2))
+        assert torch.isfinite(ya).all()
+        e_act.append(rel_err(ya.cpu().double() * keep, want * keep))
+    if stride == 1:
+        dx = ops.conv2d_x3(planes(w32.flip(2, 3).transpose(0, 1)), dyP, B, O, Ho, Ho, C, k, k, 1, k - 1 - pad)
+        e_dx = rel_err(dx, gx)
+    elif k > 1:
+        banks, w_off = ops.dgrad_s2_banks(w32)
+        dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, dyP, B, C, H, H, O, k, k)
+        e_dx = rel_err(ops.parity_to_nchw(dxp, out_off, B, C, H, H),
+                       F.conv_transpose2d(dy, w.detach(), stride=2, output_padding=(H - k) % 2))
+    else:
+        e_dx = None             # a one-tap stride-2 gradient has no op of its own (its odd parity classes are zero)
+    dw = ops.conv2d_x3_wgrad(dyP, xP, B, C, H, H, O, k, k, stride, pad)
+    how = "conv2d_x3_wgrad"
+    if dw is None:
+        assert (B * N) % 32, (B, N)
+        dw, how = dm._conv_bwd_weight(dy32, x32, tuple(w.shape), stride, pad), "_conv_bwd_weight (wgrad: None)"
+    e_dw = rel_err(dw, gw)
+    print(f"conv {C}->{O} k{k} s{stride} {H}x{H} -> {Ho}x{Ho} B={B} (fold {N < 256 and B > 1}, ksplit {ks}): dm.conv2d y/dx/dw "
+          f"{e_mod[0]:.2e}/{e_mod[1]:.2e}/{e_mod[2]:.2e}; bias+act ksplit={ks} {e_act[0]:.2e}, ksplit=1 {e_act[1]:.2e} "
+          f"({n_amb} outputs within rounding of 0 left out); dx {'-' if e_dx is None else format(e_dx, '.2e')}; dw via {how} {e_dw:.2e}")
+    assert max(e_mod) < tol, e_mod
+    assert max(e_act) < tol, e_act
+    assert e_dx is None or e_dx < tol, e_dx
+    assert e_dw < tol, e_dw
+    if B == 8:
+        # one launch (folded where the plane has under 256 pixels) against eight single-image launches on the same planes
+        singles = torch.cat([ops.conv2d_x3(wP, ops.split_planes_nhwc(x32[i:i + 1]), 1, C, H, H, O, k, k, stride, pad, ksplit=1)
+                             for i in range(B)])
+        for ksplit in (1, None):
+            e8 = rel_err(ops.conv2d_x3(wP, xP, B, C, H, H, O, k, k, stride, pad, ksplit=ksplit), singles)
+            assert e8 < 2e-6, (ksplit, e8)

@@ -733,6 +733,58 @@ def test_gemm_bf16x3_kmajor_grouped():
             assert torch.isfinite(C).all() and rel_err(C, ref) < 3e-5
 
 
+@pytest.mark.parametrize("nb,n", [(4, 16384), (8, 16384), (4, 65536)])
+def test_head_wgrad_pixel_split_at_stage_geometries(nb, n, monkeypatch):
+    """ops._head_wgrad at the per-GPU geometries of the r128 / r256 stages (C3: 8 images of 128^2 pixels, C4 / C5: 4 images of
+    128^2 .. 256^2), both block kinds (32 -> 512 first block, 512 -> 512), against fp64.  The pixel-split factors follow
+    (nb, n) — `_pixel_split` doubles while nb * s stays under a tile budget — and every other test of the head runs at
+    (2, 4096) or smaller, where the factors are 8 / 8 / 8.  The factors picked here are recorded and must differ from those
+    (the 512 -> 512 pair keeps 8 parts at nb = 4, with 4x / 16x longer parts; the 32 -> 512 block's two problems go to 16 and
+    32 parts, and nb = 8 halves the common factor)."""
+    from cips3d_amd import ops
+    d = dev()
+    picked = []
+    real_split = ops._pixel_split
+
+    def spy(n_, ksp, more):
+        r = real_split(n_, ksp, more)
+        picked.append(r)
+        return r
+    monkeypatch.setattr(ops, "_pixel_split", spy)
+
+    def run(nb_, n_, cin, cout, seed, check):
+        g = torch.Generator(device=d).manual_seed(seed)
+        x, a1 = torch.randn(nb_, n_, cin, device=d, generator=g), torch.randn(nb_, n_, cout, device=d, generator=g)
+        gg, g1 = torch.randn(nb_, n_, cout, device=d, generator=g), torch.randn(nb_, n_, cout, device=d, generator=g)
+        L = ops._HeadLayer()
+        L.cin, L.cout, L.xP, L.a1P = cin, cout, ops.Planes(*_planes(x)), ops.Planes(*_planes(a1))
+        gwb1 = torch.full((nb_, cin, cout), float("nan"), device=d)
+        gwb2 = torch.full((nb_, cout, cout), float("nan"), device=d)
+        del picked[:]
+        ops._head_wgrad(L, ops.Planes(*_planes(gg)), ops.Planes(*_planes(g1)), gwb1, gwb2, n_)
+        torch.cuda.synchronize()
+        ks = tuple(picked)
+        if check:
+            for what, got, a, b in (("dWb2 = a1^T g", gwb2, a1, gg), ("dWb1 = x^T g1", gwb1, x, g1)):
+                e = 0.0
+                for i in range(nb_):            # image by image: the fp64 copies of one image are 2 x n x 512 x 8 bytes
+                    ref = torch.bmm(a[i:i + 1].double().transpose(1, 2), b[i:i + 1].double())
+                    assert torch.isfinite(got[i]).all()
+                    e = max(e, rel_err(got[i:i + 1], ref))
+                print(f"head wgrad nb={nb_} n={n_} {cin}->{cout} {what}: split factors {ks}, worst image rel err vs fp64 {e:.3e}")
+                assert e < 3e-5, (what, e)
+        return ks
+
+    table = []
+    for cin, cout in ((32, 512), (512, 512)):
+        old = run(2, 4096, cin, cout, 5, False)
+        new = run(nb, n, cin, cout, nb + n + cin, True)
+        table.append(((cin, cout), old, new))
+    print(f"head wgrad split factors, (block, at nb=2 n=4096, at nb={nb} n={n}): {table}")
+    assert any(o != n_ for _, o, n_ in table), table
+    assert table[0][1] != table[0][2], table           # the 32 -> 512 block's own splits move at every stage geometry
+
+
 def test_gemm_bf16x3_epilogues():
     from cips3d_amd import ops
     d = dev()

@@ -36,9 +36,10 @@ def _draws(g, b, img, S, hier):
     return zs, rand
 
 
-def _slice(zs, rand, i, b, n, S):
-    z1 = {k: v[i:i + 1] for k, v in zs.items()}
-    r1 = {k: (v[i:i + 1] if k != "u" else v.view(b, n, S)[i].reshape(n, S)) for k, v in rand.items()}
+def _slice(zs, rand, i, b, n, S, count=1):
+    """the draws of images i .. i + count - 1 of a batch of b"""
+    z1 = {k: v[i:i + count] for k, v in zs.items()}
+    r1 = {k: (v[i:i + count] if k != "u" else v.view(b, n, S)[i:i + count].reshape(count * n, S)) for k, v in rand.items()}
     return z1, r1
 
 
@@ -209,6 +210,47 @@ FREE_AB = None           # scripts/free_running_parity.py: [(label, ops.TRIG_MOD
 FREE_RUNNING = {}        # what -> {"final_layer.weight": e, "final_layer.bias": e, "worst": (name, e)}: scripts/free_running_parity.py
 
 
+def _oracle_g_step(zs, rand, G0, img, S, hier, aux, nerf_noise, pin_fine, pin_clamp, want64=False, freeze=False):
+    """One oracle evaluation of `(imgs * G0).sum()` on the images of (zs, rand), forward and backward, recording what the
+    product is pinned to: -> dict(imgs, grads, pins: the LeakyReLU gates as bit planes (b, n, C/8), gate_shapes, fine_z
+    (b*n, S) / clamp (b*n, E) uint8 / pre (b*n, E): placement of the fine samples and branch + pre-activation of
+    relu(sigma + noise) when pin_fine / pin_clamp, grads64: with want64 the same network, gates, placement and branches in
+    fp64 — how far the reference's OWN fp32 arithmetic is from the exact gradient; the sigma head's gradients
+    (siren.final_layer.*: sums of d sigma over every sample of the batch, with heavy cancellation) are ill-conditioned at
+    these sizes, the fp32 oracle itself is 1e-3 off there).  The autograd state is gone when this returns."""
+    b = zs["z_nerf"].shape[0]
+    Gc = seeded_generator(1234, freeze=freeze)
+    tape = orc.GateTape()
+    ctape = orc.ClampTape()
+    with orc.gate_tape(tape), orc.clamp_tape(ctape if pin_clamp else None):
+        ref = orc.generator_forward(dict(Gc.named_parameters()), zs, rand, img, KW["fov"], KW["ray_start"], KW["ray_end"],
+                                    S, KW["h_stddev"], KW["v_stddev"], hier, nerf_noise=nerf_noise, return_aux_img=aux,
+                                    freeze_nerf=freeze, keep=pin_fine)
+    (ref["imgs"] * G0).sum().backward()
+    E = 2 * S if hier else S
+    out = dict(clamp=ctape.rec[0].reshape(b * img * img, E).to(torch.uint8) if pin_clamp else None,
+               pre=ctape.preact[0].reshape(b * img * img, E) if pin_clamp else None,
+               grads={k: p.grad for k, p in Gc.named_parameters() if p.grad is not None}, imgs=ref["imgs"].detach(),
+               fine_z=ref["fine_z"].detach().reshape(b * img * img, S) if pin_fine else None,
+               pins=[pack_bitplane(t) for t in tape.rec], gate_shapes=[tuple(t.shape) for t in tape.rec], grads64=None)
+    if want64:
+        G64 = seeded_generator(1234, freeze=freeze).double()
+        t64 = orc.GateTape(pin=tape.rec)
+        c64 = orc.ClampTape(pin=ctape.rec) if pin_clamp else None
+        torch.set_default_dtype(torch.float64)
+        try:
+            with orc.gate_tape(t64), orc.fine_z_pin(ref["fine_z"].detach().double() if pin_fine else None), orc.clamp_tape(c64):
+                r64 = orc.generator_forward(dict(G64.named_parameters()), {k: v.double() for k, v in zs.items()},
+                                            {k: v.double() for k, v in rand.items()}, img, KW["fov"], KW["ray_start"], KW["ray_end"],
+                                            S, KW["h_stddev"], KW["v_stddev"], hier, nerf_noise=nerf_noise, return_aux_img=aux,
+                                            freeze_nerf=freeze)
+            (r64["imgs"] * G0.double()).sum().backward()
+        finally:
+            torch.set_default_dtype(torch.float32)
+        out["grads64"] = {k: p.grad for k, p in G64.named_parameters() if p.grad is not None}
+    return out
+
+
 def _g_forward_backward_vs_oracle(what, b, img, S, hier, aux, nerf_noise, seed, pin_fine=False, pin_clamp=False, tol=None,
                                   free_bar=None, free_gates=None):
     """forward + every parameter gradient of `(imgs * G0).sum()` against the oracle, the oracle's LeakyReLU gates pinned.
@@ -235,42 +277,10 @@ def _g_forward_backward_vs_oracle(what, b, img, S, hier, aux, nerf_noise, seed, 
     zs, rand = _draws(g, b, img, S, hier)
     nimg = 2 * b if aux else b
     G0 = torch.randn(nimg, 3, img, img, generator=g) / (nimg * 3 * img * img)
-    Gc = seeded_generator(1234)
-    tape = orc.GateTape()
-    ctape = orc.ClampTape()
-    with orc.gate_tape(tape), orc.clamp_tape(ctape if pin_clamp else None):
-        ref = orc.generator_forward(dict(Gc.named_parameters()), zs, rand, img, KW["fov"], KW["ray_start"], KW["ray_end"],
-                                    S, KW["h_stddev"], KW["v_stddev"], hier, nerf_noise=nerf_noise, return_aux_img=aux,
-                                    keep=pin_fine)
-    (ref["imgs"] * G0).sum().backward()
-    E = 2 * S if hier else S
-    ref_clamp = ctape.rec[0].reshape(b * img * img, E).to(torch.uint8) if pin_clamp else None
-    ref_pre = ctape.preact[0].reshape(b * img * img, E) if pin_clamp else None
-    ref_grads = {k: p.grad for k, p in Gc.named_parameters() if p.grad is not None}
-    ref_imgs = ref["imgs"].detach()
-    ref_fz = ref["fine_z"].detach().reshape(b * img * img, S) if pin_fine else None
-    pins = [pack_bitplane(t) for t in tape.rec]
-    gate_shapes = [tuple(t.shape) for t in tape.rec]
-    ref64 = None
-    if pin_fine:
-        # the same network, gates and sample placement in fp64: how far the reference's OWN fp32 arithmetic is from the
-        # exact gradient.  The sigma head's gradients (siren.final_layer.*: sums of d sigma over every sample of the batch,
-        # with heavy cancellation) are ill-conditioned at this size — the fp32 oracle itself is 1e-3 off there.
-        G64 = seeded_generator(1234).double()
-        t64 = orc.GateTape(pin=tape.rec)
-        c64 = orc.ClampTape(pin=ctape.rec) if pin_clamp else None
-        torch.set_default_dtype(torch.float64)
-        try:
-            with orc.gate_tape(t64), orc.fine_z_pin(ref["fine_z"].detach().double()), orc.clamp_tape(c64):
-                r64 = orc.generator_forward(dict(G64.named_parameters()), {k: v.double() for k, v in zs.items()},
-                                            {k: v.double() for k, v in rand.items()}, img, KW["fov"], KW["ray_start"], KW["ray_end"],
-                                            S, KW["h_stddev"], KW["v_stddev"], hier, nerf_noise=nerf_noise, return_aux_img=aux)
-            (r64["imgs"] * G0.double()).sum().backward()
-        finally:
-            torch.set_default_dtype(torch.float32)
-        ref64 = {k: p.grad for k, p in G64.named_parameters() if p.grad is not None}
-        del r64, t64
-    del ref, tape, ctape
+    o = _oracle_g_step(zs, rand, G0, img, S, hier, aux, nerf_noise, pin_fine, pin_clamp, want64=pin_fine)
+    ref_grads, ref_imgs, ref_fz, ref_clamp, ref_pre, ref64 = o["grads"], o["imgs"], o["fine_z"], o["clamp"], o["pre"], o["grads64"]
+    pins, gate_shapes = o["pins"], o["gate_shapes"]
+    del o
     Gd = seeded_generator(1234, device=d)
     if pin_fine:
         rec = []
@@ -429,6 +439,91 @@ def _aug_draws(g, nb, size):
     return out
 
 
+def _c5_oracle_steps(D, sdD, zs, rand, real, aug_g, aug_r, aug_f, img, S, alpha, red):
+    """the oracle's G step and D step of C5 (train.py:334-466) on the images of (zs, rand, real); `red` reduces the per-image
+    loss terms (2b, 1) to the loss.  The fake images of the D step are the oracle's own, so that the D comparison stands on its
+    own.  -> everything the product is pinned to and compared with; the autograd state is gone on return."""
+    F = torch.nn.functional
+    Gc = seeded_generator(1234, freeze=True)
+    tape_g, tape_d = orc.GateTape(), orc.GateTape()
+    with orc.gate_tape(tape_g):
+        ref = orc.generator_forward(dict(Gc.named_parameters()), zs, rand, img, KW["fov"], KW["ray_start"], KW["ray_end"], S,
+                                    KW["h_stddev"], KW["v_stddev"], True, nerf_noise=0.0, return_aux_img=True, freeze_nerf=True)
+    with orc.gate_tape(tape_d):
+        gp = orc.discriminator_forward(sdD, ref["imgs"], alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_g])
+    red(F.softplus(-gp)).backward()
+    o = dict(g_grads={k: p.grad for k, p in Gc.named_parameters() if p.grad is not None})
+    assert not any(k.startswith(("siren", "mapping_network_nerf", "aux_to_rbg")) for k in o["g_grads"])
+    o.update(imgs=ref["imgs"].detach(), gp=gp.detach(), pins_g=[pack_bitplane(t) for t in tape_g.rec], pins_dg=tape_d.rec)
+    D.zero_grad(set_to_none=True)
+    del ref, gp, tape_g
+    x = real.clone().requires_grad_(True)
+    tape_dd = orc.GateTape()
+    with orc.gate_tape(tape_dd):
+        rp = orc.discriminator_forward(sdD, x, alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_r])
+        gr, = torch.autograd.grad(rp.sum(), x, create_graph=True)
+        fp = orc.discriminator_forward(sdD, o["imgs"], alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_f])
+    pen = 0.5 * 10. * gr.flatten(1).square().sum(1, keepdim=True) * 1 + 0. * rp           # train.py:397-398
+    d_loss = red(F.softplus(fp) + F.softplus(-rp) + pen)
+    d_loss.backward()
+    o.update(d_grads={k: p.grad.clone() for k, p in D.named_parameters() if p.grad is not None}, rp=rp.detach(), gr=gr.detach(),
+             fp=fp.detach(), d_loss=float(d_loss), pins_dd=tape_dd.rec)
+    D.zero_grad(set_to_none=True)
+    return o
+
+
+def _c5_product_steps(Gd, Dd, d, zs, rand, real, fake, aug_g, aug_r, aug_f, img, S, alpha, red, pins_g, pins_dg, pins_dd):
+    """the product's G step and D step of C5 with the oracle's gates pinned and its DiffAugment draws replayed; parameter
+    gradients are left on Gd (G step) and Dd (D step) -> imgs, G-step logits, real logits, R1 input gradient, fake logits, d_loss"""
+    from conftest import ReplayDraws
+    from cips3d_amd import discriminator as dmod
+    F = torch.nn.functional
+    for p in Dd.parameters():
+        p.requires_grad_(False)                               # train.py:441-442
+    imgs = _product_forward(Gd, zs, rand, d, img, S, True, aux=True, pin=pins_g)
+    with dmod.gate_debug(pin=pins_dg), ReplayDraws(aug_g):
+        gpd = Dd(imgs, alpha=alpha, use_aux_disc=True)[0]
+    red(F.softplus(-gpd)).backward()
+    torch.cuda.synchronize()
+    imgs, gpd = imgs.detach(), gpd.detach()
+    for p in Dd.parameters():
+        p.requires_grad_(True)
+    xd = real.to(d).requires_grad_(True)
+    with dmod.gate_debug(pin=pins_dd), ReplayDraws(aug_r + aug_f):
+        rpd = Dd(xd, alpha=alpha, use_aux_disc=True)[0]
+        grd, = torch.autograd.grad(rpd.sum(), xd, create_graph=True)
+        fpd = Dd(fake.to(d), alpha=alpha, use_aux_disc=True)[0]
+    pend = 0.5 * 10. * grd.flatten(1).square().sum(1, keepdim=True) * 1 + 0. * rpd
+    dl = red(F.softplus(fpd) + F.softplus(-rpd) + pend)
+    dl.backward()
+    torch.cuda.synchronize()
+    return imgs, gpd, rpd.detach(), grd.detach(), fpd.detach(), float(dl)
+
+
+def _c5_compare(what, b, img, Gd, Dd, got, o):
+    imgs, gpd, rpd, grd, fpd, dl = got
+    e_img, e_gp = max_rel(imgs, o["imgs"]), max_rel(gpd, o["gp"])
+    print(f"C5 G step {what}: imgs max_rel {e_img:.3e}, logits max_rel {e_gp:.3e}")
+    assert imgs.shape == (2 * b, 3, img, img) and e_img < TOL and e_gp < TOL
+    _grad_compare(list(Gd.named_parameters()), o["g_grads"], "C5 G-step generator gradients (oracle's gates pinned)")
+    e_r, e_g, e_f = max_rel(rpd, o["rp"]), max_rel(grd, o["gr"]), max_rel(fpd, o["fp"])
+    print(f"C5 D step: real logits {e_r:.3e}, R1 input gradient {e_g:.3e}, fake logits {e_f:.3e}, d_loss {dl:.6f} vs {o['d_loss']:.6f}")
+    assert e_r < TOL and e_f < TOL and e_g < GRAD_TOL and abs(dl - o["d_loss"]) < TOL * max(1.0, abs(o["d_loss"]))
+    _grad_compare(list(Dd.named_parameters()), o["d_grads"], "C5 D-step gradients, main + aux discriminator (oracle's gates pinned)")
+
+
+def _c5_setup(b, img, S, seed):
+    from cips3d_amd.discriminator import Discriminator_MultiScale_Aux
+    g = torch.Generator().manual_seed(seed)
+    zs, rand = _draws(g, b, img, S, True)
+    real = torch.rand(2 * b, 3, img, img, generator=g) * 2 - 1          # train.py:376-377: real_imgs twice when aux_reg
+    aug_g, aug_r, aug_f = (_aug_draws(g, b, img) + _aug_draws(g, b, img) for _ in range(3))      # main + aux disc, per D forward
+    torch.manual_seed(4321)
+    D = Discriminator_MultiScale_Aux(**dict(D_CFG, diffaug=True))
+    sdD = dict(D.state_dict()); sdD.update(dict(D.named_parameters()))
+    return zs, rand, real, aug_g, aug_r, aug_f, D, sdD
+
+
 def test_c5_finetune_step_r256_aux_two_discriminators_vs_oracle():
     """BASELINE configs[4] (finetune_afhq.yaml:38,70,89 with train_aux_img): r256, num_steps 12 + hierarchical (E = 24),
     GeneratorNerfINR_freeze_NeRF, aux image, Discriminator_MultiScale_Aux with diffaug=True, the aux discriminator and a
@@ -437,77 +532,305 @@ def test_c5_finetune_step_r256_aux_two_discriminators_vs_oracle():
               generator gradient of the stage (through both discriminators, the augmentation and the fade-in);
       D step: r_preds on real images (requires_grad), R1 penalty through the double-backward graph, g_preds on the
               generated images: logits, R1 input gradient, loss and every parameter gradient of both discriminators."""
-    from conftest import ReplayDraws
-    from cips3d_amd import ops, discriminator as dmod
-    from cips3d_amd.discriminator import Discriminator_MultiScale_Aux
     d = torch.device("cuda:0")
     b, img, S, alpha = 1, 256, 12, 0.8
-    g = torch.Generator().manual_seed(555)
-    zs, rand = _draws(g, b, img, S, True)
-    real = torch.rand(2 * b, 3, img, img, generator=g) * 2 - 1          # train.py:376-377: real_imgs twice when aux_reg
-    aug_g, aug_r, aug_f = (_aug_draws(g, b, img) + _aug_draws(g, b, img) for _ in range(3))      # main + aux disc, per D forward
-    torch.manual_seed(4321)
-    D = Discriminator_MultiScale_Aux(**dict(D_CFG, diffaug=True))
-    sdD = dict(D.state_dict()); sdD.update(dict(D.named_parameters()))
-    Gc = seeded_generator(1234, freeze=True)
-    F = torch.nn.functional
-    # ---------------- oracle: G step
-    tape_g, tape_d = orc.GateTape(), orc.GateTape()
-    with orc.gate_tape(tape_g):
-        ref = orc.generator_forward(dict(Gc.named_parameters()), zs, rand, img, KW["fov"], KW["ray_start"], KW["ray_end"], S,
-                                    KW["h_stddev"], KW["v_stddev"], True, nerf_noise=0.0, return_aux_img=True, freeze_nerf=True)
-    with orc.gate_tape(tape_d):
-        gp = orc.discriminator_forward(sdD, ref["imgs"], alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_g])
-    F.softplus(-gp).mean().backward()
-    ref_g_grads = {k: p.grad for k, p in Gc.named_parameters() if p.grad is not None}
-    assert not any(k.startswith(("siren", "mapping_network_nerf", "aux_to_rbg")) for k in ref_g_grads)
-    ref_imgs, ref_gp = ref["imgs"].detach(), gp.detach()
-    pins_g, pins_dg = [pack_bitplane(t) for t in tape_g.rec], tape_d.rec
-    D.zero_grad(set_to_none=True)
-    del ref, gp, tape_g
-    # ---------------- oracle: D step (fake images = the oracle's, so that the D comparison stands on its own)
-    x = real.clone().requires_grad_(True)
-    tape_dd = orc.GateTape()
-    with orc.gate_tape(tape_dd):
-        rp = orc.discriminator_forward(sdD, x, alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_r])
-        gr, = torch.autograd.grad(rp.sum(), x, create_graph=True)
-        fp = orc.discriminator_forward(sdD, ref_imgs, alpha=alpha, use_aux_disc=True, draws=[t for _, t in aug_f])
-    pen = 0.5 * 10. * gr.flatten(1).square().sum(1, keepdim=True) * 1 + 0. * rp           # train.py:397-398
-    d_loss = (F.softplus(fp) + F.softplus(-rp) + pen).mean()
-    d_loss.backward()
-    ref_d_grads = {k: p.grad.clone() for k, p in D.named_parameters() if p.grad is not None}
-    ref_rp, ref_gr, ref_fp, ref_dl = rp.detach(), gr.detach(), fp.detach(), float(d_loss)
-    D.zero_grad(set_to_none=True)
-    del rp, gr, fp, pen, d_loss
-    # ---------------- product: G step
+    zs, rand, real, aug_g, aug_r, aug_f, D, sdD = _c5_setup(b, img, S, 555)
+    red = lambda t: t.mean()
+    o = _c5_oracle_steps(D, sdD, zs, rand, real, aug_g, aug_r, aug_f, img, S, alpha, red)
     Gd = seeded_generator(1234, freeze=True, device=d)
     Dd = D.to(d)
-    for p in Dd.parameters():
-        p.requires_grad_(False)                               # train.py:441-442
-    imgs = _product_forward(Gd, zs, rand, d, img, S, True, aux=True, pin=pins_g)
-    with dmod.gate_debug(pin=pins_dg), ReplayDraws(aug_g):
-        gpd = Dd(imgs, alpha=alpha, use_aux_disc=True)[0]
-    F.softplus(-gpd).mean().backward()
-    torch.cuda.synchronize()
-    e_img, e_gp = max_rel(imgs, ref_imgs), max_rel(gpd, ref_gp)
-    print(f"C5 G step b=1 r256 S=12+12 frozen NeRF + aux image + aux D + DiffAugment, alpha={alpha}: imgs max_rel {e_img:.3e}, "
-          f"logits max_rel {e_gp:.3e}")
-    assert imgs.shape == (2 * b, 3, img, img) and e_img < TOL and e_gp < TOL
-    _grad_compare(list(Gd.named_parameters()), ref_g_grads, "C5 G-step generator gradients (oracle's gates pinned)")
-    del imgs, gpd
-    # ---------------- product: D step
-    for p in Dd.parameters():
-        p.requires_grad_(True)
-    xd = real.to(d).requires_grad_(True)
-    with dmod.gate_debug(pin=tape_dd.rec), ReplayDraws(aug_r + aug_f):
-        rpd = Dd(xd, alpha=alpha, use_aux_disc=True)[0]
-        grd, = torch.autograd.grad(rpd.sum(), xd, create_graph=True)
-        fpd = Dd(ref_imgs.to(d), alpha=alpha, use_aux_disc=True)[0]
-    pend = 0.5 * 10. * grd.flatten(1).square().sum(1, keepdim=True) * 1 + 0. * rpd
-    dl = (F.softplus(fpd) + F.softplus(-rpd) + pend).mean()
-    dl.backward()
-    torch.cuda.synchronize()
-    e_r, e_g, e_f = max_rel(rpd, ref_rp), max_rel(grd, ref_gr), max_rel(fpd, ref_fp)
-    print(f"C5 D step: real logits {e_r:.3e}, R1 input gradient {e_g:.3e}, fake logits {e_f:.3e}, d_loss {float(dl):.6f} vs {ref_dl:.6f}")
-    assert e_r < TOL and e_f < TOL and e_g < GRAD_TOL and abs(float(dl) - ref_dl) < TOL * max(1.0, abs(ref_dl))
-    _grad_compare(list(Dd.named_parameters()), ref_d_grads, "C5 D-step gradients, main + aux discriminator (oracle's gates pinned)")
+    got = _c5_product_steps(Gd, Dd, d, zs, rand, real, o["imgs"], aug_g, aug_r, aug_f, img, S, alpha, red, o["pins_g"], o["pins_dg"],
+                            o["pins_dd"])
+    _c5_compare(f"b=1 r256 S=12+12 frozen NeRF + aux image + aux D + DiffAugment, alpha={alpha}", b, img, Gd, Dd, got, o)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The stages' REAL per-GPU batches (C3: 8, C4 / C5: 4, D: 8 + 8 at 64^2 and 4 + 4 at 256^2).  The host cannot hold the
+# oracle at those batches, and does not have to: nothing in G or D couples the images of a batch (stddev_group = 0, PixelNorm
+# per row, DiffAugment per image) and the losses are sums over images, so the oracle's outputs at batch B are the
+# concatenation, and its parameter gradients the sum, over slices it can hold (proven on the CPU in
+# test_oracle_golden.py / test_discriminator_cpu.py).  The product runs ONCE at the full batch.
+# ------------------------------------------------------------------------------------------------------------------------
+class _DispatchSpy:
+    """Records the batch-dependent choices the launchers make while a step of the product runs: the contraction split and the
+    batch fold of every cips_conv2d_x3 launch (forward and stride-1 data gradient), the fold of the parity data gradient, the
+    chunk count of cips_conv2d_x3_wgrad (or that ops.conv2d_x3_wgrad declined the shape: the fallback path), the pixel-split
+    factors of the head's weight gradients, whether the head's GEMMs take the planes addend and the gradient ports.
+    choices: {(op, layer shape without the batch): choice}."""
+
+    def __init__(self):
+        self.choices = {}
+
+    def __enter__(self):
+        from cips3d_amd import ops, _lib
+        lib = _lib.load()
+        self._lib, self._ops = lib, ops
+        self._saved_lib = {k: getattr(lib, k) for k in ("cips_conv2d_x3", "cips_conv2d_x3_wgrad", "cips_conv2d_x3_dgrad_s2")}
+        self._saved_ops = {k: getattr(ops, k) for k in ("conv2d_x3_wgrad", "_pixel_split", "_head_wgrad", "_addp_shape_ok",
+                                                        "inr_head_ports_ok")}
+        real, rops, ch = self._saved_lib, self._saved_ops, self.choices
+        head = []
+
+        def conv(ref, stream):
+            c = ref._obj
+            Ho, Wo = (c.H + 2 * c.pad - c.kh) // c.stride + 1, (c.W + 2 * c.pad - c.kw) // c.stride + 1
+            ks = max(c.ksplit, 1)
+            fold = Ho * Wo < 256 and c.B > 1 and (c.kh * c.kw * c.C // 32) // ks >= 2          # the launcher's rule
+            ch["conv2d_x3", c.C, c.H, c.W, c.O, c.kh, c.stride, c.pad] = \
+                f"ksplit {ks}" + (f", batch folded: {-(-c.B * Ho * Wo // 256)} column tile(s)" + (", the last ragged" if c.B * Ho * Wo % 256 else "")
+                                 if fold else "") + \
+                (", bias + act in sum_chunks" if c.act and ks > 1 else ", bias + act in the GEMM epilogue" if c.act else "")
+            return real["cips_conv2d_x3"](ref, stream)
+
+        def wgrad(ref, stream):
+            c = ref._obj
+            ch["conv2d_x3_wgrad", c.C, c.H, c.W, c.O, c.kh, c.stride, c.pad] = f"{c.nchunks} chunks"
+            return real["cips_conv2d_x3_wgrad"](ref, stream)
+
+        def dgrad(ref, stream):
+            c = ref._obj
+            nps = ops.dgrad_s2_layout(c.H, c.W)
+            ch["conv2d_x3_dgrad_s2", c.C, c.H, c.W, c.O, c.kh] = "parity planes " + "/".join(
+                "folded" if c.B > 1 and n_ % 256 else "per image" for n_ in nps)
+            return real["cips_conv2d_x3_dgrad_s2"](ref, stream)
+
+        def wgrad_op(dyP, xP, B, C, H, W, O, kh, kw, stride, pad, *a, **k):
+            dw = rops["conv2d_x3_wgrad"](dyP, xP, B, C, H, W, O, kh, kw, stride, pad, *a, **k)
+            if dw is None:
+                ch["conv2d_x3_wgrad", C, H, W, O, kh, stride, pad] = "declined (B * N not a multiple of 32): fallback path"
+            return dw
+
+        def pixel_split(n, ksp, more):
+            r = rops["_pixel_split"](n, ksp, more)
+            head.append(r)
+            return r
+
+        def head_wgrad(L, gP, g1P, gwb1, gwb2, n):
+            del head[:]
+            rops["_head_wgrad"](L, gP, g1P, gwb1, gwb2, n)
+            ch["head wgrad pixel split", gwb1.shape[1], gwb1.shape[2], n] = "factors " + "/".join(map(str, head))
+
+        def addp(n, cin, cout, nb, dev):
+            ok = rops["_addp_shape_ok"](n, cin, cout, nb, dev)
+            ch["head planes addend", cin, cout, n] = str(ok)
+            return ok
+
+        def ports(nblocks, B, n, in0, params, dev):
+            ok = rops["inr_head_ports_ok"](nblocks, B, n, in0, params, dev)
+            ch["head gradient ports", n] = str(ok)
+            return ok
+
+        lib.cips_conv2d_x3, lib.cips_conv2d_x3_wgrad, lib.cips_conv2d_x3_dgrad_s2 = conv, wgrad, dgrad
+        ops.conv2d_x3_wgrad, ops._pixel_split, ops._head_wgrad, ops._addp_shape_ok, ops.inr_head_ports_ok = \
+            wgrad_op, pixel_split, head_wgrad, addp, ports
+        return self
+
+    def __exit__(self, *exc):
+        for k, v in self._saved_lib.items():
+            setattr(self._lib, k, v)
+        for k, v in self._saved_ops.items():
+            setattr(self._ops, k, v)
+
+
+def _assert_dispatch_differs(what, old_b, old, new_b, new):
+    """the table of (layer shape, choice at the batch the suite checked before, choice at the training batch); the new batch
+    must take at least one branch the old one does not, or the test adds nothing"""
+    assert old and set(old) == set(new), (sorted(set(old) ^ set(new)))
+    changed = [k for k in old if old[k] != new[k]]
+    print(f"{what}: dispatch at b = {old_b} -> b = {new_b}: {len(changed)} of {len(old)} choices differ")
+    for k in sorted(old, key=str):
+        print(f"    {'*' if old[k] != new[k] else ' '} {k}: {old[k]}  ->  {new[k]}")
+    assert changed, f"{what}: b = {new_b} takes the same branches as b = {old_b}: this test adds nothing"
+
+
+def _g_real_batch_vs_oracle_in_slices(what, b, old_b, step, img, S, hier, aux, nerf_noise, seed, pin_fine=False, pin_clamp=False,
+                                      tol=None, want64=False, freeze=False):
+    """forward + every parameter gradient of `(imgs * G0).sum()` at the stage's per-GPU batch b, the product run ONCE, the
+    oracle in slices of `step` images on G0's rows of those images: images compared slice by slice, parameter gradients
+    against the slices' sum (fp64).  The product's pins (LeakyReLU gate bit planes (b, n, C/8), fine-sample placement (b*n, S),
+    relu-clamp branches (b*n, E)) are the slices' joined along the image dimension."""
+    from cips3d_amd import ops
+    d = torch.device("cuda:0")
+    n = img * img
+    g = torch.Generator().manual_seed(seed)
+    zs, rand = _draws(g, b, img, S, hier)
+    nimg = 2 * b if aux else b
+    G0 = torch.randn(nimg, 3, img, img, generator=g) / (nimg * 3 * img * img)
+    rows = lambda i: torch.cat([torch.arange(i, i + step)] + ([torch.arange(b + i, b + i + step)] if aux else []))
+    sums, sums64, parts = {}, ({} if want64 else None), []
+    for i in range(0, b, step):
+        z1, r1 = _slice(zs, rand, i, b, n, S, count=step)
+        o = _oracle_g_step(z1, r1, G0[rows(i)], img, S, hier, aux, nerf_noise, pin_fine, pin_clamp, want64=want64, freeze=freeze)
+        for acc, gr in ((sums, o["grads"]), (sums64, o["grads64"])):
+            if acc is not None:
+                for k, v in gr.items():
+                    acc[k] = v.double() if k not in acc else acc[k] + v.double()
+        parts.append({k: o[k] for k in ("imgs", "pins", "fine_z", "clamp")})
+        del o
+    assert all(len(p["pins"]) == len(parts[0]["pins"]) for p in parts)
+    pins = [torch.cat([p["pins"][k] for p in parts]) for k in range(len(parts[0]["pins"]))]
+    assert all(t.shape[:2] == (b, n) for t in pins)
+    fz = torch.cat([p["fine_z"] for p in parts]) if pin_fine else None
+    clamp = torch.cat([p["clamp"] for p in parts]) if pin_clamp else None
+    Gd = seeded_generator(1234, freeze=freeze, device=d)
+    # the branches the suite's batch takes: the same step, pinned the same way, on the first old_b images; nothing compared
+    with _DispatchSpy() as spy_old, ops.resample_debug(pin=[fz[:old_b * n]] if pin_fine else None), \
+            ops.clamp_debug(pin=[clamp[:old_b * n]] if pin_clamp else None):
+        zo, ro = _slice(zs, rand, 0, b, n, S, count=old_b)
+        _product_forward(Gd, zo, ro, d, img, S, hier, aux=aux, pin=[t[:old_b] for t in pins], nerf_noise=nerf_noise).sum().backward()
+        torch.cuda.synchronize()
+    Gd.zero_grad(set_to_none=True)
+    with _DispatchSpy() as spy, ops.resample_debug(pin=[fz] if pin_fine else None), ops.clamp_debug(pin=[clamp] if pin_clamp else None):
+        imgs = _product_forward(Gd, zs, rand, d, img, S, hier, aux=aux, pin=pins, nerf_noise=nerf_noise)
+        assert imgs.shape == (nimg, 3, img, img)
+        (imgs * G0.to(d)).sum().backward()
+        torch.cuda.synchronize()
+    _assert_dispatch_differs(what, old_b, spy_old.choices, b, spy.choices)
+    worst = 0.0
+    imgs = imgs.detach().cpu()
+    for i, p in zip(range(0, b, step), parts):
+        e = max_rel(imgs[rows(i)], p["imgs"])
+        worst = max(worst, e)
+        assert e < TOL, (i, e)
+    print(f"{what}: worst slice of {step} image(s): imgs max_rel {worst:.3e} ({worst / TOL:.3f} of the bar)")
+    _grad_compare(list(Gd.named_parameters()), sums, f"{what} gradients (oracle in {len(parts)} slices, its pins joined)", ref64=sums64,
+                  tol=tol)
+    return len(sums)
+
+
+def test_c3_r128_real_batch_forward_backward_vs_sliced_oracle():
+    """C3 at its per-GPU batch: r128, S = 12 + 12, aux image, nerf_noise 0.1, b = 8 (test_c3_r128_pair_forward_backward_vs_oracle
+    runs b = 2), all three discontinuities pinned, the bars of that test: max(2e-4, 4 x the fp32 oracle's own distance from the
+    fp64 evaluation), images 1e-3.  The oracle (fp32 and fp64) runs in four slices of two images."""
+    n = _g_real_batch_vs_oracle_in_slices("C3 b=8 r128 S=12+12, aux, nerf_noise 0.1", 8, 2, 2, 128, 12, True, True, 0.1, 1288,
+                                          pin_fine=True, pin_clamp=True, tol=2e-4, want64=True)
+    assert n == 130, n
+
+
+def test_c4_r256_real_batch_forward_backward_vs_sliced_oracle():
+    """C4 at its per-GPU batch: r256, S = 24 + 24 (E = 48), GeneratorNerfINR_freeze_NeRF, b = 4
+    (test_c4_r256_e48_frozen_nerf_forward_backward_vs_oracle runs b = 2), the oracle's gates pinned, the bars of that test
+    (images 1e-3, gradients 5e-4).  The oracle runs image by image (~6 GB of autograd state each)."""
+    _g_real_batch_vs_oracle_in_slices("C4 b=4 r256 S=24+24 frozen NeRF", 4, 2, 1, 256, 24, True, False, 0.0, 2564, freeze=True)
+
+
+@pytest.mark.parametrize("size,b,old_b,step,alpha", [(64, 8, 2, 2, 0.6), (256, 4, 1, 1, 0.75)])
+def test_discriminator_real_batches_vs_sliced_oracle(size, b, old_b, step, alpha):
+    """Discriminator_MultiScale_Aux at the batches the stages train on — 8 + 8 images at 64^2, 4 + 4 at 256^2
+    (test_discriminator_real_sizes_vs_oracle: 2 + 2 and 1 + 1) — at that test's bars.  d_loss as sums over the images divided
+    by their count n = 2 b, so that slices add exactly: softplus(-out).sum() / n + 5 * |dout/dx|^2.sum() / n.  The module
+    gives the first half of the batch to the main network and the second half to the auxiliary one: slice i holds images
+    [i, i + step) of each half.  GateTape records in call order, main network first, so entry k of the full-batch pins is the
+    slices' entries k joined along the batch."""
+    from cips3d_amd import discriminator as dmod
+    from cips3d_amd.discriminator import Discriminator_MultiScale_Aux
+    F = torch.nn.functional
+    d = torch.device("cuda:0")
+    torch.manual_seed(4321)
+    D = Discriminator_MultiScale_Aux(**D_CFG)
+    g = torch.Generator().manual_seed(size + b)
+    nimg = 2 * b
+    x0 = torch.rand(nimg, 3, size, size, generator=g) * 2 - 1
+    sd = dict(D.state_dict())
+    sd.update(dict(D.named_parameters()))
+    loss_of = lambda out, gr: F.softplus(-out).sum() / nimg + 0.5 * 10. * gr.flatten(1).pow(2).sum() / nimg
+    ref_out, ref_gr = torch.empty(nimg, 1), torch.empty_like(x0)
+    sums, tapes, ref_loss = {}, [], 0.0
+    for i in range(0, b, step):
+        rows = torch.cat([torch.arange(i, i + step), torch.arange(b + i, b + i + step)])
+        x = x0[rows].clone().requires_grad_(True)
+        tape = orc.GateTape()
+        with orc.gate_tape(tape):
+            out = orc.discriminator_forward(sd, x, alpha=alpha, use_aux_disc=True)
+        gr, = torch.autograd.grad(out.sum(), x, create_graph=True)
+        loss = loss_of(out, gr)
+        loss.backward()
+        for k, p in D.named_parameters():
+            if p.grad is not None:
+                sums[k] = p.grad.double() if k not in sums else sums[k] + p.grad.double()
+        ref_out[rows], ref_gr[rows], ref_loss = out.detach().reshape(-1, 1), gr.detach(), ref_loss + float(loss)
+        tapes.append(tape.rec)
+        D.zero_grad(set_to_none=True)
+        del out, gr, loss, tape, x
+    assert all(len(t) == len(tapes[0]) for t in tapes)
+    pins = [torch.cat([t[k] for t in tapes]) for k in range(len(tapes[0]))]
+    assert all(t.shape[0] == b for t in pins)
+    Dd = D.to(d)
+
+    def step_(x_cpu, pin):
+        xd = x_cpu.to(d).requires_grad_(True)
+        with dmod.gate_debug(pin=pin):
+            o = Dd(xd, alpha=alpha, use_aux_disc=True)[0]
+        gd, = torch.autograd.grad(o.sum(), xd, create_graph=True)
+        ld = F.softplus(-o).sum() / nimg + 0.5 * 10. * gd.flatten(1).pow(2).sum() / nimg
+        ld.backward()
+        torch.cuda.synchronize()
+        return o, gd, ld
+
+    what = f"D {size}x{size} {b}+{b} images, main+aux, alpha={alpha}"
+    small = torch.cat([x0[:old_b], x0[b:b + old_b]])
+    # the step as training runs it (no gate instrumentation: bias + LeakyReLU in the convolutions' epilogues, the gated
+    # gradient as planes only) at the batch the suite checked before and at the training batch: the branches taken, and
+    # the logits (continuous in the gates) against the oracle
+    with _DispatchSpy() as spy_old:
+        step_(small, None)
+    Dd.zero_grad(set_to_none=True)
+    with _DispatchSpy() as spy:
+        o_free = step_(x0, None)[0].detach()
+    Dd.zero_grad(set_to_none=True)
+    _assert_dispatch_differs(what + ", free-running", old_b, spy_old.choices, b, spy.choices)
+    e_free = max_rel(o_free, ref_out)
+    print(f"{what}, free-running: logits max_rel {e_free:.3e} ({e_free / TOL:.3f} of the bar)")
+    assert e_free < TOL
+    # the same with the oracle's gates pinned (the separate activation op): the compared step
+    with _DispatchSpy() as spy_old:
+        step_(small, [t[:old_b] for t in pins])
+    Dd.zero_grad(set_to_none=True)
+    with _DispatchSpy() as spy:
+        o, gd, ld = step_(x0, pins)
+    _assert_dispatch_differs(what + ", gates pinned", old_b, spy_old.choices, b, spy.choices)
+    e, eg = max_rel(o, ref_out), max_rel(gd, ref_gr)
+    print(f"{what} (oracle in {len(tapes)} slices of {step}+{step}): logits max_rel {e:.3e} ({e / TOL:.3f} of the bar), R1 "
+          f"input-gradient max_rel {eg:.3e} ({eg / GRAD_TOL:.3f} of the bar), loss {float(ld):.6f} vs {ref_loss:.6f}")
+    assert e < TOL and eg < GRAD_TOL and abs(float(ld) - ref_loss) < TOL * max(1.0, abs(ref_loss))
+    _grad_compare(list(Dd.named_parameters()), sums, f"{what} gradients (oracle's gates pinned)")
+
+
+def test_c5_finetune_step_real_batch_vs_sliced_oracle():
+    """C5's G step and D step at the stage's per-GPU batch, b = 4 (test_c5_finetune_step_r256_aux_two_discriminators_vs_oracle
+    runs b = 1), at that test's bars.  The `.mean()` losses are sums over the 2 b per-image terms divided by 2 b; the oracle
+    runs image by image — latents, rays, real images and the recorded DiffAugment draws (per-image tensors, the main and
+    the auxiliary network's halves cut separately) of image i — and the product once, with the slices' pins joined."""
+    d = torch.device("cuda:0")
+    b, img, S, alpha = 4, 256, 12, 0.8
+    n = img * img
+    zs, rand, real, aug_g, aug_r, aug_f, D, sdD = _c5_setup(b, img, S, 5554)
+    red = lambda t: t.sum() / (2 * b)
+    cut = lambda aug, i: [(k, t[i:i + 1]) for k, t in aug]          # 7 draws of the main network's images, 7 of the auxiliary's
+    parts = []
+    for i in range(b):
+        z1, r1 = _slice(zs, rand, i, b, n, S)
+        parts.append(_c5_oracle_steps(D, sdD, z1, r1, real[[i, b + i]], cut(aug_g, i), cut(aug_r, i), cut(aug_f, i), img, S, alpha, red))
+    halves = lambda k: torch.cat([p[k][:1] for p in parts] + [p[k][1:] for p in parts])          # rows (i, b + i) of slice i
+    joined = lambda k: [torch.cat([p[k][j] for p in parts]) for j in range(len(parts[0][k]))]
+    total = lambda k: {name: sum(p[k][name].double() for p in parts) for name in parts[0][k]}
+    o = dict({k: halves(k) for k in ("imgs", "gp", "rp", "gr", "fp")}, **{k: joined(k) for k in ("pins_g", "pins_dg", "pins_dd")},
+             g_grads=total("g_grads"), d_grads=total("d_grads"), d_loss=sum(p["d_loss"] for p in parts))
+    assert all(set(p["g_grads"]) == set(o["g_grads"]) and set(p["d_grads"]) == set(o["d_grads"]) for p in parts)
+    Gd = seeded_generator(1234, freeze=True, device=d)
+    Dd = D.to(d)
+    # the branches of the batch the suite checked before: the same two steps on image 0 alone, pinned the same way
+    p0 = parts[0]
+    z1, r1 = _slice(zs, rand, 0, b, n, S)
+    with _DispatchSpy() as spy_old:
+        _c5_product_steps(Gd, Dd, d, z1, r1, real[[0, b]], p0["imgs"], cut(aug_g, 0), cut(aug_r, 0), cut(aug_f, 0), img, S, alpha, red,
+                          p0["pins_g"], p0["pins_dg"], p0["pins_dd"])
+    Gd.zero_grad(set_to_none=True)
+    Dd.zero_grad(set_to_none=True)
+    del parts, p0
+    with _DispatchSpy() as spy:
+        got = _c5_product_steps(Gd, Dd, d, zs, rand, real, o["imgs"], aug_g, aug_r, aug_f, img, S, alpha, red, o["pins_g"], o["pins_dg"],
+                                o["pins_dd"])
+    what = f"b={b} r256 S=12+12 frozen NeRF + aux image + aux D + DiffAugment, alpha={alpha} (oracle in {b} slices)"
+    _assert_dispatch_differs("C5 " + what, 1, spy_old.choices, b, spy.choices)
+    _c5_compare(what, b, img, Gd, Dd, got, o)

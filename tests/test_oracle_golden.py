@@ -229,3 +229,79 @@ def test_oracle_clamp_tape_records_and_replays_the_reference_branches(tag):
         assert (g_rec[name] is None) == (g_pin[name] is None), name
         if g_rec[name] is not None:
             assert torch.equal(g_pin[name], g_rec[name]), name
+
+
+G_SLICE_FP64_BAR = 1e-12         # fp64 rounding over the sums of a gradient (eps 1.1e-16 x their length), 10x the ~1e-13 expected
+G_SLICE_FP32_BAR = None          # set below the test: 4 x the largest fp32 parameter-gradient difference measured
+
+
+def test_generator_oracle_is_additive_over_batch_slices():
+    """What the GPU tests at the training batches stand on (test_gpu_real_configs.py, the *_vs_sliced_oracle tests): nothing in
+    the generator couples the images of a batch (PixelNorm is per row, every ray and style belongs to one image), so for the
+    loss `(imgs * G0).sum()` the oracle's images on a batch are the concatenation, and its parameter gradients the sum, over
+    slices of the batch evaluated on G0's rows of those images (with the aux image: rows i and b + i).  r16, S = 4 + 4
+    hierarchical, aux image, nerf_noise 0.1, 4 images, whole against four slices of one image:
+      fp64, nothing pinned:                   images 2.8e-15, worst parameter gradient 1.0e-14 (relative): the identity;
+      fp32, the whole run's LeakyReLU gates, fine-sample placement and relu-clamp branches pinned in the slices:
+                                              images 1.0e-06, worst parameter gradient 4.8e-06 (mapping_network_inr.base_net.1.weight);
+                                              bar 4 x that, 1.9e-05.
+    A gate, placement or branch that differs between the whole and the free-running sliced fp32 run is one of the path's
+    discontinuities, not a slicing error: they are counted and printed (7 of 9.4 million gates, 1 of 4096 fine samples, no clamp branch here)."""
+    from test_gpu_real_configs import _draws, _slice, KW
+    b, img, S, noise = 4, 16, 4, 0.1
+    n = img * img
+    g = torch.Generator().manual_seed(416)
+    zs, rand = _draws(g, b, img, S, True)
+    G0 = torch.randn(2 * b, 3, img, img, generator=g) / (2 * b * 3 * img * img)
+
+    def run(dtype, z1, r1, G01, pin=None, grad=True):
+        G = seeded_generator(1234)
+        cast = lambda t: t.to(dtype) if torch.is_floating_point(t) else t
+        if dtype == torch.float64:
+            G = G.double()
+        tape = orc.GateTape(pin=pin and pin["gates"])
+        ctape = orc.ClampTape(pin=pin and [pin["clamp"]])
+        torch.set_default_dtype(dtype)
+        try:
+            with orc.gate_tape(tape), orc.clamp_tape(ctape), orc.fine_z_pin(pin and pin["fine_z"]), torch.set_grad_enabled(grad):
+                out = orc.generator_forward(dict(G.named_parameters()), {k: cast(v) for k, v in z1.items()},
+                                            {k: cast(v) for k, v in r1.items()}, img, KW["fov"], KW["ray_start"], KW["ray_end"], S,
+                                            KW["h_stddev"], KW["v_stddev"], True, nerf_noise=noise, return_aux_img=True, keep=True)
+            if grad:
+                (out["imgs"] * cast(G01)).sum().backward()
+        finally:
+            torch.set_default_dtype(torch.float32)
+        tape.done()
+        return (out["imgs"].detach(), {k: p.grad.double() for k, p in G.named_parameters() if p.grad is not None},
+                dict(gates=tape.rec, clamp=ctape.rec[0], fine_z=out["fine_z"].detach()))
+
+    for dtype in (torch.float64, torch.float32):
+        imgs, grads, whole = run(dtype, zs, rand, G0)
+        assert len(grads) == 130
+        s_imgs, s_grads, flips = torch.empty_like(imgs), {}, [0, 0, 0]
+        for i in range(b):
+            rows = torch.tensor([i, b + i])
+            z1, r1 = _slice(zs, rand, i, b, n, S)
+            pin = None
+            if dtype == torch.float32:
+                pin = dict(gates=[t[i:i + 1] for t in whole["gates"]], clamp=whole["clamp"][i:i + 1], fine_z=whole["fine_z"][i:i + 1])
+                free = run(dtype, z1, r1, G0[rows], grad=False)[2]
+                flips[0] += sum(int((a != w).sum()) for a, w in zip(free["gates"], pin["gates"]))
+                flips[1] += int(((free["fine_z"] - pin["fine_z"]).abs() > 1e-4 * (KW["ray_end"] - KW["ray_start"])).sum())
+                flips[2] += int((free["clamp"] != pin["clamp"]).sum())
+            o, gs, _ = run(dtype, z1, r1, G0[rows], pin=pin)
+            s_imgs[rows] = o
+            for k, v in gs.items():
+                s_grads[k] = v if k not in s_grads else s_grads[k] + v
+        assert set(s_grads) == set(grads)
+        errs = {k: float((s_grads[k] - v).norm() / v.norm().clamp_min(1e-300)) for k, v in grads.items()}
+        wk = max(errs, key=errs.get)
+        e_img = max_rel(s_imgs, imgs)
+        print(f"G oracle whole vs sliced, {dtype}: images {e_img:.2e}, worst parameter gradient {errs[wk]:.2e} ({wk})"
+              + (f"; free-running slices: {flips[0]} of {sum(t.numel() for t in whole['gates'])} gates, {flips[1]} of {whole['fine_z'].numel()} fine samples, {flips[2]} clamp branches differ from the whole run's"
+                 if dtype == torch.float32 else ""))
+        bar = G_SLICE_FP64_BAR if dtype == torch.float64 else G_SLICE_FP32_BAR
+        assert e_img < bar and errs[wk] < bar, (dtype, e_img, wk, errs[wk])
+
+
+G_SLICE_FP32_BAR = 4 * 4.75e-6
