@@ -133,6 +133,11 @@ SIGNATURES = {
     "cips_equal_linear": (i32, [i32, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
     "cips_gemm_bf16x3_km": (i32, [C.POINTER(GemmX3Desc), vp]),
     "cips_gemm_bf16x3_km_grouped": (i32, [C.POINTER(GemmX3Desc), i32, vp]),
+    "cips_gemm_bf16": (i32, [C.POINTER(GemmX3Desc), vp]),
+    "cips_gemm_bf16_fuses_torgb": (i32, [C.POINTER(GemmX3Desc)]),
+    "cips_gemm_bf16_takes_addp": (i32, [C.POINTER(GemmX3Desc)]),
+    "cips_gemm_bf16_km": (i32, [C.POINTER(GemmX3Desc), vp]),
+    "cips_gemm_bf16_km_grouped": (i32, [C.POINTER(GemmX3Desc), i32, vp]),
     "cips_lrelu_bwd_bias_slices": (i32, [i32]),
     "cips_lrelu_bwd_bias": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, vp]),
     "cips_lrelu_bwd_bias_finish": (i32, [vp, vp, i32, i32, i32, vp]),

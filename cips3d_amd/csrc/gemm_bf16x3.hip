@@ -59,6 +59,9 @@ struct Args {
   int tiles_m, tiles_n, total;
 };
 
+// X1 (here and in the K-major kernel below): the single-pass form behind cips_gemm_bf16* — sum_k a_hi b_hi only; the lo
+// operand planes are neither staged nor multiplied (their LDS planes stay unused), everything else is the same code.
+template <bool X1>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
   using CF = Cfg;
   constexpr int BM = CF::BM, OFF_AHI = CF::OFF_AHI, OFF_ALO = CF::OFF_ALO, OFF_BHI = CF::OFF_BHI, OFF_BLO = CF::OFF_BLO,
@@ -129,13 +132,13 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
     for (int i = 0; i < 2; ++i) {            // A: BM/16 row groups per plane, 2 per wave
       const int gidx = uw + NW * i;
       lds_dma16(ah, offA_nt[i], s + OFF_AHI + gidx * 16 * ROWB);
-      lds_dma16(al, offA_nt[i], s + OFF_ALO + gidx * 16 * ROWB);
+      if constexpr (!X1) lds_dma16(al, offA_nt[i], s + OFF_ALO + gidx * 16 * ROWB);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {           // B: 8 row groups per plane
       const int gidx = uw + NW * i;
       lds_dma16(bh, offB_nt[i], s + OFF_BHI + gidx * 16 * ROWB);
-      lds_dma16(bl, offB_nt[i], s + OFF_BLO + gidx * 16 * ROWB);
+      if constexpr (!X1) lds_dma16(bl, offB_nt[i], s + OFF_BLO + gidx * 16 * ROWB);
     }
   };
   auto compute = [&](int stage) {
@@ -148,21 +151,23 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
         const int R = wm * 64 + i * 32 + l31;
         const int off = R * ROWB + (((ks * 2 + hf) ^ ((R >> 2) & 3)) << 4);
         ah[i] = *reinterpret_cast<const bf16x8*>(s + OFF_AHI + off);
-        al[i] = *reinterpret_cast<const bf16x8*>(s + OFF_ALO + off);
+        if constexpr (!X1) al[i] = *reinterpret_cast<const bf16x8*>(s + OFF_ALO + off);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int R = wn * 64 + j * 32 + l31;
         const int off = R * ROWB + (((ks * 2 + hf) ^ ((R >> 2) & 3)) << 4);
         bh[j] = *reinterpret_cast<const bf16x8*>(s + OFF_BHI + off);
-        bl[j] = *reinterpret_cast<const bf16x8*>(s + OFF_BLO + off);
+        if constexpr (!X1) bl[j] = *reinterpret_cast<const bf16x8*>(s + OFF_BLO + off);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          if constexpr (!X1) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          }
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
         }
     }
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_bf16x3_kernel(Args g) {
   // Ring of NSTAGE LDS stages, NSTAGE-1 tiles of LDS-DMA in flight across the (raw) barriers: the wait in
   // front of tile kt is a COUNTED vmcnt that leaves the younger tiles' pieces outstanding
   // (cdna_hip_programming.md T3/T4: never drain to 0 in the main loop).
-  constexpr int NSTAGE = CF::NSTAGE, PIECES = CF::PIECES, DIST = NSTAGE - 1;
+  constexpr int NSTAGE = CF::NSTAGE, PIECES = X1 ? CF::PIECES / 2 : CF::PIECES, DIST = NSTAGE - 1;
   const int nk = K / BK;
 #pragma unroll
   for (int t = 0; t < DIST; ++t)
@@ -454,10 +459,10 @@ struct KmCfg {
   static constexpr int SMEM_BYTES = (NSTAGE * STAGE > SMEM_EPI) ? NSTAGE * STAGE : SMEM_EPI;
 };
 
-template <int WM>
+template <int WM, bool X1>
 __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(Args g) {
   using KC = KmCfg<WM>;
-  constexpr int BM = KC::BM, NSTAGE = KC::NSTAGE, PIECES = KC::PIECES, DIST = NSTAGE - 1, NW = KC::NW;
+  constexpr int BM = KC::BM, NSTAGE = KC::NSTAGE, PIECES = X1 ? KC::PIECES / 2 : KC::PIECES, DIST = NSTAGE - 1, NW = KC::NW;
   constexpr int AROW = KC::AROW, BROW = KC::BROW;
   constexpr int OFF_AHI = KC::OFF_AHI, OFF_ALO = KC::OFF_ALO, OFF_BHI = KC::OFF_BHI, OFF_BLO = KC::OFF_BLO;
   constexpr int STAGE = KC::STAGE;
@@ -521,13 +526,13 @@ __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(A
     for (int i = 0; i < KC::A_PER_WAVE; ++i) {
       const int idx = uw + NW * i;
       lds_dma16(ah, offA_km[i], s + OFF_AHI + idx * 1024);
-      lds_dma16(al, offA_km[i], s + OFF_ALO + idx * 1024);
+      if constexpr (!X1) lds_dma16(al, offA_km[i], s + OFF_ALO + idx * 1024);
     }
 #pragma unroll
     for (int i = 0; i < KC::B_PER_WAVE; ++i) {
       const int idx = uw + NW * i;
       lds_dma16(bh, offB_km[i], s + OFF_BHI + idx * 1024);
-      lds_dma16(bl, offB_km[i], s + OFF_BLO + idx * 1024);
+      if constexpr (!X1) lds_dma16(bl, offB_km[i], s + OFF_BLO + idx * 1024);
     }
   };
   // transpose-read one 32(m) x 16(k) fragment: two ds_read_b64_tr_b16 (rows kb.. and kb+4..)
@@ -549,19 +554,21 @@ __global__ __launch_bounds__(KmCfg<WM>::THREADS, 2) void gemm_bf16x3_km_kernel(A
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         ah[i] = frag(s + OFF_AHI, AROW, wm * 64 + i * 32, ks);
-        al[i] = frag(s + OFF_ALO, AROW, wm * 64 + i * 32, ks);
+        if constexpr (!X1) al[i] = frag(s + OFF_ALO, AROW, wm * 64 + i * 32, ks);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         bh[j] = frag(s + OFF_BHI, BROW, wn * 64 + j * 32, ks);
-        bl[j] = frag(s + OFF_BLO, BROW, wn * 64 + j * 32, ks);
+        if constexpr (!X1) bl[j] = frag(s + OFF_BLO, BROW, wn * 64 + j * 32, ks);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          if constexpr (!X1) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          }
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
         }
     }
@@ -786,7 +793,13 @@ static inline bool x3_big(const cips_gemm_x3_desc* d) {
 }
 static inline bool x3_wants_256(const cips_gemm_x3_desc* d) { return d->kernel >= 2 || (d->kernel == 0 && x3_big(d)); }
 
-extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream) {
+extern "C" CIPS_INTERNAL int cips_gemm_bf16_v3(const cips_gemm_x3_desc* d, cips_stream_t stream);       // single-pass forms
+extern "C" CIPS_INTERNAL int cips_gemm_bf16_v3_accepts(const cips_gemm_x3_desc* d);
+
+// The NT entry points.  X1: cips_gemm_bf16 — the 256x256 kernel's single-pass form where it takes the shape, else the
+// single-pass form of the 256x128 kernel below (never a 3-pass kernel: the wide kernel has no single-pass form and is skipped).
+template <bool X1>
+static int gemm_nt(const cips_gemm_x3_desc* d, cips_stream_t stream) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return (int)hipErrorInvalidValue;
   if ((d->K & 31) || (d->lda & 7) || (d->ldb & 7) || (d->strideA & 7) || (d->strideB & 7))
     return (int)hipErrorInvalidValue;
@@ -794,12 +807,12 @@ extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream
   if (d->gate_bits && ((d->N & 31) || (d->ldp & 31) || (d->strideP & 31))) return (int)hipErrorInvalidValue;
   // large square-ish problems: 256x256 tiles (less operand traffic per flop, prefetched epilogue inputs)
   if (x3_wants_256(d) && d->kernel != 3) {
-    const int rc3 = cips_gemm_bf16x3_v3(d, stream);
+    const int rc3 = X1 ? cips_gemm_bf16_v3(d, stream) : cips_gemm_bf16x3_v3(d, stream);
     if (rc3 != (int)hipErrorNotSupported) return rc3;
   }
   if (d->torgb_w) return (int)hipErrorNotSupported;       // only the v3 kernel folds ToRGB in: never drop it silently
   if (d->addp_hi) return (int)hipErrorNotSupported;       // ... and only it takes the addend as gated planes
-  if (x3_wants_256(d)) {
+  if (!X1 && x3_wants_256(d)) {
     const int rc = cips_gemm_bf16x3_wide(d, stream);
     if (rc != (int)hipErrorNotSupported) return rc;
   }
@@ -807,7 +820,7 @@ extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    hipFuncSetAttribute((const void*)gemm_bf16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES);
+    hipFuncSetAttribute((const void*)gemm_bf16x3_kernel<X1>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES);
     attr = true;
   }
   Args g;
@@ -819,24 +832,24 @@ extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream
   g.total = (int)total;
   const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
-  hipLaunchKernelGGL(gemm_bf16x3_kernel, dim3(grid), dim3(512), Cfg::SMEM_BYTES, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(gemm_bf16x3_kernel<X1>, dim3(grid), dim3(512), Cfg::SMEM_BYTES, (hipStream_t)stream, g);
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream) { return gemm_nt<false>(d, stream); }
+extern "C" int cips_gemm_bf16(const cips_gemm_x3_desc* d, cips_stream_t stream) { return gemm_nt<true>(d, stream); }
 
-
-extern "C" int cips_gemm_bf16x3_fuses_torgb(const cips_gemm_x3_desc* d) {
-  if (!d || !d->torgb_w) return 0;
+// would the NT entry point run this descriptor on the 256x256 v3 kernel (x1: on its single-pass form)?
+static int x3_on_v3(const cips_gemm_x3_desc* d, bool x1) {
   if (!(x3_wants_256(d) && d->kernel != 3)) return 0;
-  return cips_gemm_bf16x3_v3_accepts(d) == 0 ? 1 : 0;
+  return (x1 ? cips_gemm_bf16_v3_accepts(d) : cips_gemm_bf16x3_v3_accepts(d)) == 0 ? 1 : 0;
 }
+extern "C" int cips_gemm_bf16x3_fuses_torgb(const cips_gemm_x3_desc* d) { return (d && d->torgb_w) ? x3_on_v3(d, false) : 0; }
+extern "C" int cips_gemm_bf16x3_takes_addp(const cips_gemm_x3_desc* d) { return (d && d->addp_hi) ? x3_on_v3(d, false) : 0; }
+extern "C" int cips_gemm_bf16_fuses_torgb(const cips_gemm_x3_desc* d) { return (d && d->torgb_w) ? x3_on_v3(d, true) : 0; }
+extern "C" int cips_gemm_bf16_takes_addp(const cips_gemm_x3_desc* d) { return (d && d->addp_hi) ? x3_on_v3(d, true) : 0; }
 
-extern "C" int cips_gemm_bf16x3_takes_addp(const cips_gemm_x3_desc* d) {
-  if (!d || !d->addp_hi) return 0;
-  if (!(x3_wants_256(d) && d->kernel != 3)) return 0;
-  return cips_gemm_bf16x3_v3_accepts(d) == 0 ? 1 : 0;
-}
-
-extern "C" int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t stream) {
+template <bool X1>
+static int gemm_km(const cips_gemm_x3_desc* d, cips_stream_t stream) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || !d->C) return (int)hipErrorInvalidValue;
   if ((d->K & 31) || (d->M & 7) || (d->N & 7) || (d->lda & 7) || (d->ldb & 7) || (d->strideA & 7) || (d->strideB & 7))
     return (int)hipErrorInvalidValue;
@@ -847,7 +860,7 @@ extern "C" int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t str
   if (d->kernel < 0 || d->kernel > 3) return (int)hipErrorInvalidValue;
   if (d->kernel != 1 && d->M >= 256 && d->N >= 256 &&
       ((long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * d->batch >= 192 || d->kernel >= 2)) {
-    const int rc = cips_gemm_bf16x3_km_grouped(d, 1, stream);
+    const int rc = X1 ? cips_gemm_bf16_km_grouped(d, 1, stream) : cips_gemm_bf16x3_km_grouped(d, 1, stream);
     if (rc != (int)hipErrorNotSupported) return rc;
   }
   // 256-row tiles when M fills them, else the 128-row form (SIREN weight gradients: M = 128 / 64)
@@ -862,20 +875,22 @@ extern "C" int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t str
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<4>::SMEM_BYTES);
-    hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<2>::SMEM_BYTES);
+    hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<4, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<4>::SMEM_BYTES);
+    hipFuncSetAttribute((const void*)gemm_bf16x3_km_kernel<2, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, KmCfg<2>::SMEM_BYTES);
     attr = true;
   }
   const int ncu = cips_persistent_cus();
   if (bm == 256) {
     const int grid = g.total < ncu ? g.total : ncu;
-    hipLaunchKernelGGL(gemm_bf16x3_km_kernel<4>, dim3(grid), dim3(512), KmCfg<4>::SMEM_BYTES, (hipStream_t)stream, g);
+    hipLaunchKernelGGL((gemm_bf16x3_km_kernel<4, X1>), dim3(grid), dim3(512), KmCfg<4>::SMEM_BYTES, (hipStream_t)stream, g);
   } else {
     const int grid = g.total < 2 * ncu ? g.total : 2 * ncu;
-    hipLaunchKernelGGL(gemm_bf16x3_km_kernel<2>, dim3(grid), dim3(256), KmCfg<2>::SMEM_BYTES, (hipStream_t)stream, g);
+    hipLaunchKernelGGL((gemm_bf16x3_km_kernel<2, X1>), dim3(grid), dim3(256), KmCfg<2>::SMEM_BYTES, (hipStream_t)stream, g);
   }
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t stream) { return gemm_km<false>(d, stream); }
+extern "C" int cips_gemm_bf16_km(const cips_gemm_x3_desc* d, cips_stream_t stream) { return gemm_km<true>(d, stream); }
 
 extern "C" int cips_split_planes(const float* x, void* p_hi, void* p_lo, void* t_hi, void* t_lo, int rows,
                                  int cols, int ldx, int ldp, int ldt, int batch, long long stride_x,

@@ -242,8 +242,13 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_wide_kernel(KArgs g) {
 //     earlier, not half of one) and frees the current stage for k-tile t+2, whose eight pieces follow one per two MFMAs.
 // Same MFMA order per accumulator as the kernel above: results are bit-identical.
 
-template <bool CONV>
+// X1: the single-pass form (cips_gemm_bf16_km*: hi planes only) on the stage contents and the k-tile schedule x1_ktile of
+// gemm_x3_common.h — planes 1 and 3 of a stage hold the hi planes' k-rows 32..63 of a 64-deep k-tile.  K is a multiple of 64,
+// at least 128.
+template <bool CONV, bool X1 = false>
 __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
+  static_assert(!(CONV && X1), "the convolution weight gradient has no single-pass form");
+  constexpr int KT = X1 ? X1_BK : BK;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
   const int tid = threadIdx.x;
@@ -251,7 +256,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
   const int uw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wave = uw, wm = wave >> 1, wn = wave & 1;       // 4 x 2 waves, 64 x 128 outputs each
   const int M = d.M, N = d.N;
-  const int nk_all = d.K / BK;
+  const int nk_all = d.K / KT;
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
 
   for (int tseq = blockIdx.x; tseq < g.total; tseq += gridDim.x) {
@@ -268,9 +273,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
     const long long kt0 = CONV ? (long long)bz * g.cv.ktiles / g.cv.nchunks : 0;
     const int nk = CONV ? (int)((long long)(bz + 1) * g.cv.ktiles / g.cv.nchunks - kt0) : nk_all;     // >= 2 (host)
     const u16* Ahi = (const u16*)g.A_hi[gp] + (CONV ? kt0 * BK * d.lda : (long long)bz * d.strideA);
-    const u16* Alo = (const u16*)g.A_lo[gp] + (CONV ? kt0 * BK * d.lda : (long long)bz * d.strideA);
+    const u16* Alo = X1 ? Ahi + 32LL * d.lda : (const u16*)g.A_lo[gp] + (CONV ? kt0 * BK * d.lda : (long long)bz * d.strideA);
     const u16* Bhi = (const u16*)g.B_hi[gp] + (CONV ? 0 : (long long)bz * d.strideB);
-    const u16* Blo = (const u16*)g.B_lo[gp] + (CONV ? 0 : (long long)bz * d.strideB);
+    const u16* Blo = X1 ? Bhi + 32LL * d.ldb : (const u16*)g.B_lo[gp] + (CONV ? 0 : (long long)bz * d.strideB);
     float* Cg = g.C[gp] + (CONV ? (long long)gi * d.M * d.ldc : 0);
     const int tap_ky = CONV ? gi / g.cv.kw : 0, tap_kx = CONV ? gi - tap_ky * g.cv.kw : 0;
 
@@ -395,19 +400,59 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       });
     };
 
+    // ---- single pass: the same k-tile forms on x1_ktile, the eight pieces of k-tile kt+2 behind the barrier
+    bf16x8 G[2][6];
+    auto ktile1 = [&](auto MODE_, int kt) {
+      constexpr int MODE = decltype(MODE_)::value;
+      const unsigned cur = (unsigned)(kt & 1) * STAGE, nxt = STAGE - cur;
+      unsigned ac[2][2], bc[2][4], an[2] = {fa[0][0] + nxt, fa[0][1] + nxt}, bn[4] = {fb[0][0] + nxt, fb[0][1] + nxt, fb[0][2] + nxt, fb[0][3] + nxt};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { ac[ks][i] = fa[ks][i] + cur; asm volatile("" : "+v"(ac[ks][i])); }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { bc[ks][j] = fb[ks][j] + cur; asm volatile("" : "+v"(bc[ks][j])); }
+      }
+      asm volatile("" : "+v"(an[0]), "+v"(an[1]), "+v"(bn[0]), "+v"(bn[1]), "+v"(bn[2]), "+v"(bn[3]));
+      auto rd1 = [&](auto Q_, auto S_, auto NEXT_) -> bf16x8 {
+        constexpr int q = decltype(Q_)::value, s = decltype(S_)::value, tl = x1_frag_tile(q);
+        if constexpr (decltype(NEXT_)::value) return frag(x1_frag_is_a(q) ? an[tl] : bn[tl], x1_frag_plane(q, s));
+        else return frag(x1_frag_is_a(q) ? ac[s & 1][tl] : bc[s & 1][tl], x1_frag_plane(q, s));
+      };
+      auto slot = [&](auto S_, auto M_) {
+        constexpr int s = decltype(S_)::value, m = decltype(M_)::value;
+        if constexpr (MODE == 0 && s == 3 && m >= 2) {
+#pragma unroll
+          for (int i = 0; i < x1_pieces(m); ++i) dma_piece(x1_piece0(m) + i, (kt + 2) * KT, cur);
+        }
+      };
+      x1_ktile<MODE>(acc, G, rd1, slot);
+    };
+
     // ---- tile start: k-tiles 0 and 1 requested; k-tile 0 has landed everywhere; its first fragments
     conv_prep(0);
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, 0, 0);
     conv_prep(BK);
 #pragma unroll
-    for (int pc = 0; pc < 8; ++pc) dma_piece(pc, BK, STAGE);
+    for (int pc = 0; pc < 8; ++pc) dma_piece(pc, KT, STAGE);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    static_for(std::make_integer_sequence<int, 12>{}, [&](auto Q_) { F0[decltype(Q_)::value] = rd(Q_, fa[0], fb[0]); });
-    __builtin_amdgcn_sched_barrier(0);
-    for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
-    ktile(std::integral_constant<int, 1>{}, nk - 2);
-    ktile(std::integral_constant<int, 2>{}, nk - 1);
+    if constexpr (X1) {
+      static_for(std::make_integer_sequence<int, 6>{}, [&](auto Q_) {
+        constexpr int q = decltype(Q_)::value, tl = x1_frag_tile(q);
+        G[0][q] = frag(x1_frag_is_a(q) ? fa[0][tl] : fb[0][tl], x1_frag_plane(q, 0));
+      });
+      __builtin_amdgcn_sched_barrier(0);
+      for (int kt = 0; kt < nk - 2; ++kt) ktile1(std::integral_constant<int, 0>{}, kt);
+      ktile1(std::integral_constant<int, 1>{}, nk - 2);
+      ktile1(std::integral_constant<int, 2>{}, nk - 1);
+    } else {
+      static_for(std::make_integer_sequence<int, 12>{}, [&](auto Q_) { F0[decltype(Q_)::value] = rd(Q_, fa[0], fb[0]); });
+      __builtin_amdgcn_sched_barrier(0);
+      for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
+      ktile(std::integral_constant<int, 1>{}, nk - 2);
+      ktile(std::integral_constant<int, 2>{}, nk - 1);
+    }
     __syncthreads();
 
     // ---- epilogue: 32 x 32 sub-tiles through a per-wave fp32 scratch (aliases stage 1), 16-byte row-contiguous stores
@@ -445,7 +490,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
 // Grouped entry: descs[0..ngroups) must agree in M, N, K, batch, leading dimensions and strides; only the operand
 // and output pointers differ.  Returns hipErrorNotSupported when the shape does not qualify (caller falls back to
 // one cips_gemm_bf16x3_km per problem).
-extern "C" int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream) {
+template <bool X1>
+static int km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream) {
   if (!descs || ngroups < 1) return (int)hipErrorInvalidValue;
   if (ngroups > MAXG) return (int)hipErrorNotSupported;
   const cips_gemm_x3_desc* d = &descs[0];
@@ -453,11 +499,12 @@ extern "C" int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int n
   if ((d->N & 7) || (d->M & 7) || (d->ldc & 3) || (d->strideC & 3) || (d->K & 31) || (d->lda & 7) || (d->ldb & 7) ||
       (d->strideA & 7) || (d->strideB & 7) || d->M < 256 || d->N < 256)
     return (int)hipErrorNotSupported;
+  if (X1 && ((d->K % X1_BK) || d->K < 2 * X1_BK)) return (int)hipErrorNotSupported;      // whole 64-deep k-tiles, two or more
   KArgs g;
   g.d = *d;
   for (int i = 0; i < ngroups; ++i) {
     const cips_gemm_x3_desc& e = descs[i];
-    if (!e.C || !e.A_hi || !e.A_lo || !e.B_hi || !e.B_lo) return (int)hipErrorInvalidValue;
+    if (!e.C || !e.A_hi || !e.B_hi || (!X1 && (!e.A_lo || !e.B_lo))) return (int)hipErrorInvalidValue;
     if (e.M != d->M || e.N != d->N || e.K != d->K || e.batch != d->batch || e.lda != d->lda || e.ldb != d->ldb ||
         e.ldc != d->ldc || e.strideA != d->strideA || e.strideB != d->strideB || e.strideC != d->strideC)
       return (int)hipErrorNotSupported;
@@ -475,16 +522,26 @@ extern "C" int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int n
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<false, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr = true;
   }
   const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
-  if (d->K >= 2 * BK)                         // else: the one-k-tile form
+  if constexpr (X1)
+    hipLaunchKernelGGL((gemm_bf16x3_km_v3_kernel<false, true>), dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
+  else if (d->K >= 2 * BK)                    // else: the one-k-tile form
     hipLaunchKernelGGL(gemm_bf16x3_km_v3_kernel<false>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
   else
     hipLaunchKernelGGL(gemm_bf16x3_km_wide_kernel<false>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
   return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream) {
+  return km_grouped<false>(descs, ngroups, stream);
+}
+// Single-pass form: hipErrorNotSupported also when K is not a whole number (two or more) of 64-deep k-tiles
+extern "C" int cips_gemm_bf16_km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream) {
+  return km_grouped<true>(descs, ngroups, stream);
 }
 
 // Convolution weight gradient (see include/cips3d_hip.h): part[chunk][tap][o][c] = sum over the chunk's output pixels q

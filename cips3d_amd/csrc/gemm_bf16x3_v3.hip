@@ -59,7 +59,10 @@ struct VArgs {
 // ADDP: the addend (HAS_ADD) arrives as the split planes of a gated tensor plus the bit plane of that gate (descriptor fields
 // addp_*): value = (hi + lo) * (bit ? 1 : addp_gain), same bytes in as the fp32 addend, and no C_unmasked copy is needed by
 // the next layer.
-template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool RGBF = false, bool ADDP = false>
+// X1: the single-pass form (cips_gemm_bf16: sum_k a_hi b_hi, lo operand planes never addressed) — stage contents, fragment
+// numbering and the k-tile schedule x1_ktile are described in gemm_x3_common.h; tile walk, DMA pieces and epilogue are
+// the ones below.  K is a multiple of 128 (an even number of 64-deep k-tiles, at least two).
+template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool RGBF = false, bool ADDP = false, bool X1 = false>
 __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
@@ -67,7 +70,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
   const int lane0 = tid & 63;
   const int uw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = uw >> 1, wn = uw & 1;                     // 4 x 2 waves, 64 x 128 outputs each
-  const int nk = d.K / BK;                                 // even, >= 2
+  constexpr int KT = X1 ? X1_BK : BK;                      // contraction depth of an LDS stage
+  const int nk = d.K / KT;                                 // even, >= 2
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)smem);
 
   auto decode = [&](int t, int& tm, int& tn, int& bz) {
@@ -82,9 +86,15 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
   struct Src { const u16 *Ahi, *Alo, *Bhi, *Blo; unsigned offA[2], offB[2]; };
   auto make_src = [&](int tm, int tn, int bz, int lane, Src& sr) {
     sr.Ahi = (const u16*)d.A_hi + (long long)bz * d.strideA + (long long)tm * BM * d.lda;
-    sr.Alo = (const u16*)d.A_lo + (long long)bz * d.strideA + (long long)tm * BM * d.lda;
-    sr.Bhi = (const u16*)d.B_hi + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
-    sr.Blo = (const u16*)d.B_lo + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
+    if constexpr (X1) {                   // planes 1 and 3 of the stage: the hi planes' second 32 contraction indices
+      sr.Bhi = (const u16*)d.B_hi + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
+      sr.Alo = sr.Ahi + 32;
+      sr.Blo = sr.Bhi + 32;
+    } else {
+      sr.Alo = (const u16*)d.A_lo + (long long)bz * d.strideA + (long long)tm * BM * d.lda;
+      sr.Bhi = (const u16*)d.B_hi + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
+      sr.Blo = (const u16*)d.B_lo + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
+    }
     const int drow = lane >> 2, dslot = lane & 3;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(s0, pc, 0, 0);
 #pragma unroll
-    for (int pc = 0; pc < 8; ++pc) dma_piece(s0, pc, BK, STAGE);
+    for (int pc = 0; pc < 8; ++pc) dma_piece(s0, pc, KT, STAGE);
   }
   int younger = 0;        // lower bound of the VMEM operations issued after the 16 DMA pieces of the coming tile
 
@@ -144,7 +154,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     const unsigned fa0 = sbase + (wm * 64 + l31) * ROWB + ((hf ^ csw) << 4), fa1 = sbase + (wm * 64 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
     const unsigned fb0 = sbase + (wn * 128 + l31) * ROWB + ((hf ^ csw) << 4), fb1 = sbase + (wn * 128 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
 
-    bf16x8 F0[12], F1[12];
+    bf16x8 F0[12], F1[12];        // the 3-pass schedule's two fragment sets
+    bf16x8 G[2][6];               // the single-pass schedule's
 
     // ---- epilogue plumbing declared here: the first inputs are requested inside the last k-tile
     const long long cbase = (long long)bz * d.strideC + (long long)m0 * d.ldc + n0;      // fp32 tensors (ld = ldc)
@@ -258,16 +269,71 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       });
     };
 
+    // ---- single pass: the same three k-tile forms on x1_ktile.  MODE 0 refills this stage behind the barrier; MODE 2 requests
+    // the next output tile's k-tile 0 into the other stage (free since the previous k-tile's barrier) under its first two
+    // k-steps, the first epilogue inputs under the third, and k-tile 1 into this stage behind the barrier
+    auto ktile1 = [&](auto MODE_, int kt) {
+      constexpr int MODE = decltype(MODE_)::value;
+      const unsigned cur = (unsigned)(kt & 1) * STAGE, nxt = STAGE - cur;
+      unsigned ac0 = fa0 + cur, ac1 = fa1 + cur, bc0 = fb0 + cur, bc1 = fb1 + cur, an = fa0 + nxt, bn = fb0 + nxt;
+      asm volatile("" : "+v"(ac0), "+v"(ac1), "+v"(bc0), "+v"(bc1), "+v"(an), "+v"(bn));
+      Src nsrc;
+      if constexpr (MODE == 2) {
+        if (have_next) {
+          int tm2, tn2, bz2;
+          decode(tnext, tm2, tn2, bz2);
+          make_src(tm2, tn2, bz2, lane, nsrc);
+        }
+      }
+      auto rd = [&](auto Q_, auto S_, auto NEXT_) -> bf16x8 {
+        constexpr int q = decltype(Q_)::value, s = decltype(S_)::value;
+        constexpr int off = x1_frag_plane(q, s) + x1_frag_tile(q) * 32 * ROWB;
+        if constexpr (decltype(NEXT_)::value) return LDS_B128((x1_frag_is_a(q) ? an : bn) + off);
+        else return LDS_B128((x1_frag_is_a(q) ? ((s & 1) ? ac1 : ac0) : ((s & 1) ? bc1 : bc0)) + off);
+      };
+      auto slot = [&](auto S_, auto M_) {
+        constexpr int s = decltype(S_)::value, m = decltype(M_)::value;
+        if constexpr (MODE == 0 && s == 3 && m >= 2) {
+#pragma unroll
+          for (int i = 0; i < x1_pieces(m); ++i) dma_piece(src, x1_piece0(m) + i, (kt + 2) * KT, cur);
+        }
+        if constexpr (MODE == 2) {
+          if constexpr (s < 2 && (m & 1) == 0) {
+            if (have_next) dma_piece(nsrc, 4 * s + (m >> 1), 0, 0);
+          }
+          if constexpr (HAS_IN && s == 2 && m < NPF - 1) prefetch(m, pre[m]);
+          if constexpr (s == 3 && m >= 2) {
+            if (have_next) {
+#pragma unroll
+              for (int i = 0; i < x1_pieces(m); ++i) dma_piece(nsrc, x1_piece0(m) + i, KT, STAGE);
+            }
+          }
+        }
+      };
+      x1_ktile<MODE>(acc, G, rd, slot);
+    };
+
     // ---- tile start: k-tile 0 has landed everywhere; its first fragments (the only exposed reads of the tile)
     if (younger >= 24) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");      // 8 pieces of k-tile 1 + >= 24 younger ops stay in flight
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
+    if constexpr (X1) {
+      static_for(std::make_integer_sequence<int, 6>{}, [&](auto Q_) {
+        constexpr int q = decltype(Q_)::value;
+        G[0][q] = LDS_B128((x1_frag_is_a(q) ? fa0 : fb0) + x1_frag_plane(q, 0) + x1_frag_tile(q) * 32 * ROWB);
+      });
+      SB();
+      for (int kt = 0; kt < nk - 2; ++kt) ktile1(std::integral_constant<int, 0>{}, kt);
+      ktile1(std::integral_constant<int, 1>{}, nk - 2);
+      ktile1(std::integral_constant<int, 2>{}, nk - 1);
+    } else {
 #pragma unroll
-    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
-    SB();
-    for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
-    ktile(std::integral_constant<int, 1>{}, nk - 2);
-    ktile(std::integral_constant<int, 2>{}, nk - 1);
+      for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
+      SB();
+      for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
+      ktile(std::integral_constant<int, 1>{}, nk - 2);
+      ktile(std::integral_constant<int, 2>{}, nk - 1);
+    }
 
     // ---- epilogue (order of operations: +add, +rgb term, C_unmasked, gate, act, mask_out, +res, outputs)
     u16* Phi = (u16*)d.P_hi; u16* Plo = (u16*)d.P_lo;
@@ -438,36 +504,37 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
 
 }  // namespace
 
-template <bool A, bool Mk, bool R, bool FAST, bool RGBF = false, bool ADDP = false>
+template <bool X1, bool A, bool Mk, bool R, bool FAST, bool RGBF = false, bool ADDP = false>
 static void launch_v3f(const VArgs& g, int grid, hipStream_t stream) {
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
+  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
 }
-template <bool A, bool Mk, bool R>
+template <bool X1, bool A, bool Mk, bool R>
 static void launch_v3(const VArgs& g, int grid, hipStream_t stream) {
   const cips_gemm_x3_desc& d = g.d;
   // the training step's epilogues take the compile-time form
   const bool fwd = !Mk && d.act == 1 && d.mask_out != nullptr, bwd = Mk && d.act == 0 && d.mask_out == nullptr;
   const bool fast = d.P_hi != nullptr && d.C == nullptr && (fwd || bwd) && (A || d.C_unmasked == nullptr);
   if constexpr (!A && !Mk) {
-    if (d.torgb_w) { launch_v3f<A, Mk, R, true, true>(g, grid, stream); return; }     // the entry point checked `fast`
+    if (d.torgb_w) { launch_v3f<X1, A, Mk, R, true, true>(g, grid, stream); return; }     // the entry point checked `fast`
   }
   if constexpr (A && Mk && !R) {
-    if (d.addp_hi) { launch_v3f<A, Mk, R, true, false, true>(g, grid, stream); return; }   // likewise
+    if (d.addp_hi) { launch_v3f<X1, A, Mk, R, true, false, true>(g, grid, stream); return; }   // likewise
   }
-  if (fast) launch_v3f<A, Mk, R, true>(g, grid, stream);
-  else launch_v3f<A, Mk, R, false>(g, grid, stream);
+  if (fast) launch_v3f<X1, A, Mk, R, true>(g, grid, stream);
+  else launch_v3f<X1, A, Mk, R, false>(g, grid, stream);
 }
 
-// 0: this kernel takes the descriptor; else the error code cips_gemm_bf16x3_v3 returns for it
-static int v3_accepts(const cips_gemm_x3_desc* d) {
+// 0: this kernel takes the descriptor (x1: in its single-pass form); else the error code cips_gemm_bf16x3_v3 / cips_gemm_bf16_v3
+// returns for it
+static int v3_accepts(const cips_gemm_x3_desc* d, bool x1 = false) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return (int)hipErrorInvalidValue;
-  if ((d->M % BM) || (d->N % BN) || (d->K % (2 * BK))) return (int)hipErrorNotSupported;
+  if ((d->M % BM) || (d->N % BN) || (d->K % (2 * (x1 ? X1_BK : BK)))) return (int)hipErrorNotSupported;
   if ((d->lda & 7) || (d->ldb & 7) || (d->strideA & 7) || (d->strideB & 7)) return (int)hipErrorInvalidValue;
   if (d->T_hi || (d->ldc & 3) || (d->strideC & 3) || (d->ldp & 31) || (d->strideP & 31)) return (int)hipErrorNotSupported;
   const bool a = d->add != nullptr || d->addp_hi != nullptr, m = d->mask != nullptr, r = d->res_hi != nullptr;
@@ -489,11 +556,13 @@ static int v3_accepts(const cips_gemm_x3_desc* d) {
   return 0;
 }
 extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_v3_accepts(const cips_gemm_x3_desc* d) { return v3_accepts(d); }
+extern "C" CIPS_INTERNAL int cips_gemm_bf16_v3_accepts(const cips_gemm_x3_desc* d) { return v3_accepts(d, true); }
 
 // Internal entry (called by cips_gemm_bf16x3 ahead of the wide kernel): same descriptor.  hipErrorNotSupported for
 // every shape / epilogue it has no code for.
-extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_v3(const cips_gemm_x3_desc* d, cips_stream_t stream) {
-  { const int rc = v3_accepts(d); if (rc) return rc; }
+template <bool X1>
+static int run_v3(const cips_gemm_x3_desc* d, cips_stream_t stream) {
+  { const int rc = v3_accepts(d, X1); if (rc) return rc; }
   const bool a = d->add != nullptr || d->addp_hi != nullptr, m = d->mask != nullptr, r = d->res_hi != nullptr;
   VArgs g = {};
   g.d = *d;
@@ -505,9 +574,12 @@ extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_v3(const cips_gemm_x3_desc* d, cip
   const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
   hipStream_t st = (hipStream_t)stream;
-  if (a) launch_v3<true, true, false>(g, grid, st);
-  else if (m) launch_v3<false, true, false>(g, grid, st);
-  else if (r) launch_v3<false, false, true>(g, grid, st);
-  else launch_v3<false, false, false>(g, grid, st);
+  if (a) launch_v3<X1, true, true, false>(g, grid, st);
+  else if (m) launch_v3<X1, false, true, false>(g, grid, st);
+  else if (r) launch_v3<X1, false, false, true>(g, grid, st);
+  else launch_v3<X1, false, false, false>(g, grid, st);
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_v3(const cips_gemm_x3_desc* d, cips_stream_t stream) { return run_v3<false>(d, stream); }
+// the single-pass form, called by cips_gemm_bf16 (gemm_bf16x3.hip) ahead of its 256x128 kernel
+extern "C" CIPS_INTERNAL int cips_gemm_bf16_v3(const cips_gemm_x3_desc* d, cips_stream_t stream) { return run_v3<true>(d, stream); }

@@ -59,6 +59,53 @@ __device__ __forceinline__ constexpr int x3_frag_off_nt(int q) { return x3_frag_
 __device__ __forceinline__ constexpr int x3_mfma_a(int m) { return (m >> 3) == 0 ? (((m >> 2) & 1) ? 5 : 0) : (((m >> 2) & 1) ? 11 : 6); }
 __device__ __forceinline__ constexpr int x3_mfma_b(int m) { return (m >> 3) == 1 ? 7 + (m & 3) : 1 + (m & 3); }
 
+// ---- single-pass ("bf16") forms of the 256x256 kernels: sum_k a_hi b_hi only, the lo planes are never addressed.
+// The LDS stage keeps its four 16 KiB planes, DMA pieces, swizzle and fragment reads; what changes is what the planes hold —
+// A_hi[k0, k0+32), A_hi[k0+32, k0+64), B_hi[k0, k0+32), B_hi[k0+32, k0+64) — so a stage is a 64-deep k-tile of four
+// 16-deep k-steps: k-step s reads planes (s >> 1) and (2 + (s >> 1)), k-chunk pair s & 1.  A k-step is 8 MFMAs (output
+// tile (m >> 2, m & 3)) on 6 fragments, numbered in the order the MFMA stream first needs them:
+//   0: a[0]   1..4: b[0..3]   5: a[1]
+constexpr int X1_BK = 64;
+__device__ __forceinline__ constexpr bool x1_frag_is_a(int q) { return q == 0 || q == 5; }
+__device__ __forceinline__ constexpr int x1_frag_tile(int q) { return q == 0 ? 0 : q == 5 ? 1 : q - 1; }
+__device__ __forceinline__ constexpr int x1_frag_plane(int q, int s) { return ((x1_frag_is_a(q) ? 0 : 2) + (s >> 1)) * X3_PLANE_BYTES; }
+__device__ __forceinline__ constexpr int x1_mfma_a(int m) { return (m >> 2) ? 5 : 0; }
+__device__ __forceinline__ constexpr int x1_mfma_b(int m) { return 1 + (m & 3); }
+// first DMA piece and number of pieces behind MFMA m = 2..7 of a k-tile's last k-step (eight pieces in six slots)
+__device__ __forceinline__ constexpr int x1_piece0(int m) { return m == 2 ? 0 : m == 3 ? 2 : m == 4 ? 3 : m == 5 ? 4 : m == 6 ? 6 : 7; }
+__device__ __forceinline__ constexpr int x1_pieces(int m) { return (m == 2 || m == 5) ? 2 : 1; }
+
+// One 64-deep k-tile of the single-pass schedule: 32 MFMAs on two fragment sets G[0] / G[1] (k-step s multiplies set s & 1
+// while the six fragments of k-step s + 1 are read into the other, one per MFMA).  The k-tile's one barrier stands behind the
+// second MFMA of the last k-step: every wave has then received all its fragments of this stage, so the barrier publishes the
+// other stage (its DMA pieces were issued a k-tile period ago and are waited for here) and frees this one; the first k-step
+// of the next k-tile is read behind it, two fragments per MFMA.  MODE 0: steady state; 1: next-to-last k-tile (same, the
+// kernel's `slot` issues no DMA); 2: last (no next k-tile to read or wait for).
+//   rd(q, s, next): fragment q of k-step s from this stage (next = false) or the other one (true)
+//   slot(s, m): the kernel's own work behind MFMA m of k-step s (DMA pieces, epilogue prefetch)
+template <int MODE, typename Rd, typename Slot>
+__device__ __forceinline__ void x1_ktile(f32x16 (&acc)[2][4], bf16x8 (&G)[2][6], Rd&& rd, Slot&& slot) {
+  static_for(std::make_integer_sequence<int, 32>{}, [&](auto T_) {
+    constexpr int t = decltype(T_)::value, s = t >> 3, m = t & 7;
+    acc[m >> 2][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(G[s & 1][x1_mfma_a(m)], G[s & 1][x1_mfma_b(m)], acc[m >> 2][m & 3], 0, 0, 0);
+    if constexpr (s < 3) {
+      if constexpr (m < 6) G[(s + 1) & 1][m] = rd(std::integral_constant<int, m>{}, std::integral_constant<int, s + 1>{}, std::false_type{});
+    } else {
+      if constexpr (m == 1) {
+        if constexpr (MODE == 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      }
+      if constexpr (MODE <= 1 && m >= 2 && m <= 4) {
+        constexpr int q = 2 * (m - 2);
+        G[0][q] = rd(std::integral_constant<int, q>{}, std::integral_constant<int, 0>{}, std::true_type{});
+        G[0][q + 1] = rd(std::integral_constant<int, q + 1>{}, std::integral_constant<int, 0>{}, std::true_type{});
+      }
+    }
+    slot(std::integral_constant<int, s>{}, std::integral_constant<int, m>{});
+    __builtin_amdgcn_sched_barrier(0);
+  });
+}
+
 // Persistent grids: one workgroup per CU, the CU count rounded down to a multiple of 8 so that a workgroup striding by the
 // grid size stays on its XCD.  256 if the device properties cannot be read.
 static inline int cips_persistent_cus() {

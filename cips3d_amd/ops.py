@@ -972,7 +972,17 @@ class InrHeadFunction(torch.autograd.Function):
 # H4 on the bf16 matrix cores: 3-pass split GEMM ("bf16x3"), see csrc/gemm_bf16x3.hip
 # --------------------------------------------------------------------------------------
 import os as _os
-INR_MODE = _os.environ.get("CIPS_INR_MODE", "bf16x3")   # "bf16x3" (default, ~1e-5 rel. per layer) or "f32" (exact fp32 MFMA)
+# "bf16x3" (default, ~1e-5 rel. per layer), "f32" (exact fp32 MFMA) or "bf16" (single pass on the hi planes: the AMP-class
+# arithmetic — operands rounded to bf16, fp32 accumulate; ~1e-3 of the image range, ~1 % of the gradients — on one third of
+# the matrix work; every GEMM of the head, forward and backward, through the cips_gemm_bf16* entry points).  Read when a head
+# evaluation starts: a captured graph keeps the mode it was captured in.
+INR_MODE = _os.environ.get("CIPS_INR_MODE", "bf16x3")
+
+
+def _x3_entry(single, suffix=""):
+    """the split-plane GEMM entry point `suffix` of the 3-pass family or, with `single`, of the single-pass one"""
+    name = ("cips_gemm_bf16" if single else "cips_gemm_bf16x3") + suffix
+    return name, getattr(_lib.load(), name)
 BF = torch.bfloat16
 # The head's weight-gradient tail (style / modulated-weight gradients of all layers, ToRGB weight gradients: ~0.75 ms of streaming
 # kernels at C2) depends on nothing that follows the head in the backward pass.  "side": it hangs off the head through two
@@ -1028,52 +1038,53 @@ def _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C=None, P=None, 
 _ADDP_OK = {}
 
 
-def _addp_shape_ok(n, cin, cout, nb, dev):
-    """does the library take the planes addend at this shape?  (a property of the shape and of the kernel selector: asked
-    once per shape with stand-in pointers — the query reads only shapes, flags and pointer alignment)"""
-    key = (n, cin, cout, nb, dev.index, X3_KERNEL)
+def _addp_shape_ok(n, cin, cout, nb, dev, single=False):
+    """does the library take the planes addend at this shape?  (a property of the shape, of the kernel selector and of the
+    kernel family: asked once per shape with stand-in pointers — the query reads only shapes, flags and pointer alignment)"""
+    key = (n, cin, cout, nb, dev.index, X3_KERNEL, single)
     ok = _ADDP_OK.get(key)
     if ok is None:
         gq = Planes.empty(1, 8, 8, device=dev)
         ok = _ADDP_OK[key] = gemm_x3_takes_addp(gq, gq, n, cin, cout, cout, cout, nb, n * cout, cin * cout, P=gq,
-                                                addp=(gq, gq.hi), mask=gq.hi, gate_bits=1)
+                                                addp=(gq, gq.hi), mask=gq.hi, gate_bits=1, single=single)
     return ok
 
 
-def gemm_x3_takes_addp(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi):
+def gemm_x3_takes_addp(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **epi):
     """True when the library runs this descriptor with the planes addend (256x256-tile kernel, interior shapes)"""
-    lib = _lib.load()
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi)
-    return bool(lib.cips_gemm_bf16x3_takes_addp(_ct.byref(d)))
+    return bool(_x3_entry(single, "_takes_addp")[1](_ct.byref(d)))
 
 
-def gemm_x3(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi):
-    """C[b][m][n] = epi(sum_k A[b][m][k] * B[b][n][k]); A, B, P, T, res: Planes; row-major aux use ld = N."""
-    lib = _lib.load()
+def gemm_x3(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **epi):
+    """C[b][m][n] = epi(sum_k A[b][m][k] * B[b][n][k]); A, B, P, T, res: Planes; row-major aux use ld = N.
+    single: sum_k A_hi * B_hi only (cips_gemm_bf16; here and in the functions below)"""
+    name, fn = _x3_entry(single)
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi)
-    check(lib.cips_gemm_bf16x3(_ct.byref(d), _stream()), "cips_gemm_bf16x3")
+    check(fn(_ct.byref(d), _stream()), name)
 
 
-def gemm_x3_torgb(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P, rgb_w, rgb_b, rgb2d, accumulate, **epi):
+def gemm_x3_torgb(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P, rgb_w, rgb_b, rgb2d, accumulate, single=False, **epi):
     """gemm_x3 with planes output P followed by ToRGB forward on it (rgb2d (batch*M, 3) (+)= P . rgb_w^T + rgb_b):
     folded into the GEMM epilogue when the library's 256x256-tile kernel takes the shape (partials per 128-column
     block + one finishing launch), else the ToRGB kernel on the written planes."""
     lib = _lib.load()
+    name, fn = _x3_entry(single)
     part = torch.empty(max(N // 128, 1), batch * M, 4, device=P.hi.device)
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P=P, torgb=(rgb_w, part), **epi)
-    if N % 128 == 0 and rgb_w.is_contiguous() and lib.cips_gemm_bf16x3_fuses_torgb(_ct.byref(d)):
-        check(lib.cips_gemm_bf16x3(_ct.byref(d), _stream()), "cips_gemm_bf16x3")
+    if N % 128 == 0 and rgb_w.is_contiguous() and _x3_entry(single, "_fuses_torgb")[1](_ct.byref(d)):
+        check(fn(_ct.byref(d), _stream()), name)
         check(lib.cips_torgb_finish(_p(part), N // 128, _p(rgb_b), _p(rgb2d), batch * M, 1 if accumulate else 0, _stream()),
               "cips_torgb_finish")
         return
     d.torgb_w, d.torgb_part = None, None
-    check(lib.cips_gemm_bf16x3(_ct.byref(d), _stream()), "cips_gemm_bf16x3")
+    check(fn(_ct.byref(d), _stream()), name)
     torgb_fwd_x3(P, rgb_w, rgb_b, rgb2d, accumulate)
 
 
-def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C):
+def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C, single=False):
     """C[b][m][n] = sum_k A[b][k][m] * B[b][k][n]; A, B: Planes stored [K][ld] (k-major), C fp32 (M,N)."""
-    lib = _lib.load()
+    name, fn = _x3_entry(single, "_km")
     d = GemmX3Desc()
     d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
     d.M, d.N, d.K, d.lda, d.ldb = M, N, K, lda, ldb
@@ -1081,13 +1092,13 @@ def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C):
     d.C, d.ldc, d.strideC = _p(C), N, M * N
     d.slope = LRELU_SLOPE
     d.kernel = X3_KERNEL
-    check(lib.cips_gemm_bf16x3_km(_ct.byref(d), _stream()), "cips_gemm_bf16x3_km")
+    check(fn(_ct.byref(d), _stream()), name)
 
 
-def gemm_x3_km_grouped(problems, M, N, K, lda, ldb, batch, strideA, strideB):
+def gemm_x3_km_grouped(problems, M, N, K, lda, ldb, batch, strideA, strideB, single=False):
     """problems: list of (A Planes, B Planes, C fp32) of one shape -> one launch when the library supports the shape
     (256x256 tiles), else one K-major GEMM per problem."""
-    lib = _lib.load()
+    name, fn = _x3_entry(single, "_km_grouped")
     descs = (GemmX3Desc * len(problems))()
     for d, (A, Bm, C) in zip(descs, problems):
         d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
@@ -1096,12 +1107,12 @@ def gemm_x3_km_grouped(problems, M, N, K, lda, ldb, batch, strideA, strideB):
         d.C, d.ldc, d.strideC = _p(C), N, M * N
         d.slope = LRELU_SLOPE
         d.kernel = X3_KERNEL
-    rc = lib.cips_gemm_bf16x3_km_grouped(descs, len(problems), _stream())
+    rc = fn(descs, len(problems), _stream())
     if rc == 801:      # hipErrorNotSupported
         for (A, Bm, C) in problems:
-            gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C)
+            gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C, single=single)
         return
-    check(rc, "cips_gemm_bf16x3_km_grouped")
+    check(rc, name)
 
 
 def split_planes(x, want_p=True, want_t=True):
@@ -1454,21 +1465,21 @@ def _sum_split(part, out):
         torch.sum(part.view(out.shape[0], -1, *out.shape[1:]), dim=1, out=out)
 
 
-def _wgrad_km(A, G, out, n, ksp, defer=False):
+def _wgrad_km(A, G, out, n, ksp, defer=False, single=False):
     """out[b] (M, N) = A[b]^T G[b] over the n pixels of image b (A (nb, n, M), G (nb, n, N) row-major Planes) on the K-major
     GEMM, the pixel range split in `ksp` parts — a pure view, (nb, n, C) -> (nb*ksp, n/ksp, C).  The partial products are
     summed into `out` here, or with `defer` by the caller's _sum_split of what this returns."""
     nb, M, N = out.shape
     part = _split_parts(out, ksp)
     nk = n // ksp
-    gemm_x3_km(A, G, M, N, nk, M, N, nb * ksp, nk * M, nk * N, part)
+    gemm_x3_km(A, G, M, N, nk, M, N, nb * ksp, nk * M, nk * N, part, single=single)
     if defer:
         return part
     _sum_split(part, out)
     return out
 
 
-def _head_wgrad(L, gP, g1P, gwb1, gwb2, n):
+def _head_wgrad(L, gP, g1P, gwb1, gwb2, n, single=False):
     """the per-image weight gradients of one block: dWb2 = a1^T g, dWb1 = x^T g1.  Each contracts over the n pixels of one
     image; with few images per GPU a 512x512 output is too few tiles for the chip, so the pixel range is split in parts and
     the partial products are summed."""
@@ -1477,23 +1488,26 @@ def _head_wgrad(L, gP, g1P, gwb1, gwb2, n):
     if cin == cout:
         part2, part1 = _split_parts(gwb2, ksp), _split_parts(gwb1, ksp)
         nk = n // ksp
-        gemm_x3_km_grouped([(L.a1P, gP, part2), (L.xP, g1P, part1)], cout, cout, nk, cout, cout, nb * ksp, nk * cout, nk * cout)
+        gemm_x3_km_grouped([(L.a1P, gP, part2), (L.xP, g1P, part1)], cout, cout, nk, cout, cout, nb * ksp, nk * cout, nk * cout,
+                           single=single)
     else:
         # the block's square problem alone is half a chip of 256 x 256 tiles: two pixel halves fill it
         tiles = (cout + 255) // 256
         ksp2 = _pixel_split(n, ksp, lambda s: nb * s * tiles * tiles < 192)
-        part2 = _wgrad_km(L.a1P, gP, gwb2, n, ksp2, defer=ksp2 == ksp)
+        part2 = _wgrad_km(L.a1P, gP, gwb2, n, ksp2, defer=ksp2 == ksp, single=single)
         # a narrow first layer (cin = 32: one row tile, 2 column tiles per image = 64 workgroups) streams the whole gradient
         # plane through a quarter of the chip: split its pixel range further
         ksp1 = _pixel_split(n, ksp, lambda s: cin <= 128 and nb * s * tiles < 192)
-        part1 = _wgrad_km(L.xP, g1P, gwb1, n, ksp1, defer=ksp1 == ksp)
+        part1 = _wgrad_km(L.xP, g1P, gwb1, n, ksp1, defer=ksp1 == ksp, single=single)
     # partials of the common split `ksp` are summed here, dWb2 first (those of a split of its own right after their GEMM)
     _sum_split(part2, gwb2)
     _sum_split(part1, gwb1)
 
 
 class InrHeadX3Function(torch.autograd.Function):
-    """Same contract as InrHeadFunction, on the bf16x3 GEMM.  Every activation / gradient lives in HBM as row-major bf16
+    """Same contract as InrHeadFunction, on the split-plane GEMMs: 3 passes (INR_MODE "bf16x3") or, in INR_MODE "bf16", the
+    single pass on the hi planes for every GEMM of the forward and of the backward (the mode of the forward holds for its
+    backward).  Every activation / gradient lives in HBM as row-major bf16
     hi/lo planes written by the producing GEMM's epilogue: the A operand of the next forward GEMM and of the dX GEMM, read
     k-major by the weight-gradient GEMMs.
 
@@ -1508,6 +1522,7 @@ class InrHeadX3Function(torch.autograd.Function):
         if n % 32 or in0 % 32:
             raise RuntimeError("bf16x3 INR path needs pixels per image and feature width to be multiples of 32")
         dev = x0.device
+        sp = ctx.single = INR_MODE == "bf16"
         blocks = [tuple(_c(p.detach()) for p in params[4 * k:4 * k + 4]) for k in range(nblocks)]
         # (T, tau) of the ToRGB tap of every block k >= 3; what follows them are the ports' handles
         rgbp = [_c(p.detach()) for p in params[4 * nblocks:4 * nblocks + 2 * max(nblocks - 3, 0)]]
@@ -1556,24 +1571,24 @@ class InrHeadX3Function(torch.autograd.Function):
             res = L.xP if L.skip else None
             if L.pinned1:
                 # pinned: `gate ? 1 : slope` from the supplied plane in place of the LeakyReLU on the computed sign
-                gemm_x3(L.xP, wbt1, n, cout, cin, cin, cin, B, n * cin, cout * cin, P=L.a1P, mask=L.gate1, gate_bits=1)
+                gemm_x3(L.xP, wbt1, n, cout, cin, cin, cin, B, n * cin, cout * cin, P=L.a1P, mask=L.gate1, gate_bits=1, single=sp)
             else:
                 gemm_x3(L.xP, wbt1, n, cout, cin, cin, cin, B, n * cin, cout * cin, P=L.a1P, act=1,
-                        mask_out=L.gate1 if L.bits else None, gate_bits=2 if L.bits else 0)
+                        mask_out=L.gate1 if L.bits else None, gate_bits=2 if L.bits else 0, single=sp)
             mod2 = (L.a1P, wbt2, n, cout, cout, cout, cout, B, n * cout, cout * cout)
             if L.pinned2:
-                gemm_x3(*mod2, P=L.oP, res=res, mask=L.gate2, gate_bits=1)
+                gemm_x3(*mod2, P=L.oP, res=res, mask=L.gate2, gate_bits=1, single=sp)
             elif L.bits and k >= 3:
                 gemm_x3_torgb(*mod2, L.oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb.view(B * n, 3), not first_rgb,
-                              act=1, res=res, mask_out=L.gate2, gate_bits=2)
+                              act=1, res=res, mask_out=L.gate2, gate_bits=2, single=sp)
                 first_rgb = False
                 continue
             elif L.bits:
-                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2, gate_bits=2)
+                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2, gate_bits=2, single=sp)
             elif L.skip:
-                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2)
+                gemm_x3(*mod2, P=L.oP, act=1, res=res, mask_out=L.gate2, single=sp)
             else:
-                gemm_x3(*mod2, P=L.oP, act=1)
+                gemm_x3(*mod2, P=L.oP, act=1, single=sp)
             if k >= 3:
                 torgb_fwd_x3(L.oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb.view(B * n, 3), accumulate=not first_rgb)
                 first_rgb = False
@@ -1597,6 +1612,8 @@ class InrHeadX3Function(torch.autograd.Function):
         layers, blocks, rgbp, ports = ctx.layers, ctx.blocks, ctx.rgbp, ctx.ports
         nblocks = len(layers)
         B, n = ctx.dims
+        sp = ctx.single
+        fam = {"single": True} if sp else {}       # the default mode calls the two helpers below exactly as before
         drgb = _c(drgb)
         dev = drgb.device
         drgb2 = drgb.reshape(B * n, 3)
@@ -1608,7 +1625,7 @@ class InrHeadX3Function(torch.autograd.Function):
         # the skip gradient D (un-gated) is either kept as an fp32 copy next to the gated planes every GEMM writes
         # for its successors, or — when every layer has bit-plane gates and the 256x256-tile kernel takes the shapes —
         # recovered from those planes by the consumer: no copy written, same bytes read
-        addp = all(L.bits for L in layers) and all(_addp_shape_ok(n, L.cin, L.cout, B, dev) for L in layers[1:] if L.skip)
+        addp = all(L.bits for L in layers) and all(_addp_shape_ok(n, L.cin, L.cout, B, dev, **fam) for L in layers[1:] if L.skip)
         k, L = nblocks - 1, layers[-1]
         Dout = None
         if k >= 3 and L.bits and width % 8 == 0:
@@ -1623,7 +1640,7 @@ class InrHeadX3Function(torch.autograd.Function):
             dP, _ = split_planes(dpad, want_t=False)
             Dout = torch.empty(B, n, width, device=dev) if L.skip and not addp else None
             gemm_x3(dP, tP, n, width, 32, 32, 32, B, n * 32, 0, P=gP, C_unmasked=Dout, mask=L.gate2,
-                    gate_bits=1 if L.bits else 0)
+                    gate_bits=1 if L.bits else 0, single=sp)
         else:
             gP.hi.zero_(); gP.lo.zero_()
             Dout = torch.zeros(B, n, width, device=dev) if L.skip and not addp else None
@@ -1639,10 +1656,10 @@ class InrHeadX3Function(torch.autograd.Function):
             # ---- mod2: gradient through the gate of a1 ----
             g1P = Planes.empty(B, n, cout, device=dev)
             gemm_x3(gP, L.wb2, n, cout, cout, cout, cout, B, n * cout, cout * cout, P=g1P, mask=L.gate1,
-                    gate_bits=1 if L.bits else 0)
-            _head_wgrad(L, gP, g1P, *gwb[k], n)
+                    gate_bits=1 if L.bits else 0, single=sp)
+            _head_wgrad(L, gP, g1P, *gwb[k], n, **fam)
             if k == 0:
-                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, C=dx0)
+                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, C=dx0, single=sp)
             else:
                 prev = layers[k - 1]
                 newD = torch.empty(B, n, cin, device=dev) if prev.skip and not addp else None
@@ -1650,7 +1667,7 @@ class InrHeadX3Function(torch.autograd.Function):
                 gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, P=gP,
                         add=Dout if L.skip and not addp else None, addp=(gP_in, L.gate2) if L.skip and addp else None,
                         rgb_g=drgb2 if k - 1 >= 3 else None, rgb_w=rgbp[2 * (k - 1 - 3)] if k - 1 >= 3 else None,
-                        C_unmasked=newD, mask=prev.gate2, gate_bits=1 if prev.bits else 0)
+                        C_unmasked=newD, mask=prev.gate2, gate_bits=1 if prev.bits else 0, single=sp)
                 Dout = newD
         if ports is not None:
             _TAIL_GATE[dev.index] = ports        # armed: the next compositing backward publishes its event to the ports
@@ -1764,7 +1781,7 @@ def _tail_gate_publish(dev):
 
 def inr_head_ports_ok(nblocks, B, n, in0, params, dev):
     """the gradient-port form applies: split-bf16 head in training, batch within the co-resident kernels' limit, ToRGB taps present"""
-    return (INR_TAIL == "side" and INR_MODE == "bf16x3" and torch.device(dev).type == "cuda" and torch.is_grad_enabled()
+    return (INR_TAIL == "side" and INR_MODE in ("bf16x3", "bf16") and torch.device(dev).type == "cuda" and torch.is_grad_enabled()
             and nblocks > 3 and n % 32 == 0 and in0 % 32 == 0 and B <= 64 and any(t.requires_grad for t in params))
 
 
@@ -1787,9 +1804,9 @@ def inr_head_with_ports(nblocks, x0, params, ports):
 
 
 def inr_head(nblocks, x0, *params):
-    # the split-bf16 kernels tile pixels and features by 32; anything else (part_grad_forward with an arbitrary
-    # grad_points, generator.py:1591-1593) runs on the exact fp32 MFMA path, which has no such granule
-    x3 = INR_MODE == "bf16x3" and x0.shape[1] % 32 == 0 and x0.shape[2] % 32 == 0
+    # the split-bf16 kernels (both pass counts) tile pixels and features by 32; anything else (part_grad_forward with an
+    # arbitrary grad_points, generator.py:1591-1593) runs on the exact fp32 MFMA path, which has no such granule
+    x3 = INR_MODE in ("bf16x3", "bf16") and x0.shape[1] % 32 == 0 and x0.shape[2] % 32 == 0
     fn = InrHeadX3Function if x3 else InrHeadFunction
     # the caller's grad mode: under torch.no_grad() nothing is kept for a backward
     return fn.apply(nblocks, torch.is_grad_enabled(), None, x0, *params)

@@ -333,6 +333,19 @@ int cips_gemm_bf16x3_km(const cips_gemm_x3_desc* d, cips_stream_t stream);
  * issue them one by one with cips_gemm_bf16x3_km then. */
 int cips_gemm_bf16x3_km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream);
 
+/* Single-pass forms of the five entry points above ("bf16": the AMP-class arithmetic, operands rounded to bf16, fp32
+ * accumulate):  sum_k A_hi * B_hi  only.  Same descriptor, same validation and return codes, same epilogues on the fp32
+ * accumulator, same hi / lo OUTPUT planes; A_lo and B_lo are ignored and may be NULL.  No 3-pass kernel is ever used: the NT
+ * form runs on the 256x256-tile kernel (interior shapes with K % 128 == 0; the only one with the fused ToRGB partials and the
+ * planes addend, as the queries report) or on the 256x128 kernel, the K-major forms on the 256x256-tile kernel (K % 64 == 0,
+ * K >= 128; the grouped entry returns hipErrorNotSupported otherwise) or on the 256x128 / 128x128 kernels.  Relative error
+ * of a product sum ~2^-9 per operand: three orders of magnitude coarser than cips_gemm_bf16x3. */
+int cips_gemm_bf16(const cips_gemm_x3_desc* d, cips_stream_t stream);
+int cips_gemm_bf16_fuses_torgb(const cips_gemm_x3_desc* d);
+int cips_gemm_bf16_takes_addp(const cips_gemm_x3_desc* d);
+int cips_gemm_bf16_km(const cips_gemm_x3_desc* d, cips_stream_t stream);
+int cips_gemm_bf16_km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t stream);
+
 /* Implicit-GEMM convolution on the split-bf16 NT kernel (EqualConv2d forward, exp/cips3d/models/discriminator.py:40-48,
  * and — with the flipped, transposed weights — its data gradient at stride 1):
  *   y[b][o][oy*Wo+ox] = sum_{ky,kx,c} w[o][(ky*kw+kx)*C + c] * x[b][oy*stride-pad+ky][ox*stride-pad+kx][c]
