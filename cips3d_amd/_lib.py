@@ -190,7 +190,6 @@ SIGNATURES = {
     "cips_upfirdn2d": (i32, [vp, vp, vp] + [i32] * 14 + [vp]),
     "cips_upfirdn2d_parity": (i32, [vp, C.POINTER(i64 * 4), vp, vp] + [i32] * 7 + [vp]),
     "cips_im2col": (i32, [vp, vp] + [i32] * 8 + [vp]),
-    "cips_im2col_x3": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cips_col2im": (i32, [vp, vp] + [i32] * 8 + [vp]),
 }
 

@@ -6,9 +6,11 @@ Native ops, same contracts as the reference's CUDA extensions (exp/comm/op/fused
 exp/comm/op/upfirdn2d.py) but backed by libcips3d_hip.so:
   * fused_leaky_relu / FusedLeakyReLU   -> cips_fused_bias_act (fwd, bwd, double-bwd)
   * upfirdn2d (Blur)                     -> cips_upfirdn2d      (fwd, bwd, double-bwd)
-  * EqualConv2d                          -> cips_im2col + cips_gemm_f32 (fp32 MFMA) + cips_col2im,
-                                            as three mutually-recursive autograd Functions so the R1
-                                            double-backward of train.py:387-394 works.
+  * EqualConv2d                          -> one of three forms per shape (_conv_forms): the streaming RGB kernels
+                                            (cips_conv1x1_smallk*), the split-bf16 implicit-GEMM family
+                                            (cips_conv2d_x3 / _dgrad_s2 / _wgrad), or exact fp32 (cips_im2col +
+                                            cips_gemm_f32 + cips_col2im); three mutually-recursive autograd Functions
+                                            so the R1 double-backward of train.py:387-394 works.
 """
 import collections
 import math
@@ -186,65 +188,57 @@ def upfirdn2d(input, kernel, up=1, down=1, pad=(0, 0)):
 
 
 # ------------------------------------------------------------------------------------------
-# conv2d on the fp32 MFMA GEMM (replaces F.conv2d in EqualConv2d.forward, discriminator.py:40-48)
+# conv2d (replaces F.conv2d in EqualConv2d.forward, discriminator.py:40-48) in three forms, chosen per shape by _conv_forms:
+#   rgb       the RGB input convolutions (1 x 1, at most 4 input channels): streaming kernels, no GEMM (cips_conv1x1_smallk*);
+#   implicit  3-pass split-bf16 MFMA (~5e-6 relative, ~3x the fp32 MFMA rate) as an implicit GEMM: the activation is transposed
+#             once into NHWC split planes and the GEMM's loader gathers the taps.  cips_conv2d_x3 is the forward and the stride-1
+#             data gradient (any plane size: planes of fewer than 256 pixels run with the batch folded into the pixel dimension),
+#             cips_conv2d_x3_wgrad the weight gradient, and cips_conv2d_x3_dgrad_s2 ("parity") the data gradient of a stride-2
+#             convolution behind a Blur, as four stride-1 sub-convolutions, one per parity class of the input pixel;
+#   f32       exact fp32: cips_im2col + cips_gemm_f32 (fp32 MFMA) + cips_col2im — every shape the other two do not take, and
+#             every GEMM convolution when CIPS_D_CONV_MODE=f32.
 # ------------------------------------------------------------------------------------------
 def _pad4(n):
     return (n + 3) // 4 * 4
 
 
-# Conv GEMMs of eligible layers run as 3-pass split-bf16 MFMA (cips_gemm_bf16x3*, ~5e-6 relative, ~3x the fp32 MFMA
-# rate); CIPS_D_CONV_MODE=f32 keeps every layer on the exact fp32 MFMA GEMM.  Eligible: all three contraction lengths
-# (C*kh*kw, Ho*Wo, O) multiples of 32 — i.e. everything but the RGB input convs and the 4x4 tail.
 import os as _os
 CONV_MODE = _os.environ.get("CIPS_D_CONV_MODE", "bf16x3")
 
 
-def _x3_ok(K, N, O):
-    return CONV_MODE == "bf16x3" and K % 32 == 0 and N % 32 == 0 and O % 32 == 0
+def _implicit_channels_ok(C, O):
+    """the implicit-GEMM kernels contract over 32-channel k-tiles and write 32-channel tiles"""
+    return C % 32 == 0 and O % 32 == 0
 
 
-# Implicit-GEMM form of the x3 convs (CIPS_D_CONV_IMPLICIT=0 keeps the materialised im2col everywhere): the activation is
-# transposed once into NHWC split planes and the NT GEMM's loader gathers the taps; used from 16x16 output planes up
-# (smaller planes leave most of a 256-pixel tile empty).
+def _parity_channels_ok(C, O):
+    """cips_conv2d_x3_dgrad_s2 contracts over O: two k-tiles at least (the single-tap parity class has no more); C in 8-channel vectors"""
+    return O % 32 == 0 and O >= 64 and C % 8 == 0
 
 
-# Small output planes (8x8, 4x4: fewer than 256 pixels per image): the batch is folded into the pixel dimension, one
-# GEMM over B*Ho*Wo columns with the shared weights instead of B GEMMs whose 16- or 64-column tiles are mostly padding
-# (the 4x4 layers spent 14 ms per GAN step in the fp32 GEMM for 5 GFLOP).  CIPS_D_CONV_FOLD=0 restores that.
-
-
-def _fold_ok(K, N, B, O):
-    return CONV_MODE == "bf16x3" and N < 256 and (B * N) % 32 == 0 and K % 32 == 0 and O % 32 == 0
-
-
-def _split_count(tiles, length):
-    """Folded GEMMs are single problems of few 256x128 tiles (16 for a 4x4 plane): cut the contraction (`length` rows,
-    in 32-row k-tiles) into chunks that become the GEMM's batch, partial sums added by the caller."""
-    n = 1
-    while tiles * n < 192 and length % (64 * n) == 0 and length // (2 * n) >= 128:
-        n *= 2
-    return n
-
-
-def _folded_col_planes(x, kh, kw, stride, pad):
-    """im2col with the batch folded into the columns: Planes (1, K, B*N), k-major"""
-    col, Ho, Wo = ops.im2col(x, kh, kw, stride, pad)                  # (B, K, N) fp32
-    B, K, N = col.shape
-    colP, _ = ops.split_planes(col.permute(1, 0, 2).reshape(1, K, B * N).contiguous(), want_p=True, want_t=False)
-    return colP, Ho, Wo
-
-
-def _folded_rows_planes(t):
-    """(B, O, Ho, Wo) -> Planes (1, O, B*N)"""
-    B, O = t.shape[0], t.shape[1]
-    P, _ = ops.split_planes(t.reshape(B, O, -1).permute(1, 0, 2).reshape(1, O, -1).contiguous(), want_p=True, want_t=False)
-    return P
-
-
-def _implicit_ok(C, N, O):
-    # any plane size: output planes of fewer than 256 pixels (8 x 8, 4 x 4) run with the batch folded into the pixel
-    # dimension of the same kernel (round 6; before, im2col + a K-major GEMM + col2im and their permuting copies)
-    return CONV_MODE == "bf16x3" and C % 32 == 0 and O % 32 == 0 and N % 8 == 0
+def _conv_forms(x_shape, w_shape, stride, pad, pre=None):
+    """THE dispatch rule of y = conv(Blur(x), w): which form the forward, the data gradient and the weight gradient of a
+    (B, C, H, W) input under an (O, C, kh, kw) filter bank take -> three names out of "rgb" / "implicit" / "parity" / "f32".
+    Shapes and CONV_MODE only.  `pre` is the folded Blur (see below; only its pads and its sampling stride are read): the
+    convolution proper then runs on the blurred (Hb, Wb) map, and a data gradient that is not "parity" is the un-blurred
+    convolution's, followed by the Blur's transpose.  An "implicit" weight gradient is still declined by
+    ops.conv2d_x3_wgrad when ops.conv2d_x3_wgrad_declines(B, Ho * Wo), and is then computed in the f32 form."""
+    B, C, H, W = x_shape
+    O, _, kh, kw = w_shape
+    x3 = CONV_MODE == "bf16x3"
+    Hb, Wb = _pre_shape(H, W, pre)
+    Ho, Wo = (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
+    planes8 = Ho > 0 and Wo > 0 and (Ho * Wo) % 8 == 0             # output planes in 8-pixel vectors
+    rgb = kh == 1 and kw == 1 and stride == 1 and pad == 0 and C <= 4 and (Hb * Wb) % 4 == 0
+    fallback = "rgb" if rgb else "f32"
+    fwd = wgrad = "implicit" if x3 and _implicit_channels_ok(C, O) and planes8 else fallback
+    if pre is not None and pre[3] == 1 and stride == 2 and pad == 0 and x3 and _parity_channels_ok(C, O) and planes8:
+        dgrad = "parity"
+    elif stride == 1 and kh - 1 - pad >= 0 and x3 and _implicit_channels_ok(O, C) and (Hb * Wb) % 8 == 0:
+        dgrad = "implicit"            # dx = conv(dy, flipped weights with the channel roles swapped), padding kh - 1 - pad
+    else:
+        dgrad = fallback
+    return fwd, dgrad, wgrad
 
 
 # NHWC planes of an activation / gradient are shared between the convolution ops that read the same tensor inside ONE
@@ -418,7 +412,7 @@ def _pre_adjoint(dxb, pre, in_shape):
 # split_planes launches per GAN step).  They are cached per nn.Parameter and invalidated by the tensor's version
 # counter (bumped by every in-place update: torch.optim, load_state_dict, and cips3d_amd.optim.FusedClipAdamEMA, which
 # writes through raw pointers and therefore bumps it explicitly).  Transient weights (the double-backward's `ggw`) are
-# never cached.  CIPS_D_WCACHE=0 disables the cache.
+# never cached.
 # A write that bypasses the version counter (`p.data.copy_()`, `p.data.mul_()` — the reference's own EMA helper writes
 # through .data —, an optimiser step replayed from a hipGraph, a raw-pointer kernel) leaves stale planes in use: such
 # writers call invalidate_weight_cache(module_or_parameters) afterwards.  The cache lives in a weakly keyed table beside
@@ -493,8 +487,8 @@ def prepare_weight_planes(layers):
         if not (isinstance(w, nn.Parameter) and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
             continue
         O, Cc, kh, kw = w.shape
-        if Cc % 32 or O % 32 or (alt == "s2banks" and O < 64):
-            continue
+        if not _implicit_channels_ok(Cc, O) or (alt == "s2banks" and not _parity_channels_ok(Cc, O)):
+            continue                               # no implicit-GEMM form for these channel counts (_conv_forms): no planes
         slot = _WCACHE.get(id(w))
         if slot is None or slot[0]() is not w:
             key_id = id(w)
@@ -569,17 +563,13 @@ def _w_banks_s2(w, scale=1.0):
     return _cached(w, scale, "s2banks", ops.dgrad_s2_banks)
 
 
-def _w_rows(w, scale, want_t):
-    """(O, K) matrix of w * scale as planes (1, O, K) (want_t False) or transposed (1, K, O)"""
-    def build(we):
-        O = we.shape[0]
-        P, T = ops.split_planes(we.reshape(1, O, -1).contiguous(), want_p=not want_t, want_t=want_t)
-        return T if want_t else P
-    return _cached(w, scale, "rowsT" if want_t else "rows", build)
-
-
 def _scaled(w, scale):
     return w if scale == 1.0 else w * scale
+
+
+def _grad_planes(dy):
+    """NHWC planes of a gradient: a planes-only placeholder carries them, anything else is split here"""
+    return _nhwc(dy if _is_planes_only(dy) else dy.contiguous())
 
 
 def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
@@ -587,41 +577,21 @@ def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
     B, C, H, W = x.shape
     O, _, kh, kw = w.shape
     x = x.contiguous()
-    if pre is not None:
+    form = _conv_forms(x.shape, w.shape, stride, pad, pre)[0]
+    if form == "implicit":
         Hb, Wb = _pre_shape(H, W, pre)
-        if _implicit_ok(C, ((Hb + 2 * pad - kh) // stride + 1) * ((Wb + 2 * pad - kw) // stride + 1), O):
-            return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad)
+        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad)
+    if pre is not None:
         x = _pre_fp32(x, pre)
-        H, W = Hb, Wb
-    Ho_, Wo_ = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and C <= 4 and (H * W) % 4 == 0:
-        return ops.conv1x1_smallk(x, _scaled(w, scale).reshape(O, C).contiguous())      # RGB input convs: streaming, no GEMM
-    if _implicit_ok(C, Ho_ * Wo_, O):
-        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x), B, C, H, W, O, kh, kw, stride, pad)
-    if _fold_ok(C * kh * kw, Ho_ * Wo_, B, O):
-        K, N = C * kh * kw, Ho_ * Wo_
-        colP, _, _ = _folded_col_planes(x, kh, kw, stride, pad)
-        wT = _w_rows(w, scale, True)                                                           # (1, K, O)
-        nch = _split_count(((O + 255) // 256) * ((B * N + 127) // 128), K)
-        kc = K // nch
-        y2 = torch.empty(nch, O, B * N, device=x.device)
-        ops.gemm_x3_km(wT, colP, O, B * N, kc, O, B * N, nch, kc * O, kc * B * N, y2)   # y (O, B*N) = W (O,K) @ col (K, B*N)
-        y2 = y2.sum(0) if nch > 1 else y2[0]
-        return y2.view(O, B, Ho_, Wo_).permute(1, 0, 2, 3).contiguous()
-    if _x3_ok(C * kh * kw, Ho_ * Wo_, O):
-        K, N = C * kh * kw, Ho_ * Wo_
-        colP, _, _ = ops.im2col_x3(x, kh, kw, stride, pad)               # planes (B, K, N): k-major B operand
-        wT = _w_rows(w, scale, True)                                     # (1, K, O): k-major A operand
-        y = torch.empty(B, O, Ho_, Wo_, device=x.device)
-        ops.gemm_x3_km(wT, colP, O, N, K, O, N, B, 0, K * N, y)          # y[b] (O,N) = W (O,K) @ col[b] (K,N)
-        return y
+    if form == "rgb":
+        return ops.conv1x1_smallk(x, _scaled(w, scale).reshape(O, C).contiguous())      # streaming, no GEMM
     col, Ho, Wo = ops.im2col(x, kh, kw, stride, pad)                  # (B, K, Ho*Wo)
     K, N = C * kh * kw, Ho * Wo
     if N % 4:
         raise NotImplementedError("conv output plane must have a multiple of 4 pixels")
     wm = _scaled(w, scale).reshape(O, K)
     Kp = _pad4(K)
-    if Kp != K:   # RGB input (C_in = 3, 1x1): pad the contraction dim to the GEMM's 16-byte vector granule
+    if Kp != K:   # pad the contraction dim to the GEMM's 16-byte vector granule
         wm = F.pad(wm, (0, Kp - K))
         col = F.pad(col, (0, 0, 0, Kp - K))
     wm = wm.contiguous()
@@ -630,48 +600,25 @@ def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
     return y
 
 
-def _s2_parity_ok(C, O, N):
-    """stride-2 data gradient as parity sub-convolutions: O a multiple of 32 with two k-tiles in the single-tap class (small
-    planes: the batch folded into the pixel dimension)"""
-    return CONV_MODE == "bf16x3" and O % 32 == 0 and O >= 64 and C % 8 == 0 and N % 8 == 0
-
-
 def _conv_bwd_data(dy, w, in_shape, stride, pad, scale=1.0, pre=None):
+    B, C, H, W = in_shape
+    O, _, kh, kw = w.shape
+    form = _conv_forms(in_shape, w.shape, stride, pad, pre)[1]
     if pre is not None:
-        B, C, H, W = in_shape
-        O, _, kh, kw = w.shape
         Hb, Wb = _pre_shape(H, W, pre)
-        if (stride == 2 and pad == 0 and pre[3] == 1 and dy.is_cuda and _s2_parity_ok(C, O, dy.shape[2] * dy.shape[3])):
+        if form == "parity":
             banks, w_off = _w_banks_s2(w, scale)
-            dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, _nhwc(dy if _is_planes_only(dy) else dy.contiguous()), B, C, Hb, Wb, O, kh, kw)
+            dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, _grad_planes(dy), B, C, Hb, Wb, O, kh, kw)
             gx0, gx1, gy0, gy1 = _pre_adjoint_pads(H, W, pre)
             return ops.upfirdn2d_parity(dxp, out_off, _flipped(pre[0]), B * C, Hb, Wb, gx0, gx1, gy0, gy1).view(B, C, H, W)
         return _pre_adjoint(_conv_bwd_data(dy, w, (B, C, Hb, Wb), stride, pad, scale), pre, in_shape)
-    B, C, H, W = in_shape
-    O, _, kh, kw = w.shape
-    po = _is_planes_only(dy)
-    if not po:
-        dy = dy.contiguous()
-    Ho, Wo = dy.shape[2], dy.shape[3]
-    K, N = C * kh * kw, Ho * Wo
-    if stride == 1 and _implicit_ok(O, H * W, C) and Ho + kh - 1 - 2 * pad == H and kh - 1 - pad >= 0 and not (kh == 1 and kw == 1 and C <= 4):
+    if form == "implicit":
         # dx = conv(dy, flipped weights with the channel roles swapped), padding kh-1-pad
-        return ops.conv2d_x3(_w_planes_flipT(w, scale), _nhwc(dy), B, O, Ho, Wo, C, kh, kw, 1, kh - 1 - pad)
-    if po:
-        dy = _dense(dy)                   # raises: every path below reads values
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and C <= 4 and (H * W) % 4 == 0:
+        return ops.conv2d_x3(_w_planes_flipT(w, scale), _grad_planes(dy), B, O, dy.shape[2], dy.shape[3], C, kh, kw, 1, kh - 1 - pad)
+    dy = _dense(dy)                       # raises on a planes-only gradient: the forms below read values
+    if form == "rgb":
         return ops.conv1x1_smallk_bwd_data(dy, _scaled(w, scale).reshape(O, C).contiguous(), C)
-    if _fold_ok(K, N, B, O):
-        wP = _w_rows(w, scale, False)                                                            # (1, O, K)
-        dcol2 = torch.empty(K, B * N, device=dy.device)
-        ops.gemm_x3_km(wP, _folded_rows_planes(dy), K, B * N, O, K, B * N, 1, 0, 0, dcol2)       # dcol (K, B*N) = W^T dy
-        return ops.col2im(dcol2.view(K, B, N).permute(1, 0, 2).contiguous(), B, C, H, W, kh, kw, stride, pad)
-    if _x3_ok(K, N, O):
-        wP = _w_rows(w, scale, False)                                    # (1, O, K): contraction index o = rows
-        dyP, _ = ops.split_planes(dy.view(B, O, N), want_p=True, want_t=False)
-        dcol = torch.empty(B, K, N, device=dy.device)
-        ops.gemm_x3_km(wP, dyP, K, N, O, K, N, B, 0, O * N, dcol)        # dcol[b] (K,N) = W^T (K,O) @ dy[b] (O,N)
-        return ops.col2im(dcol, B, C, H, W, kh, kw, stride, pad)
+    K, N = C * kh * kw, dy.shape[2] * dy.shape[3]
     wm = _scaled(w, scale).reshape(O, K)
     Kp = _pad4(K)
     if Kp != K:
@@ -686,53 +633,27 @@ def _conv_bwd_data(dy, w, in_shape, stride, pad, scale=1.0, pre=None):
 
 def _conv_bwd_weight(dy, x, w_shape, stride, pad, scale=1.0, pre=None):
     """d/dw of conv(Blur(x), w * scale): scale * (dy correlated with Blur(x))"""
-    if pre is not None:
-        O, C, kh, kw = w_shape
-        Hb, Wb = _pre_shape(x.shape[2], x.shape[3], pre)
-        if _implicit_ok(C, dy.shape[2] * dy.shape[3], O) and x.is_cuda:
-            dw = ops.conv2d_x3_wgrad(_nhwc(dy if _is_planes_only(dy) else dy.contiguous()), _nhwc(x.contiguous(), pre), x.shape[0], C, Hb, Wb, O, kh, kw, stride, pad, scale)
-            if dw is not None:
-                return dw
-        x = _pre_fp32(x, pre)
-    dw = _conv_bwd_weight_raw(dy, x, w_shape, stride, pad, scale)
-    if isinstance(dw, tuple):            # (tensor,): the path applied the scale itself
-        return dw[0]
-    return dw if scale == 1.0 else dw * scale
-
-
-def _conv_bwd_weight_raw(dy, x, w_shape, stride, pad, scale):
     O, C, kh, kw = w_shape
     B = x.shape[0]
     x = x.contiguous()
-    po = _is_planes_only(dy)
-    if not po:
-        dy = dy.contiguous()
-    K, N = C * kh * kw, dy.shape[2] * dy.shape[3]
-    if _implicit_ok(C, N, O):
-        dw = ops.conv2d_x3_wgrad(_nhwc(dy), _nhwc(x), B, C, x.shape[2], x.shape[3], O, kh, kw, stride, pad, scale)
-        if dw is not None:
-            return (dw,)
-    if po:
-        dy = _dense(dy)                   # raises: every path below reads values
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and C <= 4 and N % 4 == 0:
-        return ops.conv1x1_smallk_bwd_weight(dy, x).view(O, C, 1, 1)       # RGB input convs: streaming reduction
-    if _fold_ok(K, N, B, O):
-        colP, _, _ = _folded_col_planes(x, kh, kw, stride, pad)
-        nch = _split_count(((O + 255) // 256) * ((K + 127) // 128), B * N)
-        nc = B * N // nch
-        part = torch.empty(nch, O, K, device=x.device)
-        ops.gemm_x3(_folded_rows_planes(dy), colP, O, K, nc, B * N, B * N, nch, nc, nc, C=part)   # dW (O,K) = dy (O,B*N) col^T
-        return (part.sum(0) if nch > 1 else part[0]).view(O, C, kh, kw)
-    if _x3_ok(K, N, O):
-        colP, _, _ = ops.im2col_x3(x, kh, kw, stride, pad)
-        dyP, _ = ops.split_planes(dy.view(B, O, N), want_p=True, want_t=False)
+    form = _conv_forms(x.shape, w_shape, stride, pad, pre)[2]
+    if form == "implicit":
+        Hb, Wb = _pre_shape(x.shape[2], x.shape[3], pre)
+        dw = ops.conv2d_x3_wgrad(_grad_planes(dy), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, scale)
+        if dw is not None:                # None: declined (ops.conv2d_x3_wgrad_declines), the f32 form below
+            return dw
+    if pre is not None:
+        x = _pre_fp32(x, pre)
+    dy = _dense(dy)                       # raises on a planes-only gradient: the forms below read values
+    if form == "rgb":
+        dw = ops.conv1x1_smallk_bwd_weight(dy, x).view(O, C, 1, 1)       # streaming reduction
+    else:
+        K, N = C * kh * kw, dy.shape[2] * dy.shape[3]
+        col, Ho, Wo = ops.im2col(x, kh, kw, stride, pad)
         part = torch.empty(B, O, K, device=x.device)
-        ops.gemm_x3(dyP, colP, O, K, N, N, N, B, O * N, K * N, C=part)   # part[b] (O,K) = dy[b] (O,N) @ col[b]^T (N,K)
-        return part.sum(0).view(O, C, kh, kw)
-    col, Ho, Wo = ops.im2col(x, kh, kw, stride, pad)
-    part = torch.empty(B, O, K, device=x.device)
-    ops.gemm(dy, col, part, O, K, N, N, N, K, batch=B, strideA=O * N, strideB=K * N, strideC=O * K, b_nmajor=True)
-    return part.sum(0).view(O, C, kh, kw)
+        ops.gemm(dy, col, part, O, K, N, N, N, K, batch=B, strideA=O * N, strideB=K * N, strideC=O * K, b_nmajor=True)
+        dw = part.sum(0).view(O, C, kh, kw)
+    return dw if scale == 1.0 else dw * scale
 
 
 class _WeightGradPort(Function):
@@ -859,24 +780,13 @@ PLANES_ONLY_GRADIENT = True      # False: FusedLeakyReLU's backward writes the f
 
 def _planes_only_ok(x_shape, w_shape, stride, pad, pre, need_dx, dout):
     """may the gated gradient of this ConvBiasAct layer exist as NHWC planes only?  Yes when BOTH of its consumers — the
-    convolution's data gradient (if asked for) and weight gradient — take their implicit-GEMM forms, which read planes and
-    nothing else (the conditions of _conv_bwd_data / _conv_bwd_weight, restated)"""
-    if not (CONV_MODE == "bf16x3" and dout.is_cuda and dout.dtype == torch.float32 and dout.dim() == 4):
+    convolution's data gradient (if asked for) and weight gradient — take forms that read planes and nothing else"""
+    if not (dout.is_cuda and dout.dtype == torch.float32 and dout.dim() == 4):
         return False
-    B, C, H, W = x_shape
-    O, _, kh, kw = w_shape
-    Hb, Wb = _pre_shape(H, W, pre)
-    Ho, Wo = dout.shape[2], dout.shape[3]
-    N = Ho * Wo
-    if not _implicit_ok(C, N, O) or (B * N) % 32 or O % 8:
-        return False                                                     # weight gradient: cips_conv2d_x3_wgrad's conditions
-    if need_dx:
-        if stride == 1:
-            if pre is not None or not (_implicit_ok(O, Hb * Wb, C) and Ho + kh - 1 - 2 * pad == Hb and kh - 1 - pad >= 0):
-                return False
-        elif not (stride == 2 and pad == 0 and pre is not None and pre[3] == 1 and _s2_parity_ok(C, O, N)):
-            return False
-    return True
+    _, dgrad, wgrad = _conv_forms(x_shape, w_shape, stride, pad, pre)
+    if wgrad != "implicit" or ops.conv2d_x3_wgrad_declines(dout.shape[0], dout.shape[2] * dout.shape[3]):
+        return False
+    return not need_dx or dgrad in ("implicit", "parity")
 
 
 def _conv_bias_act_apply(x, w, bias, stride, pad, scale, slope, act_scale, pre=None):
@@ -890,17 +800,12 @@ _CONV_ACT_FUSED = True      # False: bias + LeakyReLU as a separate pass after t
 
 
 def _conv_act_fusable(x, conv, act, pre=None):
-    """EqualConv2d (no bias of its own) + FusedLeakyReLU on a GPU batch whose conv takes the implicit-GEMM path"""
+    """EqualConv2d (no bias of its own) + FusedLeakyReLU on a GPU batch whose forward takes the implicit-GEMM form"""
     if not (_CONV_ACT_FUSED and x.is_cuda and x.dtype == torch.float32 and conv.bias is None and isinstance(act, FusedLeakyReLU)):
         return False
     if GATE_PIN is not None or GATE_REC is not None:        # gate instrumentation works on the separate activation op
         return False
-    B, C, H, W = x.shape
-    H, W = _pre_shape(H, W, pre)
-    O, _, kh, kw = conv.weight.shape
-    Ho, Wo = (H + 2 * conv.padding - kh) // conv.stride + 1, (W + 2 * conv.padding - kw) // conv.stride + 1
-    rgb = kh == 1 and kw == 1 and C <= 4
-    return (not rgb) and Ho > 0 and Wo > 0 and _implicit_ok(C, Ho * Wo, O)
+    return _conv_forms(x.shape, conv.weight.shape, conv.stride, conv.padding, pre)[0] == "implicit"
 
 
 class Conv2dBwdDataFunction(Function):

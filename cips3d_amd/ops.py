@@ -1281,16 +1281,21 @@ def upfirdn2d_parity(dxp, out_off, kernel, major, in_h, in_w, pad_x0, pad_x1, pa
     return out
 
 
+def conv2d_x3_wgrad_declines(B, N):
+    """conv2d_x3_wgrad's contraction runs over the B * N output pixels of the batch in 32-row k-tiles"""
+    return (B * N) % 32 != 0
+
+
 def conv2d_x3_wgrad(dyP, xP, B, C, H, W, O, kh, kw, stride, pad, scale=1.0, nch=None):
     """Weight gradient of conv2d_x3: dyP, xP NHWC Planes from split_planes_nhwc -> dW (O, C, kh, kw) fp32, or None when
-    the pixel count does not split into 32-row k-tiles.  The pixel range is cut into chunks so that a 512x512 filter bank
-    still fills the chip (4 tiles per tap and chunk); cips_conv_wgrad_finish adds the partial sums, applies `scale` and
-    lays the result out as (O, C, kh, kw)."""
+    the pixel count does not split into 32-row k-tiles (conv2d_x3_wgrad_declines).  The pixel range is cut into chunks so
+    that a 512x512 filter bank still fills the chip (4 tiles per tap and chunk); cips_conv_wgrad_finish adds the partial
+    sums, applies `scale` and lays the result out as (O, C, kh, kw)."""
     lib = _lib.load()
     from ._lib import ConvWgradDesc
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     K = B * Ho * Wo
-    if K % 32:
+    if conv2d_x3_wgrad_declines(B, Ho * Wo):
         return None
     # chunks of the pixel range: the persistent grid runs ceil(tiles*nch / 256) rounds of ~K/nch rows each (+ an
     # epilogue worth ~512 rows); 36 tiles x 7 chunks = 252 of 256 CUs in one round (powers of two: 144, or 288 in two)
@@ -1908,17 +1913,6 @@ def im2col(x, kh, kw, stride, pad):
     Wo = (W + 2 * pad - kw) // stride + 1
     col = torch.empty(B, Cc * kh * kw, Ho * Wo, device=x.device)
     check(lib.cips_im2col(_p(x), _p(col), B, Cc, H, W, kh, kw, stride, pad, _stream()), "cips_im2col")
-    return col, Ho, Wo
-
-
-def im2col_x3(x, kh, kw, stride, pad):
-    """im2col as split-bf16 planes (B, C*kh*kw, Ho*Wo)"""
-    lib = _lib.load()
-    B, Cc, H, W = x.shape
-    Ho = (H + 2 * pad - kh) // stride + 1
-    Wo = (W + 2 * pad - kw) // stride + 1
-    col = Planes.empty(B, Cc * kh * kw, Ho * Wo, device=x.device)
-    check(lib.cips_im2col_x3(_p(x), _p(col.hi), _p(col.lo), B, Cc, H, W, kh, kw, stride, pad, _stream()), "cips_im2col_x3")
     return col, Ho, Wo
 
 

@@ -186,3 +186,80 @@ def test_discriminator_oracle_is_additive_over_batch_slices():
 
 
 D_SLICE_FP32_BAR = 4 * 8.5e-7
+
+
+def test_conv_dispatch_rule_over_the_shipped_discriminator(monkeypatch):
+    """_conv_forms — the one rule that the convolution functions, the planes-only gradient and the conv + activation fusion
+    consult — over every convolution of Discriminator_MultiScale (channel_multiplier 2, with and without the stddev channel
+    in front of the final convolution) at input sizes 16 ... 1024 and batches 1 ... 32: the conv_in layers take the streaming
+    RGB kernels, everything else the implicit-GEMM family (the data gradient of a 3 x 3 stride-2 convolution behind its Blur
+    as parity sub-convolutions), and the exact fp32 form is met at the 513-channel final convolution only.  The layer list is
+    the module's own (_conv_layers + conv_in); shapes and the folded Blur are derived from the ConvLayers as ConvLayer.forward
+    does.  Also: the weight gradient the rule calls "implicit" is declined by ops.conv2d_x3_wgrad exactly where the batch's
+    pixel count B * N is no multiple of 32 — restated here from the shapes: the 4 x 4 output planes at odd B."""
+    import math
+    from cips3d_amd import discriminator as dm
+    from cips3d_amd import ops
+    assert dm.CONV_MODE == "bf16x3" and dm.FOLD_BLUR
+    monkeypatch.setattr(torch, "randn", torch.empty)           # only shapes are read: 37 M parameters stay uninitialised
+
+    def call_of(layer, h):
+        """(input shape without the batch, stride, pad, pre) of the convolution call ConvLayer.forward makes on an h x h map"""
+        conv, blur = layer.equal_conv, getattr(layer, "down_blur", None)
+        c = conv.weight.shape[1]
+        if blur is None:
+            return (c, h, h), conv.stride, conv.padding, None
+        if conv.weight.shape[2] == 1:                          # the skip branch: Blur sampled at stride 2, 1 x 1 at stride 1
+            return (c, h, h), 1, 0, (None, blur.pad[0], blur.pad[1], 2)
+        return (c, h, h), conv.stride, conv.padding, (None, blur.pad[0], blur.pad[1], 1)
+
+    seen_f32, declined, n_layers = set(), set(), 0
+    for stddev_group in (0, 4):
+        D = dm.Discriminator_MultiScale(diffaug=False, max_size=1024, channel_multiplier=2, stddev_group=stddev_group)
+        c_final = D.final_conv.equal_conv.weight.shape[1]
+        assert c_final == (513 if stddev_group else 512)
+        for size in (16, 32, 64, 128, 256, 512, 1024):
+            log_size = int(math.log2(size))
+            listed = D._conv_layers(log_size)
+            calls = []                                         # (EqualConv2d, call, expected forms)
+            for i in range(log_size, 2, -1):
+                blk, h = D.convs[f"{2 ** i}"], 2 ** i
+                for layer, h_in in ((blk.conv1, h), (blk.conv2, h // 2 if hasattr(blk.conv1, "down_blur") else h), (blk.skip, h)):
+                    call = call_of(layer, h_in)
+                    parity = call[3] is not None and layer.equal_conv.weight.shape[2] == 3
+                    assert parity or call[1] == 1              # stride 1, or a 3 x 3 stride-2 convolution behind its Blur
+                    calls.append((layer.equal_conv, call, ("implicit", "parity" if parity else "implicit", "implicit")))
+            calls.append((D.final_conv.equal_conv, call_of(D.final_conv, 4), ("f32",) * 3 if c_final == 513 else ("implicit",) * 3))
+            assert [c for c, _ in listed] == [c for c, _, _ in calls]
+            for (conv, alt), (_, _, want) in zip(listed, calls):             # the weight form prepared for the data gradient
+                assert alt == ("s2banks" if want[1] == "parity" else "flipT")
+            conv_in = D.conv_in[f"{size}"].equal_conv
+            calls.append((conv_in, call_of(D.conv_in[f"{size}"], size), ("rgb",) * 3))
+            for conv, ((c, h, w), stride, pad, pre), want in calls:
+                hb, wb = dm._pre_shape(h, w, pre)
+                kh = conv.weight.shape[2]
+                n = ((hb + 2 * pad - kh) // stride + 1) ** 2
+                for B in range(1, 33):
+                    got = dm._conv_forms((B, c, h, w), tuple(conv.weight.shape), stride, pad, pre)
+                    assert got == want, (size, B, tuple(conv.weight.shape), stride, pad, got, want)
+                    n_layers += 1
+                    if "f32" in got:
+                        seen_f32.add(c)
+                    if got[2] == "implicit":
+                        declines = (B * n) % 32 != 0
+                        assert ops.conv2d_x3_wgrad_declines(B, n) == declines
+                        if declines:
+                            declined.add((n, B))
+    assert seen_f32 == {513}
+    assert declined == {(16, B) for B in range(1, 33, 2)}
+    assert n_layers == 2 * 32 * sum(3 * (ls - 2) + 2 for ls in range(4, 11))
+    # CONV_MODE "f32": no split-bf16 form anywhere, the RGB kernels stay
+    monkeypatch.setattr(dm, "CONV_MODE", "f32")
+    assert dm._conv_forms((4, 512, 8, 8), (512, 512, 3, 3), 1, 1) == ("f32",) * 3
+    assert dm._conv_forms((4, 512, 9, 9), (512, 512, 3, 3), 2, 0, (None, 2, 2, 1)) == ("f32",) * 3
+    assert dm._conv_forms((4, 3, 8, 8), (512, 3, 1, 1), 1, 0) == ("rgb",) * 3
+    monkeypatch.setattr(dm, "CONV_MODE", "bf16x3")
+    # shapes outside the networks that the removed split-bf16 im2col forms used to take are exact fp32 now
+    assert dm._conv_forms((2, 64, 17, 17), (32, 64, 3, 3), 2, 0)[1] == "f32"          # a stride-2 data gradient without a Blur
+    assert dm._conv_forms((2, 48, 16, 16), (64, 48, 2, 2), 1, 0) == ("f32",) * 3      # channels that are no multiple of 32
+    assert dm._conv_forms((2, 64, 17, 17), (32, 64, 3, 3), 2, 0, (None, 2, 2, 1))[1] == "f32"   # O = 32 behind a Blur: one k-tile
