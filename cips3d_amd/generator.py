@@ -226,47 +226,33 @@ class NeRFNetwork(nn.Module):
         c = torch.sin(gain.unsqueeze(1) * self.color_layer_sine.linear(x) + bias.unsqueeze(1))
         return self.color_layer_linear(c), sigma
 
+    def _siren_args(self, style_dict):
+        """the 16 tensors of the fused SIREN Functions in their order (ops._SIREN_NAMES): the FiLM vectors of the three sine
+        layers for these styles (one grouped launch), then the ten weights"""
+        p = self.name_prefix
+        (g0, p0), (g1, p1), (gc, pc) = _film_all([self.network[0], self.network[1], self.color_layer_sine],
+                                                 [style_dict[f'{p}_w0'], style_dict[f'{p}_w1'], style_dict[f'{p}_rgb']])
+        return (g0, p0, g1, p1, gc, pc,
+                self.network[0].linear.weight, self.network[0].linear.bias,
+                self.network[1].linear.weight, self.network[1].linear.bias,
+                self.final_layer.weight, self.final_layer.bias,
+                self.color_layer_sine.linear.weight, self.color_layer_sine.linear.bias,
+                self.color_layer_linear[0].weight, self.color_layer_linear[0].bias)
+
     def evaluate(self, points, style_dict):
         """points (b,P,3) -> feat (b,P,32), sigma (b,P) via the fused HIP kernel (shipped shape) or tensor operations."""
         if not self.fused:
             return self._evaluate_unfused(points, style_dict)
-        p = self.name_prefix
-        (g0, p0), (g1, p1), (gc, pc) = _film_all([self.network[0], self.network[1], self.color_layer_sine],
-                                                 [style_dict[f'{p}_w0'], style_dict[f'{p}_w1'], style_dict[f'{p}_rgb']])
-        return ops.SirenFunction.apply(
-            points, g0, p0, g1, p1, gc, pc,
-            self.network[0].linear.weight, self.network[0].linear.bias,
-            self.network[1].linear.weight, self.network[1].linear.bias,
-            self.final_layer.weight, self.final_layer.bias,
-            self.color_layer_sine.linear.weight, self.color_layer_sine.linear.bias,
-            self.color_layer_linear[0].weight, self.color_layer_linear[0].bias)
+        return ops.SirenFunction.apply(points, *self._siren_args(style_dict))
 
     def evaluate_rays(self, style_dict, geom, xg, yg, zg, cam2world, jitter=None, zvals=None):
         """evaluate() with the sample points generated in-kernel (coarse: from the jitter draw; fine: from the resampled
         depths `zvals`) -> feat (b,P,32), sigma (b,P), z (b,P)"""
-        p = self.name_prefix
-        (g0, p0), (g1, p1), (gc, pc) = _film_all([self.network[0], self.network[1], self.color_layer_sine],
-                                                 [style_dict[f'{p}_w0'], style_dict[f'{p}_w1'], style_dict[f'{p}_rgb']])
-        return ops.SirenRaysFunction.apply(
-            geom, xg, yg, zg, cam2world, jitter, zvals, g0, p0, g1, p1, gc, pc,
-            self.network[0].linear.weight, self.network[0].linear.bias,
-            self.network[1].linear.weight, self.network[1].linear.bias,
-            self.final_layer.weight, self.final_layer.bias,
-            self.color_layer_sine.linear.weight, self.color_layer_sine.linear.bias,
-            self.color_layer_linear[0].weight, self.color_layer_linear[0].bias)
+        return ops.SirenRaysFunction.apply(geom, xg, yg, zg, cam2world, jitter, zvals, *self._siren_args(style_dict))
 
     def march(self, style_dict, geom, xg, yg, zg, cam2world, jitter, noise):
         """fused rays + SIREN + composite for non-hierarchical sampling -> pixels_fea (b,n,32), depth (b,n)"""
-        p = self.name_prefix
-        (g0, p0), (g1, p1), (gc, pc) = _film_all([self.network[0], self.network[1], self.color_layer_sine],
-                                                 [style_dict[f'{p}_w0'], style_dict[f'{p}_w1'], style_dict[f'{p}_rgb']])
-        return ops.RayMarchFunction.apply(
-            geom, xg, yg, zg, cam2world, jitter, noise, g0, p0, g1, p1, gc, pc,
-            self.network[0].linear.weight, self.network[0].linear.bias,
-            self.network[1].linear.weight, self.network[1].linear.bias,
-            self.final_layer.weight, self.final_layer.bias,
-            self.color_layer_sine.linear.weight, self.color_layer_sine.linear.bias,
-            self.color_layer_linear[0].weight, self.color_layer_linear[0].bias)
+        return ops.RayMarchFunction.apply(geom, xg, yg, zg, cam2world, jitter, noise, *self._siren_args(style_dict))
 
     def forward(self, input, style_dict, ray_directions=None, **kwargs):
         feat, sigma = self.evaluate(input, style_dict)

@@ -6,15 +6,15 @@ kernel on the hot path is a hand-written HIP kernel in libcips3d_hip.so.  There 
 fallback: tensors must live on a ROCm device and the extension must be built.
 """
 import ctypes as C
-import ctypes as _ct
 import math
-import os as _os
+import os
 import weakref
 
 import torch
 
 from . import _lib
-from ._lib import GemmDesc, GemmX3Desc, SirenWeights, check
+from ._lib import (ConvDgradS2Desc, ConvWgradDesc, ConvX3Desc, GemmDesc, GemmX3Desc, GlinJob, ModfcBwdJob, ModfcPrepJob,
+                   RayParams, SirenGrads, SirenWeights, check)
 
 LRELU_SLOPE = 0.2
 
@@ -146,7 +146,9 @@ def bmm_tn(a, b, out=None):
 # --------------------------------------------------------------------------------------
 # H2 SIREN
 # --------------------------------------------------------------------------------------
-_SIREN_NAMES = ("w0", "b0", "w1", "b1", "ws", "bs", "wc", "bc", "wf", "bf", "g0", "p0", "g1", "p1", "gc", "pc")
+# the 16 SIREN tensors (FiLM vectors, then weights) in the one order the Functions take them, save them and return their
+# gradients; "d" + name are the fields of SirenGrads
+_SIREN_NAMES = ("g0", "p0", "g1", "p1", "gc", "pc", "w0", "b0", "w1", "b1", "ws", "bs", "wc", "bc", "wf", "bf")
 BOX_SCALE = 2.0 / 0.24   # UniformBoxWarp(0.24), generator.py:249
 TRIG_MODE = 1            # 1 hardware v_sin_f32/v_cos_f32 after Cody-Waite reduction (default; measured as accurate
                          # as the polynomial on MI355X: 1.2e-6 vs 1.3e-6), 0 minimax polynomial
@@ -161,6 +163,15 @@ def _siren_struct(t):
     return s
 
 
+def _siren_prep(siren):
+    """the 16 SIREN tensors in _SIREN_NAMES order -> {name: detached contiguous fp32 tensor}, checked"""
+    if len(siren) != len(_SIREN_NAMES):
+        raise TypeError(f"expected the {len(_SIREN_NAMES)} SIREN tensors {_SIREN_NAMES}, got {len(siren)}")
+    t = {n: _c(v.detach()) for n, v in zip(_SIREN_NAMES, siren)}
+    _chk(*t.values())
+    return t
+
+
 def _split_k(P, target=8):
     """Largest split count <= target such that P/split is a multiple of 32."""
     for s in range(target, 0, -1):
@@ -173,12 +184,12 @@ def _split_k(P, target=8):
 # CIPS_INR_MODE and CIPS_D_CONV_MODE).  Forward "x3": split-operand matrix-core chain (default: fp16 planes, sigma to fp32
 # class); "f32": exact fp32 MFMA.  Backward "x3": fused split-bf16 kernel; "staged": fp32 data pass + split-bf16 K-major GEMMs;
 # "staged_f32" (round 6): fp32 data pass with fp32-staged activations + fp32-MFMA weight-gradient GEMMs (the all-fp32 leg).
-SIREN_FWD_MODE = __import__("os").environ.get("CIPS_SIREN_FWD", "x3")
-SIREN_BWD_MODE = __import__("os").environ.get("CIPS_SIREN_BWD", "x3")
+SIREN_FWD_MODE = os.environ.get("CIPS_SIREN_FWD", "x3")
+SIREN_BWD_MODE = os.environ.get("CIPS_SIREN_BWD", "x3")
 
 
 class SirenFunction(torch.autograd.Function):
-    """feat (B,P,32), sigma (B,P) = siren(points; weights, per-image FiLM vectors).
+    """feat (B,P,32), sigma (B,P) = siren(points; per-image FiLM vectors, weights: `siren` in _SIREN_NAMES order).
 
     Mirrors NeRFNetwork.forward_with_frequencies_phase_shifts (generator.py:260-317); gains g*
     are already 15*gain_fc(style)+30 and phases p* = bias_fc(style) (film_layer.py:88-93), both
@@ -187,20 +198,18 @@ class SirenFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, points, g0, p0, g1, p1, gc, pc, w0, b0, w1, b1, ws, bs, wc, bc, wf, bf):
+    def forward(ctx, points, *siren):
         lib = _lib.load()
-        t = dict(w0=w0, b0=b0, w1=w1, b1=b1, ws=ws, bs=bs, wc=wc, bc=bc, wf=wf, bf=bf,
-                 g0=g0, p0=p0, g1=g1, p1=p1, gc=gc, pc=pc)
-        t = {k: _c(v.detach()) for k, v in t.items()}
+        t = _siren_prep(siren)
         points = _c(points.detach())
-        _chk(points, *t.values())
+        _chk(points)
         B, P, _ = points.shape
         feat = torch.empty(B, P, 32, device=points.device)
         sigma = torch.empty(B, P, device=points.device)
         sw = _siren_struct(t)
         fwd = lib.cips_siren_fwd_x3 if SIREN_FWD_MODE == "x3" else lib.cips_siren_fwd
         check(fwd(C.byref(sw), _p(points), _p(feat), _p(sigma), B, P, _stream()), "cips_siren_fwd")
-        ctx.save_for_backward(points, *[t[n] for n in _SIREN_NAMES])
+        ctx.save_for_backward(points, *t.values())
         return feat, sigma
 
     @staticmethod
@@ -208,122 +217,112 @@ class SirenFunction(torch.autograd.Function):
         points = ctx.saved_tensors[0]
         t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[1:]))
         B, P, _ = points.shape
-        dev = points.device
-        dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
-        dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
         return (None,) + _siren_backward(t, dfeat, dsigma, B, P, points=points)
 
 
 def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None):
-    """SIREN backward for upstream gradients dfeat (B,P,32), dsigma (B,P): -> (dg0, dp0, dg1, dp1, dgc, dpc, dw0, db0, dw1,
-    db1, dws, dbs, dwc, dbc, dwf, dbf).  The sample points are either given (B,P,3) or regenerated in-kernel from
-    `rays` (a RayParams struct; fused bf16x3 form only)."""
+    """SIREN backward for upstream gradients dfeat (B,P,32), dsigma (B,P) (None: zeros) -> the gradients of the 16 tensors
+    in _SIREN_NAMES order.  The sample points are either given (B,P,3) or regenerated in-kernel from `rays` (a RayParams
+    struct).  SIREN_BWD_MODE picks the form for given points; `rays` always takes the fused form, whatever the mode says
+    (the staged data passes read a points tensor)."""
+    dev = t["w0"].device
+    dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
+    dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
+    if SIREN_BWD_MODE == "x3" or points is None:
+        return _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays)
+    return _siren_backward_staged(t, dfeat, dsigma, B, P, points, f32=SIREN_BWD_MODE == "staged_f32")
+
+
+def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays):
+    """one kernel: recompute + data gradients + weight-gradient contractions on split bf16, nothing staged in HBM"""
     lib = _lib.load()
     dev = dfeat.device
     sw = _siren_struct(t)
-    if True:
-        if SIREN_BWD_MODE == "x3" or points is None:
-            # fused kernel: recompute + data gradients + weight-gradient contractions, nothing staged in HBM
-            chunks = lib.cips_siren_bwd_x3_chunks(B, P)
-            gw = lib.cips_siren_bwd_x3_gpart()
-            sw_ = lib.cips_siren_bwd_x3_sred()
-            sred = torch.empty(B * chunks, sw_, device=dev)
-            gpart = torch.empty(B * chunks, gw, device=dev)
-            if points is not None:
-                check(lib.cips_siren_bwd_x3(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(sred), _p(gpart), B, P,
-                                            _stream()), "cips_siren_bwd_x3")
-            else:
-                check(lib.cips_siren_bwd_x3_rays(C.byref(sw), C.byref(rays), _p(dfeat), _p(dsigma), _p(sred), _p(gpart), B,
-                                                 _stream()), "cips_siren_bwd_x3_rays")
-            # the 16 gradient tensors from the partials in one launch (was ~40 tiny torch reductions)
-            from ._lib import SirenGrads
-            shapes = dict(dg0=(B, 128), dp0=(B, 128), dg1=(B, 128), dp1=(B, 128), dgc=(B, 64), dpc=(B, 64), dw0=(128, 3),
-                          db0=(128,), dw1=(128, 128), db1=(128,), dws=(1, 128), dbs=(1,), dwc=(64, 128), dbc=(64,),
-                          dwf=(32, 64), dbf=(32,))
-            outs = {k: torch.empty(*v, device=dev) for k, v in shapes.items()}
-            sg = SirenGrads()
-            for k, v in outs.items():
-                setattr(sg, k, _p(v))
-            # the chunk partials are summed by two streaming reductions first (88 MB at C2: bandwidth-bound, one
-            # launch each); the finalisation then walks B rows instead of B * chunks
-            SRr = sred.view(B, chunks, sw_).sum(1) if chunks > 1 else sred
-            Gpr = gpart.view(B, chunks, gw).sum(1) if chunks > 1 else gpart
-            check(lib.cips_siren_bwd_x3_finalize(C.byref(sw), _p(SRr), _p(Gpr), B, 1, C.byref(sg), _stream()),
-                  "cips_siren_bwd_x3_finalize")
-            return tuple(outs[k] for k in ("dg0", "dp0", "dg1", "dp1", "dgc", "dpc", "dw0", "db0", "dw1", "db1", "dws",
-                                           "dbs", "dwc", "dbc", "dwf", "dbf"))
-        elif SIREN_BWD_MODE == "staged_f32":
-            # the all-fp32 leg (round 6): the data pass stages fp32 rows, every weight-gradient contraction runs on the exact-fp32
-            # MFMA GEMM (k-major A): no split operand anywhere in the SIREN backward
-            BP = B * P
-            h1, h2, da2 = (torch.empty(BP, 128, device=dev) for _ in range(3))
-            hc, dac = (torch.empty(BP, 64, device=dev) for _ in range(2))
-            rows = lib.cips_siren_bwd_rows(B, P)
-            red = torch.empty(rows, 868, device=dev)
-            check(lib.cips_siren_bwd_data_f32(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(h1), _p(h2), _p(hc), _p(da2), _p(dac),
-                                              _p(red), B, P, _stream()), "cips_siren_bwd_data_f32")
-            R = red.view(B, rows // B, 868).sum(1)
-            sp = _split_k(P, 16)
-            Kc = P // sp
-            G1 = torch.empty(B * sp, 128, 128, device=dev)   # da2^T @ h1 per image and point chunk
-            gemm(da2, h1, G1, 128, 128, Kc, 128, 128, 128, batch=B * sp, strideA=Kc * 128, strideB=Kc * 128, strideC=128 * 128,
-                 a_kmajor=True)
-            G1 = G1.view(B, sp, 128, 128).sum(1)
-            Gc = torch.empty(B * sp, 64, 128, device=dev)    # dac^T @ h2
-            gemm(dac, h2, Gc, 64, 128, Kc, 64, 128, 128, batch=B * sp, strideA=Kc * 64, strideB=Kc * 128, strideC=64 * 128,
-                 a_kmajor=True)
-            Gc = Gc.view(B, sp, 64, 128).sum(1)
-            spf = _split_k(BP, 1024)
-            Kf = BP // spf
-            Gf = torch.empty(spf, 32, 64, device=dev)        # dfeat^T @ hc (no per-image scale)
-            gemm(dfeat, hc, Gf, 32, 64, Kf, 32, 64, 64, batch=spf, strideA=Kf * 32, strideB=Kf * 64, strideC=32 * 64, a_kmajor=True)
-            dwf = Gf.sum(0)
+    chunks = lib.cips_siren_bwd_x3_chunks(B, P)
+    gw = lib.cips_siren_bwd_x3_gpart()
+    sw_ = lib.cips_siren_bwd_x3_sred()
+    sred = torch.empty(B * chunks, sw_, device=dev)
+    gpart = torch.empty(B * chunks, gw, device=dev)
+    if points is not None:
+        check(lib.cips_siren_bwd_x3(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(sred), _p(gpart), B, P,
+                                    _stream()), "cips_siren_bwd_x3")
+    else:
+        check(lib.cips_siren_bwd_x3_rays(C.byref(sw), C.byref(rays), _p(dfeat), _p(dsigma), _p(sred), _p(gpart), B,
+                                         _stream()), "cips_siren_bwd_x3_rays")
+    # the 16 gradient tensors from the partials in one launch (was ~40 tiny torch reductions)
+    outs = tuple(torch.empty_like(t[n]) for n in _SIREN_NAMES)
+    sg = SirenGrads()
+    for n, v in zip(_SIREN_NAMES, outs):
+        setattr(sg, "d" + n, _p(v))
+    # the chunk partials are summed by two streaming reductions first (88 MB at C2: bandwidth-bound, one
+    # launch each); the finalisation then walks B rows instead of B * chunks
+    SRr = sred.view(B, chunks, sw_).sum(1) if chunks > 1 else sred
+    Gpr = gpart.view(B, chunks, gw).sum(1) if chunks > 1 else gpart
+    check(lib.cips_siren_bwd_x3_finalize(C.byref(sw), _p(SRr), _p(Gpr), B, 1, C.byref(sg), _stream()),
+          "cips_siren_bwd_x3_finalize")
+    return outs
+
+
+def _siren_backward_staged(t, dfeat, dsigma, B, P, points, f32):
+    """data pass that stages the activations and their gradients in HBM, then the weight-gradient contractions over the
+    points as split-K GEMMs.  f32 False ("staged"): rows staged as split-bf16 Planes, contractions on the bf16x3 K-major
+    GEMM; f32 True ("staged_f32", the all-fp32 leg): fp32 rows, contractions on the exact-fp32 MFMA GEMM (K-major A)."""
+    lib = _lib.load()
+    dev = dfeat.device
+    sw = _siren_struct(t)
+    BP = B * P
+    empty = torch.empty if f32 else Planes.empty
+    h1, h2, da2 = (empty(BP, 128, device=dev) for _ in range(3))
+    hc, dac = (empty(BP, 64, device=dev) for _ in range(2))
+    rows = lib.cips_siren_bwd_rows(B, P)
+    red = torch.empty(rows, 868, device=dev)
+    if f32:
+        check(lib.cips_siren_bwd_data_f32(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(h1), _p(h2), _p(hc), _p(da2),
+                                          _p(dac), _p(red), B, P, _stream()), "cips_siren_bwd_data_f32")
+    else:
+        check(lib.cips_siren_bwd_data(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(h1.hi), _p(h1.lo),
+                                      _p(h2.hi), _p(h2.lo), _p(hc.hi), _p(hc.lo), _p(da2.hi), _p(da2.lo),
+                                      _p(dac.hi), _p(dac.lo), _p(red), B, P, _stream()), "cips_siren_bwd_data")
+    R = red.view(B, rows // B, 868).sum(1)          # (B, 868) deterministic reduction of partial rows
+
+    def contract(A, Bm, M, N, batch):
+        """(batch, M, N) = A^T @ Bm per chunk of BP / batch rows (split-K): A (BP, M), Bm (BP, N) row-major, i.e. K-major;
+        Planes on the bf16x3 K-major GEMM, fp32 tensors on the fp32 GEMM"""
+        Kc = BP // batch
+        G = torch.empty(batch, M, N, device=dev)
+        if isinstance(A, Planes):
+            gemm_x3_km(A, Bm, M, N, Kc, M, N, batch, Kc * M, Kc * N, G)
         else:
-            BP = B * P
-            h1, h2, da2 = (Planes.empty(BP, 128, device=dev) for _ in range(3))
-            hc, dac = (Planes.empty(BP, 64, device=dev) for _ in range(2))
-            rows = lib.cips_siren_bwd_rows(B, P)
-            red = torch.empty(rows, 868, device=dev)
-            check(lib.cips_siren_bwd_data(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(h1.hi), _p(h1.lo),
-                                          _p(h2.hi), _p(h2.lo), _p(hc.hi), _p(hc.lo), _p(da2.hi), _p(da2.lo),
-                                          _p(dac.hi), _p(dac.lo), _p(red), B, P, _stream()), "cips_siren_bwd_data")
-            R = red.view(B, rows // B, 868).sum(1)          # (B, 868) deterministic reduction of partial rows
-            # weight-gradient contractions over the points (K = P per image, split-K) on the bf16x3 K-major GEMM
-            sp = _split_k(P, 16)
-            Kc = P // sp
-            G1 = torch.empty(B * sp, 128, 128, device=dev)   # da2^T @ h1
-            gemm_x3_km(da2, h1, 128, 128, Kc, 128, 128, B * sp, Kc * 128, Kc * 128, G1)
-            G1 = G1.view(B, sp, 128, 128).sum(1)
-            Gc = torch.empty(B * sp, 64, 128, device=dev)    # dac^T @ h2
-            gemm_x3_km(dac, h2, 64, 128, Kc, 64, 128, B * sp, Kc * 64, Kc * 128, Gc)
-            Gc = Gc.view(B, sp, 64, 128).sum(1)
-            hcf = hc.float()                                 # the 32x64 colour-linear gradient stays on the fp32 GEMM
-            spf = _split_k(BP, 1024)
-            Kf = BP // spf
-            Gf = torch.empty(spf, 32, 64, device=dev)        # dfeat^T @ hc (no per-image scale)
-            gemm(dfeat, hcf, Gf, 32, 64, Kf, 32, 64, 64, batch=spf, strideA=Kf * 32, strideB=Kf * 64,
-                 strideC=32 * 64, a_kmajor=True)
-            dwf = Gf.sum(0)
-        # ---- assemble parameter / FiLM gradients (tiny tensors) ----
-        g0, g1, gc = t["g0"], t["g1"], t["gc"]
-        w0, b0, w1, b1, wc, bc = t["w0"], t["b0"], t["w1"], t["b1"], t["wc"], t["bc"]
-        dp0 = R[:, 0:128]
-        S0 = R[:, 128:512].view(B, 3, 128).transpose(1, 2) * BOX_SCALE   # (B,128,3): sum_p da1 * x0_c
-        dg0 = (S0 * w0.unsqueeze(0)).sum(-1) + b0.unsqueeze(0) * dp0
-        dw0 = (g0.unsqueeze(-1) * S0).sum(0)
-        db0 = (g0 * dp0).sum(0)
-        dp1 = R[:, 512:640]
-        dg1 = (G1 * w1.unsqueeze(0)).sum(-1) + b1.unsqueeze(0) * dp1
-        dw1 = (g1.unsqueeze(-1) * G1).sum(0)
-        db1 = (g1 * dp1).sum(0)
-        dpc = R[:, 640:704]
-        dgc = (Gc * wc.unsqueeze(0)).sum(-1) + bc.unsqueeze(0) * dpc
-        dwc = (gc.unsqueeze(-1) * Gc).sum(0)
-        dbc = (gc * dpc).sum(0)
-        dws = R[:, 704:832].sum(0, keepdim=True)
-        dbf = R[:, 832:864].sum(0)
-        dbs = R[:, 864].sum().view(1)
-        return (dg0, dp0, dg1, dp1, dgc, dpc, dw0, db0, dw1, db1, dws, dbs, dwc, dbc, dwf, dbf)
+            gemm(A, Bm, G, M, N, Kc, M, N, N, batch=batch, strideA=Kc * M, strideB=Kc * N, strideC=M * N, a_kmajor=True)
+        return G
+
+    sp = _split_k(P, 16)                             # per image: K = P
+    G1 = contract(da2, h1, 128, 128, B * sp).view(B, sp, 128, 128).sum(1)
+    Gc = contract(dac, h2, 64, 128, B * sp).view(B, sp, 64, 128).sum(1)
+    # the 32x64 colour-linear gradient (no per-image scale) stays on the fp32 GEMM in both modes
+    dwf = contract(dfeat, hc if f32 else hc.float(), 32, 64, _split_k(BP, 1024)).sum(0)
+    # ---- assemble parameter / FiLM gradients (tiny tensors) ----
+    g0, g1, gc = t["g0"], t["g1"], t["gc"]
+    w0, b0, w1, b1, wc, bc = t["w0"], t["b0"], t["w1"], t["b1"], t["wc"], t["bc"]
+    d = {}
+    d["p0"] = dp0 = R[:, 0:128]
+    S0 = R[:, 128:512].view(B, 3, 128).transpose(1, 2) * BOX_SCALE   # (B,128,3): sum_p da1 * x0_c
+    d["g0"] = (S0 * w0.unsqueeze(0)).sum(-1) + b0.unsqueeze(0) * dp0
+    d["w0"] = (g0.unsqueeze(-1) * S0).sum(0)
+    d["b0"] = (g0 * dp0).sum(0)
+    d["p1"] = dp1 = R[:, 512:640]
+    d["g1"] = (G1 * w1.unsqueeze(0)).sum(-1) + b1.unsqueeze(0) * dp1
+    d["w1"] = (g1.unsqueeze(-1) * G1).sum(0)
+    d["b1"] = (g1 * dp1).sum(0)
+    d["pc"] = dpc = R[:, 640:704]
+    d["gc"] = (Gc * wc.unsqueeze(0)).sum(-1) + bc.unsqueeze(0) * dpc
+    d["wc"] = (gc.unsqueeze(-1) * Gc).sum(0)
+    d["bc"] = (gc * dpc).sum(0)
+    d["ws"] = R[:, 704:832].sum(0, keepdim=True)
+    d["bf"] = R[:, 832:864].sum(0)
+    d["bs"] = R[:, 864].sum().view(1)
+    d["wf"] = dwf
+    return tuple(d[n] for n in _SIREN_NAMES)
 
 
 # --------------------------------------------------------------------------------------
@@ -421,7 +420,6 @@ class GroupedLinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *wb):
         lib = _lib.load()
-        from ._lib import GlinJob
         x = _c(x.detach())
         ws = [_c(w.detach()) for w in wb[0::2]]
         bs = [_c(b.detach()) if b is not None else None for b in wb[1::2]]
@@ -445,7 +443,6 @@ class GroupedLinearFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dys):
         lib = _lib.load()
-        from ._lib import GlinJob
         x, *ws = ctx.saved_tensors
         B, in_dim = x.shape
         n = len(ws)
@@ -551,10 +548,17 @@ def march_available():
 
 
 def _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S, zvals=None):
-    from ._lib import RayParams
     r = RayParams()
     r.xg, r.yg, r.zg, r.cam2world, r.jitter, r.zvals = _p(xg), _p(yg), _p(zg), _p(cam2world), _p(jitter), _p(zvals)
     r.zc, r.H, r.W, r.S = float(zc), H, W, S
+    return r
+
+
+def _ray_prep(xg, yg, zg, cam2world, jitter, per_sample):
+    """the ray inputs of SirenRaysFunction / RayMarchFunction as detached contiguous fp32 tensors, checked: pixel grids,
+    cam2world, the optional jitter draw and the Function's optional per-sample tensor (`zvals` / `noise`)"""
+    r = [_c(v.detach()) if v is not None else None for v in (xg, yg, zg, cam2world, jitter, per_sample)]
+    _chk(*r)
     return r
 
 
@@ -565,17 +569,11 @@ class SirenRaysFunction(torch.autograd.Function):
     `zvals`: origin + direction * z (generator_nerf_inr.py:590-592).  Backward: cips_siren_bwd_x3_rays."""
 
     @staticmethod
-    def forward(ctx, geom, xg, yg, zg, cam2world, jitter, zvals, g0, p0, g1, p1, gc, pc, w0, b0, w1, b1, ws, bs, wc, bc,
-                wf, bf):
+    def forward(ctx, geom, xg, yg, zg, cam2world, jitter, zvals, *siren):
         lib = _lib.load()
         B, H, W, S, zc = geom
-        t = dict(w0=w0, b0=b0, w1=w1, b1=b1, ws=ws, bs=bs, wc=wc, bc=bc, wf=wf, bf=bf,
-                 g0=g0, p0=p0, g1=g1, p1=p1, gc=gc, pc=pc)
-        t = {k: _c(v.detach()) for k, v in t.items()}
-        xg, yg, zg, cam2world = _c(xg), _c(yg), _c(zg), _c(cam2world)
-        jitter = _c(jitter) if jitter is not None else None
-        zvals = _c(zvals.detach()) if zvals is not None else None
-        _chk(xg, yg, zg, cam2world, jitter, zvals, *t.values())
+        t = _siren_prep(siren)
+        xg, yg, zg, cam2world, jitter, zvals = _ray_prep(xg, yg, zg, cam2world, jitter, zvals)
         dev = cam2world.device
         P = H * W * S
         feat = torch.empty(B, P, 32, device=dev)
@@ -585,7 +583,7 @@ class SirenRaysFunction(torch.autograd.Function):
         rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S, zvals)
         check(lib.cips_siren_fwd_x3_rays(C.byref(sw), C.byref(rp), _p(feat), _p(sigma), _p(z) if zvals is None else None, B,
                                          _stream()), "cips_siren_fwd_x3_rays")
-        ctx.save_for_backward(xg, yg, zg, cam2world, jitter, zvals, *[t[k] for k in _SIREN_NAMES])
+        ctx.save_for_backward(xg, yg, zg, cam2world, jitter, zvals, *t.values())
         ctx.geom = geom
         ctx.mark_non_differentiable(z)
         return feat, sigma, z
@@ -595,12 +593,8 @@ class SirenRaysFunction(torch.autograd.Function):
         xg, yg, zg, cam2world, jitter, zvals = ctx.saved_tensors[:6]
         t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[6:]))
         B, H, W, S, zc = ctx.geom
-        P = H * W * S
-        dev = cam2world.device
-        dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
-        dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
         rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S, zvals)
-        return (None,) * 7 + _siren_backward(t, dfeat, dsigma, B, P, rays=rp)
+        return (None,) * 7 + _siren_backward(t, dfeat, dsigma, B, H * W * S, rays=rp)
 
 
 class RayMarchFunction(torch.autograd.Function):
@@ -612,17 +606,11 @@ class RayMarchFunction(torch.autograd.Function):
     SIREN backward with the points regenerated in-kernel (cips_siren_bwd_x3_rays)."""
 
     @staticmethod
-    def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, g0, p0, g1, p1, gc, pc, w0, b0, w1, b1, ws, bs, wc, bc,
-                wf, bf):
+    def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
         lib = _lib.load()
         B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom
-        t = dict(w0=w0, b0=b0, w1=w1, b1=b1, ws=ws, bs=bs, wc=wc, bc=bc, wf=wf, bf=bf,
-                 g0=g0, p0=p0, g1=g1, p1=p1, gc=gc, pc=pc)
-        t = {k: _c(v.detach()) for k, v in t.items()}
-        xg, yg, zg, cam2world = _c(xg), _c(yg), _c(zg), _c(cam2world)
-        jitter = _c(jitter) if jitter is not None else None
-        noise = _c(noise) if (noise is not None and noise_std != 0.0) else None
-        _chk(xg, yg, zg, cam2world, jitter, noise, *t.values())
+        t = _siren_prep(siren)
+        xg, yg, zg, cam2world, jitter, noise = _ray_prep(xg, yg, zg, cam2world, jitter, noise if noise_std != 0.0 else None)
         dev = cam2world.device
         n = H * W
         # per-sample outputs only when a backward can follow: the caller's grad mode counts (inside forward() it is
@@ -643,7 +631,7 @@ class RayMarchFunction(torch.autograd.Function):
             CLAMP_REC.append(rec.reshape(B * n, S))
         ctx.clamp_mask = pin
         if train:
-            ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *[t[k] for k in _SIREN_NAMES])
+            ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values())
         ctx.geom = geom
         ctx.mark_non_differentiable(depth)
         return fea, depth
@@ -971,12 +959,11 @@ class InrHeadFunction(torch.autograd.Function):
 # --------------------------------------------------------------------------------------
 # H4 on the bf16 matrix cores: 3-pass split GEMM ("bf16x3"), see csrc/gemm_bf16x3.hip
 # --------------------------------------------------------------------------------------
-import os as _os
 # "bf16x3" (default, ~1e-5 rel. per layer), "f32" (exact fp32 MFMA) or "bf16" (single pass on the hi planes: the AMP-class
 # arithmetic — operands rounded to bf16, fp32 accumulate; ~1e-3 of the image range, ~1 % of the gradients — on one third of
 # the matrix work; every GEMM of the head, forward and backward, through the cips_gemm_bf16* entry points).  Read when a head
 # evaluation starts: a captured graph keeps the mode it was captured in.
-INR_MODE = _os.environ.get("CIPS_INR_MODE", "bf16x3")
+INR_MODE = os.environ.get("CIPS_INR_MODE", "bf16x3")
 
 
 def _x3_entry(single, suffix=""):
@@ -988,7 +975,7 @@ BF = torch.bfloat16
 # kernels at C2) depends on nothing that follows the head in the backward pass.  "side": it hangs off the head through two
 # gradient ports whose autograd nodes live on the generator's side stream, so it runs next to the compositing / SIREN backward
 # instead of in front of it (CIPSNet.forward; profiles/r6_cores_tail_probe.txt).  "main": everything inside InrHeadX3Function.
-INR_TAIL = _os.environ.get("CIPS_INR_TAIL", "side")
+INR_TAIL = os.environ.get("CIPS_INR_TAIL", "side")
 
 
 class Planes:
@@ -1053,7 +1040,7 @@ def _addp_shape_ok(n, cin, cout, nb, dev, single=False):
 def gemm_x3_takes_addp(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **epi):
     """True when the library runs this descriptor with the planes addend (256x256-tile kernel, interior shapes)"""
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi)
-    return bool(_x3_entry(single, "_takes_addp")[1](_ct.byref(d)))
+    return bool(_x3_entry(single, "_takes_addp")[1](C.byref(d)))
 
 
 def gemm_x3(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **epi):
@@ -1061,7 +1048,7 @@ def gemm_x3(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **e
     single: sum_k A_hi * B_hi only (cips_gemm_bf16; here and in the functions below)"""
     name, fn = _x3_entry(single)
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi)
-    check(fn(_ct.byref(d), _stream()), name)
+    check(fn(C.byref(d), _stream()), name)
 
 
 def gemm_x3_torgb(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P, rgb_w, rgb_b, rgb2d, accumulate, single=False, **epi):
@@ -1072,27 +1059,27 @@ def gemm_x3_torgb(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P, rgb_w, r
     name, fn = _x3_entry(single)
     part = torch.empty(max(N // 128, 1), batch * M, 4, device=P.hi.device)
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P=P, torgb=(rgb_w, part), **epi)
-    if N % 128 == 0 and rgb_w.is_contiguous() and _x3_entry(single, "_fuses_torgb")[1](_ct.byref(d)):
-        check(fn(_ct.byref(d), _stream()), name)
+    if N % 128 == 0 and rgb_w.is_contiguous() and _x3_entry(single, "_fuses_torgb")[1](C.byref(d)):
+        check(fn(C.byref(d), _stream()), name)
         check(lib.cips_torgb_finish(_p(part), N // 128, _p(rgb_b), _p(rgb2d), batch * M, 1 if accumulate else 0, _stream()),
               "cips_torgb_finish")
         return
     d.torgb_w, d.torgb_part = None, None
-    check(fn(_ct.byref(d), _stream()), name)
+    check(fn(C.byref(d), _stream()), name)
     torgb_fwd_x3(P, rgb_w, rgb_b, rgb2d, accumulate)
 
 
-def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C, single=False):
+def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, Cm, single=False):
     """C[b][m][n] = sum_k A[b][k][m] * B[b][k][n]; A, B: Planes stored [K][ld] (k-major), C fp32 (M,N)."""
     name, fn = _x3_entry(single, "_km")
     d = GemmX3Desc()
     d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
     d.M, d.N, d.K, d.lda, d.ldb = M, N, K, lda, ldb
     d.strideA, d.strideB, d.batch = strideA, strideB, batch
-    d.C, d.ldc, d.strideC = _p(C), N, M * N
+    d.C, d.ldc, d.strideC = _p(Cm), N, M * N
     d.slope = LRELU_SLOPE
     d.kernel = X3_KERNEL
-    check(fn(_ct.byref(d), _stream()), name)
+    check(fn(C.byref(d), _stream()), name)
 
 
 def gemm_x3_km_grouped(problems, M, N, K, lda, ldb, batch, strideA, strideB, single=False):
@@ -1177,17 +1164,16 @@ def split_planes_nhwc(x):
     return Planes(hi, lo)
 
 
-def conv2d_x3(wP, xP, B, C, H, W, O, kh, kw, stride, pad, ksplit=None, bias=None, act=False, slope=0.2, act_scale=1.0):
-    """Implicit-GEMM convolution: wP Planes (O, kh*kw*C) with contraction index (tap, channel), xP NHWC Planes from
+def conv2d_x3(wP, xP, B, Cin, H, W, O, kh, kw, stride, pad, ksplit=None, bias=None, act=False, slope=0.2, act_scale=1.0):
+    """Implicit-GEMM convolution: wP Planes (O, kh*kw*Cin) with contraction index (tap, channel), xP NHWC Planes from
     split_planes_nhwc -> y (B, O, Ho, Wo) fp32."""
     lib = _lib.load()
-    from ._lib import ConvX3Desc
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     y = torch.empty(B, O, Ho, Wo, device=xP.hi.device)
     d = ConvX3Desc()
     d.w_hi, d.w_lo, d.x_hi, d.x_lo, d.y = _p(wP.hi), _p(wP.lo), _p(xP.hi), _p(xP.lo), _p(y)
-    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad = B, C, H, W, O, kh, kw, stride, pad
-    ks = lib.cips_conv2d_x3_ksplit(B, O, Ho * Wo, kh * kw * C) if ksplit is None else ksplit
+    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad = B, Cin, H, W, O, kh, kw, stride, pad
+    ks = lib.cips_conv2d_x3_ksplit(B, O, Ho * Wo, kh * kw * Cin) if ksplit is None else ksplit
     part = None
     if ks > 1:                                   # few output tiles: split the contraction over the idle CUs
         part = torch.empty(ks, B, O, Ho, Wo, device=xP.hi.device)
@@ -1196,7 +1182,7 @@ def conv2d_x3(wP, xP, B, C, H, W, O, kh, kw, stride, pad, ksplit=None, bias=None
         d.ksplit, d.part = 1, None
     d.bias = _p(bias) if bias is not None else None            # EqualConv2d + FusedLeakyReLU in the epilogue
     d.act, d.slope, d.act_scale = (1 if act else 0), float(slope), float(act_scale)
-    check(lib.cips_conv2d_x3(_ct.byref(d), _stream()), "cips_conv2d_x3")
+    check(lib.cips_conv2d_x3(C.byref(d), _stream()), "cips_conv2d_x3")
     return y
 
 
@@ -1229,12 +1215,11 @@ def dgrad_s2_layout(H, W):
     return nps
 
 
-def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, C, H, W, O, kh, kw):
+def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, Cin, H, W, O, kh, kw):
     """Data gradient of a stride-2 unpadded convolution as four parity sub-convolutions in one launch (cips_conv2d_x3_dgrad_s2).
     banks / w_off: dgrad_s2_banks(w); dyP: NHWC Planes of dy (B, O, Ho, Wo).  -> (dxp fp32 flat, out_off [4]): the gradient w.r.t.
-    the (B, C, H, W) input in parity-block layout, consumed by upfirdn2d_parity (or parity_to_nchw in tests)."""
+    the (B, Cin, H, W) input in parity-block layout, consumed by upfirdn2d_parity (or parity_to_nchw in tests)."""
     lib = _lib.load()
-    from ._lib import ConvDgradS2Desc
     nps = dgrad_s2_layout(H, W)
     # the four blocks are read TOGETHER by upfirdn2d_parity (one output needs all four parities); with B*C a power of two
     # their natural offsets are congruent modulo 64 KiB and the four streams queue on the same memory channels — skew them
@@ -1242,15 +1227,15 @@ def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, C, H, W, O, kh, kw):
     for i, n_ in enumerate(nps):
         tot += i * 1184                     # floats: 4 736 B, 16-byte granular
         out_off.append(tot)
-        tot += B * C * n_
+        tot += B * Cin * n_
     dxp = torch.empty(tot, device=dyP.hi.device)
     d = ConvDgradS2Desc()
     d.w_hi, d.w_lo, d.dy_hi, d.dy_lo, d.dxp = _p(banks.hi), _p(banks.lo), _p(dyP.hi), _p(dyP.lo), _p(dxp)
-    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw = B, C, H, W, O, kh, kw
+    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw = B, Cin, H, W, O, kh, kw
     for i in range(4):
         d.w_off[i] = w_off[i]
         d.out_off[i] = out_off[i]
-    check(lib.cips_conv2d_x3_dgrad_s2(_ct.byref(d), _stream()), "cips_conv2d_x3_dgrad_s2")
+    check(lib.cips_conv2d_x3_dgrad_s2(C.byref(d), _stream()), "cips_conv2d_x3_dgrad_s2")
     return dxp, out_off
 
 
@@ -1275,8 +1260,8 @@ def upfirdn2d_parity(dxp, out_off, kernel, major, in_h, in_w, pad_x0, pad_x1, pa
         raise RuntimeError("upfirdn2d_parity: 4 x 4 kernels only")
     out_h, out_w = in_h + pad_y0 + pad_y1 - 3, in_w + pad_x0 + pad_x1 - 3
     out = torch.empty(major, out_h, out_w, device=dxp.device)
-    offs = (_ct.c_longlong * 4)(*out_off)
-    check(lib.cips_upfirdn2d_parity(_p(dxp), _ct.byref(offs), _p(k), _p(out), major, in_h, in_w, pad_x0, pad_x1, pad_y0, pad_y1,
+    offs = (C.c_longlong * 4)(*out_off)
+    check(lib.cips_upfirdn2d_parity(_p(dxp), C.byref(offs), _p(k), _p(out), major, in_h, in_w, pad_x0, pad_x1, pad_y0, pad_y1,
                                     _stream()), "cips_upfirdn2d_parity")
     return out
 
@@ -1286,20 +1271,19 @@ def conv2d_x3_wgrad_declines(B, N):
     return (B * N) % 32 != 0
 
 
-def conv2d_x3_wgrad(dyP, xP, B, C, H, W, O, kh, kw, stride, pad, scale=1.0, nch=None):
-    """Weight gradient of conv2d_x3: dyP, xP NHWC Planes from split_planes_nhwc -> dW (O, C, kh, kw) fp32, or None when
+def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nch=None):
+    """Weight gradient of conv2d_x3: dyP, xP NHWC Planes from split_planes_nhwc -> dW (O, Cin, kh, kw) fp32, or None when
     the pixel count does not split into 32-row k-tiles (conv2d_x3_wgrad_declines).  The pixel range is cut into chunks so
     that a 512x512 filter bank still fills the chip (4 tiles per tap and chunk); cips_conv_wgrad_finish adds the partial
-    sums, applies `scale` and lays the result out as (O, C, kh, kw)."""
+    sums, applies `scale` and lays the result out as (O, Cin, kh, kw)."""
     lib = _lib.load()
-    from ._lib import ConvWgradDesc
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     K = B * Ho * Wo
     if conv2d_x3_wgrad_declines(B, Ho * Wo):
         return None
     # chunks of the pixel range: the persistent grid runs ceil(tiles*nch / 256) rounds of ~K/nch rows each (+ an
     # epilogue worth ~512 rows); 36 tiles x 7 chunks = 252 of 256 CUs in one round (powers of two: 144, or 288 in two)
-    tiles = ((O + 255) // 256) * ((C + 255) // 256) * kh * kw
+    tiles = ((O + 255) // 256) * ((Cin + 255) // 256) * kh * kw
     T = K // 32
     best = None
     forced = nch
@@ -1312,13 +1296,13 @@ def conv2d_x3_wgrad(dyP, xP, B, C, H, W, O, kh, kw, stride, pad, scale=1.0, nch=
             nch, best = cand, cost
     if forced is not None:
         nch = forced
-    part = torch.empty(nch, kh * kw, O, C, device=xP.hi.device)
+    part = torch.empty(nch, kh * kw, O, Cin, device=xP.hi.device)
     d = ConvWgradDesc()
     d.dy_hi, d.dy_lo, d.x_hi, d.x_lo, d.part = _p(dyP.hi), _p(dyP.lo), _p(xP.hi), _p(xP.lo), _p(part)
-    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad, d.nchunks = B, C, H, W, O, kh, kw, stride, pad, nch
-    check(lib.cips_conv2d_x3_wgrad(_ct.byref(d), _stream()), "cips_conv2d_x3_wgrad")
-    dw = torch.empty(O, C, kh, kw, device=xP.hi.device)
-    check(lib.cips_conv_wgrad_finish(_p(part), _p(dw), nch, kh * kw, O, C, float(scale), _stream()), "cips_conv_wgrad_finish")
+    d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad, d.nchunks = B, Cin, H, W, O, kh, kw, stride, pad, nch
+    check(lib.cips_conv2d_x3_wgrad(C.byref(d), _stream()), "cips_conv2d_x3_wgrad")
+    dw = torch.empty(O, Cin, kh, kw, device=xP.hi.device)
+    check(lib.cips_conv_wgrad_finish(_p(part), _p(dw), nch, kh * kw, O, Cin, float(scale), _stream()), "cips_conv_wgrad_finish")
     return dw
 
 
@@ -1339,7 +1323,6 @@ def modfc_prep_x3_batch(layers, eps=1e-8):
     """layers: list of (W (in,out), s (B,in)) -> list of (wb Planes (B,in,out), wbt Planes (B,out,in), demod (B,out)),
     all layers in two launches."""
     lib = _lib.load()
-    from ._lib import ModfcPrepJob
     mx = lib.cips_modfc_max_jobs()
     out = []
     for c0 in range(0, len(layers), mx):
@@ -1364,7 +1347,6 @@ def modfc_prep_bwd_batch(layers, cores=False):
     """layers: list of (W, s, demod, gwb) -> list of (dW, ds), all layers in three launches.  cores=True: the co-resident
     form (no LDS, <= 40 VGPRs: runs beside the fused SIREN backward when issued on a side stream; B <= 64, out % 4 == 0)."""
     lib = _lib.load()
-    from ._lib import ModfcBwdJob
     mx = lib.cips_modfc_max_jobs()
     out = []
     cores = bool(cores) and layers[0][1].shape[0] <= 64 and all(W.shape[1] % 4 == 0 for W, _, _, _ in layers)
@@ -1428,8 +1410,8 @@ def torgb_bwd_w_x3_batch(xps, drgb2d, cores=False):
     part = torch.empty(n, chunks, 4, K, device=dev)
     dw = torch.empty(n, 3, K, device=dev)
     db = torch.empty(n, 3, device=dev)
-    hi = (_ct.c_void_p * n)(*[_p(xp.hi) for xp in xps])
-    lo = (_ct.c_void_p * n)(*[_p(xp.lo) for xp in xps])
+    hi = (C.c_void_p * n)(*[_p(xp.hi) for xp in xps])
+    lo = (C.c_void_p * n)(*[_p(xp.lo) for xp in xps])
     fn = lib.cips_torgb_bwd_w_x3_batch_cores if cores else lib.cips_torgb_bwd_w_x3_batch
     check(fn(hi, lo, n, _p(drgb2d), _p(part), _p(dw), _p(db), M, K, _stream()), "cips_torgb_bwd_w_x3_batch")
     return [(dw[i], db[i]) for i in range(n)]

@@ -77,6 +77,17 @@ def test_struct_layouts_match_header_field_order():
     assert fields("cips_gemm_x3_desc") == [f[0] for f in _lib.GemmX3Desc._fields_]
 
 
+def test_siren_tensor_order_agrees_with_the_structs():
+    """ops._SIREN_NAMES is the one order of the 16 SIREN tensors (Function arguments, saved tensors, returned gradients):
+    "d" + name must be the fields of SirenGrads in order, and the names exactly the 16 pointer fields of SirenWeights"""
+    import ctypes
+    from cips3d_amd import _lib, ops
+    assert len(ops._SIREN_NAMES) == 16 and len(set(ops._SIREN_NAMES)) == 16
+    assert ["d" + n for n in ops._SIREN_NAMES] == [f[0] for f in _lib.SirenGrads._fields_]
+    pointers = [f[0] for f in _lib.SirenWeights._fields_ if f[1] is ctypes.c_void_p]
+    assert len(pointers) == 16 and sorted(ops._SIREN_NAMES) == sorted(pointers)
+
+
 def test_product_path_has_no_cpu_fallback():
     G = seeded_generator(0)
     zs = G.get_zs(1)

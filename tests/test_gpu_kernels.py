@@ -187,9 +187,14 @@ def test_siren_forward_x3_sigma_is_fp32_class(scale_w, monkeypatch):
 
 
 @pytest.mark.parametrize("trig,mode,b,P", [(0, "x3", 2, 2048 + 96), (1, "x3", 2, 2048 + 96), (1, "x3", 3, 128 * 7 + 5),
-                                             (1, "x3", 1, 4096 * 3), (0, "staged", 2, 2048 + 96), (1, "staged", 2, 2048 + 96)])
+                                             (1, "x3", 1, 4096 * 3), (0, "staged", 2, 2048 + 96), (1, "staged", 2, 2048 + 96),
+                                             (1, "staged_f32", 2, 2048 + 96),
+                                             (1, "x3", 2, 2240), (1, "staged", 2, 2240), (1, "staged_f32", 2, 2240)])
 def test_siren_backward(trig, mode, b, P, monkeypatch):
-    """fused bf16x3 backward ("x3", default) and the staged data-pass + GEMM form, vs the fp32 CPU oracle's autograd"""
+    """fused bf16x3 backward ("x3", default) and the staged data-pass + GEMM forms (split-bf16 "staged", all-fp32
+    "staged_f32"), vs the fp32 CPU oracle's autograd.  P = 2240 = 2048 + 192: two data-pass chunks per image, the second
+    ragged, and the staged contractions really split K (_split_k(2240, 16) == 14, _split_k(2 * 2240, 1024) == 140; at
+    P = 2144 the per-image split count is 1)."""
     from cips3d_amd import ops
     monkeypatch.setattr(ops, "SIREN_BWD_MODE", mode)
     G, pts, style = _siren_inputs(4, b, P)
