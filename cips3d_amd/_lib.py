@@ -156,6 +156,10 @@ SIGNATURES = {
     "cips_conv_weight_prep_batch": (i32, [C.POINTER(WPrepJob), i32, vp]),
     "cips_conv2d_x3_dgrad_s2": (i32, [C.POINTER(ConvDgradS2Desc), vp]),
     "cips_conv_wgrad_finish": (i32, [vp, vp, i32, i32, i32, i32, f32, vp]),
+    "cips_conv2d_bf16": (i32, [C.POINTER(ConvX3Desc), vp]),
+    "cips_conv2d_bf16_ksplit": (i32, [i32, i32, i32, i32]),
+    "cips_conv2d_bf16_dgrad_s2": (i32, [C.POINTER(ConvDgradS2Desc), vp]),
+    "cips_conv2d_bf16_wgrad": (i32, [C.POINTER(ConvWgradDesc), vp]),
     "cips_modfc_prep_x3": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "cips_torgb_fwd_x3": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "cips_torgb_bwd_w_x3": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp]),

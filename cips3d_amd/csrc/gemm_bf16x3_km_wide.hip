@@ -244,10 +244,10 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_wide_kernel(KArgs g) {
 
 // X1: the single-pass form (cips_gemm_bf16_km*: hi planes only) on the stage contents and the k-tile schedule x1_ktile of
 // gemm_x3_common.h — planes 1 and 3 of a stage hold the hi planes' k-rows 32..63 of a 64-deep k-tile.  K is a multiple of 64,
-// at least 128.
+// at least 128.  CONV && X1 (cips_conv2d_bf16_wgrad): cv.ktiles counts 64-row k-tiles; the dy rows of a k-tile's second half
+// are contiguous (+ 32 * lda), the gathered x rows of the second half have their own offsets (cvoff[2], cvoff[3]).
 template <bool CONV, bool X1 = false>
 __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
-  static_assert(!(CONV && X1), "the convolution weight gradient has no single-pass form");
   constexpr int KT = X1 ? X1_BK : BK;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
@@ -272,10 +272,10 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
     const int gp = CONV ? 0 : gi;
     const long long kt0 = CONV ? (long long)bz * g.cv.ktiles / g.cv.nchunks : 0;
     const int nk = CONV ? (int)((long long)(bz + 1) * g.cv.ktiles / g.cv.nchunks - kt0) : nk_all;     // >= 2 (host)
-    const u16* Ahi = (const u16*)g.A_hi[gp] + (CONV ? kt0 * BK * d.lda : (long long)bz * d.strideA);
-    const u16* Alo = X1 ? Ahi + 32LL * d.lda : (const u16*)g.A_lo[gp] + (CONV ? kt0 * BK * d.lda : (long long)bz * d.strideA);
+    const u16* Ahi = (const u16*)g.A_hi[gp] + (CONV ? kt0 * KT * d.lda : (long long)bz * d.strideA);
+    const u16* Alo = X1 ? Ahi + 32LL * d.lda : (const u16*)g.A_lo[gp] + (CONV ? kt0 * KT * d.lda : (long long)bz * d.strideA);
     const u16* Bhi = (const u16*)g.B_hi[gp] + (CONV ? 0 : (long long)bz * d.strideB);
-    const u16* Blo = X1 ? Bhi + 32LL * d.ldb : (const u16*)g.B_lo[gp] + (CONV ? 0 : (long long)bz * d.strideB);
+    const u16* Blo = X1 ? (CONV ? Bhi : Bhi + 32LL * d.ldb) : (const u16*)g.B_lo[gp] + (CONV ? 0 : (long long)bz * d.strideB);
     float* Cg = g.C[gp] + (CONV ? (long long)gi * d.M * d.ldc : 0);
     const int tap_ky = CONV ? gi / g.cv.kw : 0, tap_kx = CONV ? gi - tap_ky * g.cv.kw : 0;
 
@@ -311,12 +311,16 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       const long long row = ok ? ((long long)b * g.cv.H + iy) * g.cv.W + ix : g.cv.zero_row;
       return (unsigned)(row * d.ldb * 2) + colB[par];
     };
-    unsigned cvoff[2] = {0, 0};
+    unsigned cvoff[X1 ? 4 : 2] = {};       // B pieces idx = uw, uw + 8 of the k-tile being issued; X1: [2], [3] = its rows 32 .. 63
     auto conv_prep = [&](int k0) {
       if constexpr (CONV) {
-        const long long qb = kt0 * BK + k0 + lh;
+        const long long qb = kt0 * KT + k0 + lh;
         cvoff[0] = conv_row_off(qb + 2 * uw, uw & 1);
         cvoff[1] = conv_row_off(qb + 2 * (uw + 8), uw & 1);
+        if constexpr (X1) {
+          cvoff[2] = conv_row_off(qb + 32 + 2 * uw, uw & 1);
+          cvoff[3] = conv_row_off(qb + 32 + 2 * (uw + 8), uw & 1);
+        }
       }
     };
     auto dma_piece = [&](int pc, int k0, unsigned st) {            // st: LDS byte offset of the stage
@@ -325,7 +329,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
       const unsigned la = sbase + st + (unsigned)idx * 1024u;
       if (which == 0) lds_dma16(Ahi + rowoff * d.lda, offA[idx & 1], la + OFF_AHI);
       else if (which == 1) lds_dma16(Alo + rowoff * d.lda, offA[idx & 1], la + OFF_ALO);
-      else if constexpr (CONV) lds_dma16(which == 2 ? Bhi : Blo, cvoff[pc >> 2], la + (which == 2 ? OFF_BHI : OFF_BLO));
+      else if constexpr (CONV) lds_dma16(which == 2 ? Bhi : Blo, cvoff[(X1 && which == 3 ? 2 : 0) + (pc >> 2)], la + (which == 2 ? OFF_BHI : OFF_BLO));
       else if (which == 2) lds_dma16(Bhi + rowoff * d.ldb, offB[idx & 1], la + OFF_BHI);
       else lds_dma16(Blo + rowoff * d.ldb, offB[idx & 1], la + OFF_BLO);
     };
@@ -414,6 +418,10 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
         for (int j = 0; j < 4; ++j) { bc[ks][j] = fb[ks][j] + cur; asm volatile("" : "+v"(bc[ks][j])); }
       }
       asm volatile("" : "+v"(an[0]), "+v"(an[1]), "+v"(bn[0]), "+v"(bn[1]), "+v"(bn[2]), "+v"(bn[3]));
+      if constexpr (CONV) {
+        if constexpr (MODE == 0) conv_prep((kt + 2) * KT);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       auto rd1 = [&](auto Q_, auto S_, auto NEXT_) -> bf16x8 {
         constexpr int q = decltype(Q_)::value, s = decltype(S_)::value, tl = x1_frag_tile(q);
         if constexpr (decltype(NEXT_)::value) return frag(x1_frag_is_a(q) ? an[tl] : bn[tl], x1_frag_plane(q, s));
@@ -433,7 +441,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_km_v3_kernel(KArgs g) {
     conv_prep(0);
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, 0, 0);
-    conv_prep(BK);
+    conv_prep(KT);
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, KT, STAGE);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
@@ -546,7 +554,10 @@ extern "C" int cips_gemm_bf16_km_grouped(const cips_gemm_x3_desc* descs, int ngr
 
 // Convolution weight gradient (see include/cips3d_hip.h): part[chunk][tap][o][c] = sum over the chunk's output pixels q
 // of dy[q][o] * x[pixel(q) (+) tap][c]
-extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t stream) {
+// X1: cips_conv2d_bf16_wgrad — 64-row k-tiles, two or more per chunk, or hipErrorNotSupported; never 3-pass
+template <bool X1>
+static int conv_wgrad_entry(const cips_conv_wgrad_desc* c, cips_stream_t stream) {
+  constexpr int KT = X1 ? X1_BK : BK;
   if (!c || c->B <= 0 || c->C <= 0 || c->O <= 0 || c->H <= 0 || c->W <= 0 || c->kh <= 0 || c->kw <= 0 || c->stride <= 0 ||
       c->pad < 0 || c->nchunks <= 0 || !c->part)
     return (int)hipErrorInvalidValue;
@@ -554,6 +565,7 @@ extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t
   if (Ho <= 0 || Wo <= 0) return (int)hipErrorInvalidValue;
   const long long Kall = (long long)c->B * Ho * Wo;
   if ((c->C & 7) || (c->O & 7) || (Kall & 31) || c->nchunks > Kall / 32) return (int)hipErrorNotSupported;
+  if (X1 && ((Kall % X1_BK) || (Kall / X1_BK) / c->nchunks < 2)) return (int)hipErrorNotSupported;
   const long long rows_x = (long long)c->B * c->H * c->W + 1;
   if (rows_x * c->C * 2 >= 0xffffffffLL || Kall * c->O * 2 >= 0x7fffffffffffLL) return (int)hipErrorNotSupported;
   KArgs g = {};
@@ -563,7 +575,7 @@ extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t
   d.ldc = c->C; d.strideC = (long long)c->kh * c->kw * c->O * c->C;
   g.A_hi[0] = c->dy_hi; g.A_lo[0] = c->dy_lo; g.B_hi[0] = c->x_hi; g.B_lo[0] = c->x_lo; g.C[0] = c->part;
   g.cv.C = c->C; g.cv.H = c->H; g.cv.W = c->W; g.cv.kw = c->kw; g.cv.stride = c->stride; g.cv.pad = c->pad;
-  g.cv.Ho = Ho; g.cv.Wo = Wo; g.cv.ntap = c->kh * c->kw; g.cv.zero_row = rows_x - 1; g.cv.ktiles = (int)(Kall / 32); g.cv.nchunks = c->nchunks;
+  g.cv.Ho = Ho; g.cv.Wo = Wo; g.cv.ntap = c->kh * c->kw; g.cv.zero_row = rows_x - 1; g.cv.ktiles = (int)(Kall / KT); g.cv.nchunks = c->nchunks;
   g.tiles_m = (d.M + BM - 1) / BM;
   g.tiles_n = (d.N + BN - 1) / BN;
   g.ngroups = g.cv.ntap;
@@ -574,14 +586,16 @@ extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_km_v3_kernel<true, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr = true;
   }
   const int ncu = cips_persistent_cus();
   const int grid = g.total < ncu ? g.total : ncu;
-  if (g.cv.ktiles / g.cv.nchunks >= 2)          // every chunk has at least two k-tiles (else: the one-k-tile form)
-    hipLaunchKernelGGL(gemm_bf16x3_km_v3_kernel<true>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
+  if (X1 || g.cv.ktiles / g.cv.nchunks >= 2)    // every chunk has at least two k-tiles (else: the one-k-tile form, 3-pass only)
+    hipLaunchKernelGGL((gemm_bf16x3_km_v3_kernel<true, X1>), dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
   else
     hipLaunchKernelGGL(gemm_bf16x3_km_wide_kernel<true>, dim3(grid), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t stream) { return conv_wgrad_entry<false>(c, stream); }
+extern "C" int cips_conv2d_bf16_wgrad(const cips_conv_wgrad_desc* c, cips_stream_t stream) { return conv_wgrad_entry<true>(c, stream); }

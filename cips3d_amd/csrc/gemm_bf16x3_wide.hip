@@ -465,7 +465,13 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_wide_kernel(WArgs g) {
 // k-tile t+2 follows that barrier).  Same tile, LDS image, gather addressing (make_src / prep_b above) and MFMA order per
 // accumulator as the CONV instantiation of the kernel above: bit-identical outputs.  A convolution's contraction is long
 // (9 C / 32 k-tiles), so tiles do not overlap here: k-tiles 0 and 1 are requested at the tile start.
+// X1: the single-pass form (cips_conv2d_bf16*: sum_k w_hi x_hi, lo planes never addressed) on the stage contents and the k-tile
+// schedule x1_ktile of gemm_x3_common.h — planes 1 and 3 of a stage hold the hi planes' second 32 contraction indices of a
+// 64-deep k-tile.  The contraction channels are a multiple of 64 (host), so a 64-deep k-tile lies inside one tap: the second
+// half of a gathered row is the first half's offset + 64 bytes, in the zero row too.
+template <bool X1 = false>
 __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
+  constexpr int KT = X1 ? X1_BK : BK;                      // contraction depth of an LDS stage
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
   const int tid = threadIdx.x;
@@ -518,16 +524,16 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
       kc = bk % ksplit;
       bz = bk / ksplit;
     }
-    const int nk_all = K / BK;
+    const int nk_all = K / KT;
     auto chunk_kt0 = [&](int kc_) -> int { return (int)((long long)kc_ * nk_all / ksplit); };
     const int m0 = tm * BM, n0 = tn * BN;
-    const int kbase = chunk_kt0(kc) * BK;
+    const int kbase = chunk_kt0(kc) * KT;
     const int nk = chunk_kt0(kc + 1) - chunk_kt0(kc);          // >= 2 (host)
     // ---- sources: weights (A) row-major [O][kh*kw*C]; pixels (B) gathered per tap from the NHWC planes of image bz
     const u16* Ahi = (const u16*)d.A_hi + a_off + (long long)m0 * lda + kbase;
-    const u16* Alo = (const u16*)d.A_lo + a_off + (long long)m0 * lda + kbase;
+    const u16* Alo = X1 ? Ahi + 32 : (const u16*)d.A_lo + a_off + (long long)m0 * lda + kbase;
     const u16* Bhi = (const u16*)d.B_hi + (long long)bz * g.cv.img_stride;
-    const u16* Blo = (const u16*)d.B_lo + (long long)bz * g.cv.img_stride;
+    const u16* Blo = X1 ? Bhi + 32 : (const u16*)d.B_lo + (long long)bz * g.cv.img_stride;
     const unsigned zero_rel = (unsigned)((g.cv.zero_elem - (long long)bz * g.cv.img_stride) * 2);
     unsigned offA[2], offB[2], chunk[2], imgoff[2];
     int iy0[2], ix0[2];
@@ -582,7 +588,8 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
     const int csw = (l31 >> 2) & 3;
     const unsigned fa0 = sbase + (wm * 64 + l31) * ROWB + ((hf ^ csw) << 4), fa1 = sbase + (wm * 64 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
     const unsigned fb0 = sbase + (wn * 128 + l31) * ROWB + ((hf ^ csw) << 4), fb1 = sbase + (wn * 128 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
-    bf16x8 F0[12], F1[12];
+    bf16x8 F0[12], F1[12];        // the 3-pass schedule's two fragment sets
+    bf16x8 G[2][6];               // the single-pass schedule's
 
     auto ktile = [&](auto MODE_, int kt) {                     // MODE 0 steady, 1 next-to-last, 2 last
       constexpr int MODE = decltype(MODE_)::value;
@@ -618,19 +625,55 @@ __global__ __launch_bounds__(512) void conv2d_x3_v3_kernel(WArgs g) {
       });
     };
 
+    // ---- single pass: the same three k-tile forms on x1_ktile, the eight pieces of k-tile kt+2 behind the barrier (as many
+    // pieces per stage as in the 3-pass form: the vmcnt counts at the tile start and at the barrier are the same)
+    auto ktile1 = [&](auto MODE_, int kt) {
+      constexpr int MODE = decltype(MODE_)::value;
+      const unsigned cur = (unsigned)(kt & 1) * STAGE, nxt = STAGE - cur;
+      unsigned ac0 = fa0 + cur, ac1 = fa1 + cur, bc0 = fb0 + cur, bc1 = fb1 + cur, an = fa0 + nxt, bn = fb0 + nxt;
+      asm volatile("" : "+v"(ac0), "+v"(ac1), "+v"(bc0), "+v"(bc1), "+v"(an), "+v"(bn));
+      if constexpr (MODE == 0) prep_b((kt + 2) * KT);
+      __builtin_amdgcn_sched_barrier(0);
+      auto rd = [&](auto Q_, auto S_, auto NEXT_) -> bf16x8 {
+        constexpr int q = decltype(Q_)::value, s = decltype(S_)::value;
+        constexpr int off = x1_frag_plane(q, s) + x1_frag_tile(q) * 32 * ROWB;
+        if constexpr (decltype(NEXT_)::value) return LDS_B128((x1_frag_is_a(q) ? an : bn) + off);
+        else return LDS_B128((x1_frag_is_a(q) ? ((s & 1) ? ac1 : ac0) : ((s & 1) ? bc1 : bc0)) + off);
+      };
+      auto slot = [&](auto S_, auto M_) {
+        constexpr int s = decltype(S_)::value, m = decltype(M_)::value;
+        if constexpr (MODE == 0 && s == 3 && m >= 2) {
+#pragma unroll
+          for (int i = 0; i < x1_pieces(m); ++i) dma_piece(x1_piece0(m) + i, (kt + 2) * KT, cur);
+        }
+      };
+      x1_ktile<MODE>(acc, G, rd, slot);
+    };
+
     prep_b(0);
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) dma_piece(pc, 0, 0);
-    prep_b(BK);
+    prep_b(KT);
 #pragma unroll
-    for (int pc = 0; pc < 8; ++pc) dma_piece(pc, BK, STAGE);
+    for (int pc = 0; pc < 8; ++pc) dma_piece(pc, KT, STAGE);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+    if constexpr (X1) {
+      static_for(std::make_integer_sequence<int, 6>{}, [&](auto Q_) {
+        constexpr int q = decltype(Q_)::value;
+        G[0][q] = LDS_B128((x1_frag_is_a(q) ? fa0 : fb0) + x1_frag_plane(q, 0) + x1_frag_tile(q) * 32 * ROWB);
+      });
+      __builtin_amdgcn_sched_barrier(0);
+      for (int kt = 0; kt < nk - 2; ++kt) ktile1(std::integral_constant<int, 0>{}, kt);
+      ktile1(std::integral_constant<int, 1>{}, nk - 2);
+      ktile1(std::integral_constant<int, 2>{}, nk - 1);
+    } else {
 #pragma unroll
-    for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
-    __builtin_amdgcn_sched_barrier(0);
-    for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
-    ktile(std::integral_constant<int, 1>{}, nk - 2);
-    ktile(std::integral_constant<int, 2>{}, nk - 1);
+      for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
+      __builtin_amdgcn_sched_barrier(0);
+      for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
+      ktile(std::integral_constant<int, 1>{}, nk - 2);
+      ktile(std::integral_constant<int, 2>{}, nk - 1);
+    }
     __syncthreads();
 
     // ---- epilogue: bias + FusedLeakyReLU (unsplit launches), fp32 rows of 8 through the per-wave scratch (stage 1)
@@ -729,11 +772,22 @@ __global__ __launch_bounds__(256) void sum_chunks_kernel(const float4* __restric
 }
 }  // namespace
 
+template <bool X1>
+static void launch_conv_v3(const WArgs& g, hipStream_t stream) {
+  static bool attr = false;
+  CIPS_PER_DEVICE(attr, false);
+  if (!attr) { (void)hipFuncSetAttribute((const void*)conv2d_x3_v3_kernel<X1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES); attr = true; }
+  hipLaunchKernelGGL(conv2d_x3_v3_kernel<X1>, dim3(wide_grid(g.total)), dim3(512), SMEM_BYTES, stream, g);
+}
+
 // Implicit-GEMM convolution (see include/cips3d_hip.h): y[b] (O, Ho*Wo) = Wp (O, kh*kw*C) . gather(x[b])^T
-extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) {
+// X1: cips_conv2d_bf16 — the single-pass kernel or hipErrorNotSupported (C % 64, two 64-deep k-tiles per chunk), never 3-pass
+template <bool X1>
+static int conv2d_entry(const cips_conv_x3_desc* c, cips_stream_t stream) {
+  constexpr int KT = X1 ? X1_BK : BK;
   if (!c || c->B <= 0 || c->C <= 0 || c->O <= 0 || c->H <= 0 || c->W <= 0 || c->kh <= 0 || c->kw <= 0 || c->stride <= 0 || c->pad < 0)
     return (int)hipErrorInvalidValue;
-  if (c->C & 31) return (int)hipErrorNotSupported;
+  if (c->C & (KT - 1)) return (int)hipErrorNotSupported;
   const int Ho = (c->H + 2 * c->pad - c->kh) / c->stride + 1, Wo = (c->W + 2 * c->pad - c->kw) / c->stride + 1;
   const long long N = (long long)Ho * Wo, K = (long long)c->kh * c->kw * c->C;
   if (Ho <= 0 || Wo <= 0 || (N & 7)) return (int)hipErrorNotSupported;
@@ -748,7 +802,7 @@ extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) 
   g.cv.img_stride = img; g.cv.zero_elem = img * c->B;
   // small output planes: the batch folded into the pixel dimension (the two-register-set kernel only: every chunk of the
   // contraction needs two k-tiles; a one-k-tile problem keeps the per-image tiles of the wide kernel)
-  const bool fold = N < BN && c->B > 1 && (K / 32) / (c->ksplit > 1 ? c->ksplit : 1) >= 2;
+  const bool fold = N < BN && c->B > 1 && (K / KT) / (c->ksplit > 1 ? c->ksplit : 1) >= 2;
   if (fold) {
     if ((long long)c->B * N > 0x7fffffffLL) return (int)hipErrorNotSupported;
     g.cv.nimg = (int)N; d.N = (int)(c->B * N); d.batch = 1; d.strideC = (long long)c->B * c->O * N;
@@ -766,14 +820,12 @@ extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) 
   const long long total = (long long)g.tiles_m * g.tiles_n * d.batch * ks;
   if (total > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   g.total = (int)total;
-  const bool v3 = (K / 32) / ks >= 2;           // every chunk has at least two k-tiles (else: the one-k-tile form of the wide kernel)
+  const bool v3 = (K / KT) / ks >= 2;           // every chunk has at least two k-tiles (else: the one-k-tile form of the wide kernel)
   if (v3) {
-    static bool attr = false;
-    CIPS_PER_DEVICE(attr, false);
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv2d_x3_v3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES); attr = true; }
-    hipLaunchKernelGGL(conv2d_x3_v3_kernel, dim3(wide_grid(g.total)), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
+    launch_conv_v3<X1>(g, (hipStream_t)stream);
   } else {
-    launch_wide<false, false, false, true>(g, wide_grid(g.total), (hipStream_t)stream);
+    if constexpr (X1) return (int)hipErrorNotSupported;       // the one-k-tile form is 3-pass only
+    else launch_wide<false, false, false, true>(g, wide_grid(g.total), (hipStream_t)stream);
   }
   if (ks > 1) {
     const long long n4 = (long long)c->B * c->O * N / 4;        // N % 8 == 0
@@ -784,14 +836,19 @@ extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) 
   }
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" int cips_conv2d_x3(const cips_conv_x3_desc* c, cips_stream_t stream) { return conv2d_entry<false>(c, stream); }
+extern "C" int cips_conv2d_bf16(const cips_conv_x3_desc* c, cips_stream_t stream) { return conv2d_entry<true>(c, stream); }
 
 // Data gradient of a stride-2, unpadded convolution as four parity sub-convolutions in one launch (include/cips3d_hip.h)
-extern "C" int cips_conv2d_x3_dgrad_s2(const cips_conv_dgrad_s2_desc* c, cips_stream_t stream) {
-  if (!c || !c->w_hi || !c->w_lo || !c->dy_hi || !c->dy_lo || !c->dxp || c->B <= 0 || c->C <= 0 || c->O <= 0 || c->H <= 0 || c->W <= 0 ||
+// X1: cips_conv2d_bf16_dgrad_s2 — O % 64 == 0 and O >= 128 (the single-tap parity class contracts over O alone)
+template <bool X1>
+static int dgrad_s2_entry(const cips_conv_dgrad_s2_desc* c, cips_stream_t stream) {
+  constexpr int KT = X1 ? X1_BK : BK;
+  if (!c || !c->w_hi || (!X1 && !c->w_lo) || !c->dy_hi || (!X1 && !c->dy_lo) || !c->dxp || c->B <= 0 || c->C <= 0 || c->O <= 0 || c->H <= 0 || c->W <= 0 ||
       c->kh <= 0 || c->kw <= 0)
     return (int)hipErrorInvalidValue;
   if (c->H < c->kh || c->W < c->kw) return (int)hipErrorInvalidValue;
-  if ((c->O & 31) || (c->C & 7)) return (int)hipErrorNotSupported;
+  if ((c->O & (KT - 1)) || (c->C & 7)) return (int)hipErrorNotSupported;
   const int Ho = (c->H - c->kh) / 2 + 1, Wo = (c->W - c->kw) / 2 + 1;
   const long long img = (long long)Ho * Wo * c->O;
   if ((img * c->B + c->O) * 2 >= 0xffffffffLL) return (int)hipErrorNotSupported;          // 32-bit lane offsets
@@ -820,7 +877,7 @@ extern "C" int cips_conv2d_x3_dgrad_s2(const cips_conv_dgrad_s2_desc* c, cips_st
       cp.nimg = fold ? np_img : 0;
       cp.N = fold ? np_img * c->B : np_img;
       cp.K = Ta * Tb * c->O; cp.lda = cp.K;
-      if (cp.K / BK < 2) return (int)hipErrorNotSupported;
+      if (cp.K / KT < 2) return (int)hipErrorNotSupported;
       cp.ldc = np_img; cp.strideC = (long long)c->C * np_img;
       cp.a_off = c->w_off[2 * a + b]; cp.c_off = c->out_off[2 * a + b];
       if ((cp.a_off & 7) || (cp.c_off & 3)) return (int)hipErrorInvalidValue;
@@ -844,28 +901,32 @@ extern "C" int cips_conv2d_x3_dgrad_s2(const cips_conv_dgrad_s2_desc* c, cips_st
   g.nparts = np;
   g.total = 8 * longest;
   g.tiles_n = g.part[0].tiles_n;
-  static bool attr = false;
-  CIPS_PER_DEVICE(attr, false);
-  if (!attr) { (void)hipFuncSetAttribute((const void*)conv2d_x3_v3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES); attr = true; }
-  hipLaunchKernelGGL(conv2d_x3_v3_kernel, dim3(wide_grid(g.total)), dim3(512), SMEM_BYTES, (hipStream_t)stream, g);
+  launch_conv_v3<X1>(g, (hipStream_t)stream);
   return CIPS_CHECK_LAUNCH();
 }
+extern "C" int cips_conv2d_x3_dgrad_s2(const cips_conv_dgrad_s2_desc* c, cips_stream_t stream) { return dgrad_s2_entry<false>(c, stream); }
+extern "C" int cips_conv2d_bf16_dgrad_s2(const cips_conv_dgrad_s2_desc* c, cips_stream_t stream) { return dgrad_s2_entry<true>(c, stream); }
 
-extern "C" int cips_conv2d_x3_ksplit(int B, int O, int N, int K) {
+// kt_depth / kt_cost: contraction depth of a k-tile and its cost in the model's unit (one 32-deep 3-pass k-tile = 32; a
+// 64-deep single-pass k-tile is 32 MFMAs per wave against that k-tile's 48: 21)
+static int conv_ksplit(int B, int O, int N, int K, int kt_depth, int kt_cost) {
   // chunks of the contraction that fill the chip when the output has few 256 x 256 tiles (16 x 16 planes: 64 of 256 CUs)
   const long long tiles = (N < BN && B > 1) ? (long long)((O + BM - 1) / BM) * (((long long)B * N + BN - 1) / BN)      // folded batch
                                             : (long long)((O + BM - 1) / BM) * ((N + BN - 1) / BN) * B;
-  const int T = K / 32;
+  const int T = K / kt_depth;
   int best = 1;
   long long best_cost = -1;
   for (int c = 1; c <= 8; ++c) {
     if (c > 1 && T / c < 8) break;
     const long long rounds = (tiles * c + 255) / 256;
-    const long long cost = rounds * ((T + c - 1) / c * 32 + 256) + (c > 1 ? 64 * c : 0);     // + the partial-sum pass
+    const long long cost = rounds * ((T + c - 1) / c * kt_cost + 256) + (c > 1 ? 64 * c : 0);     // + the partial-sum pass
     if (best_cost < 0 || cost < best_cost) { best = c; best_cost = cost; }
   }
   return best;
 }
+extern "C" int cips_conv2d_x3_ksplit(int B, int O, int N, int K) { return conv_ksplit(B, O, N, K, BK, 32); }
+// the single-pass form's proposal: cuts at 64-deep granularity, every chunk at least eight k-tiles
+extern "C" int cips_conv2d_bf16_ksplit(int B, int O, int N, int K) { return conv_ksplit(B, O, N, K, X1_BK, 21); }
 
 extern "C" CIPS_INTERNAL int cips_gemm_bf16x3_wide(const cips_gemm_x3_desc* d, cips_stream_t stream) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return (int)hipErrorInvalidValue;

@@ -197,13 +197,27 @@ def upfirdn2d(input, kernel, up=1, down=1, pad=(0, 0)):
 #             convolution behind a Blur, as four stride-1 sub-convolutions, one per parity class of the input pixel;
 #   f32       exact fp32: cips_im2col + cips_gemm_f32 (fp32 MFMA) + cips_col2im — every shape the other two do not take, and
 #             every GEMM convolution when CIPS_D_CONV_MODE=f32.
+# CIPS_D_CONV_MODE=bf16 (the counterpart of the reference's use_amp_D) keeps this rule and its three form names: an "implicit" /
+# "parity" convolution then multiplies the bf16 hi planes alone, in one MFMA pass with fp32 accumulation (cips_conv2d_bf16*),
+# wherever _single_pass says the shape qualifies, and runs the 3-pass kernel where it does not.  "rgb" and "f32" stay exact.
 # ------------------------------------------------------------------------------------------
 def _pad4(n):
     return (n + 3) // 4 * 4
 
 
 import os as _os
+CONV_MODES = ("bf16x3", "f32", "bf16")
 CONV_MODE = _os.environ.get("CIPS_D_CONV_MODE", "bf16x3")
+
+
+def _conv_mode():
+    """CONV_MODE, read per call; anything but the three values raises (it used to select exact fp32 silently)"""
+    if CONV_MODE not in CONV_MODES:
+        raise ValueError(f"cips3d_amd: CIPS_D_CONV_MODE / discriminator.CONV_MODE is {CONV_MODE!r}; the values are {', '.join(CONV_MODES)}")
+    return CONV_MODE
+
+
+_conv_mode()
 
 
 def _implicit_channels_ok(C, O):
@@ -216,6 +230,26 @@ def _parity_channels_ok(C, O):
     return O % 32 == 0 and O >= 64 and C % 8 == 0
 
 
+def _single_pass(x_shape, w_shape, stride, pad, pre=None):
+    """Which of the forward, the data gradient and the weight gradient of an "implicit" / "parity" convolution (_conv_forms)
+    the single-pass kernels take -> three booleans, from the shapes alone (the mode is the caller's question).  The kernels walk
+    64-deep k-tiles, two at least: the contraction channels are a multiple of 64 (a k-tile then lies inside one tap) and the
+    contraction is 128 long or longer — for the parity data gradient that is O >= 128, its single-tap class contracts over O
+    alone; the weight gradient contracts over the B * Ho * Wo output pixels (ops.conv2d_bf16_wgrad_declines).  A split of the
+    contraction keeps at least eight k-tiles per chunk (cips_conv2d_bf16_ksplit, ops.conv2d_x3_wgrad)."""
+    B, C, H, W = x_shape
+    O, _, kh, kw = w_shape
+    Hb, Wb = _pre_shape(H, W, pre)
+    Ho, Wo = (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
+    fwd = C % 64 == 0 and kh * kw * C >= 128
+    if pre is not None and pre[3] == 1 and stride == 2 and pad == 0:        # the parity form's geometry
+        dgrad = O % 64 == 0 and O >= 128
+    else:
+        dgrad = O % 64 == 0 and kh * kw * O >= 128
+    wgrad = not ops.conv2d_bf16_wgrad_declines(B, Ho * Wo)
+    return fwd, dgrad, wgrad
+
+
 def _conv_forms(x_shape, w_shape, stride, pad, pre=None):
     """THE dispatch rule of y = conv(Blur(x), w): which form the forward, the data gradient and the weight gradient of a
     (B, C, H, W) input under an (O, C, kh, kw) filter bank take -> three names out of "rgb" / "implicit" / "parity" / "f32".
@@ -225,7 +259,7 @@ def _conv_forms(x_shape, w_shape, stride, pad, pre=None):
     ops.conv2d_x3_wgrad when ops.conv2d_x3_wgrad_declines(B, Ho * Wo), and is then computed in the f32 form."""
     B, C, H, W = x_shape
     O, _, kh, kw = w_shape
-    x3 = CONV_MODE == "bf16x3"
+    x3 = _conv_mode() != "f32"                    # "bf16": the same forms, single-pass where _single_pass allows
     Hb, Wb = _pre_shape(H, W, pre)
     Ho, Wo = (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
     planes8 = Ho > 0 and Wo > 0 and (Ho * Wo) % 8 == 0             # output planes in 8-pixel vectors
@@ -475,7 +509,7 @@ def prepare_weight_planes(layers):
     network's planes used to be rebuilt layer by layer, form by form (multiply, permuting copy, flip, split: ~12 launches per
     layer, ~480 per GAN step).  Same values bit for bit.  Not under hipGraph capture (planes built there live in the graph's pool and
     are rebuilt by every replay: _cached handles that case per layer)."""
-    if CONV_MODE != "bf16x3" or torch.cuda.is_current_stream_capturing():
+    if _conv_mode() == "f32" or torch.cuda.is_current_stream_capturing():
         return
     import ctypes as C
     from . import _lib
@@ -580,7 +614,8 @@ def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
     form = _conv_forms(x.shape, w.shape, stride, pad, pre)[0]
     if form == "implicit":
         Hb, Wb = _pre_shape(H, W, pre)
-        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad)
+        single = CONV_MODE == "bf16" and _single_pass(x.shape, w.shape, stride, pad, pre)[0]
+        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, single=single)
     if pre is not None:
         x = _pre_fp32(x, pre)
     if form == "rgb":
@@ -604,17 +639,19 @@ def _conv_bwd_data(dy, w, in_shape, stride, pad, scale=1.0, pre=None):
     B, C, H, W = in_shape
     O, _, kh, kw = w.shape
     form = _conv_forms(in_shape, w.shape, stride, pad, pre)[1]
+    single = CONV_MODE == "bf16" and _single_pass(in_shape, w.shape, stride, pad, pre)[1]
     if pre is not None:
         Hb, Wb = _pre_shape(H, W, pre)
         if form == "parity":
             banks, w_off = _w_banks_s2(w, scale)
-            dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, _grad_planes(dy), B, C, Hb, Wb, O, kh, kw)
+            dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, _grad_planes(dy), B, C, Hb, Wb, O, kh, kw, single=single)
             gx0, gx1, gy0, gy1 = _pre_adjoint_pads(H, W, pre)
             return ops.upfirdn2d_parity(dxp, out_off, _flipped(pre[0]), B * C, Hb, Wb, gx0, gx1, gy0, gy1).view(B, C, H, W)
         return _pre_adjoint(_conv_bwd_data(dy, w, (B, C, Hb, Wb), stride, pad, scale), pre, in_shape)
     if form == "implicit":
         # dx = conv(dy, flipped weights with the channel roles swapped), padding kh-1-pad
-        return ops.conv2d_x3(_w_planes_flipT(w, scale), _grad_planes(dy), B, O, dy.shape[2], dy.shape[3], C, kh, kw, 1, kh - 1 - pad)
+        return ops.conv2d_x3(_w_planes_flipT(w, scale), _grad_planes(dy), B, O, dy.shape[2], dy.shape[3], C, kh, kw, 1, kh - 1 - pad,
+                             single=single)
     dy = _dense(dy)                       # raises on a planes-only gradient: the forms below read values
     if form == "rgb":
         return ops.conv1x1_smallk_bwd_data(dy, _scaled(w, scale).reshape(O, C).contiguous(), C)
@@ -639,7 +676,8 @@ def _conv_bwd_weight(dy, x, w_shape, stride, pad, scale=1.0, pre=None):
     form = _conv_forms(x.shape, w_shape, stride, pad, pre)[2]
     if form == "implicit":
         Hb, Wb = _pre_shape(x.shape[2], x.shape[3], pre)
-        dw = ops.conv2d_x3_wgrad(_grad_planes(dy), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, scale)
+        single = CONV_MODE == "bf16" and _single_pass(x.shape, w_shape, stride, pad, pre)[2]      # else 3-pass, where that takes it
+        dw = ops.conv2d_x3_wgrad(_grad_planes(dy), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, scale, single=single)
         if dw is not None:                # None: declined (ops.conv2d_x3_wgrad_declines), the f32 form below
             return dw
     if pre is not None:
@@ -752,9 +790,10 @@ class ConvBiasActFunction(Function):
         O, _, kh, kw = w.shape
         x = x.contiguous()
         Hb, Wb = _pre_shape(H, W, pre)
+        single = CONV_MODE == "bf16" and _single_pass(x.shape, w.shape, stride, pad, pre)[0]
         with _share_planes():
             out = ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, bias=bias.detach().contiguous(),
-                                act=True, slope=slope, act_scale=act_scale)
+                                act=True, slope=slope, act_scale=act_scale, single=single)
         ctx.save_for_backward(x, w, out)
         ctx.cfg = (stride, pad, scale, slope, act_scale, pre)
         ctx.w_obj = w if isinstance(w, nn.Parameter) else None

@@ -1164,16 +1164,21 @@ def split_planes_nhwc(x):
     return Planes(hi, lo)
 
 
-def conv2d_x3(wP, xP, B, Cin, H, W, O, kh, kw, stride, pad, ksplit=None, bias=None, act=False, slope=0.2, act_scale=1.0):
+def conv2d_x3(wP, xP, B, Cin, H, W, O, kh, kw, stride, pad, ksplit=None, bias=None, act=False, slope=0.2, act_scale=1.0,
+              single=False):
     """Implicit-GEMM convolution: wP Planes (O, kh*kw*Cin) with contraction index (tap, channel), xP NHWC Planes from
-    split_planes_nhwc -> y (B, O, Ho, Wo) fp32."""
+    split_planes_nhwc -> y (B, O, Ho, Wo) fp32.
+    single: sum over the contraction of w_hi * x_hi only (cips_conv2d_bf16; here and in the two functions below): the lo
+    planes are not read, and a shape the single-pass kernel does not take raises (hipError 801) — the caller decides
+    (discriminator._single_pass)."""
     lib = _lib.load()
+    name = "cips_conv2d_bf16" if single else "cips_conv2d_x3"
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     y = torch.empty(B, O, Ho, Wo, device=xP.hi.device)
     d = ConvX3Desc()
     d.w_hi, d.w_lo, d.x_hi, d.x_lo, d.y = _p(wP.hi), _p(wP.lo), _p(xP.hi), _p(xP.lo), _p(y)
     d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad = B, Cin, H, W, O, kh, kw, stride, pad
-    ks = lib.cips_conv2d_x3_ksplit(B, O, Ho * Wo, kh * kw * Cin) if ksplit is None else ksplit
+    ks = getattr(lib, name + "_ksplit")(B, O, Ho * Wo, kh * kw * Cin) if ksplit is None else ksplit
     part = None
     if ks > 1:                                   # few output tiles: split the contraction over the idle CUs
         part = torch.empty(ks, B, O, Ho, Wo, device=xP.hi.device)
@@ -1182,7 +1187,7 @@ def conv2d_x3(wP, xP, B, Cin, H, W, O, kh, kw, stride, pad, ksplit=None, bias=No
         d.ksplit, d.part = 1, None
     d.bias = _p(bias) if bias is not None else None            # EqualConv2d + FusedLeakyReLU in the epilogue
     d.act, d.slope, d.act_scale = (1 if act else 0), float(slope), float(act_scale)
-    check(lib.cips_conv2d_x3(C.byref(d), _stream()), "cips_conv2d_x3")
+    check(getattr(lib, name)(C.byref(d), _stream()), name)
     return y
 
 
@@ -1215,7 +1220,7 @@ def dgrad_s2_layout(H, W):
     return nps
 
 
-def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, Cin, H, W, O, kh, kw):
+def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, Cin, H, W, O, kh, kw, single=False):
     """Data gradient of a stride-2 unpadded convolution as four parity sub-convolutions in one launch (cips_conv2d_x3_dgrad_s2).
     banks / w_off: dgrad_s2_banks(w); dyP: NHWC Planes of dy (B, O, Ho, Wo).  -> (dxp fp32 flat, out_off [4]): the gradient w.r.t.
     the (B, Cin, H, W) input in parity-block layout, consumed by upfirdn2d_parity (or parity_to_nchw in tests)."""
@@ -1235,7 +1240,8 @@ def conv2d_x3_dgrad_s2(banks, w_off, dyP, B, Cin, H, W, O, kh, kw):
     for i in range(4):
         d.w_off[i] = w_off[i]
         d.out_off[i] = out_off[i]
-    check(lib.cips_conv2d_x3_dgrad_s2(C.byref(d), _stream()), "cips_conv2d_x3_dgrad_s2")
+    name = "cips_conv2d_bf16_dgrad_s2" if single else "cips_conv2d_x3_dgrad_s2"
+    check(getattr(lib, name)(C.byref(d), _stream()), name)
     return dxp, out_off
 
 
@@ -1271,27 +1277,34 @@ def conv2d_x3_wgrad_declines(B, N):
     return (B * N) % 32 != 0
 
 
-def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nch=None):
+def conv2d_bf16_wgrad_declines(B, N):
+    """the single-pass weight gradient (conv2d_x3_wgrad(single=True)) walks 64-row k-tiles, two at least"""
+    return (B * N) % 64 != 0 or B * N < 128
+
+
+def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nch=None, single=False):
     """Weight gradient of conv2d_x3: dyP, xP NHWC Planes from split_planes_nhwc -> dW (O, Cin, kh, kw) fp32, or None when
-    the pixel count does not split into 32-row k-tiles (conv2d_x3_wgrad_declines).  The pixel range is cut into chunks so
+    the pixel count does not split into 32-row k-tiles (conv2d_x3_wgrad_declines; single: into 64-row k-tiles,
+    conv2d_bf16_wgrad_declines).  The pixel range is cut into chunks so
     that a 512x512 filter bank still fills the chip (4 tiles per tap and chunk); cips_conv_wgrad_finish adds the partial
     sums, applies `scale` and lays the result out as (O, Cin, kh, kw)."""
     lib = _lib.load()
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     K = B * Ho * Wo
-    if conv2d_x3_wgrad_declines(B, Ho * Wo):
+    if (conv2d_bf16_wgrad_declines if single else conv2d_x3_wgrad_declines)(B, Ho * Wo):
         return None
     # chunks of the pixel range: the persistent grid runs ceil(tiles*nch / 256) rounds of ~K/nch rows each (+ an
     # epilogue worth ~512 rows); 36 tiles x 7 chunks = 252 of 256 CUs in one round (powers of two: 144, or 288 in two)
     tiles = ((O + 255) // 256) * ((Cin + 255) // 256) * kh * kw
-    T = K // 32
+    kt_rows, kt_cost = (64, 21) if single else (32, 32)       # a 64-row single-pass k-tile: 32 MFMAs against a 32-row k-tile's 48
+    T = K // kt_rows
     best = None
     forced = nch
     nch = 1
     for cand in range(1, 33):                   # any count: the kernel cuts the range at k-tile granularity
         if cand > 1 and T // cand < 8:
             break
-        cost = -(-tiles * cand // 256) * (-(-T // cand) * 32 + 512)
+        cost = -(-tiles * cand // 256) * (-(-T // cand) * kt_cost + 512)
         if best is None or cost < best:
             nch, best = cand, cost
     if forced is not None:
@@ -1300,7 +1313,8 @@ def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nc
     d = ConvWgradDesc()
     d.dy_hi, d.dy_lo, d.x_hi, d.x_lo, d.part = _p(dyP.hi), _p(dyP.lo), _p(xP.hi), _p(xP.lo), _p(part)
     d.B, d.C, d.H, d.W, d.O, d.kh, d.kw, d.stride, d.pad, d.nchunks = B, Cin, H, W, O, kh, kw, stride, pad, nch
-    check(lib.cips_conv2d_x3_wgrad(C.byref(d), _stream()), "cips_conv2d_x3_wgrad")
+    name = "cips_conv2d_bf16_wgrad" if single else "cips_conv2d_x3_wgrad"
+    check(getattr(lib, name)(C.byref(d), _stream()), name)
     dw = torch.empty(O, Cin, kh, kw, device=xP.hi.device)
     check(lib.cips_conv_wgrad_finish(_p(part), _p(dw), nch, kh * kw, O, Cin, float(scale), _stream()), "cips_conv_wgrad_finish")
     return dw

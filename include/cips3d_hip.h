@@ -421,6 +421,20 @@ int cips_conv2d_x3_wgrad(const cips_conv_wgrad_desc* d, cips_stream_t stream);
  * EqualConv2d's 1/sqrt(C k^2) (discriminator.py:33, 44), which the autograd of `weight * scale` applies to the gradient. */
 int cips_conv_wgrad_finish(const float* part, float* dw, int nchunks, int taps, int O, int C, float scale,
                            cips_stream_t stream);
+/* Single-pass forms of the four convolution entry points above ("bf16": operands rounded to bf16, fp32 accumulate — the
+ * AMP-class arithmetic of cips_gemm_bf16):  sum over the contraction of hi * hi  only.  Same descriptors, same argument
+ * validation and return codes; the *_lo pointers are ignored and may be NULL.  A shape the single-pass kernels do not take
+ * returns hipErrorNotSupported — it is never run 3-pass (the caller's choice: cips_conv2d_x3* is always more accurate):
+ *   cips_conv2d_bf16            C % 64 == 0 (a 64-deep k-tile lies inside one tap) and at least two 64-deep k-tiles in every
+ *                               chunk of the contraction: (kh*kw*C / 64) / max(ksplit, 1) >= 2
+ *   cips_conv2d_bf16_ksplit     the proposal for it (chunks cut at 64-deep granularity)
+ *   cips_conv2d_bf16_dgrad_s2   O % 64 == 0 and O >= 128 (the single-tap parity class contracts over O alone)
+ *   cips_conv2d_bf16_wgrad      B*Ho*Wo % 64 == 0 and (B*Ho*Wo / 64) / nchunks >= 2; chunk c takes the 64-row k-tiles
+ *                               [c*T/nchunks, (c+1)*T/nchunks), T = B*Ho*Wo / 64; cips_conv_wgrad_finish as before */
+int cips_conv2d_bf16(const cips_conv_x3_desc* d, cips_stream_t stream);
+int cips_conv2d_bf16_ksplit(int B, int O, int N, int K);
+int cips_conv2d_bf16_dgrad_s2(const cips_conv_dgrad_s2_desc* d, cips_stream_t stream);
+int cips_conv2d_bf16_wgrad(const cips_conv_wgrad_desc* d, cips_stream_t stream);
 /* Activation operand of cips_conv2d_x3 / cips_conv2d_x3_wgrad: x (B, C, n = H*W) fp32 NCHW -> NHWC split planes
  * t_hi, t_lo (B*n + 1, C) bf16, the last row zero (read wherever a tap falls into the padding).  C % 8 == 0 (n % 4 == 0 takes
  * 16-byte loads, any other n scalar loads). */
