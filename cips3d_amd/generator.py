@@ -11,6 +11,8 @@ import math
 import os
 import random
 from collections import OrderedDict
+from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -358,7 +360,7 @@ class CIPSNet(nn.Module):
         """The head's weight-gradient tail behind gradient ports on the side stream (ops.INR_TAIL), opened for the NEXT forward()
         with these styles and (B, n, in0) inputs.  Every autograd node between the ports and the parameters — the modulation
         Linears, the weight views — is created under that stream as well (a node on the caller's stream that consumed a port's
-        output would make the caller's stream wait for the whole tail).  GeneratorNerfINR._render calls this BEFORE the ray march:
+        output would make the caller's stream wait for the whole tail).  GeneratorNerfINR._render calls this first, BEFORE the ray march:
         nodes created earlier run later in the backward pass, so the NeRF backward is issued first and the tail starts behind
         its compositing kernel (ops._TAIL_GATE).  Returns True when ports are pending."""
         self._tail = None
@@ -515,6 +517,147 @@ def create_cam2world_matrix(forward_vector, origin, up_vector=None):
 
 
 # ------------------------------------------------------------------------------------------
+# the render path's settings, random draws and camera (no kernels of the NeRF path: these run on a CPU device too)
+# ------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class RenderSettings:
+    """What forward() / forward_camera_pos_and_lookup() were asked for, built once there and handed down."""
+    img_size: int
+    fov: float
+    ray_start: float
+    ray_end: float
+    num_steps: int
+    h_stddev: float
+    v_stddev: float
+    h_mean: float
+    v_mean: float
+    hierarchical_sample: bool
+    sample_dist: str = None
+    clamp_mode: str = 'relu'
+    nerf_noise: float = 0.
+    white_back: bool = False
+    last_back: bool = False
+    return_aux_img: bool = False
+    forward_points: int = None
+    grad_points: int = None
+    camera_pos: torch.Tensor = None
+    camera_lookup: torch.Tensor = None
+    up_vector: torch.Tensor = None
+    rand_override: dict = None          # any of jitter/theta/phi/noise_c/u/noise_f(/rand_idx): fixed draws for parity tests
+
+    n = property(lambda s: s.img_size ** 2)                                                  # rays per image
+    E = property(lambda s: 2 * s.num_steps if s.hierarchical_sample else s.num_steps)        # composited samples per ray
+    flags = property(lambda s: (1 if s.last_back else 0) | (2 if s.white_back else 0))
+    # generator.py:1325-1347: fewer grad_points than pixels is part_grad_forward, which is not handed forward_points
+    part = property(lambda s: s.grad_points is not None and s.grad_points < s.n)
+    staged = property(lambda s: s.forward_points is not None and not s.part)
+
+
+def _grad_ctx(nerf_grad):
+    return torch.enable_grad() if nerf_grad else torch.no_grad()
+
+
+# the two kinds of distribution the training configs use keep their raw camera draws separate (rand_override can inject
+# them); the others go through sample_camera_positions as a whole
+_SIMPLE_CAMS = ('gaussian', 'normal', 'uniform')
+
+
+def _draw(ro, kind, fn, shape, device):
+    """one draw; an overridden one is still drawn (the generator is consumed), then replaced"""
+    t = fn(shape, device=device)
+    return ro[kind].to(device).reshape(shape).float() if kind in ro else t
+
+
+def _draw_cam(s, ro, bs, device):
+    """-> the RAW draws (bs,1) x 2, or for the other distributions the finished (theta, phi)"""
+    if s.sample_dist not in _SIMPLE_CAMS:
+        _, ph, th = sample_camera_positions(device, bs, 1, s.h_stddev, s.v_stddev, s.h_mean, s.v_mean, s.sample_dist)
+        return th, ph
+    fn = torch.rand if s.sample_dist == 'uniform' else torch.randn
+    return _draw(ro, 'theta', fn, (bs, 1), device), _draw(ro, 'phi', fn, (bs, 1), device)
+
+
+def _draw_noise(s, ro, tag, b, m, device):
+    """the draws of points_forward for m rays of b images -> noise_c, u (None without resampling), noise_f"""
+    S, hier = s.num_steps, s.hierarchical_sample
+    noise_c = _draw(ro, 'noise_c' + tag, torch.randn, (b, m, S, 1), device) if hier else None
+    u = _draw(ro, 'u' + tag, torch.rand, (b * m, S), device) if hier else None
+    return noise_c, u, _draw(ro, 'noise_f' + tag, torch.randn, (b, m, s.E, 1), device)
+
+
+def draw_randoms(s, b, device):
+    """The random tensors of one forward, drawn with the reference's calls, shapes and order so
+    that a same-device, same-seed run consumes the generator identically -> jitter, theta / phi (_draw_cam; None with an
+    explicit camera), noise_c, u, noise_f (None in the part mode: draw_part_randoms).
+    With `forward_points` the reference evaluates image by image in chunks; the fused kernels need no chunking, so only
+    the per-image / per-chunk draw order is reproduced, and an override is taken as given."""
+    ro = s.rand_override or {}
+    n, S = s.n, s.num_steps
+    need_cam = s.camera_pos is None or s.camera_lookup is None
+    assert not need_cam or s.sample_dist in _SIMPLE_CAMS + ('hybrid', 'truncated_gaussian', 'spherical_uniform', 'mean'), \
+        f"camera distribution {s.sample_dist!r}"          # comm_utils.py:526 (`assert 0`), incl. the default None
+    if not s.staged:
+        jitter = _draw(ro, 'jitter', torch.rand, (b, n, S, 1), device)
+        theta, phi = _draw_cam(s, ro, b, device) if need_cam else (None, None)
+        noise_c, u, noise_f = (None, None, None) if s.part else _draw_noise(s, ro, '', b, n, device)
+        return SimpleNamespace(jitter=jitter, theta=theta, phi=phi, noise_c=noise_c, u=u, noise_f=noise_f)
+    js, cams, chunks = [], [], []
+    for _ in range(b):
+        js.append(torch.rand((1, n, S, 1), device=device))
+        if need_cam:
+            cams.append(_draw_cam(s, {}, 1, device))
+        for head in range(0, n, s.forward_points):
+            chunks.append(_draw_noise(s, {}, '', 1, min(s.forward_points, n - head), device))
+    ncs, us, nfs = zip(*chunks)
+    d = SimpleNamespace(jitter=ro.get('jitter', torch.cat(js, 0)), theta=None, phi=None, noise_c=None, u=None,
+                        noise_f=ro.get('noise_f', torch.cat(nfs, 1).view(b, n, s.E, 1)))
+    if need_cam:
+        d.theta = ro.get('theta', torch.cat([th for th, _ in cams], 0))
+        d.phi = ro.get('phi', torch.cat([ph for _, ph in cams], 0))
+    if s.hierarchical_sample:
+        d.noise_c = ro.get('noise_c', torch.cat(ncs, 1).view(b, n, S, 1))
+        d.u = ro.get('u', torch.cat(us, 0))
+    return d
+
+
+def draw_part_randoms(s, b, device):
+    """part_grad_forward's own draws, in its order: the permutation of the pixels, then the noise of the `grad_points`
+    pixels rendered with gradients and of the rest -> (idx_grad, (noise_c, u, noise_f)), (idx_rest, (...))"""
+    ro = s.rand_override or {}
+    rand_idx = ro['rand_idx'].to(device) if 'rand_idx' in ro else torch.randperm(s.n, device=device)
+    idx_grad, idx_rest = rand_idx[:s.grad_points], rand_idx[s.grad_points:]
+    return ((idx_grad, _draw_noise(s, ro, '_grad', b, idx_grad.numel(), device)),
+            (idx_rest, _draw_noise(s, ro, '_rest', b, idx_rest.numel(), device)))
+
+
+@torch.no_grad()
+def camera_setup(s, theta, phi, b, device):
+    """the camera draws of draw_randoms, or the explicit camera (theta is None; pitch / yaw are zeros) -> the origin of
+    every ray (b,3), cam2world (b,4,4), pitch_yaw (b,2).  O(b) host math."""
+    if theta is None:
+        origin, forward_vector = s.camera_pos, _normalize(s.camera_lookup)
+        pitch = yaw = torch.zeros(b, 1, device=device)
+    else:
+        if s.sample_dist in _SIMPLE_CAMS:
+            if theta.is_cuda and not (s.staged and s.up_vector is not None):
+                # draws -> pitch, yaw, origin, cam2world in one launch (the ~45 one-wave torch kernels of the op-by-op form
+                # below are 0.2 ms of a captured step)
+                pitch_yaw, origin, cam2world = ops.camera_pose(theta, phi, s.sample_dist == 'uniform', s.h_stddev, s.h_mean,
+                                                               s.v_stddev, s.v_mean)
+                return origin, cam2world, pitch_yaw
+            if s.sample_dist == 'uniform':
+                theta, phi = (theta - 0.5) * 2, (phi - 0.5) * 2
+            theta, phi = theta * s.h_stddev + s.h_mean, phi * s.v_stddev + s.v_mean
+        origin, pitch = camera_origin_from_angles(theta, phi)
+        yaw = theta
+        forward_vector = _normalize(-origin)
+    # reference quirk kept: only the staged branch of whole_grad_forward hands `up_vector` on
+    # (generator.py:1437 vs :1481-1497); the one-shot branch always uses (0, 1, 0)
+    cam2world = create_cam2world_matrix(forward_vector, origin, up_vector=s.up_vector if s.staged else None)
+    return cam2world[:, :3, 3].contiguous(), cam2world, torch.cat([pitch, yaw], -1)       # every ray starts at the camera
+
+
+# ------------------------------------------------------------------------------------------
 # generator
 # ------------------------------------------------------------------------------------------
 class GeneratorNerfINR(nn.Module):
@@ -570,7 +713,7 @@ class GeneratorNerfINR(nn.Module):
             with torch.cuda.stream(side):
                 inr = self._map_inr(z_inr)
             z_inr.record_stream(side)
-            style_dict.update(self.mapping_network_nerf(z_nerf))
+            style_dict.update(self._map_nerf(z_nerf))
             for t in inr.values():
                 t.record_stream(main)
             style_dict.update(inr)
@@ -578,9 +721,13 @@ class GeneratorNerfINR(nn.Module):
             if not defer_join:
                 self._join_side()
             return style_dict
-        style_dict.update(self.mapping_network_nerf(z_nerf))
+        style_dict.update(self._map_nerf(z_nerf))
         style_dict.update(self._map_inr(z_inr))
         return style_dict
+
+    def _map_nerf(self, z_nerf):
+        """z_nerf -> the NeRF-side styles (the freeze variant runs it under no_grad)"""
+        return self.mapping_network_nerf(z_nerf)
 
     def _map_inr(self, z_inr):
         """z_inr -> the INR-side styles: the chain mapping_network() runs on the side stream"""
@@ -611,273 +758,154 @@ class GeneratorNerfINR(nn.Module):
         raise NotImplementedError        # as in the reference (generator.py:1819-1820: the same two lines)
 
     # ---- the hot path ----
+    nerf_grad = True          # False (the freeze variant): the NeRF path runs under no_grad and hands the head detached features
+
     def _nerf_styles(self, style_dict):
         return style_dict
 
-    def _render(self, style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
-                v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise, white_back, last_back,
-                return_aux_img, forward_points=None, camera_pos=None, camera_lookup=None, up_vector=None,
-                nerf_grad=True, rand_override=None, grad_points=None):
-        """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path.
+    def _ray_geometry(self, s, b, device, origin, cam2world, jitter):
+        """The constants of the ray set-up (get_world_points_and_direction, generator.py:1378-1657) and the form the NeRF
+        path takes for them, named here once:
+          "march"   non-hierarchical sampling of whole images: rays + SIREN + composite fused in one kernel that walks the
+                    samples along each ray (ops.RayMarchFunction); no (b,n,S,3) points, no per-sample features in HBM
+          "rays"    hierarchical sampling of whole images: both SIREN passes and the resampler regenerate rays / points
+                    in-kernel (no rays kernel, no (b,n,S,3) point tensors for either pass)
+          "points"  everything else (pixel subsets, other SIREN shapes): the points are materialised here, once"""
+        S = s.num_steps
+        xg, yg, zg = ops.pixel_grids(s.img_size, s.img_size, S, s.ray_start, s.ray_end, device)
+        zc = float((-torch.ones(1) / np.tan((2 * math.pi * s.fov / 360) / 2)).item())
+        in_kernel = (not s.part) and ops.march_available() and self.siren.fused
+        g = SimpleNamespace(form=("rays" if s.hierarchical_sample else "march") if in_kernel else "points", b=b, xg=xg, yg=yg,
+                            zg=zg, zc=zc, origin=origin, cam2world=cam2world, jitter=jitter.reshape(b, s.n, S))
+        if g.form == "points":
+            with torch.no_grad():
+                g.points, g.z_vals, g.dirs = ops.rays_fwd(xg, yg, zg, zc, cam2world, g.jitter, b, s.img_size, s.img_size, S)
+        return g
 
-        `grad_points` (a count of pixels < img_size^2): part_grad_forward — after the ray set-up a `randperm(n)`
-        splits the pixels of every image into a subset rendered with gradients and a rest rendered under
-        no_grad (each with its own noise draws, in that order), and the two are scattered back (int64
-        bookkeeping of comm_utils.py:240-282).
+    def _nerf_features(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None):
+        """points_forward (generator.py:1659-1746) up to the composite, for all n rays of every image or for the subset
+        `idx` of them (form "points" only): -> pixels_fea (b, m, 32)"""
+        b, S, E, H, W = g.b, s.num_steps, s.E, s.img_size, s.img_size
+        m = s.n if idx is None else idx.numel()
+        clamp = ops._CLAMP[s.clamp_mode]
+        with _grad_ctx(nerf_grad):
+            if g.form == "march":
+                geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled())
+                return self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
+                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None)[0]
+            if g.form == "rays":
+                rays = (nerf_styles, (b, H, W, S, g.zc), g.xg, g.yg, g.zg, g.cam2world)
+                feat_c, sig_c, z_c = self.siren.evaluate_rays(*rays, jitter=g.jitter)
+                dirs = None
+            else:
+                points, z_c, dirs = g.points, g.z_vals, g.dirs
+                if idx is not None:
+                    points, z_c, dirs = (t.index_select(1, idx).contiguous() for t in (points, z_c, dirs))
+                feat_c, sig_c = self.siren.evaluate(points.reshape(b, m * S, 3), nerf_styles)
+            feat_c, sig_c, z_c = feat_c.view(b * m, S, 32), sig_c.view(b * m, S), z_c.reshape(b * m, S)
+            feat_f = sig_f = fine_z = None
+            if s.hierarchical_sample:
+                with torch.no_grad():
+                    rp = ops._ray_params(g.xg, g.yg, g.zg, g.zc, g.cam2world, None, H, W, S) if g.form == "rays" else None
+                    drawn_z, fine_pts = ops.resample_fwd(
+                        sig_c, z_c, noise_c.reshape(b * m, S) if s.nerf_noise != 0 else None, s.nerf_noise, u, g.origin,
+                        dirs.reshape(b * m, 3) if dirs is not None else None, b, m, S, clamp, rays=rp)
+                    fine_z = ops.fine_z_debug(drawn_z)
+                    if fine_z is not drawn_z and g.form == "points":
+                        # pinned depths, materialised points: origin + direction * depth (generator_nerf_inr.py:537-598)
+                        fine_pts = (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * fine_z.view(b, m, S, 1)).reshape(b, m * S, 3).contiguous()
+                if g.form == "rays":
+                    feat_f, sig_f, _ = self.siren.evaluate_rays(*rays, zvals=fine_z.view(b, m * S))
+                else:
+                    feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, m * S, 3), nerf_styles)
+                feat_f, sig_f = feat_f.view(b * m, S, 32), sig_f.view(b * m, S)
+            return ops.CompositeFunction.apply(
+                feat_c, sig_c, z_c, feat_f, sig_f, fine_z, noise_f.reshape(b * m, E) if s.nerf_noise != 0 else None,
+                s.nerf_noise, clamp, s.flags)[0].view(b, m, 32)
 
-        Random tensors are drawn with the reference's calls, shapes and order
-        so that a same-device, same-seed run consumes the generator identically; `rand_override`
-        (dict with any of jitter/theta/phi/noise_c/u/noise_f) injects fixed draws for parity tests.
-        With `forward_points` the reference evaluates image by image in chunks under no_grad; the
-        fused kernels need no chunking, so only the per-image/per-chunk draw order is reproduced."""
-        ro = rand_override or {}
+    def _head(self, s, pixels_fea, style_dict, nerf_grad):
+        """the tail of points_forward (generator.py:1747-1762) on features of any form: -> inr rgb (b,m,3), aux rgb or None.
+        The INR head is called WITHOUT img_size, as the reference does (see CIPSNet)."""
+        aux = None
+        if s.return_aux_img:
+            with _grad_ctx(nerf_grad):
+                aux = torch.tanh(_ToRGBFunction.apply(pixels_fea, self.aux_to_rbg[0].weight, self.aux_to_rbg[0].bias))
+        if not nerf_grad:
+            pixels_fea = pixels_fea.detach()
+        self._join_side()
+        return self.inr_net(pixels_fea, style_dict), aux
+
+    def _part_grad(self, s, g, nerf_styles, style_dict, device):
+        """part_grad_forward (generator.py:1536-1657): a `randperm(n)` splits the pixels of every image into `grad_points`
+        rendered with gradients and a rest rendered under no_grad, each with its own noise draws; the two are scattered
+        back (int64 bookkeeping of comm_utils.py:240-282) -> inr rgb (b,n,3), aux rgb or None"""
+        (idx_grad, noise_grad), (idx_rest, noise_rest) = draw_part_randoms(s, g.b, device)
+        fea = self._nerf_features(s, g, nerf_styles, *noise_grad, self.nerf_grad, idx_grad)
+        inr_g, aux_g = self._head(s, fea, style_dict, self.nerf_grad)
+        with torch.no_grad():
+            fea = self._nerf_features(s, g, nerf_styles, *noise_rest, False, idx_rest)
+            inr_r, aux_r = self._head(s, fea, style_dict, False)
+
+        def scatter(pg, pr):       # comm_utils.scatter_points: rows idx_grad <- pg (with grad), idx_rest <- pr
+            out = torch.zeros(g.b, s.n, pg.shape[-1], device=device, dtype=pg.dtype)
+            return out.index_copy(1, idx_grad, pg).index_copy(1, idx_rest, pr)
+
+        return scatter(inr_g, inr_r), scatter(aux_g, aux_r) if s.return_aux_img else None
+
+    def _render(self, style_dict, s):
+        """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path:
+        draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_features) -> head (_head), or
+        the last two per pixel subset (_part_grad)."""
         device = next(self.parameters()).device
         b = list(style_dict.values())[0].shape[0]
-        H = W = img_size
-        n = H * W
-        S = num_steps
-        E = 2 * S if hierarchical_sample else S
-        clamp = ops._CLAMP[clamp_mode]
-        flags = (1 if last_back else 0) | (2 if white_back else 0)
-        staged = forward_points is not None
-        part = grad_points is not None and grad_points < n
-        if part:
-            staged = False          # generator.py:1325-1347: part_grad_forward is not handed forward_points
-        if not part and not staged and nerf_grad and torch.is_grad_enabled():
+        if not s.part and not s.staged and self.nerf_grad and torch.is_grad_enabled():
             # the INR head's gradient ports, opened before the NeRF path so that its backward is issued first
             # (CIPSNet.open_tail_ports); they sit on the INR mapping network's side stream, joined right before the head.
             # Only where a NeRF backward follows the head's: with a frozen NeRF there is nothing to run beside, and the
             # side-stream form measured 0.4 ms slower than the plain one at the r256 stages (profiles/r6_tail_ab.txt)
-            if self.inr_net.open_tail_ports(style_dict, b, n, self.siren.rgb_dim, join=False):
+            if self.inr_net.open_tail_ports(style_dict, b, s.n, self.siren.rgb_dim, join=False):
                 self._pending_side = _side_stream(device)
-
-        # ---------------- random draws in reference order ----------------
-        def draw(kind, fn, shape, override=True):
-            t = fn(shape, device=device)
-            return ro[kind].to(device).reshape(shape).float() if (override and kind in ro) else t
-
-        need_cam = camera_pos is None or camera_lookup is None
-        mode = sample_dist
-        # the two distributions the training configs use keep their raw draws separate (rand_override can inject
-        # them); the others go through sample_camera_positions as a whole
-        simple_cam = mode in ('gaussian', 'normal', 'uniform')
-        assert not need_cam or simple_cam or mode in ('hybrid', 'truncated_gaussian', 'spherical_uniform', 'mean'), \
-            f"camera distribution {mode!r}"          # comm_utils.py:526 (`assert 0`), incl. the default None
-
-        def cam_angles(th_raw, ph_raw):
-            if mode == 'uniform':
-                return (th_raw - 0.5) * 2 * h_stddev + h_mean, (ph_raw - 0.5) * 2 * v_stddev + v_mean
-            return th_raw * h_stddev + h_mean, ph_raw * v_stddev + v_mean
-
-        def draw_cam(bs, override=True):
-            """-> the RAW draws (b,1) x 2, or for the other distributions the finished (theta, phi)"""
-            if not simple_cam:
-                _, ph, th = sample_camera_positions(device, bs, 1, h_stddev, v_stddev, h_mean, v_mean, mode)
-                return th, ph
-            fn = torch.rand if mode == 'uniform' else torch.randn
-            return draw('theta', fn, (bs, 1), override), draw('phi', fn, (bs, 1), override)
-
-        if part:
-            jitter = draw('jitter', torch.rand, (b, n, S, 1))
-            th_raw, ph_raw = draw_cam(b) if need_cam else (None, None)
-            noise_c = u = noise_f = None          # drawn per pixel subset below, after the randperm
-        elif not staged:
-            jitter = draw('jitter', torch.rand, (b, n, S, 1))
-            th_raw, ph_raw = draw_cam(b) if need_cam else (None, None)
-            noise_c = draw('noise_c', torch.randn, (b, n, S, 1)) if hierarchical_sample else None
-            u = draw('u', torch.rand, (b * n, S)) if hierarchical_sample else None
-            noise_f = draw('noise_f', torch.randn, (b, n, E, 1))
-        else:
-            js, ths, phs, ncs, us, nfs = [], [], [], [], [], []
-            for _ in range(b):
-                js.append(torch.rand((1, n, S, 1), device=device))
-                if need_cam:
-                    th, ph = draw_cam(1, override=False)
-                    ths.append(th); phs.append(ph)
-                head = 0
-                while head < n:
-                    c = min(forward_points, n - head)
-                    if hierarchical_sample:
-                        ncs.append(torch.randn((1, c, S, 1), device=device))
-                        us.append(torch.rand((c, S), device=device))
-                    nfs.append(torch.randn((1, c, E, 1), device=device))
-                    head += forward_points
-            jitter = ro.get('jitter', torch.cat(js, 0))
-            th_raw = ro.get('theta', torch.cat(ths, 0)) if need_cam else None
-            ph_raw = ro.get('phi', torch.cat(phs, 0)) if need_cam else None
-            noise_c = ro.get('noise_c', torch.cat(ncs, 1).view(b, n, S, 1)) if hierarchical_sample else None
-            u = ro.get('u', torch.cat(us, 0)) if hierarchical_sample else None
-            noise_f = ro.get('noise_f', torch.cat(nfs, 1).view(b, n, E, 1))
-
-        # ---------------- camera (O(b) host math) ----------------
-        with torch.no_grad():
-            pitch_yaw_fused = None
-            if need_cam and simple_cam and th_raw.is_cuda and not (staged and up_vector is not None):
-                # draws -> pitch, yaw, origin, cam2world in one launch (the ~45 one-wave torch kernels of the op-by-op form
-                # below are 0.2 ms of a captured step)
-                pitch_yaw_fused, origin, cam2world = ops.camera_pose(th_raw, ph_raw, mode == 'uniform', h_stddev, h_mean,
-                                                                     v_stddev, v_mean)
-                pitch, yaw = pitch_yaw_fused[:, 0:1], pitch_yaw_fused[:, 1:2]
-            else:
-                if need_cam:
-                    theta, phi = cam_angles(th_raw, ph_raw) if simple_cam else (th_raw, ph_raw)
-                    origin, pitch = camera_origin_from_angles(theta, phi)
-                    yaw = theta
-                    forward_vector = _normalize(-origin)
-                else:
-                    origin = camera_pos
-                    pitch = yaw = torch.zeros(b, 1, device=device)
-                    forward_vector = _normalize(camera_lookup)
-                # reference quirk kept: only the staged branch of whole_grad_forward hands `up_vector` on
-                # (generator.py:1437 vs :1481-1497); the one-shot branch always uses (0, 1, 0)
-                cam2world = create_cam2world_matrix(forward_vector, origin, up_vector=up_vector if staged else None)
-            xg, yg, zg = ops.pixel_grids(W, H, S, ray_start, ray_end, device)
-            zc = float((-torch.ones(1) / np.tan((2 * math.pi * fov / 360) / 2)).item())
-            # non-hierarchical sampling of whole images: rays + SIREN + composite fused in one kernel that walks the
-            # samples along each ray (ops.RayMarchFunction); no (b,n,S,3) points, no per-sample features in HBM
-            fused = (not hierarchical_sample) and (not part) and ops.march_available() and self.siren.fused
-            # hierarchical sampling of whole images: both SIREN passes and the resampler regenerate rays / points
-            # in-kernel (no rays kernel, no (b,n,S,3) point tensors for either pass)
-            gen_rays = hierarchical_sample and (not part) and ops.march_available() and self.siren.fused
-            if not fused and not gen_rays:
-                points, z_vals, dirs = ops.rays_fwd(xg, yg, zg, zc, cam2world, jitter.reshape(b, n, S), b, H, W, S)
-            ray_origins = origin if pitch_yaw_fused is not None else cam2world[:, :3, 3].contiguous()       # every ray starts at the camera
-
+        d = draw_randoms(s, b, device)
+        origin, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
+        g = self._ray_geometry(s, b, device, origin, cam2world, d.jitter)
         nerf_styles = self._nerf_styles(style_dict)
-        def pipeline(points, z_vals, dirs, n, noise_c, u, noise_f, nerf_grad):
-            """points_forward (generator.py:1659-1762) for n rays per image: -> inr rgb (b,n,3), aux rgb or None"""
-            ctx_nerf = torch.enable_grad() if nerf_grad else torch.no_grad()
-            with ctx_nerf:
-                if gen_rays:
-                    rgeom = (b, H, W, S, zc)
-                    jit3 = jitter.reshape(b, n, S)
-                    feat_c, sig_c, z_c = self.siren.evaluate_rays(nerf_styles, rgeom, xg, yg, zg, cam2world, jitter=jit3)
-                else:
-                    feat_c, sig_c = self.siren.evaluate(points.reshape(b, n * S, 3), nerf_styles)
-                    z_c = z_vals
-                feat_c = feat_c.view(b * n, S, 32)
-                sig_c = sig_c.view(b * n, S)
-                z_c = z_c.reshape(b * n, S)
-                if hierarchical_sample:
-                    with torch.no_grad():
-                        rp = ops._ray_params(xg, yg, zg, zc, cam2world, None, H, W, S) if gen_rays else None
-                        fine_z, fine_pts = ops.resample_fwd(
-                            sig_c, z_c, noise_c.reshape(b * n, S) if nerf_noise != 0 else None, nerf_noise,
-                            u, ray_origins, dirs.reshape(b * n, 3) if dirs is not None else None, b, n, S, clamp, rays=rp)
-                        if ops.FINE_Z_REC is not None:
-                            ops.FINE_Z_REC.append(fine_z.detach().clone())
-                        if ops.FINE_Z_PIN is not None:       # parity tests: the reference's sample placement
-                            fine_z = next(ops.FINE_Z_PIN).to(fine_z.device).reshape(fine_z.shape).contiguous()
-                            if not gen_rays:             # materialised points: origin + direction * depth (generator_nerf_inr.py:537-598)
-                                fine_pts = (ray_origins.view(b, 1, 1, 3) + dirs.reshape(b, n, 1, 3) * fine_z.view(b, n, S, 1)).reshape(b, n * S, 3).contiguous()
-                    if gen_rays:
-                        feat_f, sig_f, _ = self.siren.evaluate_rays(nerf_styles, rgeom, xg, yg, zg, cam2world,
-                                                                    zvals=fine_z.view(b, n * S))
-                    else:
-                        feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, n * S, 3), nerf_styles)
-                    feat_f = feat_f.view(b * n, S, 32)
-                    sig_f = sig_f.view(b * n, S)
-                else:
-                    feat_f = sig_f = fine_z = None
-                pixels_fea, depth, weights, order, zsorted = ops.CompositeFunction.apply(
-                    feat_c, sig_c, z_c, feat_f, sig_f, fine_z,
-                    noise_f.reshape(b * n, E) if nerf_noise != 0 else None, nerf_noise, clamp, flags)
-                pixels_fea = pixels_fea.view(b, n, 32)
-                if return_aux_img:
-                    aux = torch.tanh(_ToRGBFunction.apply(pixels_fea, self.aux_to_rbg[0].weight,
-                                                          self.aux_to_rbg[0].bias))
-                else:
-                    aux = None
-            if not nerf_grad:
-                pixels_fea = pixels_fea.detach()
-            self._join_side()
-            return self.inr_net(pixels_fea, style_dict), aux
-
-        if fused:
-            ctx_nerf = torch.enable_grad() if nerf_grad else torch.no_grad()
-            with ctx_nerf:
-                geom = (b, H, W, S, zc, float(nerf_noise), clamp, flags, torch.is_grad_enabled())
-                pixels_fea, _depth = self.siren.march(nerf_styles, geom, xg, yg, zg, cam2world, jitter.reshape(b, n, S),
-                                                      noise_f.reshape(b, n, S) if nerf_noise != 0 else None)
-                aux_img = torch.tanh(_ToRGBFunction.apply(pixels_fea, self.aux_to_rbg[0].weight,
-                                                          self.aux_to_rbg[0].bias)) if return_aux_img else None
-            if not nerf_grad:
-                pixels_fea = pixels_fea.detach()
-            self._join_side()
-            inr_img = self.inr_net(pixels_fea, style_dict)
-        elif gen_rays:
-            inr_img, aux_img = pipeline(None, None, None, n, noise_c, u, noise_f, nerf_grad)
-        elif not part:
-            inr_img, aux_img = pipeline(points, z_vals, dirs, n, noise_c, u, noise_f, nerf_grad)
+        if s.part:
+            inr_img, aux_img = self._part_grad(s, g, nerf_styles, style_dict, device)
         else:
-            # ---- part_grad_forward (generator.py:1536-1657) ----
-            rand_idx = ro['rand_idx'].to(device) if 'rand_idx' in ro else torch.randperm(n, device=device)
-            idx_grad, idx_rest = rand_idx[:grad_points], rand_idx[grad_points:]
-            pts4, z3, dirs3 = points.view(b, n, S, 3), z_vals.view(b, n, S), dirs.view(b, n, 3)
-
-            def subset(idx, tag, with_grad):
-                m = idx.numel()
-                nc = draw('noise_c' + tag, torch.randn, (b, m, S, 1)) if hierarchical_sample else None
-                uu = draw('u' + tag, torch.rand, (b * m, S)) if hierarchical_sample else None
-                nf = draw('noise_f' + tag, torch.randn, (b, m, E, 1))
-                return pipeline(pts4.index_select(1, idx).contiguous(), z3.index_select(1, idx).contiguous(),
-                                dirs3.index_select(1, idx).contiguous(), m, nc, uu, nf, with_grad)
-
-            inr_g, aux_g = subset(idx_grad, '_grad', nerf_grad)
-            with torch.no_grad():
-                inr_r, aux_r = subset(idx_rest, '_rest', False)
-
-            def scatter(pg, pr):       # comm_utils.scatter_points: rows idx_grad <- pg (with grad), idx_rest <- pr
-                out = torch.zeros(b, n, pg.shape[-1], device=device, dtype=pg.dtype)
-                out = out.index_copy(1, idx_grad, pg)
-                return out.index_copy(1, idx_rest, pr)
-
-            inr_img = scatter(inr_g, inr_r)
-            aux_img = scatter(aux_g, aux_r) if return_aux_img else None
-
-        inr_img = inr_img.view(b, H, W, 3).permute(0, 3, 1, 2)
+            fea = self._nerf_features(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad)
+            inr_img, aux_img = self._head(s, fea, style_dict, self.nerf_grad)
+        inr_img = inr_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
         inr_img = self.filters(inr_img)
-        pitch_yaw = pitch_yaw_fused if pitch_yaw_fused is not None else torch.cat([pitch, yaw], -1)
-        if return_aux_img:
-            aux_img = aux_img.view(b, H, W, 3).permute(0, 3, 1, 2)
-            imgs = torch.cat([inr_img, aux_img])
-            pitch_yaw = torch.cat([pitch_yaw, pitch_yaw])
-        else:
-            imgs = inr_img.contiguous()
-        return imgs, pitch_yaw
+        if not s.return_aux_img:
+            return inr_img.contiguous(), pitch_yaw
+        aux_img = aux_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
+        return torch.cat([inr_img, aux_img]), torch.cat([pitch_yaw, pitch_yaw])
 
     def forward(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                 h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, lock_view_dependence=False,
                 clamp_mode='relu', nerf_noise=0., white_back=False, last_back=False, return_aux_img=False,
                 grad_points=None, forward_points=None, **kwargs):
         """generator.py:1256-1370.  Returns (imgs (b or 2b,3,H,W), pitch_yaw (b or 2b,2))."""
-        style_dict = self.mapping_network(**zs, defer_join=not psi < 1)     # joined right before the INR head (_render)
+        return self._forward_styles(zs, psi, RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
+            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
+            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
+            rand_override=kwargs.get('rand_override')))
+
+    def _forward_styles(self, zs, psi, s):
+        """the two entry points' common path: latents -> styles (truncated towards the average for psi < 1) -> _render"""
+        style_dict = self.mapping_network(**zs, defer_join=not psi < 1)     # joined right before the INR head (_head)
         if psi < 1:
             avg_styles = self.generate_avg_frequencies(device=self.device)
             style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles,
                                                        raw_lambda=psi)
-        part = grad_points if (grad_points is not None and grad_points < img_size ** 2) else None
-        return self._forward_styles(style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
-                                    h_mean, v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise,
-                                    white_back, last_back, return_aux_img, forward_points,
-                                    rand_override=kwargs.get('rand_override'), grad_points=part)
-
-    def _forward_styles(self, style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
-                        h_mean, v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise, white_back,
-                        last_back, return_aux_img, forward_points, rand_override=None, grad_points=None, **cam):
         try:
-            part = grad_points is not None and grad_points < img_size ** 2       # generator.py:1325: part_grad_forward, forward_points unused
-            if forward_points is not None and not part:
-                with torch.no_grad():
-                    return self._render(style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
-                                        h_mean, v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise,
-                                        white_back, last_back, return_aux_img, forward_points=forward_points,
-                                        rand_override=rand_override, **cam)
-            return self._render(style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
-                                v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise, white_back, last_back,
-                                return_aux_img, rand_override=rand_override, grad_points=grad_points, **cam)
+            # with forward_points the reference evaluates image by image in chunks under no_grad (generator.py:1325-1347)
+            with torch.set_grad_enabled(torch.is_grad_enabled() and not s.staged):
+                return self._render(style_dict, s)
         finally:
-            # a deferred INR-mapping side stream is joined on EVERY exit (no-op after _render's own join): an exception
+            # a deferred INR-mapping side stream is joined on EVERY exit (no-op after _head's own join): an exception
             # before the INR head must not leave the fork open — the main stream would never wait for it, and a
             # hipGraph capture would end with an unjoined stream.  Nor may it leave the gradient ports _render opened
             # for the head pending: they hold the modulation graph, and the next forward() must not find them
@@ -890,51 +918,25 @@ class GeneratorNerfINR(nn.Module):
                                       nerf_noise=0., white_back=False, last_back=False, return_aux_img=False,
                                       grad_points=None, forward_points=None, up_vector=None, **kwargs):
         """generator.py:1828-1951 (explicit camera; pitch/yaw are zeros)."""
-        style_dict = self.mapping_network(**zs, defer_join=not psi < 1)     # joined right before the INR head (_render)
-        if psi < 1:
-            avg_styles = self.generate_avg_frequencies(device=self.device)
-            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles,
-                                                       raw_lambda=psi)
-        part = grad_points if (grad_points is not None and grad_points < img_size ** 2) else None
-        return self._forward_styles(style_dict, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
-                                    h_mean, v_mean, hierarchical_sample, sample_dist, clamp_mode, nerf_noise,
-                                    white_back, last_back, return_aux_img, forward_points,
-                                    rand_override=kwargs.get('rand_override'), grad_points=part,
-                                    camera_pos=camera_pos, camera_lookup=camera_lookup, up_vector=up_vector)
+        return self._forward_styles(zs, psi, RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
+            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
+            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
+            rand_override=kwargs.get('rand_override'), camera_pos=camera_pos, camera_lookup=camera_lookup,
+            up_vector=up_vector))
 
 
 class GeneratorNerfINR_freeze_NeRF(GeneratorNerfINR):
     """generator.py:1955-2083: mapping_nerf, both SIREN passes, the composite and aux_to_rbg run
     under no_grad; gradients flow only through the CIPS INR head and mapping_inr."""
+    nerf_grad = False
 
     def load_nerf_ema(self, G_ema):
         self.siren.load_state_dict(G_ema.siren.state_dict())
         self.mapping_network_nerf.load_state_dict(G_ema.mapping_network_nerf.state_dict())
         self.aux_to_rbg.load_state_dict(G_ema.aux_to_rbg.state_dict())
 
-    def mapping_network(self, z_nerf, z_inr, defer_join=False):
-        style_dict = {}
-        if z_inr.is_cuda and z_inr.shape[0] <= 256:       # see GeneratorNerfINR.mapping_network
-            main = torch.cuda.current_stream(z_inr.device)
-            side = _side_stream(z_inr.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                inr = self._map_inr(z_inr)
-            z_inr.record_stream(side)
-            with torch.no_grad():
-                style_dict.update(self.mapping_network_nerf(z_nerf))
-            for t in inr.values():
-                t.record_stream(main)
-            style_dict.update(inr)
-            self._pending_side = side
-            if not defer_join:
-                self._join_side()
-            return style_dict
+    def _map_nerf(self, z_nerf):
         with torch.no_grad():
-            style_dict.update(self.mapping_network_nerf(z_nerf))
-        style_dict.update(self._map_inr(z_inr))
-        return style_dict
-
-    def _render(self, *args, **kwargs):
-        kwargs['nerf_grad'] = False
-        return super()._render(*args, **kwargs)
+            return super()._map_nerf(z_nerf)

@@ -795,6 +795,16 @@ class resample_debug:
         FINE_Z_PIN, FINE_Z_REC = self.old
 
 
+def fine_z_debug(fine_z):
+    """-> the depths one hierarchical forward is to use: `fine_z` itself (recorded under resample_debug(rec=...)), or the next
+    pinned tensor in its shape — a different object, so a caller that materialised points from `fine_z` can tell"""
+    if FINE_Z_REC is not None:
+        FINE_Z_REC.append(fine_z.detach().clone())
+    if FINE_Z_PIN is None:
+        return fine_z
+    return next(FINE_Z_PIN).to(fine_z.device).reshape(fine_z.shape).contiguous()
+
+
 class gate_debug:
     """with gate_debug(pin=planes or None, rec=list or None): ..."""
 
