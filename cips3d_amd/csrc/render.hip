@@ -178,6 +178,9 @@ struct CompArgs {
   const int* order_in;
   const float* dfea;
   float *dfeat_c, *dsig_c, *dfeat_f, *dsig_f;
+  // optional (cips_composite_bwd_live): one byte per sample in the order of dfeat_* / dsig_*, 1 iff the sample's dfeat row or
+  // its dsigma can be non-zero.  When given, the dfeat rows of the other samples are NOT written.
+  unsigned char *live_c, *live_f;
   long long R;
   int S, E, clamp_mode, flags;
   // optional branch masks of the relu clamp per (ray, sorted position), see cips_composite_fwd in cips3d_hip.h:
@@ -381,7 +384,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
       drow = a.dfeat_c + (ray * S + i) * 32;
       dsg = a.dsig_c + ray * S + i;
     }
-    if (active) *reinterpret_cast<float4*>(drow + 4 * sub) = make_float4(w * G.x, w * G.y, w * G.z, w * G.w);
+    if (active && !a.live_c) *reinterpret_cast<float4*>(drow + 4 * sub) = make_float4(w * G.x, w * G.y, w * G.z, w * G.w);
+    float dsv = 0.f;
     if ((k % SEG) == sub && active) {
       const float delta = (k + 1 < E) ? (zall[k + 1] - zall[k]) : 1e10f;
       const float x = xs[k];
@@ -393,9 +397,71 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
         dgrad = pass ? 1.f : 0.f;
       }
       // d alpha / d dens = delta * exp(-delta*dens)
-      *dsg = dalpha * (delta * expf(-delta * dens)) * dgrad;
+      dsv = dalpha * (delta * expf(-delta * dens)) * dgrad;
+      *dsg = dsv;
+    }
+    if (a.live_c) {
+      // live: the weight that scales the row or the dsigma just stored is not zero (a NaN is not zero).  A relu-clamped sample
+      // has alpha == 0 exactly, hence w == 0, and the clamp's gradient 0 in dsigma: everything downstream of it is linear in
+      // (row, dsigma) and adds +-0.  The segment's lanes all hold w; dsigma is with lane k % SEG.
+      const float dsb = __shfl(dsv, k % SEG, SEG);
+      const bool live = (w != 0.f) || (dsb != 0.f);
+      if (active && live) *reinterpret_cast<float4*>(drow + 4 * sub) = make_float4(w * G.x, w * G.y, w * G.z, w * G.w);
+      unsigned char* lv = a.live_c + ray * S + i;
+      if (a.feat_f) lv = (i < S) ? a.live_f + ray * S + i : a.live_c + ray * S + (i - S);
+      if ((k % SEG) == sub && active) *lv = live ? 1 : 0;
     }
   }
+}
+
+// Ascending indices of an image's non-zero mask bytes, and their number: one workgroup per image walks its P bytes in tiles
+// of 16 per thread; within a tile a thread's position is the block-wide exclusive scan of the per-thread counts, so the
+// order is the index order whatever the scheduling (no atomics).  Every write lands at a position <= its own index.
+constexpr int LIVE_THREADS = 1024, LIVE_TILE = LIVE_THREADS * 16;
+__global__ __launch_bounds__(LIVE_THREADS) void live_points_kernel(const unsigned char* __restrict__ live, int P,
+                                                                   int* __restrict__ idx, int* __restrict__ count) {
+  __shared__ int wsum[LIVE_THREADS / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned char* src = live + (long long)b * P;
+  int* dst = idx + (long long)b * P;
+  const bool vec = (P & 15) == 0 && (reinterpret_cast<uintptr_t>(live) & 15) == 0;
+  auto load16 = [&](int o) {              // the 16 mask bytes from o on, zeros past the end
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (o >= P) return v;
+    if (vec) return *reinterpret_cast<const uint4*>(src + o);
+    unsigned wd[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < 16 && o + j < P; ++j) wd[j >> 2] |= (unsigned)src[o + j] << (8 * (j & 3));
+    return make_uint4(wd[0], wd[1], wd[2], wd[3]);
+  };
+  int base = 0;
+  uint4 cur = load16(tid * 16);
+  for (int t0 = 0; t0 < P; t0 += LIVE_TILE) {
+    const int o = t0 + tid * 16;
+    const uint4 nxt = load16(o + LIVE_TILE);
+    const unsigned wd[4] = {cur.x, cur.y, cur.z, cur.w};
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) n += ((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) ? 1 : 0;
+    int incl = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int u = __shfl_up(incl, off);
+      if (lane >= off) incl += u;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int wv = 0; wv < LIVE_THREADS / 64; ++wv) { const int c = wsum[wv]; before += wv < wave ? c : 0; total += c; }
+    int pos = base + before + incl - n;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if ((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) dst[pos++] = o + j;
+    base += total;
+    cur = nxt;
+    __syncthreads();
+  }
+  if (tid == 0) count[b] = base;
 }
 
 inline int rays_per_block_for(size_t bytes_per_ray) {
@@ -463,11 +529,29 @@ extern "C" int cips_composite_bwd(const float* feat_c, const float* sig_c, const
                                   const float* noise, float noise_std, const int* order, const float* dfea,
                                   float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f, int R, int S,
                                   int clamp_mode, int flags, const unsigned char* clamp_in, cips_stream_t stream) {
+  return cips_composite_bwd_live(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, order, dfea, dfeat_c, dsig_c,
+                                 dfeat_f, dsig_f, nullptr, nullptr, R, S, clamp_mode, flags, clamp_in, stream);
+}
+
+extern "C" int cips_live_points(const unsigned char* live, int B, int P, int* idx, int* count, cips_stream_t stream) {
+  if (!live || !idx || !count || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_points_kernel, dim3(B), dim3(LIVE_THREADS), 0, (hipStream_t)stream, live, P, idx, count);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_composite_bwd_live(const float* feat_c, const float* sig_c, const float* z_c,
+                                       const float* feat_f, const float* sig_f, const float* z_f,
+                                       const float* noise, float noise_std, const int* order, const float* dfea,
+                                       float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                                       unsigned char* live_c, unsigned char* live_f, int R, int S,
+                                       int clamp_mode, int flags, const unsigned char* clamp_in, cips_stream_t stream) {
   if (R <= 0 || S <= 0 || (!order && feat_f)) return (int)hipErrorInvalidValue;
+  if ((live_c || live_f) && (!live_c || (feat_f && !live_f))) return (int)hipErrorInvalidValue;   // both masks or none
   CompArgs a = {};
   a.feat_c = feat_c; a.sig_c = sig_c; a.z_c = z_c; a.feat_f = feat_f; a.sig_f = sig_f; a.z_f = z_f;
   a.noise = noise; a.noise_std = noise_std; a.order_in = order; a.dfea = dfea;
   a.dfeat_c = dfeat_c; a.dsig_c = dsig_c; a.dfeat_f = dfeat_f; a.dsig_f = dsig_f;
+  a.live_c = live_c; a.live_f = live_f;
   a.R = R; a.S = S; a.E = feat_f ? 2 * S : S; a.clamp_mode = clamp_mode; a.flags = flags;
   a.clamp_pin = clamp_in; a.clamp_rec = nullptr;
   size_t per_ray = (size_t)6 * a.E * sizeof(float);

@@ -421,6 +421,8 @@ struct BwdX3Args {
   unsigned long long* prof;
   int dbg;        // timing attribution, probe builds only (-DCIPS_TUNING, env CIPS_X3_DBG): bit0/1/2 skip the dWf / dWc / dW1 phases
   RayGen rg;      // points == NULL: the points are generated from the ray parameters (point index = ray * S + s)
+  const int* idx;    // LIVE instances of siren_bwd_x4_kernel only: [B][P] ascending indices of the points to process, and
+  const int* count;  // [B] how many of them are defined
 };
 constexpr int GP_G1 = 0, GP_GC = H * H, GP_GF0 = GP_GC + HC * H, GP_GF1 = GP_GF0 + CF * HC, GPART = GP_GF1 + CF * HC;
 constexpr int SRED = 4 * 32 * 8 + 8;   // per wave a 32x8 tile of column sums, then 4 per-wave sums of dsigma (+ pad)
@@ -910,7 +912,7 @@ extern "C" int cips_siren_bwd_x3_sred(void) { return SRED; }
 
 static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays,
                                const float* dfeat, const float* dsigma, float* sred, float* gpart, int B, int P,
-                               cips_stream_t stream);
+                               cips_stream_t stream, const int* idx = nullptr, const int* count = nullptr);
 
 extern "C" int cips_siren_bwd_x3(const cips_siren_weights* w, const float* points, const float* dfeat,
                                  const float* dsigma, float* sred, float* gpart, int B, int P,
@@ -925,11 +927,26 @@ extern "C" int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ra
   return siren_bwd_x3_launch(w, nullptr, rays, dfeat, dsigma, sred, gpart, B, rays->W * rays->H * rays->S, stream);
 }
 
+extern "C" int cips_siren_bwd_x3_live(const cips_siren_weights* w, const float* points, const float* dfeat,
+                                      const float* dsigma, const int* idx, const int* count, float* sred, float* gpart,
+                                      int B, int P, cips_stream_t stream) {
+  if (!points || !idx || !count) return (int)hipErrorInvalidValue;
+  return siren_bwd_x3_launch(w, points, nullptr, dfeat, dsigma, sred, gpart, B, P, stream, idx, count);
+}
+
+extern "C" int cips_siren_bwd_x3_rays_live(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
+                                           const float* dsigma, const int* idx, const int* count, float* sred,
+                                           float* gpart, int B, cips_stream_t stream) {
+  if (!rays || !idx || !count) return (int)hipErrorInvalidValue;
+  return siren_bwd_x3_launch(w, nullptr, rays, dfeat, dsigma, sred, gpart, B, rays->W * rays->H * rays->S, stream, idx, count);
+}
+
 static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays,
                                const float* dfeat, const float* dsigma, float* sred, float* gpart, int B, int P,
-                               cips_stream_t stream) {
+                               cips_stream_t stream, const int* idx, const int* count) {
   if (!w || !dfeat || !dsigma || !sred || !gpart || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
   BwdX3Args a;
+  a.idx = idx; a.count = count;
   a.w = *w; a.points = points; a.dfeat = dfeat; a.dsigma = dsigma; a.sred = sred; a.gpart = gpart;
   a.B = B; a.P = P;
   a.rg = RayGen{};
@@ -951,14 +968,20 @@ static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points,
   static bool attr4 = false;
   CIPS_PER_DEVICE(attr4, false);
   if (!attr4) {
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr4 = true;
   }
-  if (w->trig_mode & 1)
-    hipLaunchKernelGGL(siren_bwd_x4_kernel<true>, grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(siren_bwd_x4_kernel<false>, grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+  const bool hw = (w->trig_mode & 1) != 0;
+  if (idx) {
+    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, true>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, true>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+  } else {
+    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, false>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, false>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+  }
   return CIPS_CHECK_LAUNCH();
 }
 

@@ -21,7 +21,13 @@ template <bool HW> __device__ __forceinline__ float sin_rev(float x) {
   float s_, c_; sincos_reduced(reduce_2pi(x), &s_, &c_); return s_;
 }
 
-template <bool HW>
+// LIVE: the workgroup walks a list of point indices instead of a contiguous range (cips_siren_bwd_x3_live in cips3d_hip.h).
+// Image b's list is a.idx[b * P + 0 .. a.count[b]); workgroup (c, b) takes the slots [c * len, min((c + 1) * len, count[b])),
+// len = ceil(count[b] / chunks) rounded up to whole 128-point rounds.  cstart / cend / pbase then count list SLOTS, and the
+// three places that form a point index look it up; everything else in a round is the dense kernel's.  The trip count comes
+// from device memory, so a replayed graph follows the data.  With every point listed in order the partition is the dense one
+// whenever the dense chunk is a multiple of 128 that divides P, and the partials are bit-identical.
+template <bool HW, bool LIVE>
 __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   extern __shared__ __attribute__((aligned(1024))) uchar smem[];
   const int b = blockIdx.y;
@@ -30,8 +36,15 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   constexpr float TWO_PI = 6.283185307179586f;
 
   const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int cstart = blockIdx.x * a.chunk;
-  const int cend = min(cstart + a.chunk, a.P);
+  int cstart = blockIdx.x * a.chunk;
+  int cend = min(cstart + a.chunk, a.P);
+  if (LIVE) {
+    const int cnt = a.count[b];
+    const int len = ((cnt + a.chunks - 1) / a.chunks + 127) & ~127;
+    cstart = blockIdx.x * len;
+    cend = min(cstart + len, cnt);          // >= 1 unless the image has no live point at all
+  }
+  const int* const lidx = LIVE ? a.idx + (long long)b * a.P : nullptr;
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
 
   // weight-gradient accumulators, owned per wave for the whole chunk; aS: column sums (see SRED)
@@ -42,11 +55,13 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   // inputs of the first round
   float px, py, pz, dsg;
   {
-    const int p = cstart + wave * 32 + (lane0 & 31);
-    const bool valid = p < cend;
-    const long long gp = (long long)b * a.P + (valid ? p : cend - 1);
+    const int slot = cstart + wave * 32 + (lane0 & 31);
+    const bool valid = slot < cend;
+    int p = valid ? slot : cend - 1;
+    if (LIVE) p = cend > 0 ? lidx[p] : 0;   // an image without live points: no list entry is defined, any point will do
+    const long long gp = (long long)b * a.P + p;
     if (a.points) { px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2]; }
-    else gen_point(a.rg, b, valid ? p : cend - 1, px, py, pz);
+    else gen_point(a.rg, b, p, px, py, pz);
     dsg = valid ? a.dsigma[gp] : 0.f;
   }
 
@@ -112,9 +127,11 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
     // ---- upstream gradient of the 32 colour features: requested now, consumed after two layers ----
     float4 df4[4];
     {
-      const int p = pbase + prow;
-      const bool valid = p < cend;
-      const float* dp = a.dfeat + ((long long)b * a.P + (valid ? p : cend - 1)) * CF + 4 * hf;
+      const int slot = pbase + prow;
+      const bool valid = slot < cend;
+      int p = valid ? slot : cend - 1;
+      if (LIVE) p = lidx[p];
+      const float* dp = a.dfeat + ((long long)b * a.P + p) * CF + 4 * hf;
 #pragma unroll
       for (int g = 0; g < 4; ++g) df4[g] = valid ? ld4(dp + 8 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -397,11 +414,13 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
       // ---- inputs of the next round: requested here, a whole layer before their first use (layer 0 of the next round inside
       //      the dW1 phase below) ----
       {
-        const int p = pbase + 128 + prow;
-        const bool valid = p < cend;
-        const long long gp = (long long)b * a.P + (valid ? p : cend - 1);
+        const int slot = pbase + 128 + prow;
+        const bool valid = slot < cend;
+        int p = valid ? slot : cend - 1;
+        if (LIVE) p = lidx[p];
+        const long long gp = (long long)b * a.P + p;
         if (a.points) { npx = a.points[gp * 3 + 0]; npy = a.points[gp * 3 + 1]; npz = a.points[gp * 3 + 2]; }
-        else gen_point(a.rg, b, valid ? p : cend - 1, npx, npy, npz);
+        else gen_point(a.rg, b, p, npx, npy, npz);
         ndsg = valid ? a.dsigma[gp] : 0.f;
       }
       // ---- d h1 = W1^T dp2  (K = 128, M = 128), m-major;  da1 = d h1 * cos(layer-0 argument), the layer-0 sines recomputed

@@ -186,6 +186,10 @@ def _split_k(P, target=8):
 # "staged_f32" (round 6): fp32 data pass with fp32-staged activations + fp32-MFMA weight-gradient GEMMs (the all-fp32 leg).
 SIREN_FWD_MODE = os.environ.get("CIPS_SIREN_FWD", "x3")
 SIREN_BWD_MODE = os.environ.get("CIPS_SIREN_BWD", "x3")
+# The fused ray-march's backward (RayMarchFunction, backward "x3") skips the samples whose upstream gradient is exactly zero:
+# the compositing backward reports them, a list kernel turns the mask into per-image point lists, and the fused SIREN
+# backward walks the lists.  "0": the dense calls.
+SIREN_BWD_LIVE = os.environ.get("CIPS_SIREN_BWD_LIVE", "1") != "0"
 
 
 class SirenFunction(torch.autograd.Function):
@@ -220,20 +224,33 @@ class SirenFunction(torch.autograd.Function):
         return (None,) + _siren_backward(t, dfeat, dsigma, B, P, points=points)
 
 
-def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None):
+def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None, live=None):
     """SIREN backward for upstream gradients dfeat (B,P,32), dsigma (B,P) (None: zeros) -> the gradients of the 16 tensors
     in _SIREN_NAMES order.  The sample points are either given (B,P,3) or regenerated in-kernel from `rays` (a RayParams
     struct).  SIREN_BWD_MODE picks the form for given points; `rays` always takes the fused form, whatever the mode says
-    (the staged data passes read a points tensor)."""
+    (the staged data passes read a points tensor).  `live` (fused form only): (idx (B,P) int32, count (B) int32), the
+    points to process per image (cips_siren_bwd_x3_live); the rows of dfeat / dsigma at other points are never read."""
     dev = t["w0"].device
     dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
     dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
     if SIREN_BWD_MODE == "x3" or points is None:
-        return _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays)
+        return _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live)
+    assert live is None
     return _siren_backward_staged(t, dfeat, dsigma, B, P, points, f32=SIREN_BWD_MODE == "staged_f32")
 
 
-def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays):
+def live_points(mask):
+    """(idx (B,P) int32, count (B) int32) of a (B,P) uint8 mask: idx[b, :count[b]] = the ascending indices of its non-zero
+    bytes (cips_live_points; the rest of idx is uninitialised).  No host synchronisation."""
+    lib = _lib.load()
+    B, P = mask.shape
+    idx = torch.empty(B, P, dtype=torch.int32, device=mask.device)
+    count = torch.empty(B, dtype=torch.int32, device=mask.device)
+    check(lib.cips_live_points(_p(mask), B, P, _p(idx), _p(count), _stream()), "cips_live_points")
+    return idx, count
+
+
+def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
     """one kernel: recompute + data gradients + weight-gradient contractions on split bf16, nothing staged in HBM"""
     lib = _lib.load()
     dev = dfeat.device
@@ -243,7 +260,15 @@ def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays):
     sw_ = lib.cips_siren_bwd_x3_sred()
     sred = torch.empty(B * chunks, sw_, device=dev)
     gpart = torch.empty(B * chunks, gw, device=dev)
-    if points is not None:
+    if live is not None:
+        idx, count = live
+        if points is not None:
+            check(lib.cips_siren_bwd_x3_live(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(idx), _p(count), _p(sred),
+                                             _p(gpart), B, P, _stream()), "cips_siren_bwd_x3_live")
+        else:
+            check(lib.cips_siren_bwd_x3_rays_live(C.byref(sw), C.byref(rays), _p(dfeat), _p(dsigma), _p(idx), _p(count),
+                                                  _p(sred), _p(gpart), B, _stream()), "cips_siren_bwd_x3_rays_live")
+    elif points is not None:
         check(lib.cips_siren_bwd_x3(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(sred), _p(gpart), B, P,
                                     _stream()), "cips_siren_bwd_x3")
     else:
@@ -603,7 +628,8 @@ class RayMarchFunction(torch.autograd.Function):
     NeRFNetwork (generator.py:260-317) -> fancy_integration (pigan_utils.py:212-273) as ONE kernel that walks the
     samples along each ray (cips_march_fwd_x3).  Under no_grad nothing per-sample reaches HBM (4 S + 132 B per ray);
     a training forward also writes feat / sigma / z for the backward, which is cips_composite_bwd followed by the fused
-    SIREN backward with the points regenerated in-kernel (cips_siren_bwd_x3_rays)."""
+    SIREN backward with the points regenerated in-kernel (cips_siren_bwd_x3_rays) — with SIREN_BWD_LIVE their *_live forms
+    and cips_live_points between them: the SIREN backward then runs over the samples with a non-zero upstream gradient."""
 
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
@@ -647,12 +673,19 @@ class RayMarchFunction(torch.autograd.Function):
         dfea = _c(dfea)
         dfeat = torch.empty_like(feat)
         dsig = torch.empty_like(sigma)
-        check(lib.cips_composite_bwd(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
-                                     _p(dfea), _p(dfeat), _p(dsig), None, None, R, S, clamp_mode, flags, _p(ctx.clamp_mask),
-                                     _stream()), "cips_composite_bwd")
+        use_live = SIREN_BWD_LIVE and SIREN_BWD_MODE == "x3"
+        if use_live:
+            mask = torch.empty(B, n * S, dtype=torch.uint8, device=dfea.device)
+            check(lib.cips_composite_bwd_live(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
+                                              _p(dfea), _p(dfeat), _p(dsig), None, None, _p(mask), None, R, S, clamp_mode, flags,
+                                              _p(ctx.clamp_mask), _stream()), "cips_composite_bwd_live")
+        else:
+            check(lib.cips_composite_bwd(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
+                                         _p(dfea), _p(dfeat), _p(dsig), None, None, R, S, clamp_mode, flags, _p(ctx.clamp_mask),
+                                         _stream()), "cips_composite_bwd")
         _tail_gate_publish(dfea.device)
         rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
-        grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp)
+        grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live_points(mask) if use_live else None)
         return (None,) * 7 + grads
 
 

@@ -160,6 +160,20 @@ int cips_siren_fwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* r
 int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
                            const float* dsigma, float* sred, float* gpart, int B, cips_stream_t stream);
 
+/* The fused backward over a LIST of points per image instead of all P (the points whose upstream gradient is not exactly
+ * zero: every output is linear in a point's (dfeat row, dsigma), so the others add nothing).  idx (B,P) int32: image b's
+ * point indices, ascending, in idx[b*P + 0 .. count[b]); count (B) int32, 0 <= count[b] <= P; both device memory, read by
+ * the kernel (no host read-back: the call can be captured in a graph and replayed on other data).  Same grid, same
+ * partial layout and same finalisation as cips_siren_bwd_x3; workgroup c of image b takes the list slots
+ * [c*len, min((c+1)*len, count[b])), len = ceil(count[b] / chunks) rounded up to a multiple of 128, and writes all-zero
+ * partials when that range is empty.  dfeat / dsigma are read at the listed points ONLY (the other rows may be
+ * uninitialised).  With every point listed the result is that of cips_siren_bwd_x3, bit for bit when its chunk divides P. */
+int cips_siren_bwd_x3_live(const cips_siren_weights* w, const float* points, const float* dfeat, const float* dsigma,
+                           const int* idx, const int* count, float* sred, float* gpart, int B, int P, cips_stream_t stream);
+int cips_siren_bwd_x3_rays_live(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
+                                const float* dsigma, const int* idx, const int* count, float* sred, float* gpart, int B,
+                                cips_stream_t stream);
+
 /* Fused ray-march for NON-hierarchical sampling: ray set-up + FiLM-SIREN + alpha-composite in one kernel that walks
  * the samples along the ray (a wave owns 32 rays, one lane pair per ray; the running transmittance / feature / depth
  * accumulators live in registers).  Replaces, for hierarchical_sample=False,
@@ -231,6 +245,25 @@ int cips_composite_bwd(const float* feat_c, const float* sig_c, const float* z_c
                        const float* dfea,
                        float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
                        int R, int S, int clamp_mode, int flags, const unsigned char* clamp_in, cips_stream_t stream);
+
+/* cips_composite_bwd that also reports which samples are live: live_c (R,S) / live_f (R,S; with a fine set) receive one
+ * byte per sample in the order of dfeat_* / dsig_*: 1 iff the weight the sample's dfeat row is scaled with is != 0 or the
+ * dsigma stored for it is != 0 (a NaN is != 0), else 0.  A relu-clamped sample (sigma + noise <= 0) has alpha == 0, so
+ * both vanish; softplus comes out all ones, and so does the last sample under last_back (bit 0 of flags).  The dfeat rows
+ * of samples reported 0 are NOT written (undefined); every dsigma is.  live_c == NULL (then live_f must be too): exactly
+ * cips_composite_bwd. */
+int cips_composite_bwd_live(const float* feat_c, const float* sig_c, const float* z_c,
+                            const float* feat_f, const float* sig_f, const float* z_f,
+                            const float* noise, float noise_std, const int* order,
+                            const float* dfea,
+                            float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                            unsigned char* live_c, unsigned char* live_f,
+                            int R, int S, int clamp_mode, int flags, const unsigned char* clamp_in, cips_stream_t stream);
+
+/* The list form of a mask: for each of B images with P mask bytes, idx[b*P + j] (j < count[b]) = the ascending indices of
+ * its non-zero bytes, count[b] their number; idx entries from count[b] on are left as they were.  Deterministic (the order
+ * is the index order, no atomics), one launch, one workgroup per image. */
+int cips_live_points(const unsigned char* live, int B, int P, int* idx, int* count, cips_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* generic batched fp32 GEMM on v_mfma_f32_32x32x2_f32 with fused epilogues */
