@@ -32,6 +32,10 @@ class RayParams(C.Structure):
                 ("W", i32), ("S", i32)]
 
 
+class GridParams(C.Structure):
+    _fields_ = [("gx", vp), ("gy", vp), ("gz", vp), ("nx", i32), ("ny", i32), ("nz", i32)]
+
+
 class GlinJob(C.Structure):
     _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("y", vp), ("dy", vp), ("dw", vp), ("db", vp), ("in_dim", i32),
                 ("out_dim", i32)]
@@ -110,6 +114,8 @@ SIGNATURES = {
     "cips_rays_fwd": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "cips_siren_fwd": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
     "cips_siren_fwd_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
+    "cips_siren_sigma_x3": (i32, [C.POINTER(SirenWeights), vp, vp, i32, i32, vp]),
+    "cips_siren_sigma_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, i32, vp]),
     "cips_siren_bwd_rows": (i32, [i32, i32]),
     "cips_siren_bwd_x3_chunks": (i32, [i32, i32]),
     "cips_siren_bwd_x3_gpart": (i32, []),

@@ -36,6 +36,7 @@
 #include "../../include/cips3d_hip.h"
 #include "raygen.h"
 #include <type_traits>
+#include <climits>
 
 // wave priority of the forward chain's MFMA phases (probe builds: -DCIPS_X3_PRIO)
 #ifdef CIPS_X3_PRIO
@@ -67,6 +68,11 @@ constexpr int O_STG = O_AUX + 4096;                      // 48 KiB staging
 constexpr int STG_BYTES = 49152;
 constexpr int SMEM_BYTES = O_STG + STG_BYTES;            // 163840 = the whole LDS of a CU
 static_assert(O_AUX == 110592 && SMEM_BYTES == 163840, "LDS carve");
+// The sigma-only forward (siren_sigma_x3_kernel) reads the W1 images, the layer-0 packs and G1 / C1 / WS: its own carve puts
+// the vectors right behind W1, with the spacing of the carve above (the chain addresses them relative to the layer-0 packs).
+constexpr int SG_L0 = O_WCH;                              // float4[128] where the full carve has the Wc image
+constexpr int SG_SMEM_BYTES = SG_L0 + (O_GC - O_L0);      // 69120: two workgroups fit a CU's 160 KiB
+static_assert(SG_L0 == 65536 && SG_SMEM_BYTES == 69120, "sigma LDS carve");
 
 // A wave's activations in "register-chain" layout (lane = point; tile q, register r <-> feature
 // 32q + (r&3) + 8(r>>2) + 4hf), packed to split bf16: dword j of tile q holds registers 2j, 2j+1, so dwords
@@ -292,6 +298,7 @@ __device__ __forceinline__ LaneAddr lane_addr(int lane, unsigned sbase) {
 
 // Forward-orientation dense layer: acc[m] += W[32m + i][k] * in[k][pt]; W image (R rows = out features) at
 // LDS offset IMG, lo plane PLANE bytes after the hi plane.
+// siren_sigma_chain.inc carries a copy of this fragment loader (one q at a time): a change of the image layout goes there too.
 template <int NM, int Q, int R, int IMG, int PLANE, bool F16 = false>
 __device__ __forceinline__ void layer_fwd(const LaneAddr& A, const Act<Q>& in, f32x16 (&acc)[NM]) {
   const unsigned b[2][2] = {{opaque(A.fb[0][0] + IMG), opaque(A.fb[0][1] + IMG)}, {opaque(A.fb[1][0] + IMG), opaque(A.fb[1][1] + IMG)}};
@@ -448,7 +455,9 @@ __device__ __forceinline__ float pow2_scale_for(float m, int& k) {
   k = k > 100 ? 100 : (k < -100 ? -100 : k);
   return __uint_as_float((unsigned)(k + 127) << 23);
 }
-template <bool PRE = false, bool F16 = false>
+// SIG (siren_sigma_x3_kernel): only what the chain needs up to sigma, on the sigma carve — W1, the layer-0 packs, G1, C1, WS,
+// by the same arithmetic; w.wc, w.bc, w.wf, w.gc, w.pc are not read.
+template <bool PRE = false, bool F16 = false, bool SIG = false>
 __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_weights& w, int b) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const float pre = PRE ? CIPS_INV_2PI : 1.f;
@@ -460,6 +469,7 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
       const float4 v = *reinterpret_cast<const float4*>(w.w1 + 4 * i);
       m1 = fmaxf(fmaxf(m1, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
+    if constexpr (!SIG) {
     for (int i = tid; i < HC * 32; i += nt) {
       const float4 v = *reinterpret_cast<const float4*>(w.wc + 4 * i);
       mc = fmaxf(fmaxf(mc, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
@@ -467,6 +477,7 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
     for (int i = tid; i < CF * 16; i += nt) {
       const float4 v = *reinterpret_cast<const float4*>(w.wf + 4 * i);
       mf = fmaxf(fmaxf(mf, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    }
     }
     // NaN weights: fmaxf drops them here; they reach the planes (and every output) through the split below
 #pragma unroll
@@ -496,6 +507,7 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
     *reinterpret_cast<uint2*>(sm + O_W1H + o) = ph;
     *reinterpret_cast<uint2*>(sm + O_W1L + o) = pl;
   }
+  if constexpr (!SIG) {
   for (int i = tid; i < HC * 32; i += nt) {                 // Wc: 64 rows x 32 units
     const int row = i >> 5, u = i & 31;
     float4 v = *reinterpret_cast<const float4*>(w.wc + row * H + 4 * u);
@@ -517,10 +529,11 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
     *reinterpret_cast<uint2*>(sm + O_WFH + o) = ph;
     *reinterpret_cast<uint2*>(sm + O_WFL + o) = pl;
   }
-  float* L0 = reinterpret_cast<float*>(sm + O_L0);
-  float* G1 = reinterpret_cast<float*>(sm + O_G1); float* C1 = reinterpret_cast<float*>(sm + O_C1);
-  float* WS = reinterpret_cast<float*>(sm + O_WS);
-  float* GC = reinterpret_cast<float*>(sm + O_GC); float* CC = reinterpret_cast<float*>(sm + O_CC);
+  }
+  constexpr int VB = SIG ? SG_L0 - O_L0 : 0;                // the per-feature vectors keep their spacing on the sigma carve
+  float* L0 = reinterpret_cast<float*>(sm + VB + O_L0);
+  float* G1 = reinterpret_cast<float*>(sm + VB + O_G1); float* C1 = reinterpret_cast<float*>(sm + VB + O_C1);
+  float* WS = reinterpret_cast<float*>(sm + VB + O_WS);
   for (int f = tid; f < H; f += nt) {
     const float g0 = w.g0[b * H + f], gs = g0 * w.box_scale;
     float4 pk;
@@ -531,11 +544,14 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
     const float g1 = w.g1[b * H + f];
     G1[f] = F16 ? g1 * i1 : g1; C1[f] = fmaf(g1, w.b1[f], w.p1[b * H + f]) * pre; WS[f] = w.ws[f];
   }
+  if constexpr (!SIG) {
+  float* GC = reinterpret_cast<float*>(sm + O_GC); float* CC = reinterpret_cast<float*>(sm + O_CC);
   for (int f = tid; f < HC; f += nt) {
     const float gc = w.gc[b * HC + f];
     GC[f] = F16 ? gc * ic : gc; CC[f] = fmaf(gc, w.bc[f], w.pc[b * HC + f]) * pre;
   }
   if (F16 && tid == 0) *reinterpret_cast<float*>(sm + O_AUX + 128) = isf;
+  }
 }
 
 // phase timestamps for tuning (probe builds, -DCIPS_TUNING, with CIPS_X3_PROF set): workgroup (0,0), lane 0 of each wave,
@@ -612,6 +628,64 @@ __global__ __launch_bounds__(512) void siren_fwd_x3_kernel(FwdX3Args a) {
         if (a.zout) a.zout[gp] = zpt;
       }
     }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Sigma-only forward (density volumes: cips_siren_sigma_x3, cips_siren_sigma_x3_grid): siren_fwd_x3_kernel's layout — lane =
+// point, a wave owns 32 points, the two lane halves split the features — running siren_sigma_chain.inc, the forward chain
+// up to sigma: 16 896 MAC per point instead of 27 136, 256 sines instead of 320, no operand split of h2, and one dword per
+// point to HBM instead of 132 B.  LDS: the sigma carve (67.5 KiB: W1 hi / lo, layer-0 packs, G1, C1, WS).
+// GRID: the point of index p = (i * ny + j) * nz + k is (gx[i], gy[j], gz[k]) — three host-built coordinate arrays READ by
+// the kernel, which does index arithmetic only: the lattice is whatever the host built, bit for bit.
+// Occupancy: two 512-thread workgroups fit a CU's LDS at 67.5 KiB each, and co-reside when the kernel stays at or below 128
+// VGPRs — which the chain does because it builds h1 one 32-feature tile at a time (siren_sigma_chain.inc).
+// __launch_bounds__' second argument is the minimum waves per SIMD asked of the register allocator: 4 = two workgroups of
+// 512 per CU.  profiles/density_grid.txt has this form timed against one workgroup per CU (bound 2, which also lets the
+// allocator use up to 256 VGPRs, and the launch's LDS request padded to 96 KiB): two per CU is 6.5 % faster.
+struct SigmaX3Args {
+  cips_siren_weights w;
+  const float* points;               // (B, P, 3); unused with GRID
+  const float *gx, *gy, *gz;         // GRID: the lattice's coordinates (nx), (ny), (nz)
+  float* sigma;                      // (B, P)
+  int ny, nz;
+  int B, P, chunk;
+};
+
+template <bool HW, bool F16, bool GRID>
+__global__ __launch_bounds__(512, 4) void siren_sigma_x3_kernel(SigmaX3Args a) {
+  extern __shared__ __attribute__((aligned(1024))) uchar smem[];
+  const int b = blockIdx.y;
+  stage_weights_x3<HW, F16, true>(smem, a.w, b);
+  __syncthreads();
+  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
+  const float bs = a.w.bs[0];
+  const int cstart = blockIdx.x * a.chunk;
+  const int cend = min(cstart + a.chunk, a.P);
+  for (int pbase = cstart + wave * 32; pbase < cend; pbase += 8 * 32) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int l31 = lane & 31, hf = lane >> 5;
+    LaneAddr LA = lane_addr(lane, sbase);
+    LA.v16 = opaque(sbase + SG_L0 + 16 * hf);
+    LA.v64 = opaque(sbase + SG_L0 + 64 * hf);
+    const int p = pbase + l31;
+    const bool valid = p < cend;
+    const int pc = valid ? p : cend - 1;           // ragged tail: the last valid point again, nothing stored
+    const long long gp = (long long)b * a.P + pc;
+    float px, py, pz;
+    if constexpr (GRID) {
+      const unsigned r = (unsigned)pc / (unsigned)a.nz, k = (unsigned)pc - r * (unsigned)a.nz;
+      const unsigned i = r / (unsigned)a.ny, j = r - i * (unsigned)a.ny;
+      px = a.gx[i]; py = a.gy[j]; pz = a.gz[k];
+    } else {
+      px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2];
+    }
+
+#include "siren_sigma_chain.inc"
+    if (valid && hf == 0) a.sigma[gp] = sig;
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -1027,6 +1101,53 @@ static int siren_fwd_x3_launch(const cips_siren_weights* w, const float* points,
   if (hw) { if (f16) go(T{}, T{}); else go(T{}, F{}); }
   else { if (f16) go(F{}, T{}); else go(F{}, F{}); }
   return CIPS_CHECK_LAUNCH();
+}
+
+// Sigma-only forward: siren_fwd_x3_launch's chunking (at most 4096 points, halved while B * chunks < 768; a ragged tail is
+// clamped to the last valid point in-kernel).  grid == NULL: points (B, P, 3).
+static int siren_sigma_x3_launch(const cips_siren_weights* w, const float* points, const cips_grid_params* grid, float* sigma,
+                                 int B, int P, cips_stream_t stream) {
+  SigmaX3Args a;
+  a.w = *w; a.points = points; a.sigma = sigma; a.B = B; a.P = P;
+  a.gx = a.gy = a.gz = nullptr; a.ny = a.nz = 1;
+  if (grid) { a.gx = grid->gx; a.gy = grid->gy; a.gz = grid->gz; a.ny = grid->ny; a.nz = grid->nz; }
+  a.chunk = 4096;
+  while (a.chunk > 512 && (long long)B * ((P + a.chunk - 1) / a.chunk) < 768) a.chunk >>= 1;
+  dim3 g((P + a.chunk - 1) / a.chunk, B);
+  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
+  auto go = [&](auto HW_, auto F16_, auto GRID_) {
+    constexpr bool HW = decltype(HW_)::value, F16 = decltype(F16_)::value, GRID = decltype(GRID_)::value;
+    static bool attr_set = false;
+    CIPS_PER_DEVICE(attr_set, false);
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)siren_sigma_x3_kernel<HW, F16, GRID>, hipFuncAttributeMaxDynamicSharedMemorySize, SG_SMEM_BYTES);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((siren_sigma_x3_kernel<HW, F16, GRID>), g, dim3(512), SG_SMEM_BYTES, (hipStream_t)stream, a);
+  };
+  using T = std::true_type; using F = std::false_type;
+  auto pick = [&](auto GRID_) {
+    if (hw) { if (f16) go(T{}, T{}, GRID_); else go(T{}, F{}, GRID_); }
+    else { if (f16) go(F{}, T{}, GRID_); else go(F{}, F{}, GRID_); }
+  };
+  if (grid) pick(T{}); else pick(F{});
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_siren_sigma_x3(const cips_siren_weights* w, const float* points, float* sigma, int B, int P,
+                                   cips_stream_t stream) {
+  if (!w || !points || !sigma || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
+  return siren_sigma_x3_launch(w, points, nullptr, sigma, B, P, stream);
+}
+
+extern "C" int cips_siren_sigma_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, int B,
+                                        cips_stream_t stream) {
+  if (!w || !grid || !sigma || B <= 0) return (int)hipErrorInvalidValue;
+  if (!grid->gx || !grid->gy || !grid->gz || grid->nx <= 0 || grid->ny <= 0 || grid->nz <= 0) return (int)hipErrorInvalidValue;
+  const long long nxy = (long long)grid->nx * grid->ny;               // < 2^62; times nz only once it is known to fit an int
+  if (nxy > INT_MAX || nxy * grid->nz > INT_MAX) return (int)hipErrorInvalidValue;
+  const long long P = nxy * grid->nz;
+  return siren_sigma_x3_launch(w, nullptr, grid, sigma, B, (int)P, stream);
 }
 
 #ifdef CIPS_TUNING

@@ -86,6 +86,16 @@ def save_image(imgs, path, nrow=8, padding=2, normalize=False, value_range=None,
     _save_u8(u8, path)
 
 
+def density_lattice(N, cube_length, center):
+    """The three coordinate tensors (x, y, z), each (N,) fp32 on the CPU, of GeneratorNerfINR.density_grid's lattice: axis a
+    runs from center[a] - L/2 to center[a] + L/2 as  arange(N) * (L / (N - 1)) + (center[a] - L/2)  — integer indices times
+    one voxel size (rounded to fp32 once), unlike exp/pigan/scripts/extract_shapes.py:18-31 (see density_grid)."""
+    if N < 2:
+        raise ValueError("a density lattice needs at least 2 points per axis")
+    idx = torch.arange(N, dtype=torch.float32)
+    return tuple(idx * (cube_length / (N - 1)) + (c - cube_length / 2) for c in center)
+
+
 @torch.no_grad()
 def gen_images(rank, world_size, generator, G_kwargs, fake_dir, num_imgs, img_size, batch_size, forward_points=256 ** 2,
                progress=False):

@@ -247,6 +247,38 @@ class NeRFNetwork(nn.Module):
             return self._evaluate_unfused(points, style_dict)
         return ops.SirenFunction.apply(points, *self._siren_args(style_dict))
 
+    def _sigma_args(self, style_dict):
+        """_siren_args for the density entry points.  sigma leaves the chain before the colour branch, so it does not depend
+        on the colour style: where the styles hold none (generator_v1's NeRF mapping network has no nerf_rgb head) a zero
+        style stands in — its FiLM vectors are never read by the sigma-only kernel and do not reach the sigma of the full
+        forward either."""
+        key = f'{self.name_prefix}_rgb'
+        if key not in style_dict:
+            b = style_dict[f'{self.name_prefix}_w0'].shape[0]
+            style_dict = {**style_dict, key: style_dict[f'{self.name_prefix}_w0'].new_zeros(b, self.color_layer_sine.style_dim)}
+        return style_dict
+
+    def density(self, points, style_dict):
+        """points (b,P,3) -> sigma (b,P), no gradient: the sigma-only HIP kernel for the shipped shape (the forward's sigma bit
+        for bit, without the colour branch), tensor operations for other widths / depths."""
+        with torch.no_grad():
+            style_dict = self._sigma_args(style_dict)
+            if not self.fused:
+                return self._evaluate_unfused(points, style_dict)[1]
+            return ops.siren_sigma(points, *self._siren_args(style_dict))
+
+    def density_lattice(self, gx, gy, gz, style_dict):
+        """density() over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> (b, nx, ny, nz); the fused kernel
+        reads the coordinates themselves, no points tensor is built"""
+        with torch.no_grad():
+            style_dict = self._sigma_args(style_dict)
+            if not self.fused:
+                n = (len(gx), len(gy), len(gz))
+                pts = torch.stack([gx.view(-1, 1, 1).expand(n), gy.view(1, -1, 1).expand(n), gz.view(1, 1, -1).expand(n)], -1)
+                b = style_dict[f'{self.name_prefix}_w0'].shape[0]
+                return self._evaluate_unfused(pts.reshape(1, -1, 3).expand(b, -1, 3), style_dict)[1].reshape(b, *n)
+            return ops.siren_sigma_grid(gx, gy, gz, *self._siren_args(style_dict))
+
     def evaluate_rays(self, style_dict, geom, xg, yg, zg, cam2world, jitter=None, zvals=None):
         """evaluate() with the sample points generated in-kernel (coarse: from the jitter draw; fine: from the resampled
         depths `zvals`) -> feat (b,P,32), sigma (b,P), z (b,P)"""
@@ -911,6 +943,27 @@ class GeneratorNerfINR(nn.Module):
             # for the head pending: they hold the modulation graph, and the next forward() must not find them
             self._join_side()
             self.inr_net._tail = None
+
+    @torch.no_grad()
+    def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0):
+        """The density sigma of zs['z_nerf'] on an N^3 lattice -> (b, N, N, N) fp32, no gradient: the volume that
+        exp/pigan/scripts/extract_shapes.py feeds to marching cubes (sample_generator, :38-60), from the sigma-only SIREN
+        kernel — only the NeRF mapping network runs, the INR one does not, and no points tensor is built.
+
+        Axis a in {x, y, z} has the coordinates  arange(N) * (L / (N - 1)) + (center[a] - L / 2)  (evaluation.density_lattice,
+        fp32 on the host; the kernel reads them and computes none), and element [b, i, j, k] is sigma at (x_i, y_j, z_k).
+        This is the integer lattice ON PURPOSE.  The reference's create_samples (:18-31) divides a float index by N without
+        flooring, which shears two of the axes by up to one voxel across the faster-running index, and pairs
+        voxel_origin[2] with x (and [0] with z); neither is reproduced.  For psi < 1 the NeRF styles are truncated towards
+        the average of 10 000 draws as in forward() (the same draws from the RNG as generate_avg_frequencies)."""
+        from .evaluation import density_lattice
+        style_dict = self._map_nerf(zs['z_nerf'])
+        if psi < 1:
+            avg = self._map_nerf(self.get_zs(10000)['z_nerf'])
+            avg = {name: style.mean(0, keepdim=True) for name, style in avg.items()}
+            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg, raw_lambda=psi)
+        gx, gy, gz = (g.to(zs['z_nerf'].device) for g in density_lattice(resolution, cube_length, center))
+        return self.siren.density_lattice(gx, gy, gz, self._nerf_styles(style_dict))
 
     def forward_camera_pos_and_lookup(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                       h_mean, v_mean, hierarchical_sample, camera_pos, camera_lookup, psi=1,

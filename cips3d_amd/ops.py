@@ -13,8 +13,8 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import (ConvDgradS2Desc, ConvWgradDesc, ConvX3Desc, GemmDesc, GemmX3Desc, GlinJob, ModfcBwdJob, ModfcPrepJob,
-                   RayParams, SirenGrads, SirenWeights, check)
+from ._lib import (ConvDgradS2Desc, ConvWgradDesc, ConvX3Desc, GemmDesc, GemmX3Desc, GlinJob, GridParams, ModfcBwdJob,
+                   ModfcPrepJob, RayParams, SirenGrads, SirenWeights, check)
 
 LRELU_SLOPE = 0.2
 
@@ -222,6 +222,54 @@ class SirenFunction(torch.autograd.Function):
         t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[1:]))
         B, P, _ = points.shape
         return (None,) + _siren_backward(t, dfeat, dsigma, B, P, points=points)
+
+
+def _siren_sigma_f32(t, points):
+    """sigma of the exact-fp32 forward (SIREN_FWD_MODE "f32": there is no sigma-only form of that kernel)"""
+    B, P, _ = points.shape
+    feat = torch.empty(B, P, 32, device=points.device)
+    sigma = torch.empty(B, P, device=points.device)
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_fwd(C.byref(sw), _p(points), _p(feat), _p(sigma), B, P, _stream()), "cips_siren_fwd")
+    return sigma
+
+
+def siren_sigma(points, *siren):
+    """sigma (B,P) of SirenFunction at points (B,P,3) without the colour branch (cips_siren_sigma_x3: 4 B per point written
+    instead of 132, bit for bit the forward kernel's sigma).  A plain function: inputs are detached, no gradient flows.  With
+    SIREN_FWD_MODE "f32" the exact-fp32 forward runs and its sigma is returned."""
+    t = _siren_prep(siren)
+    points = _c(points.detach())
+    _chk(points)
+    if SIREN_FWD_MODE != "x3":
+        return _siren_sigma_f32(t, points)
+    B, P, _ = points.shape
+    sigma = torch.empty(B, P, device=points.device)
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_sigma_x3(C.byref(sw), _p(points), _p(sigma), B, P, _stream()), "cips_siren_sigma_x3")
+    return sigma
+
+
+def siren_sigma_grid(gx, gy, gz, *siren):
+    """sigma (B, nx, ny, nz) over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors (cips_siren_sigma_x3_grid:
+    the kernel reads the coordinates and computes none, no (B,P,3) tensor exists).  Same value as siren_sigma on the
+    materialised points, bit for bit.  With SIREN_FWD_MODE "f32" the points are materialised for the exact-fp32 forward."""
+    t = _siren_prep(siren)
+    gx, gy, gz = (_c(v.detach()) for v in (gx, gy, gz))
+    _chk(gx, gy, gz)
+    if gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
+        raise ValueError("siren_sigma_grid takes three 1-D coordinate tensors")
+    B = t["g0"].shape[0]
+    nx, ny, nz = gx.numel(), gy.numel(), gz.numel()
+    if SIREN_FWD_MODE != "x3":
+        pts = torch.stack([gx.view(nx, 1, 1).expand(nx, ny, nz), gy.view(1, ny, 1).expand(nx, ny, nz),
+                           gz.view(1, 1, nz).expand(nx, ny, nz)], -1).reshape(1, -1, 3).expand(B, -1, 3)
+        return _siren_sigma_f32(t, pts.contiguous()).view(B, nx, ny, nz)
+    sigma = torch.empty(B, nx, ny, nz, device=gx.device)
+    sw = _siren_struct(t)
+    gp = GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz)
+    check(_lib.load().cips_siren_sigma_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), B, _stream()), "cips_siren_sigma_x3_grid")
+    return sigma
 
 
 def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None, live=None):

@@ -156,6 +156,16 @@ typedef struct cips_ray_params {
 int cips_siren_fwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, float* feat, float* sigma,
                            float* zout, int B, cips_stream_t stream);
 
+/* Density only (replaces the SIREN evaluation of exp/pigan/scripts/extract_shapes.py:54-58, sample_generator):
+ * sigma (B,P) of cips_siren_fwd_x3 without the colour branch, bit for bit; w->wc, bc, wf, bf, gc, pc are not read and may be NULL.
+ * 4 B per point written instead of 132; trig_mode as for cips_siren_fwd_x3, both bits. */
+int cips_siren_sigma_x3(const cips_siren_weights* w, const float* points, float* sigma, int B, int P, cips_stream_t stream);
+/* A lattice of points given by its three coordinate arrays (device memory, built by the host; the kernel reads them and does
+ * no coordinate arithmetic): point p = (i*ny + j)*nz + k is (gx[i], gy[j], gz[k]); nx*ny*nz <= INT_MAX. */
+typedef struct cips_grid_params { const float* gx; const float* gy; const float* gz; int nx, ny, nz; } cips_grid_params;
+/* the same over the lattice (gx[i], gy[j], gz[k]); sigma (B, nx, ny, nz) — no (B,P,3) points tensor in HBM */
+int cips_siren_sigma_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, int B, cips_stream_t stream);
+
 /* cips_siren_bwd_x3 with the points generated in-kernel from `rays` (P = H*W*S points per image). */
 int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
                            const float* dsigma, float* sred, float* gpart, int B, cips_stream_t stream);
