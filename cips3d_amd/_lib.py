@@ -125,6 +125,11 @@ SIGNATURES = {
     "cips_siren_bwd_x3_rays": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, vp, vp, vp, i32, vp]),
     "cips_siren_bwd_x3_live": (i32, [C.POINTER(SirenWeights), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "cips_siren_bwd_x3_rays_live": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, vp, vp, vp, vp, vp, i32, vp]),
+    "cips_siren_bwd_x3_live_plan": (i32, [vp, i32, i32, vp, vp, vp]),
+    "cips_siren_bwd_x3_live_plan_host": (i32, [vp, i32, i32, vp, vp]),
+    "cips_siren_bwd_x3_live_even": (i32, [C.POINTER(SirenWeights), vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "cips_siren_bwd_x3_rays_live_even": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "cips_siren_bwd_x3_reduce_segments": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "cips_siren_bwd_x3_finalize": (i32, [C.POINTER(SirenWeights), vp, vp, i32, i32, C.POINTER(SirenGrads), vp]),
     "cips_march_fwd_x3": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "cips_siren_bwd_data": (i32, [C.POINTER(SirenWeights)] + [vp] * 14 + [i32, i32, vp]),

@@ -428,9 +428,12 @@ struct BwdX3Args {
   unsigned long long* prof;
   int dbg;        // timing attribution, probe builds only (-DCIPS_TUNING, env CIPS_X3_DBG): bit0/1/2 skip the dWf / dWc / dW1 phases
   RayGen rg;      // points == NULL: the points are generated from the ray parameters (point index = ray * S + s)
-  const int* idx;    // LIVE instances of siren_bwd_x4_kernel only: [B][P] ascending indices of the points to process, and
-  const int* count;  // [B] how many of them are defined
+  const int* idx;    // LIVE / EVEN instances of siren_bwd_x4_kernel only: [B][P] ascending indices of the points to process, and
+  const int* count;  // [B] how many of them are defined (LIVE; EVEN reads its ranges from seg)
+  const int* seg;    // EVEN instances only: [B*chunks][4] image (-1: idle), first slot, end slot, rounds per flat workgroup id
 };
+// how a workgroup of siren_bwd_x4_kernel finds its points (siren_bwd_x4.inc)
+enum { X3_DENSE = 0, X3_LIVE = 1, X3_EVEN = 2 };
 constexpr int GP_G1 = 0, GP_GC = H * H, GP_GF0 = GP_GC + HC * H, GP_GF1 = GP_GF0 + CF * HC, GPART = GP_GF1 + CF * HC;
 constexpr int SRED = 4 * 32 * 8 + 8;   // per wave a 32x8 tile of column sums, then 4 per-wave sums of dsigma (+ pad)
 
@@ -566,6 +569,130 @@ __device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_wei
 #else
 #define X3_TS(i) __builtin_amdgcn_sched_barrier(0);
 #endif
+
+// ------------------------------------------------------------------------------------------------------------------
+// The EVEN partition of the live lists: G = B * chunks workgroups (the grid of the dense and LIVE launches) are dealt to the
+// images in proportion to their ROUNDS of 128 list slots, so that no workgroup walks more than T rounds, T as small as the
+// budget allows:
+//   r_b = ceil(count_b / 128), Rt = sum r_b;  T = the smallest integer >= max(1, ceil(Rt / G)) with
+//   sum_b max(1, ceil(r_b / T)) <= G  (the sum does not grow with T and is B <= G at T = max r_b: a bisection finds it);
+//   image b gets n_b = max(1, ceil(r_b / T)) workgroups, flat ids first_b = sum_{b' < b} n_b' .. first_b + n_b; its rounds are
+//   dealt as evenly as integers allow (q = r_b / n_b, e = r_b % n_b: the first e workgroups take q + 1 rounds, the rest q);
+//   slots = rounds * 128, the end clipped to count_b.  An image without live points keeps one workgroup with an empty range
+//   (it writes the all-zero partials its FiLM gradients are finalised from); ids from sum n_b up to G are idle (image -1).
+// Equal counts give every image G / B = chunks workgroups of equal length: the LIVE partition, and the dense one when every
+// point is listed and the dense chunk is a multiple of 128 that divides P.
+// Written once for a TEAM of cooperating threads: one on the host (X3Solo: cips_siren_bwd_x3_live_plan_host), a wave on the
+// device (X3Wave: siren_bwd_plan_kernel), member k of a group of size() holding image b0 + k.  Every member runs every statement;
+// sum / max / scan return the team's value to all of them.  The search for T is what the team is for: one division per image
+// and step, ~10 steps at the headline shape.  Nothing the team stores is read back, and each member writes the segments of its
+// own image one after the other (n_b of them: 1 .. 37 at the headline shape; a single image that takes the whole grid is
+// written by one member).  Measured at B = 32, G = 768 in the step's eager trace (profiles/even_siren_bwd_kernel_stats_after.txt):
+// 85 us per launch.  A first form that looked every flat id up in the img table just written (five dependent global loads per
+// id) took 185 us; where the remaining 85 us go is not attributed (serving the images one by one with the whole team instead
+// of per member measured the same), so a single-thread plan was not tried against it.
+// seg [G][4] = image, first slot, end slot, rounds;  img [B][2] = first id, n_b.  count_b is clamped to [0, P]: whatever the
+// count array holds, no range leaves the list.
+struct X3Solo {
+  __host__ __device__ int rank() const { return 0; }
+  __host__ __device__ int size() const { return 1; }
+  __host__ __device__ long long sum(long long v) const { return v; }
+  __host__ __device__ int max(int v) const { return v; }
+  __host__ __device__ int scan(int v) const { return v; }          // inclusive prefix sum over the ranks
+};
+template <class Team>
+__host__ __device__ inline void x3_even_plan(const int* count, int B, int P, int G, int* seg, int* img, const Team& tm) {
+  const int me = tm.rank(), nt = tm.size();
+  auto clamped = [&](int b) { const int c = count[b]; return c < 0 ? 0 : (c > P ? P : c); };
+  auto rounds = [](int c) { return (int)(((long long)c + 127) >> 7); };
+  auto wgs = [](int r, int T) { const int n = (r + T - 1) / T; return n < 1 ? 1 : n; };     // r + T - 1 < 2^25 + 2^24
+  const int c_own = me < B ? clamped(me) : 0;       // the first group's counts stay in registers through the search
+  auto cnt = [&](int b) { return b == me ? c_own : clamped(b); };
+  long long rt = 0;
+  int rmax = 0;
+  for (int b = me; b < B; b += nt) { const int r = rounds(cnt(b)); rt += r; rmax = r > rmax ? r : rmax; }
+  rt = tm.sum(rt); rmax = tm.max(rmax);
+  int lo = (int)((rt + G - 1) / G);                 // <= rmax, because Rt <= B * rmax <= G * rmax
+  if (lo < 1) lo = 1;
+  int hi = rmax > lo ? rmax : lo;
+  while (lo < hi) {                                 // invariant: the budget holds at hi
+    const int mid = lo + (hi - lo) / 2;
+    long long n = 0;
+    for (int b = me; b < B; b += nt) n += wgs(rounds(cnt(b)), mid);
+    if (tm.sum(n) <= G) hi = mid; else lo = mid + 1;
+  }
+  const int T = lo;
+  int first = 0;                                    // ids handed out so far
+  for (int b0 = 0; b0 < B; b0 += nt) {
+    const int b = b0 + me;
+    const int c = b < B ? cnt(b) : 0, r = rounds(c), n = b < B ? wgs(r, T) : 0;
+    const int f = first + tm.scan(n) - n;           // exclusive scan of n_b inside the group
+    if (b < B) {
+      img[2 * b] = f; img[2 * b + 1] = n;
+      const int q = r / n, e = r % n;
+      int r0 = 0;
+      for (int j = 0; j < n; ++j) {
+        const int nr = q + (j < e ? 1 : 0);
+        const long long end = ((long long)r0 + nr) * 128;
+        int* sg = seg + 4 * (long long)(f + j);
+        sg[0] = b; sg[1] = r0 * 128; sg[2] = end < c ? (int)end : c; sg[3] = nr;
+        r0 += nr;
+      }
+    }
+    first += (int)tm.sum(n);
+  }
+  for (int w = first + me; w < G; w += nt) { int* sg = seg + 4 * (long long)w; sg[0] = -1; sg[1] = 0; sg[2] = 0; sg[3] = 0; }
+}
+
+// one wave: every team operation is a shuffle, there is no barrier and no LDS
+struct X3Wave {
+  __device__ int rank() const { return threadIdx.x; }
+  __device__ int size() const { return 64; }
+  __device__ long long sum(long long v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+  }
+  __device__ int max(int v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(v, o); v = u > v ? u : v; }
+    return v;
+  }
+  __device__ int scan(int v) const {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o); if ((int)threadIdx.x >= o) v += u; }
+    return v;
+  }
+};
+__global__ __launch_bounds__(64) void siren_bwd_plan_kernel(const int* count, int B, int P, int G, int* seg, int* img) {
+  x3_even_plan(count, B, P, G, seg, img, X3Wave{});
+}
+
+// out[b][j] = sum of part[w][j] over image b's rows w = first_b .. first_b + n_b - 1 (img), in ascending w, for both partial
+// arrays in one launch: a row of gpart (GPART floats) followed by a row of sred (SRED floats), one float4 column per thread.
+// Rows that belong to no image (idle ids) are never read.
+constexpr int RS_G4 = GPART / 4, RS_S4 = SRED / 4;
+static_assert(GPART % 4 == 0 && SRED % 4 == 0, "rows of float4");
+__global__ __launch_bounds__(256) void siren_bwd_reduce_segments_kernel(const float4* sred, const float4* gpart, const int* img,
+                                                                        float4* sred_out, float4* gpart_out) {
+  const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= RS_G4 + RS_S4) return;
+  const int first = img[2 * b], n = img[2 * b + 1];
+  const bool g = j < RS_G4;
+  const int col = g ? j : j - RS_G4, w4 = g ? RS_G4 : RS_S4;
+  const float4* src = (g ? gpart : sred) + (long long)first * w4 + col;
+  float4 acc = src[0];
+  int i = 1;
+  for (; i + 4 <= n; i += 4) {                      // four rows in flight; added in row order
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = src[(long long)(i + u) * w4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
+  }
+  for (; i < n; ++i) { const float4 v = src[(long long)i * w4]; acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
+  (g ? gpart_out : sred_out)[(long long)b * w4 + col] = acc;
+}
 
 #include "siren_bwd_x4.inc"
 #define X3F_TS(i)
@@ -986,7 +1113,8 @@ extern "C" int cips_siren_bwd_x3_sred(void) { return SRED; }
 
 static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays,
                                const float* dfeat, const float* dsigma, float* sred, float* gpart, int B, int P,
-                               cips_stream_t stream, const int* idx = nullptr, const int* count = nullptr);
+                               cips_stream_t stream, const int* idx = nullptr, const int* count = nullptr,
+                               const int* seg = nullptr);
 
 extern "C" int cips_siren_bwd_x3(const cips_siren_weights* w, const float* points, const float* dfeat,
                                  const float* dsigma, float* sred, float* gpart, int B, int P,
@@ -1015,12 +1143,48 @@ extern "C" int cips_siren_bwd_x3_rays_live(const cips_siren_weights* w, const ci
   return siren_bwd_x3_launch(w, nullptr, rays, dfeat, dsigma, sred, gpart, B, rays->W * rays->H * rays->S, stream, idx, count);
 }
 
+extern "C" int cips_siren_bwd_x3_live_even(const cips_siren_weights* w, const float* points, const float* dfeat,
+                                           const float* dsigma, const int* idx, const int* count, const int* seg,
+                                           float* sred, float* gpart, int B, int P, cips_stream_t stream) {
+  if (!points || !idx || !count || !seg) return (int)hipErrorInvalidValue;
+  return siren_bwd_x3_launch(w, points, nullptr, dfeat, dsigma, sred, gpart, B, P, stream, idx, count, seg);
+}
+
+extern "C" int cips_siren_bwd_x3_rays_live_even(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
+                                                const float* dsigma, const int* idx, const int* count, const int* seg,
+                                                float* sred, float* gpart, int B, cips_stream_t stream) {
+  if (!rays || !idx || !count || !seg) return (int)hipErrorInvalidValue;
+  return siren_bwd_x3_launch(w, nullptr, rays, dfeat, dsigma, sred, gpart, B, rays->W * rays->H * rays->S, stream, idx, count, seg);
+}
+
+extern "C" int cips_siren_bwd_x3_live_plan_host(const int* count, int B, int P, int* seg, int* img) {
+  if (!count || !seg || !img || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
+  x3_even_plan(count, B, P, B * cips_siren_bwd_x3_chunks(B, P), seg, img, X3Solo{});
+  return 0;
+}
+
+extern "C" int cips_siren_bwd_x3_live_plan(const int* count, int B, int P, int* seg, int* img, cips_stream_t stream) {
+  if (!count || !seg || !img || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
+  const int G = B * cips_siren_bwd_x3_chunks(B, P);
+  hipLaunchKernelGGL(siren_bwd_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, count, B, P, G, seg, img);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_siren_bwd_x3_reduce_segments(const float* sred, const float* gpart, const int* img, int B, float* sred_out,
+                                                 float* gpart_out, cips_stream_t stream) {
+  if (!sred || !gpart || !img || !sred_out || !gpart_out || B <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(siren_bwd_reduce_segments_kernel, dim3((RS_G4 + RS_S4 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4*>(sred), reinterpret_cast<const float4*>(gpart), img,
+                     reinterpret_cast<float4*>(sred_out), reinterpret_cast<float4*>(gpart_out));
+  return CIPS_CHECK_LAUNCH();
+}
+
 static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays,
                                const float* dfeat, const float* dsigma, float* sred, float* gpart, int B, int P,
-                               cips_stream_t stream, const int* idx, const int* count) {
+                               cips_stream_t stream, const int* idx, const int* count, const int* seg) {
   if (!w || !dfeat || !dsigma || !sred || !gpart || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
   BwdX3Args a;
-  a.idx = idx; a.count = count;
+  a.idx = idx; a.count = count; a.seg = seg;
   a.w = *w; a.points = points; a.dfeat = dfeat; a.dsigma = dsigma; a.sred = sred; a.gpart = gpart;
   a.B = B; a.P = P;
   a.rg = RayGen{};
@@ -1042,19 +1206,24 @@ static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points,
   static bool attr4 = false;
   CIPS_PER_DEVICE(attr4, false);
   if (!attr4) {
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_LIVE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_LIVE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_EVEN>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_EVEN>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr4 = true;
   }
   const bool hw = (w->trig_mode & 1) != 0;
-  if (idx) {
-    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, true>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, true>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+  if (seg) {
+    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_EVEN>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_EVEN>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+  } else if (idx) {
+    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_LIVE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_LIVE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
   } else {
-    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, false>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, false>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_DENSE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_DENSE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
   }
   return CIPS_CHECK_LAUNCH();
 }

@@ -21,16 +21,31 @@ template <bool HW> __device__ __forceinline__ float sin_rev(float x) {
   float s_, c_; sincos_reduced(reduce_2pi(x), &s_, &c_); return s_;
 }
 
-// LIVE: the workgroup walks a list of point indices instead of a contiguous range (cips_siren_bwd_x3_live in cips3d_hip.h).
-// Image b's list is a.idx[b * P + 0 .. a.count[b]); workgroup (c, b) takes the slots [c * len, min((c + 1) * len, count[b])),
-// len = ceil(count[b] / chunks) rounded up to whole 128-point rounds.  cstart / cend / pbase then count list SLOTS, and the
-// three places that form a point index look it up; everything else in a round is the dense kernel's.  The trip count comes
-// from device memory, so a replayed graph follows the data.  With every point listed in order the partition is the dense one
-// whenever the dense chunk is a multiple of 128 that divides P, and the partials are bit-identical.
-template <bool HW, bool LIVE>
+// MODE X3_LIVE: the workgroup walks a list of point indices instead of a contiguous range (cips_siren_bwd_x3_live in
+// cips3d_hip.h).  Image b's list is a.idx[b * P + 0 .. a.count[b]); workgroup (c, b) takes the slots
+// [c * len, min((c + 1) * len, count[b])), len = ceil(count[b] / chunks) rounded up to whole 128-point rounds.  cstart / cend /
+// pbase then count list SLOTS, and the three places that form a point index look it up; everything else in a round is the dense
+// kernel's.  The trip count comes from device memory, so a replayed graph follows the data.  With every point listed in order
+// the partition is the dense one whenever the dense chunk is a multiple of 128 that divides P, and the partials are
+// bit-identical.
+// MODE X3_EVEN: the same list walk, but image, first slot and end slot of the workgroup come from row (flat workgroup id) of the
+// table a.seg that cips_siren_bwd_x3_live_plan wrote (x3_even_plan above: every workgroup of the launch gets about the same
+// number of rounds, whatever its image's live share), and the partials go to row = flat id.  An idle id (image -1) leaves
+// before anything is staged; the table row is the same for every thread, so the workgroup leaves together.
+template <bool HW, int MODE>
 __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   extern __shared__ __attribute__((aligned(1024))) uchar smem[];
-  const int b = blockIdx.y;
+  constexpr bool LIVE = MODE != X3_DENSE;
+  int b_ = blockIdx.y, prow_ = 0, cs_ = 0, ce_ = 0;
+  if constexpr (MODE == X3_EVEN) {
+    prow_ = blockIdx.y * gridDim.x + blockIdx.x;
+    const int* const sg = a.seg + 4 * (long long)prow_;
+    b_ = __builtin_amdgcn_readfirstlane(sg[0]);
+    if (b_ < 0) return;
+    cs_ = __builtin_amdgcn_readfirstlane(sg[1]);
+    ce_ = __builtin_amdgcn_readfirstlane(sg[2]);
+  }
+  const int b = b_;
   stage_weights_x3<HW>(smem, a.w, b);
   __syncthreads();
   constexpr float TWO_PI = 6.283185307179586f;
@@ -38,7 +53,9 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int cstart = blockIdx.x * a.chunk;
   int cend = min(cstart + a.chunk, a.P);
-  if (LIVE) {
+  if constexpr (MODE == X3_EVEN) {
+    cstart = cs_; cend = ce_;
+  } else if (LIVE) {
     const int cnt = a.count[b];
     const int len = ((cnt + a.chunks - 1) / a.chunks + 127) & ~127;
     cstart = blockIdx.x * len;
@@ -589,7 +606,7 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) part[(wave * 32 + mfma_row(r, hf)) * 32 + l31] = aS[0][r];
     __syncthreads();
-    float* sr = a.sred + (long long)(b * a.chunks + blockIdx.x) * SRED;
+    float* sr = a.sred + (long long)(MODE == X3_EVEN ? prow_ : b * a.chunks + blockIdx.x) * SRED;
     if (l31 < 8) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -614,7 +631,7 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   }
   // ---- write the workgroup's partial weight gradients ----
   {
-    float* gp_ = a.gpart + (long long)(b * a.chunks + blockIdx.x) * GPART;
+    float* gp_ = a.gpart + (long long)(MODE == X3_EVEN ? prow_ : b * a.chunks + blockIdx.x) * GPART;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll

@@ -190,6 +190,9 @@ SIREN_BWD_MODE = os.environ.get("CIPS_SIREN_BWD", "x3")
 # the compositing backward reports them, a list kernel turns the mask into per-image point lists, and the fused SIREN
 # backward walks the lists.  "0": the dense calls.
 SIREN_BWD_LIVE = os.environ.get("CIPS_SIREN_BWD_LIVE", "1") != "0"
+# ... and deals the live samples evenly to the workgroups of that launch (cips_siren_bwd_x3_live_plan / *_live_even /
+# cips_siren_bwd_x3_reduce_segments) instead of giving every image the same number of workgroups.  "0": the *_live calls.
+SIREN_BWD_EVEN = os.environ.get("CIPS_SIREN_BWD_EVEN", "1") != "0"
 
 
 class SirenFunction(torch.autograd.Function):
@@ -308,7 +311,22 @@ def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
     sw_ = lib.cips_siren_bwd_x3_sred()
     sred = torch.empty(B * chunks, sw_, device=dev)
     gpart = torch.empty(B * chunks, gw, device=dev)
-    if live is not None:
+    even = live is not None and SIREN_BWD_EVEN
+    img = None
+    if even:
+        # plan -> kernel -> segmented reduction: the partition follows the counts on the device, nothing is read back
+        idx, count = live
+        seg = torch.empty(B * chunks, 4, dtype=torch.int32, device=dev)
+        img = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        check(lib.cips_siren_bwd_x3_live_plan(_p(count), B, P, _p(seg), _p(img), _stream()), "cips_siren_bwd_x3_live_plan")
+        if points is not None:
+            check(lib.cips_siren_bwd_x3_live_even(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(idx), _p(count), _p(seg),
+                                                  _p(sred), _p(gpart), B, P, _stream()), "cips_siren_bwd_x3_live_even")
+        else:
+            check(lib.cips_siren_bwd_x3_rays_live_even(C.byref(sw), C.byref(rays), _p(dfeat), _p(dsigma), _p(idx), _p(count),
+                                                       _p(seg), _p(sred), _p(gpart), B, _stream()),
+                  "cips_siren_bwd_x3_rays_live_even")
+    elif live is not None:
         idx, count = live
         if points is not None:
             check(lib.cips_siren_bwd_x3_live(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(idx), _p(count), _p(sred),
@@ -327,10 +345,18 @@ def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
     sg = SirenGrads()
     for n, v in zip(_SIREN_NAMES, outs):
         setattr(sg, "d" + n, _p(v))
-    # the chunk partials are summed by two streaming reductions first (88 MB at C2: bandwidth-bound, one
-    # launch each); the finalisation then walks B rows instead of B * chunks
-    SRr = sred.view(B, chunks, sw_).sum(1) if chunks > 1 else sred
-    Gpr = gpart.view(B, chunks, gw).sum(1) if chunks > 1 else gpart
+    # the partials are summed per image first (88 MB at C2: bandwidth-bound); the finalisation then walks B rows instead of
+    # B * chunks
+    if even:
+        # an image's rows are img[b] = (first, n) here, n from 1 to all of them: one launch sums both arrays
+        SRr = torch.empty(B, sw_, device=dev)
+        Gpr = torch.empty(B, gw, device=dev)
+        check(lib.cips_siren_bwd_x3_reduce_segments(_p(sred), _p(gpart), _p(img), B, _p(SRr), _p(Gpr), _stream()),
+              "cips_siren_bwd_x3_reduce_segments")
+    else:
+        # every image has `chunks` rows: two streaming torch reductions, one launch each
+        SRr = sred.view(B, chunks, sw_).sum(1) if chunks > 1 else sred
+        Gpr = gpart.view(B, chunks, gw).sum(1) if chunks > 1 else gpart
     check(lib.cips_siren_bwd_x3_finalize(C.byref(sw), _p(SRr), _p(Gpr), B, 1, C.byref(sg), _stream()),
           "cips_siren_bwd_x3_finalize")
     return outs

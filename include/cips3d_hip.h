@@ -184,6 +184,36 @@ int cips_siren_bwd_x3_rays_live(const cips_siren_weights* w, const cips_ray_para
                                 const float* dsigma, const int* idx, const int* count, float* sred, float* gpart, int B,
                                 cips_stream_t stream);
 
+/* The list walk with the live samples dealt EVENLY to the workgroups of the launch.  The *_live forms give every image the
+ * same `chunks` workgroups, so a workgroup's trip count follows its own image's live share and the launch ends in a tail of
+ * the dense images; here the G = B * chunks workgroups (same grid, same sizes of sred / gpart) are dealt in proportion to the
+ * images' rounds of 128 list slots.  Three calls on one stream, no host read-back anywhere (graph-capturable):
+ *
+ * cips_siren_bwd_x3_live_plan writes the partition (one small workgroup).  With r_b = ceil(count[b] / 128) and Rt = sum r_b,
+ *   T = the smallest integer >= max(1, ceil(Rt / G)) with sum_b max(1, ceil(r_b / T)) <= G; image b gets
+ *   n_b = max(1, ceil(r_b / T)) workgroups with the flat ids first_b = sum_{b' < b} n_b' .. first_b + n_b - 1, its rounds dealt
+ *   as evenly as integers allow (the first r_b % n_b of them take one round more); slots = rounds * 128, the end clipped to
+ *   count[b].  An image without live points keeps one workgroup with an empty range; ids from sum n_b up to G are idle.
+ *   seg (G, 4) int32: image (-1: idle), first slot, end slot, rounds, per flat id;  img (B, 2) int32: first_b, n_b.
+ *   count[b] is clamped to [0, P].  Equal counts give the partition of the *_live forms.
+ *   cips_siren_bwd_x3_live_plan_host evaluates the same rule on host arrays (no device access).
+ * cips_siren_bwd_x3_live_even / _rays_live_even: the *_live calls with `seg`.  Workgroup (x, y) has the flat id
+ *   y * chunks + x, walks the slots seg says of image seg says, and writes its partials to row = flat id of sred / gpart
+ *   (all-zero partials for an empty range).  Idle ids write nothing: their rows stay as they were.
+ * cips_siren_bwd_x3_reduce_segments: sred_out (B, sred()) and gpart_out (B, gpart()), out[b] = the sum of rows
+ *   first_b .. first_b + n_b - 1 in ascending order (deterministic; idle rows are never read).  cips_siren_bwd_x3_finalize
+ *   then takes them with chunks = 1. */
+int cips_siren_bwd_x3_live_plan(const int* count, int B, int P, int* seg, int* img, cips_stream_t stream);
+int cips_siren_bwd_x3_live_plan_host(const int* count, int B, int P, int* seg, int* img);
+int cips_siren_bwd_x3_live_even(const cips_siren_weights* w, const float* points, const float* dfeat, const float* dsigma,
+                                const int* idx, const int* count, const int* seg, float* sred, float* gpart, int B, int P,
+                                cips_stream_t stream);
+int cips_siren_bwd_x3_rays_live_even(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
+                                     const float* dsigma, const int* idx, const int* count, const int* seg, float* sred,
+                                     float* gpart, int B, cips_stream_t stream);
+int cips_siren_bwd_x3_reduce_segments(const float* sred, const float* gpart, const int* img, int B, float* sred_out,
+                                      float* gpart_out, cips_stream_t stream);
+
 /* Fused ray-march for NON-hierarchical sampling: ray set-up + FiLM-SIREN + alpha-composite in one kernel that walks
  * the samples along the ray (a wave owns 32 rays, one lane pair per ray; the running transmittance / feature / depth
  * accumulators live in registers).  Replaces, for hierarchical_sample=False,
