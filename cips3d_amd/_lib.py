@@ -116,6 +116,8 @@ SIGNATURES = {
     "cips_siren_fwd_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
     "cips_siren_sigma_x3": (i32, [C.POINTER(SirenWeights), vp, vp, i32, i32, vp]),
     "cips_siren_sigma_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, i32, vp]),
+    "cips_siren_sigma_grad_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
+    "cips_siren_sigma_grad_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, vp, i32, vp]),
     "cips_siren_bwd_rows": (i32, [i32, i32]),
     "cips_siren_bwd_x3_chunks": (i32, [i32, i32]),
     "cips_siren_bwd_x3_gpart": (i32, []),

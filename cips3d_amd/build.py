@@ -38,7 +38,7 @@ def build(force=False, verbose=True):
     for f in os.listdir(objdir):
         if f.endswith(".o") and f not in keep:
             os.remove(os.path.join(objdir, f))
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_x3_common.h"), os.path.join(CSRC, "siren_fwd_chain.inc"), os.path.join(CSRC, "siren_sigma_chain.inc"), os.path.join(CSRC, "siren_bwd_x4.inc"), os.path.join(CSRC, "raygen.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_x3_common.h"), os.path.join(CSRC, "siren_fwd_chain.inc"), os.path.join(CSRC, "siren_sigma_chain.inc"), os.path.join(CSRC, "siren_sigma_grad_chain.inc"), os.path.join(CSRC, "siren_bwd_x4.inc"), os.path.join(CSRC, "raygen.h"),
                os.path.join(HERE, "..", "include", "cips3d_hip.h")]
     objs = []
     procs = []

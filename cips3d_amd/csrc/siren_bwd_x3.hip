@@ -328,7 +328,7 @@ __device__ __forceinline__ void layer_fwd_mm(const LaneAddr& A, const Act<Q>& in
 // Transposed dense layer: acc[m] += W[k][32m + i] * in[k][pt]  (dh = W^T d), same image, transpose reads.
 // KS = k-steps (16 rows each).  The B operand's k order is the register chain's: k-step ks, element e of half
 // hf <-> row 16ks + 4hf + (e&3) + 8(e>>2).
-template <int NM, int KS, int R, int IMG, int PLANE>
+template <int NM, int KS, int R, int IMG, int PLANE, bool F16 = false>
 __device__ __forceinline__ void layer_tr(const LaneAddr& A, const Act<(KS + 1) / 2>& in, f32x16 (&acc)[NM]) {
   const unsigned b[2][2] = {{opaque(A.tb[0][0] + IMG), opaque(A.tb[0][1] + IMG)}, {opaque(A.tb[1][0] + IMG), opaque(A.tb[1][1] + IMG)}};
   auto load = [&](int ks, int m, Frag& f) {
@@ -338,7 +338,7 @@ __device__ __forceinline__ void layer_tr(const LaneAddr& A, const Act<(KS + 1) /
     put(f.l, 0, lds_tr(b[ks & 1][0] + c + PLANE));
     put(f.l, 2, lds_tr(b[ks & 1][1] + c + 512 + PLANE));
   };
-  run_layer<NM, KS>(load, in, acc);
+  run_layer<NM, KS, F16>(load, in, acc);      // F16: fp16 planes (the 16-bit transpose read does not care which), x3h
 }
 
 template <int NM, int KS, int R, int IMG, int PLANE, typename SideF>
@@ -697,6 +697,18 @@ __global__ __launch_bounds__(256) void siren_bwd_reduce_segments_kernel(const fl
 #include "siren_bwd_x4.inc"
 #define X3F_TS(i)
 
+// cosine twins of sin_rev (siren_bwd_x4.inc), for siren_sigma_grad_chain.inc: the argument is in revolutions with HW, in radians
+// without.  sincos_rev's sine is sin_rev<HW>(x) expression for expression — the sigma of the gradient kernel is the sigma
+// kernel's bit for bit only while the two stay in step (tests/test_gpu_density_gradient.py asserts torch.equal).
+template <bool HW> __device__ __forceinline__ float cos_rev(float x) {
+  if (HW) return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(x));
+  float s_, c_; sincos_reduced(reduce_2pi(x), &s_, &c_); return c_;
+}
+template <bool HW> __device__ __forceinline__ void sincos_rev(float x, float* s, float* c) {
+  if (HW) { const float r = __builtin_amdgcn_fractf(x); *s = __builtin_amdgcn_sinf(r); *c = __builtin_amdgcn_cosf(r); }
+  else sincos_reduced(reduce_2pi(x), s, c);
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // Forward on the same split-bf16 register chain (default; CIPS_SIREN_FWD=f32 selects siren.hip's exact fp32 MFMA
@@ -813,6 +825,82 @@ __global__ __launch_bounds__(512, 4) void siren_sigma_x3_kernel(SigmaX3Args a) {
 
 #include "siren_sigma_chain.inc"
     if (valid && hf == 0) a.sigma[gp] = sig;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Sigma and its gradient w.r.t. the point (cips_siren_sigma_grad_x3, cips_siren_sigma_grad_x3_grid): the sigma kernel's layout,
+// LDS carve, staging, points sources and chunking, running siren_sigma_grad_chain.inc — the sigma chain, then
+//   dp1 = g1 * ws * cos(a1),  dh1 = W1^T dp1  (the W1 image read transposed: no second image),
+//   grad = box_scale * W0^T (g0 * cos(a0) * dh1) = sum_f pack[f].xyz * cos(a0[f]) * dh1[f]
+// — 16 896 + 16 384 MAC and 256 + 256 trigonometric evaluations per point.  sigma is the sigma kernel's bit for bit.
+// Two scale factors leave in fp32 at the output:
+//  * HW: the staging stores W1 and the layer-0 packs divided by 2 pi (the sines take revolutions), so both transposed factors
+//    carry 1 / (2 pi): the gradient is multiplied by (2 pi)^2;
+//  * F16: G1 holds g1 * 2^-k next to the W1 * 2^k image, so g1 * ws * cos can sit far below fp16's normal range.  Every wave
+//    takes  m = max_f |G1[f] * ws[f]|  of its image from LDS and multiplies dp1 by pow2_scale_for(m) — the staging rule: the
+//    largest |dp1| a point can have lies in [2^13, 2^14) — and the output by its inverse.  A power of two: exact to undo.
+// Registers: the packed dp1 (64) is live next to the 64 accumulators of dh1 plus the fragment ring, more than the 128 registers
+// two co-resident 512-thread workgroups would leave a wave, so the kernel asks for one workgroup per CU (bound 2: up to 256).
+struct SigmaGradX3Args {
+  cips_siren_weights w;
+  const float* points;               // (B, P, 3); unused with GRID
+  const float *gx, *gy, *gz;         // GRID: the lattice's coordinates (nx), (ny), (nz)
+  float* sigma;                      // (B, P) or NULL
+  float* grad;                       // (B, P, 3)
+  int ny, nz;
+  int B, P, chunk;
+};
+
+template <bool HW, bool F16, bool GRID>
+__global__ __launch_bounds__(512, 2) void siren_sigma_grad_x3_kernel(SigmaGradX3Args a) {
+  extern __shared__ __attribute__((aligned(1024))) uchar smem[];
+  const int b = blockIdx.y;
+  stage_weights_x3<HW, F16, true>(smem, a.w, b);
+  __syncthreads();
+  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
+  const float bs = a.w.bs[0];
+  float dscale = 1.f, oscale = HW ? 39.47841760435743f : 1.f;      // (2 pi)^2
+  if constexpr (F16) {
+    const float* G1 = reinterpret_cast<const float*>(smem + SG_L0 + (O_G1 - O_L0));
+    const float* WS = reinterpret_cast<const float*>(smem + SG_L0 + (O_WS - O_L0));
+    float m = fmaxf(fabsf(G1[lane0] * WS[lane0]), fabsf(G1[lane0 + 64] * WS[lane0 + 64]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    int k;
+    dscale = pow2_scale_for(m, k);
+    oscale *= __uint_as_float((unsigned)(127 - k) << 23);
+  }
+  const int cstart = blockIdx.x * a.chunk;
+  const int cend = min(cstart + a.chunk, a.P);
+  for (int pbase = cstart + wave * 32; pbase < cend; pbase += 8 * 32) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int l31 = lane & 31, hf = lane >> 5;
+    LaneAddr LA = lane_addr(lane, sbase);
+    LA.v16 = opaque(sbase + SG_L0 + 16 * hf);
+    LA.v64 = opaque(sbase + SG_L0 + 64 * hf);
+    const int p = pbase + l31;
+    const bool valid = p < cend;
+    const int pc = valid ? p : cend - 1;           // ragged tail: the last valid point again, nothing stored
+    const long long gp = (long long)b * a.P + pc;
+    float px, py, pz;
+    if constexpr (GRID) {
+      const unsigned r = (unsigned)pc / (unsigned)a.nz, k = (unsigned)pc - r * (unsigned)a.nz;
+      const unsigned i = r / (unsigned)a.ny, j = r - i * (unsigned)a.ny;
+      px = a.gx[i]; py = a.gy[j]; pz = a.gz[k];
+    } else {
+      px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2];
+    }
+
+#include "siren_sigma_grad_chain.inc"
+    if (valid && hf == 0) {
+      if (a.sigma) a.sigma[gp] = sig;
+      float* go = a.grad + gp * 3;
+      go[0] = gx * oscale; go[1] = gy * oscale; go[2] = gz * oscale;
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -1317,6 +1405,51 @@ extern "C" int cips_siren_sigma_x3_grid(const cips_siren_weights* w, const cips_
   if (nxy > INT_MAX || nxy * grid->nz > INT_MAX) return (int)hipErrorInvalidValue;
   const long long P = nxy * grid->nz;
   return siren_sigma_x3_launch(w, nullptr, grid, sigma, B, (int)P, stream);
+}
+
+// Sigma and its gradient: the sigma launcher's chunking and instance choice.
+static int siren_sigma_grad_x3_launch(const cips_siren_weights* w, const float* points, const cips_grid_params* grid, float* sigma,
+                                      float* grad, int B, int P, cips_stream_t stream) {
+  SigmaGradX3Args a;
+  a.w = *w; a.points = points; a.sigma = sigma; a.grad = grad; a.B = B; a.P = P;
+  a.gx = a.gy = a.gz = nullptr; a.ny = a.nz = 1;
+  if (grid) { a.gx = grid->gx; a.gy = grid->gy; a.gz = grid->gz; a.ny = grid->ny; a.nz = grid->nz; }
+  a.chunk = 4096;
+  while (a.chunk > 512 && (long long)B * ((P + a.chunk - 1) / a.chunk) < 768) a.chunk >>= 1;
+  dim3 g((P + a.chunk - 1) / a.chunk, B);
+  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
+  auto go = [&](auto HW_, auto F16_, auto GRID_) {
+    constexpr bool HW = decltype(HW_)::value, F16 = decltype(F16_)::value, GRID = decltype(GRID_)::value;
+    static bool attr_set = false;
+    CIPS_PER_DEVICE(attr_set, false);
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)siren_sigma_grad_x3_kernel<HW, F16, GRID>, hipFuncAttributeMaxDynamicSharedMemorySize, SG_SMEM_BYTES);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((siren_sigma_grad_x3_kernel<HW, F16, GRID>), g, dim3(512), SG_SMEM_BYTES, (hipStream_t)stream, a);
+  };
+  using T = std::true_type; using F = std::false_type;
+  auto pick = [&](auto GRID_) {
+    if (hw) { if (f16) go(T{}, T{}, GRID_); else go(T{}, F{}, GRID_); }
+    else { if (f16) go(F{}, T{}, GRID_); else go(F{}, F{}, GRID_); }
+  };
+  if (grid) pick(T{}); else pick(F{});
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, float* sigma, float* grad, int B, int P,
+                                        cips_stream_t stream) {
+  if (!w || !points || !grad || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
+  return siren_sigma_grad_x3_launch(w, points, nullptr, sigma, grad, B, P, stream);
+}
+
+extern "C" int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, float* grad,
+                                             int B, cips_stream_t stream) {
+  if (!w || !grid || !grad || B <= 0) return (int)hipErrorInvalidValue;
+  if (!grid->gx || !grid->gy || !grid->gz || grid->nx <= 0 || grid->ny <= 0 || grid->nz <= 0) return (int)hipErrorInvalidValue;
+  const long long nxy = (long long)grid->nx * grid->ny;
+  if (nxy > INT_MAX || nxy * grid->nz > INT_MAX) return (int)hipErrorInvalidValue;
+  return siren_sigma_grad_x3_launch(w, nullptr, grid, sigma, grad, B, (int)(nxy * grid->nz), stream);
 }
 
 #ifdef CIPS_TUNING

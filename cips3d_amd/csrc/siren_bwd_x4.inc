@@ -16,6 +16,7 @@ __device__ __forceinline__ void pinf(float& a, float& b, float& c, float& d) { a
 __device__ __forceinline__ void pinu(unsigned& a, unsigned& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 __device__ __forceinline__ void pinu(unsigned& a, unsigned& b, unsigned& c, unsigned& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
 
+// (siren_bwd_x3.hip's sincos_rev repeats this expression for its sine: a change here goes there too)
 template <bool HW> __device__ __forceinline__ float sin_rev(float x) {
   if (HW) return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(x));
   float s_, c_; sincos_reduced(reduce_2pi(x), &s_, &c_); return s_;

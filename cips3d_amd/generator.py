@@ -279,6 +279,36 @@ class NeRFNetwork(nn.Module):
                 return self._evaluate_unfused(pts.reshape(1, -1, 3).expand(b, -1, 3), style_dict)[1].reshape(b, *n)
             return ops.siren_sigma_grid(gx, gy, gz, *self._siren_args(style_dict))
 
+    def _unfused_gradient(self, points, style_dict):
+        """sigma and d sigma / d points of _evaluate_unfused by autograd (the tensor-operation path of other widths / depths)"""
+        with torch.enable_grad():
+            pts = points.detach().clone().requires_grad_(True)
+            sigma = self._evaluate_unfused(pts, style_dict)[1]
+            grad, = torch.autograd.grad(sigma.sum(), pts)
+        return sigma.detach(), grad
+
+    def density_gradient(self, points, style_dict):
+        """points (b,P,3) -> sigma (b,P), d sigma / d points (b,P,3); the outputs carry no grad_fn.  The fused HIP kernel for
+        the shipped shape (ops.siren_sigma_grad: sigma is density()'s bit for bit), autograd through the tensor operations for
+        other widths / depths."""
+        with torch.no_grad():
+            style_dict = self._sigma_args(style_dict)
+            if not self.fused:
+                return self._unfused_gradient(points, style_dict)
+            return ops.siren_sigma_grad(points, *self._siren_args(style_dict))
+
+    def density_gradient_lattice(self, gx, gy, gz, style_dict):
+        """density_gradient() over the lattice (gx[i], gy[j], gz[k]) -> (b, nx, ny, nz), (b, nx, ny, nz, 3)"""
+        with torch.no_grad():
+            style_dict = self._sigma_args(style_dict)
+            if not self.fused:
+                n = (len(gx), len(gy), len(gz))
+                pts = torch.stack([gx.view(-1, 1, 1).expand(n), gy.view(1, -1, 1).expand(n), gz.view(1, 1, -1).expand(n)], -1)
+                b = style_dict[f'{self.name_prefix}_w0'].shape[0]
+                sigma, grad = self._unfused_gradient(pts.reshape(1, -1, 3).expand(b, -1, 3), style_dict)
+                return sigma.reshape(b, *n), grad.reshape(b, *n, 3)
+            return ops.siren_sigma_grad_grid(gx, gy, gz, *self._siren_args(style_dict))
+
     def evaluate_rays(self, style_dict, geom, xg, yg, zg, cam2world, jitter=None, zvals=None):
         """evaluate() with the sample points generated in-kernel (coarse: from the jitter draw; fine: from the resampled
         depths `zvals`) -> feat (b,P,32), sigma (b,P), z (b,P)"""
@@ -817,6 +847,11 @@ class GeneratorNerfINR(nn.Module):
     def _nerf_features(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None):
         """points_forward (generator.py:1659-1746) up to the composite, for all n rays of every image or for the subset
         `idx` of them (form "points" only): -> pixels_fea (b, m, 32)"""
+        return self._nerf_features_depth(s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx)[0]
+
+    def _nerf_features_depth(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None):
+        """_nerf_features with the per-ray depth the march / composite kernels compute next to the features:
+        -> pixels_fea (b, m, 32), depth (b, m)"""
         b, S, E, H, W = g.b, s.num_steps, s.E, s.img_size, s.img_size
         m = s.n if idx is None else idx.numel()
         clamp = ops._CLAMP[s.clamp_mode]
@@ -824,7 +859,7 @@ class GeneratorNerfINR(nn.Module):
             if g.form == "march":
                 geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled())
                 return self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
-                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None)[0]
+                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None)
             if g.form == "rays":
                 rays = (nerf_styles, (b, H, W, S, g.zc), g.xg, g.yg, g.zg, g.cam2world)
                 feat_c, sig_c, z_c = self.siren.evaluate_rays(*rays, jitter=g.jitter)
@@ -851,9 +886,10 @@ class GeneratorNerfINR(nn.Module):
                 else:
                     feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, m * S, 3), nerf_styles)
                 feat_f, sig_f = feat_f.view(b * m, S, 32), sig_f.view(b * m, S)
-            return ops.CompositeFunction.apply(
+            out = ops.CompositeFunction.apply(
                 feat_c, sig_c, z_c, feat_f, sig_f, fine_z, noise_f.reshape(b * m, E) if s.nerf_noise != 0 else None,
-                s.nerf_noise, clamp, s.flags)[0].view(b, m, 32)
+                s.nerf_noise, clamp, s.flags)
+            return out[0].view(b, m, 32), out[1].view(b, m)
 
     def _head(self, s, pixels_fea, style_dict, nerf_grad):
         """the tail of points_forward (generator.py:1747-1762) on features of any form: -> inr rgb (b,m,3), aux rgb or None.
@@ -944,8 +980,68 @@ class GeneratorNerfINR(nn.Module):
             self._join_side()
             self.inr_net._tail = None
 
+    def _density_styles(self, z_nerf, psi):
+        """z_nerf -> the NeRF styles of the density entry points: only the NeRF mapping network runs; for psi < 1 the styles are
+        truncated towards the average of 10 000 draws as in forward() (the same draws from the RNG as
+        generate_avg_frequencies)"""
+        style_dict = self._map_nerf(z_nerf)
+        if psi < 1:
+            avg = self._map_nerf(self.get_zs(10000)['z_nerf'])
+            avg = {name: style.mean(0, keepdim=True) for name, style in avg.items()}
+            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg, raw_lambda=psi)
+        return style_dict
+
     @torch.no_grad()
-    def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0):
+    def density_gradient(self, zs, points, psi=1.0):
+        """sigma (b,P) and d sigma / d point (b,P,3) of zs['z_nerf'] at arbitrary world-space points (b,P,3), no grad_fn:
+        density_grid's style handling and truncation, NeRFNetwork.density_gradient's kernel."""
+        return self.siren.density_gradient(points, self._nerf_styles(self._density_styles(zs['z_nerf'], psi)))
+
+    @torch.no_grad()
+    def geometry(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
+                 h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, clamp_mode='relu', white_back=False,
+                 last_back=False, camera_pos=None, camera_lookup=None, up_vector=None, rand_override=None):
+        """The geometry of the image forward() (or, with camera_pos / camera_lookup, forward_camera_pos_and_lookup()) renders
+        for the same arguments under no_grad with nerf_noise = 0 -> SimpleNamespace of
+          depth   (b,1,H,W)  the expected ray depth the march / composite kernels compute next to the features
+          points  (b,3,H,W)  origin + direction * depth, world space (directions: ops.rays_fwd)
+          sigma   (b,1,H,W)  the density at those points
+          normals (b,3,H,W)  -grad sigma / |grad sigma| there (ops.siren_sigma_grad); exact zeros where the gradient is zero
+          pitch_yaw (b,2)
+        Only the NeRF mapping network runs: neither the INR mapping network nor the head.
+        Random numbers: the draws and the camera are draw_randoms / camera_setup on the RenderSettings of those calls, so a
+        seed gives the geometry of the image it renders, and the generator is left in the state forward() leaves it in — with
+        whole images in one shot (no grad_points / forward_points), which is all this entry point offers: every draw of a
+        forward, the noise tensors included, is made before the NeRF path starts and nothing after it draws.  For psi < 1 the
+        10 000 latents of the average styles are drawn as get_zs draws them (both z_nerf and z_inr), as in forward()."""
+        device = next(self.parameters()).device
+        if device.type != 'cuda':
+            raise RuntimeError("GeneratorNerfINR.geometry runs on the GPU only (there is no CPU path)")
+        s = RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample, sample_dist=sample_dist,
+            clamp_mode=clamp_mode, nerf_noise=0., white_back=white_back, last_back=last_back, rand_override=rand_override,
+            camera_pos=camera_pos, camera_lookup=camera_lookup, up_vector=up_vector)
+        style_dict = self.siren._sigma_args(self._density_styles(zs['z_nerf'], psi))
+        b, H = zs['z_nerf'].shape[0], img_size
+        d = draw_randoms(s, b, device)
+        origin, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
+        g = self._ray_geometry(s, b, device, origin, cam2world, d.jitter)
+        nerf_styles = self._nerf_styles(style_dict)
+        depth = self._nerf_features_depth(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, False)[1]
+        dirs = g.dirs if g.form == "points" else ops.rays_fwd(g.xg, g.yg, g.zg, g.zc, cam2world, g.jitter, b, H, H, s.num_steps)[2]
+        points = origin.view(b, 1, 3) + dirs * depth.view(b, s.n, 1)
+        sigma, grad = self.siren.density_gradient(points, nerf_styles)
+        norm = grad.norm(dim=-1, keepdim=True)
+        normals = torch.where(norm > 0, -grad / norm, torch.zeros_like(grad))
+
+        def img(t):
+            return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
+
+        return SimpleNamespace(depth=img(depth), points=img(points), sigma=img(sigma), normals=img(normals), pitch_yaw=pitch_yaw)
+
+    @torch.no_grad()
+    def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, return_gradient=False):
         """The density sigma of zs['z_nerf'] on an N^3 lattice -> (b, N, N, N) fp32, no gradient: the volume that
         exp/pigan/scripts/extract_shapes.py feeds to marching cubes (sample_generator, :38-60), from the sigma-only SIREN
         kernel — only the NeRF mapping network runs, the INR one does not, and no points tensor is built.
@@ -955,14 +1051,14 @@ class GeneratorNerfINR(nn.Module):
         This is the integer lattice ON PURPOSE.  The reference's create_samples (:18-31) divides a float index by N without
         flooring, which shears two of the axes by up to one voxel across the faster-running index, and pairs
         voxel_origin[2] with x (and [0] with z); neither is reproduced.  For psi < 1 the NeRF styles are truncated towards
-        the average of 10 000 draws as in forward() (the same draws from the RNG as generate_avg_frequencies)."""
+        the average of 10 000 draws as in forward() (the same draws from the RNG as generate_avg_frequencies).
+        return_gradient: -> (sigma (b, N, N, N), d sigma / d (x, y, z) (b, N, N, N, 3)) from the gradient lattice kernel
+        (NeRFNetwork.density_gradient_lattice); sigma is the default call's bit for bit."""
         from .evaluation import density_lattice
-        style_dict = self._map_nerf(zs['z_nerf'])
-        if psi < 1:
-            avg = self._map_nerf(self.get_zs(10000)['z_nerf'])
-            avg = {name: style.mean(0, keepdim=True) for name, style in avg.items()}
-            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg, raw_lambda=psi)
+        style_dict = self._density_styles(zs['z_nerf'], psi)
         gx, gy, gz = (g.to(zs['z_nerf'].device) for g in density_lattice(resolution, cube_length, center))
+        if return_gradient:
+            return self.siren.density_gradient_lattice(gx, gy, gz, self._nerf_styles(style_dict))
         return self.siren.density_lattice(gx, gy, gz, self._nerf_styles(style_dict))
 
     def forward_camera_pos_and_lookup(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,

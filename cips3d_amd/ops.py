@@ -275,6 +275,49 @@ def siren_sigma_grid(gx, gy, gz, *siren):
     return sigma
 
 
+def _need_x3_sigma_grad():
+    if SIREN_FWD_MODE != "x3":
+        raise RuntimeError(f"the density gradient runs on the split-operand SIREN chain only: there is no exact-fp32 kernel "
+                           f"for it (CIPS_SIREN_FWD={SIREN_FWD_MODE!r})")
+
+
+def siren_sigma_grad(points, *siren):
+    """sigma (B,P) and its gradient w.r.t. the points, grad (B,P,3), at points (B,P,3) (cips_siren_sigma_grad_x3).  sigma is
+    siren_sigma's bit for bit.  A plain function: inputs are detached, the outputs carry no grad_fn.  With SIREN_FWD_MODE
+    other than "x3" it raises: the exact-fp32 forward has no gradient kernel."""
+    t = _siren_prep(siren)
+    points = _c(points.detach())
+    _chk(points)
+    _need_x3_sigma_grad()
+    B, P, _ = points.shape
+    sigma = torch.empty(B, P, device=points.device)
+    grad = torch.empty(B, P, 3, device=points.device)
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_sigma_grad_x3(C.byref(sw), _p(points), _p(sigma), _p(grad), B, P, _stream()),
+          "cips_siren_sigma_grad_x3")
+    return sigma, grad
+
+
+def siren_sigma_grad_grid(gx, gy, gz, *siren):
+    """siren_sigma_grad over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> sigma (B, nx, ny, nz),
+    grad (B, nx, ny, nz, 3) (cips_siren_sigma_grad_x3_grid: no points tensor exists).  The points form's values bit for bit."""
+    t = _siren_prep(siren)
+    gx, gy, gz = (_c(v.detach()) for v in (gx, gy, gz))
+    _chk(gx, gy, gz)
+    if gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
+        raise ValueError("siren_sigma_grad_grid takes three 1-D coordinate tensors")
+    _need_x3_sigma_grad()
+    B = t["g0"].shape[0]
+    nx, ny, nz = gx.numel(), gy.numel(), gz.numel()
+    sigma = torch.empty(B, nx, ny, nz, device=gx.device)
+    grad = torch.empty(B, nx, ny, nz, 3, device=gx.device)
+    sw = _siren_struct(t)
+    gp = GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz)
+    check(_lib.load().cips_siren_sigma_grad_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), _p(grad), B, _stream()),
+          "cips_siren_sigma_grad_x3_grid")
+    return sigma, grad
+
+
 def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None, live=None):
     """SIREN backward for upstream gradients dfeat (B,P,32), dsigma (B,P) (None: zeros) -> the gradients of the 16 tensors
     in _SIREN_NAMES order.  The sample points are either given (B,P,3) or regenerated in-kernel from `rays` (a RayParams

@@ -165,6 +165,14 @@ int cips_siren_sigma_x3(const cips_siren_weights* w, const float* points, float*
 typedef struct cips_grid_params { const float* gx; const float* gy; const float* gz; int nx, ny, nz; } cips_grid_params;
 /* the same over the lattice (gx[i], gy[j], gz[k]); sigma (B, nx, ny, nz) — no (B,P,3) points tensor in HBM */
 int cips_siren_sigma_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, int B, cips_stream_t stream);
+/* sigma and its gradient w.r.t. the point: sigma (B,P) (may be NULL: not written; otherwise cips_siren_sigma_x3's bit for bit),
+ * grad (B,P,3) = d sigma / d point, row-major — the sigma chain, one transposed 128x128 layer on the split MFMAs and the
+ * layer-0 cosines, ~5e-6 relative (1e-6 class on the default fp16 planes).  Colour pointers of w are not read and may be NULL. */
+int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, float* sigma /* may be NULL */,
+                             float* grad, int B, int P, cips_stream_t stream);
+/* the same over the lattice of cips_grid_params; sigma (B, nx, ny, nz) or NULL, grad (B, nx, ny, nz, 3) */
+int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma /* may be NULL */,
+                                  float* grad, int B, cips_stream_t stream);
 
 /* cips_siren_bwd_x3 with the points generated in-kernel from `rays` (P = H*W*S points per image). */
 int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
