@@ -9,10 +9,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libcips3d_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "gemm_bf16x3_wide.hip", "gemm_bf16x3_v3.hip", "gemm_bf16x3_km_wide.hip", "siren.hip", "siren_bwd_x3.hip", "render.hip", "modfc.hip", "disc_ops.hip", "optim.hip", "small_ops.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "gemm_bf16x3_wide.hip", "gemm_bf16x3_v3.hip", "gemm_bf16x3_km_wide.hip", "siren.hip", "siren_bwd_x3.hip", "siren_fwd_x3.hip", "render.hip", "modfc.hip", "disc_ops.hip", "optim.hip", "small_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
-# per-source extras.  siren_bwd_x3.hip: the m-major layers of siren_bwd_x4.inc unroll 32 items x (3 MFMAs + 3 epilogue slots);
+# per-source extras.  siren_bwd_x3.hip: the m-major layers of siren_bwd_x4_kernel unroll 32 items x (3 MFMAs + 3 epilogue slots);
 # before unrolling every slot call carries all of its six variants, which puts the loop over clang's 16 384-instruction limit for
 # `#pragma unroll` — it then stays a loop, the accumulator / activation arrays are indexed dynamically and live in scratch
 # (1 728 bytes per lane, measured).  The limit is raised for this file only (the other sources' code generation is unchanged).
@@ -38,8 +38,9 @@ def build(force=False, verbose=True):
     for f in os.listdir(objdir):
         if f.endswith(".o") and f not in keep:
             os.remove(os.path.join(objdir, f))
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_x3_common.h"), os.path.join(CSRC, "siren_fwd_chain.inc"), os.path.join(CSRC, "siren_sigma_chain.inc"), os.path.join(CSRC, "siren_sigma_grad_chain.inc"), os.path.join(CSRC, "siren_bwd_x4.inc"), os.path.join(CSRC, "raygen.h"),
-               os.path.join(HERE, "..", "include", "cips3d_hip.h")]
+    # every header and textually included fragment: a change to any of them rebuilds all sources
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
+    headers.append(os.path.join(HERE, "..", "include", "cips3d_hip.h"))
     objs = []
     procs = []
     for src in SOURCES:

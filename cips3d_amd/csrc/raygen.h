@@ -1,4 +1,4 @@
-// raygen.h — in-kernel ray set-up shared by the SIREN kernels (siren_bwd_x3.hip) and the resampler (render.hip).
+// raygen.h — in-kernel ray set-up shared by the SIREN kernels (siren_bwd_x3.hip, siren_fwd_x3.hip) and the resampler (render.hip).
 #pragma once
 #include "common.h"
 #include "../../include/cips3d_hip.h"

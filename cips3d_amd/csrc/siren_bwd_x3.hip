@@ -32,327 +32,13 @@
 // plane, transposed fragments (dh = W^T d) two ds_read_b64_tr_b16.  Every image (weights and staging) is
 // XOR-swizzled at 8-byte granularity by a bijection of the row index chosen so that (a) 32 lanes touching
 // 32 consecutive rows at one column and (b) the transpose read's 4 rows x 64 B both cover all 64 banks.
-#include "common.h"
-#include "../../include/cips3d_hip.h"
-#include "raygen.h"
-#include <type_traits>
-#include <climits>
-
-// wave priority of the forward chain's MFMA phases (probe builds: -DCIPS_X3_PRIO)
-#ifdef CIPS_X3_PRIO
-#define X3_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define X3_PRIO(p)
-#endif
+//
+// This file: the backward kernel, the EVEN plan of its live lists, the segment reduction and the finaliser, with their entry
+// points.  The layout, the dense layers and the weight staging are siren_x3_common.h's, shared with the forward and march
+// kernels (siren_fwd_x3.hip) and the sigma kernels (siren_sigma_x3.inc).
+#include "siren_x3_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned char uchar;
-
-constexpr int H = 128, HC = 64, CF = 32;
-
-// ---- LDS carve (bytes) ----
-constexpr int O_W1H = 0, O_W1L = 32768;                 // [128 out][128 in] bf16, 256 B rows
-constexpr int O_WCH = 65536, O_WCL = 81920;             // [64 out][128 in]
-constexpr int O_WFH = 98304, O_WFL = 102400;            // [32 out][64 in], 128 B rows
-constexpr int O_L0 = 106496;                            // float4[128]
-constexpr int O_G1 = O_L0 + 2048, O_C1 = O_G1 + 512, O_WS = O_C1 + 512;
-constexpr int O_GC = O_WS + 512, O_CC = O_GC + 256;
-constexpr int O_AUX = O_CC + 256;                        // [128 points][8 bf16] hi plane, then lo plane (2 KiB each)
-constexpr int O_STG = O_AUX + 4096;                      // 48 KiB staging
-constexpr int STG_BYTES = 49152;
-constexpr int SMEM_BYTES = O_STG + STG_BYTES;            // 163840 = the whole LDS of a CU
-static_assert(O_AUX == 110592 && SMEM_BYTES == 163840, "LDS carve");
-// The sigma-only forward (siren_sigma_x3_kernel) reads the W1 images, the layer-0 packs and G1 / C1 / WS: its own carve puts
-// the vectors right behind W1, with the spacing of the carve above (the chain addresses them relative to the layer-0 packs).
-constexpr int SG_L0 = O_WCH;                              // float4[128] where the full carve has the Wc image
-constexpr int SG_SMEM_BYTES = SG_L0 + (O_GC - O_L0);      // 69120: two workgroups fit a CU's 160 KiB
-static_assert(SG_L0 == 65536 && SG_SMEM_BYTES == 69120, "sigma LDS carve");
-
-// A wave's activations in "register-chain" layout (lane = point; tile q, register r <-> feature
-// 32q + (r&3) + 8(r>>2) + 4hf), packed to split bf16: dword j of tile q holds registers 2j, 2j+1, so dwords
-// 2g, 2g+1 are one 8-byte LDS unit (4 consecutive features) and dwords 4t..4t+3 are the MFMA B operand of
-// k-step (q,t).  Plain dword arrays on purpose: arrays of uint2 pairs defeat SROA and end up in scratch.
-template <int Q> struct Act { unsigned hi[Q][8], lo[Q][8]; };
-
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-  f32x2 v = {a, b};
-  bf16x2 h = __builtin_convertvector(v, bf16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  f32x2 hf = {__uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
-  f32x2 r = v - hf;
-  bf16x2 l = __builtin_convertvector(r, bf16x2);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-// The same split on fp16 planes (x = hi + lo, 11 + 11 mantissa bits: 2^-22 relative where bf16 planes give 2^-17), for
-// operands of known range only — the forward chain's activations are sines and its weights are staged with a per-matrix
-// power-of-two scale (stage_weights_x3<PRE, true>) — fp16 has 5 exponent bits.  Same instruction count as split2.
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split2h(float a, float b, unsigned& hi, unsigned& lo) {
-  f32x2 v = {a, b};
-  f16x2 h = __builtin_convertvector(v, f16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  // residual x - hi in ONE instruction per element: v_fma_mix_f32 reads the fp16 half in place (op_sel picks the half,
-  // op_sel_hi marks source 0 as fp16) — hipcc's own code is v_cvt_f32_f16 x2 + v_pk_add_f32 (5 instead of 4 per pair, and
-  // a packed-f32 op between MFMAs costs more than its slot, MI355X_MICROARCH.md); it has no builtin and folds
-  // fma(-1, fpext(h), x) back into the subtraction.  Plain VALU -> VALU dependencies: no wait states to pad.
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(a));
-  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(b));
-  f32x2 r = {r0, r1};
-  f16x2 l = __builtin_convertvector(r, f16x2);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-template <bool F16>
-__device__ __forceinline__ void split2t(float a, float b, unsigned& hi, unsigned& lo) {
-  if constexpr (F16) split2h(a, b, hi, lo); else split2(a, b, hi, lo);
-}
-// 32 values of a register group (tiles q0, q0+1) -> packed
-template <int Q>
-__device__ __forceinline__ void pack32(const float (&v)[32], Act<Q>& o, int q0) {
-#pragma unroll
-  for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) split2(v[16 * qq + 2 * j], v[16 * qq + 2 * j + 1], o.hi[q0 + qq][j], o.lo[q0 + qq][j]);
-}
-// Pin packed values where they are computed: hipcc otherwise sinks the whole producing computation into the
-// `if (wave == turn)` staging blocks, serialising it across the workgroup's waves.
-template <int Q>
-__device__ __forceinline__ void pin(Act<Q>& o) {
-#pragma unroll
-  for (int q = 0; q < Q; ++q)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { asm volatile("" : "+v"(o.hi[q][j])); asm volatile("" : "+v"(o.lo[q][j])); }
-}
-__device__ __forceinline__ bf16x8 mk8(unsigned a, unsigned b, unsigned c, unsigned d) {
-  u32x4 v = {a, b, c, d};
-  return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ f32x16 x3(f32x16 acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-  return acc;
-}
-// same pass order on fp16 planes (v_mfma_f32_32x32x16_f16: the bf16 instruction's rate and fragment layout)
-__device__ __forceinline__ f32x16 x3h(f32x16 acc, u32x4 ah, u32x4 al, u32x4 bh, u32x4 bl) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bl), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
-  return acc;
-}
-
-// LDS image layout (weights and staging alike): [column/32][row][32 columns] — 64-byte rows of 8 units
-// (unit = 4 bf16 = 8 B), column blocks R*64 bytes apart, the unit index XORed with 3 bits of the row:
-//   weights  (SH = 2): unit ^ ((row >> 2) & 7)     staging (SH = 1): unit ^ ((row >> 1) & 7)
-// Probed on hardware (scripts/probe/lds_layout_probe.hip, SQ_LDS_BANK_CONFLICT = 0 for all three patterns):
-//  * ds_read_b64_tr_b16 — a 32-lane group covers 4 rows x 64 B = one 256-B bank row whatever the in-row order;
-//  * forward fragments, ds_read_b64 — 32 consecutive rows at one unit: (row & 3) picks the 64-B quarter,
-//    (row >> 2) & 7 the unit inside it;
-//  * staging stores, ds_write_b64 (16-lane groups, 128-B bank row) — (row & 1) picks the half, (row >> 1) & 7
-//    the unit.
-// and every fragment address is  lane base + compile-time immediate  (LaneAddr below).
-template <int SH> __device__ __forceinline__ int img_addr(int row, int unit, int R) {
-  return (unit >> 3) * R * 64 + row * 64 + (((unit & 7) ^ ((row >> SH) & 7)) << 3);
-}
-
-// All LDS traffic goes through 32-bit LDS byte addresses (lane base + compile-time constant), so that the
-// constant lands in the instruction's 16-bit offset field; arithmetic on generic pointers does not fold.
-#define LDS_PTR(T, a) ((__attribute__((address_space(3))) T*)(uintptr_t)(a))
-__device__ __forceinline__ uint2 lds_tr(unsigned a) {
-  short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(short4v, a));
-  return __builtin_bit_cast(uint2, v);
-}
-// plain 8-byte LDS read that the load/store optimizer must not fuse into ds_read2st64_b64 (half the
-// bandwidth and 2-way conflicts on this layout)
-__device__ __forceinline__ uint2 lds_b64(unsigned a) {
-  const unsigned long long v = *LDS_PTR(const volatile unsigned long long, a);
-  return make_uint2((unsigned)v, (unsigned)(v >> 32));
-}
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void lds_st64(unsigned a, unsigned x, unsigned y) { u32x2 v = {x, y}; *LDS_PTR(u32x2, a) = v; }
-__device__ __forceinline__ float4 lds_ld4(unsigned a) { const f32x4 v = *LDS_PTR(const f32x4, a); return make_float4(v[0], v[1], v[2], v[3]); }
-
-__device__ __forceinline__ constexpr int featidx(int q, int r, int hf) { return q * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
-template <int NM>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NM]) {
-#pragma unroll
-  for (int m = 0; m < NM; ++m)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-}
-
-struct Frag { unsigned h[4], l[4]; };   // one A (or B) fragment: 8 bf16 per plane
-__device__ __forceinline__ void put(unsigned (&d)[4], int i, uint2 v) { d[i] = v.x; d[i + 1] = v.y; }
-
-// Dense layers run as a flat list of (k-step, m-tile) items, three MFMAs each, with the A fragment of item
-// i+2 requested from LDS before the MFMAs of item i issue (ring of 3 fragments = 24 registers);
-// sched_barrier(0) pins that order — left alone, hipcc hoists hundreds of LDS reads and spills.
-template <int NM, int KS, bool F16 = false, typename LoadF>
-__device__ __forceinline__ void run_layer(LoadF load, const Act<(KS + 1) / 2>& in, f32x16 (&acc)[NM]) {
-  constexpr int NI = NM * KS, D = 2;
-  Frag ring[D + 1];
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    if (i < NI) load(i / NM, i % NM, ring[i]);
-#pragma unroll
-  for (int it = 0; it < NI; ++it) {
-    if (it + D < NI) load((it + D) / NM, (it + D) % NM, ring[(it + D) % (D + 1)]);
-    const int s = it / NM, m = it % NM, q = s >> 1, t = s & 1;
-    const Frag& f = ring[it % (D + 1)];
-    if constexpr (F16) {
-      const u32x4 bh = {in.hi[q][4 * t], in.hi[q][4 * t + 1], in.hi[q][4 * t + 2], in.hi[q][4 * t + 3]};
-      const u32x4 bl = {in.lo[q][4 * t], in.lo[q][4 * t + 1], in.lo[q][4 * t + 2], in.lo[q][4 * t + 3]};
-      const u32x4 ah = {f.h[0], f.h[1], f.h[2], f.h[3]}, al = {f.l[0], f.l[1], f.l[2], f.l[3]};
-      __builtin_amdgcn_sched_barrier(0);
-      acc[m] = x3h(acc[m], ah, al, bh, bl);
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-    const bf16x8 bh = mk8(in.hi[q][4 * t], in.hi[q][4 * t + 1], in.hi[q][4 * t + 2], in.hi[q][4 * t + 3]);
-    const bf16x8 bl = mk8(in.lo[q][4 * t], in.lo[q][4 * t + 1], in.lo[q][4 * t + 2], in.lo[q][4 * t + 3]);
-    __builtin_amdgcn_sched_barrier(0);
-    acc[m] = x3(acc[m], mk8(f.h[0], f.h[1], f.h[2], f.h[3]), mk8(f.l[0], f.l[1], f.l[2], f.l[3]), bh, bl);
-    __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-// m-major dense layer with woven side work (round 4).  scripts/probe/issue_overlap_probe.hip: with ONE wave per SIMD,
-// "MFMA, 4-6 VALU, MFMA, ..." costs max(matrix pipe, VALU issue) — 16 x (MFMA, 4 v_fma) = 528 cycles against 532 for the
-// MFMAs alone and 340 for the VALU alone — while "16 MFMA, then 64 v_fma" costs the sum (824): a wave's own VALU does hide
-// under its own MFMAs, but only when it sits BETWEEN them in program order (an MFMA waits at issue for the pipe, and
-// everything behind it waits too).  So: output tile m runs all its k-steps back to back, and after EVERY MFMA one slot
-// of `side(slot)` is emitted (slot = 3 * item + pass; the callers put tile m-1's epilogue — FiLM, sine / cosine, hi / lo
-// split — into the slots of tile m).  sched_barrier(0) pins the order.
-template <int NM, int KS, typename LoadF, typename SideF>
-__device__ __forceinline__ void run_layer_mm(LoadF load, const Act<(KS + 1) / 2>& in, f32x16 (&acc)[NM], SideF side) {
-  constexpr int NI = NM * KS, D = 2;
-  Frag ring[D + 1];
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    if (i < NI) load(i % KS, i / KS, ring[i]);
-#pragma unroll
-  for (int it = 0; it < NI; ++it) {
-    if (it + D < NI) load((it + D) % KS, (it + D) / KS, ring[(it + D) % (D + 1)]);
-    const int m = it / KS, s = it % KS, q = s >> 1, t = s & 1;
-    const bf16x8 bh = mk8(in.hi[q][4 * t], in.hi[q][4 * t + 1], in.hi[q][4 * t + 2], in.hi[q][4 * t + 3]);
-    const bf16x8 bl = mk8(in.lo[q][4 * t], in.lo[q][4 * t + 1], in.lo[q][4 * t + 2], in.lo[q][4 * t + 3]);
-    const Frag& f = ring[it % (D + 1)];
-    const bf16x8 ah = mk8(f.h[0], f.h[1], f.h[2], f.h[3]), al = mk8(f.l[0], f.l[1], f.l[2], f.l[3]);
-    __builtin_amdgcn_sched_barrier(0);
-    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    side(3 * it);
-    __builtin_amdgcn_sched_barrier(0);
-    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    side(3 * it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    side(3 * it + 2);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// The DS offset field is 16 bits and the carve is 160 KiB: a region base (lane base + image offset) is made
-// opaque with this so that hipcc keeps it in one register and folds only the in-region constant.
-__device__ __forceinline__ unsigned opaque(unsigned v) { asm volatile("" : "+v"(v)); return v; }
-
-// Per-lane LDS address bases (bytes, including the kernel's LDS base), recomputed every round from the
-// laundered lane id.
-struct LaneAddr {
-  unsigned fb[2][2];   // forward fragments: [k-step parity t][second half]
-  unsigned tb[2][2];   // transposed fragments, register-chain k order: [k-step parity][second half]
-  unsigned sb[2];      // staging fragments, natural k order: [second half]; includes O_STG
-  unsigned ab;         // aux fragments; includes O_AUX
-  unsigned v16, v64;   // per-feature vectors, relative to O_L0: + 16*hf (float4 of 4 features), + 64*hf (4 float4 L0 packs)
-};
-__device__ __forceinline__ LaneAddr lane_addr(int lane, unsigned sbase) {
-  const int l31 = lane & 31, hf = lane >> 5, s16 = lane & 15, mhalf = (lane >> 4) & 1;
-  const int ul = 4 * mhalf + (s16 & 3);
-  LaneAddr A;
-  const int e = hf ^ ((l31 >> 2) & 7);
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int sec = 0; sec < 2; ++sec) {
-      A.fb[t][sec] = sbase + l31 * 64 + ((e ^ (4 * t) ^ (2 * sec)) << 3);
-      A.tb[t][sec] = sbase + (4 * hf + (s16 >> 2)) * 64 + (((ul ^ hf) ^ (4 * t) ^ (2 * sec)) << 3);
-    }
-  const int gs = 4 * hf + (s16 >> 3);
-  A.sb[0] = opaque(sbase + O_STG + (8 * hf + (s16 >> 2)) * 64 + ((ul ^ gs) << 3));
-  A.sb[1] = opaque(sbase + O_STG + (8 * hf + (s16 >> 2)) * 64 + ((ul ^ gs ^ 2) << 3));
-  A.ab = opaque(sbase + O_AUX + (8 * hf + (s16 >> 2)) * 16 + (s16 & 1) * 8);
-  A.v16 = opaque(sbase + O_L0 + 16 * hf);
-  A.v64 = opaque(sbase + O_L0 + 64 * hf);
-  return A;
-}
-
-// Forward-orientation dense layer: acc[m] += W[32m + i][k] * in[k][pt]; W image (R rows = out features) at
-// LDS offset IMG, lo plane PLANE bytes after the hi plane.
-// siren_sigma_chain.inc carries a copy of this fragment loader (one q at a time): a change of the image layout goes there too.
-template <int NM, int Q, int R, int IMG, int PLANE, bool F16 = false>
-__device__ __forceinline__ void layer_fwd(const LaneAddr& A, const Act<Q>& in, f32x16 (&acc)[NM]) {
-  const unsigned b[2][2] = {{opaque(A.fb[0][0] + IMG), opaque(A.fb[0][1] + IMG)}, {opaque(A.fb[1][0] + IMG), opaque(A.fb[1][1] + IMG)}};
-  auto load = [&](int s, int m, Frag& f) {            // k-step s = 2q+t: units 8q+4t+hf and +2 of row 32m + lane
-    const int c = (s >> 1) * R * 64 + m * 2048;
-    put(f.h, 0, lds_b64(b[s & 1][0] + c));
-    put(f.h, 2, lds_b64(b[s & 1][1] + c));
-    put(f.l, 0, lds_b64(b[s & 1][0] + c + PLANE));
-    put(f.l, 2, lds_b64(b[s & 1][1] + c + PLANE));
-  };
-  run_layer<NM, 2 * Q, F16>(load, in, acc);
-}
-
-template <int NM, int Q, int R, int IMG, int PLANE, typename SideF>
-__device__ __forceinline__ void layer_fwd_mm(const LaneAddr& A, const Act<Q>& in, f32x16 (&acc)[NM], SideF side) {
-  const unsigned b[2][2] = {{opaque(A.fb[0][0] + IMG), opaque(A.fb[0][1] + IMG)}, {opaque(A.fb[1][0] + IMG), opaque(A.fb[1][1] + IMG)}};
-  auto load = [&](int s, int m, Frag& f) {
-    const int c = (s >> 1) * R * 64 + m * 2048;
-    put(f.h, 0, lds_b64(b[s & 1][0] + c));
-    put(f.h, 2, lds_b64(b[s & 1][1] + c));
-    put(f.l, 0, lds_b64(b[s & 1][0] + c + PLANE));
-    put(f.l, 2, lds_b64(b[s & 1][1] + c + PLANE));
-  };
-  run_layer_mm<NM, 2 * Q>(load, in, acc, side);
-}
-
-// Transposed dense layer: acc[m] += W[k][32m + i] * in[k][pt]  (dh = W^T d), same image, transpose reads.
-// KS = k-steps (16 rows each).  The B operand's k order is the register chain's: k-step ks, element e of half
-// hf <-> row 16ks + 4hf + (e&3) + 8(e>>2).
-template <int NM, int KS, int R, int IMG, int PLANE, bool F16 = false>
-__device__ __forceinline__ void layer_tr(const LaneAddr& A, const Act<(KS + 1) / 2>& in, f32x16 (&acc)[NM]) {
-  const unsigned b[2][2] = {{opaque(A.tb[0][0] + IMG), opaque(A.tb[0][1] + IMG)}, {opaque(A.tb[1][0] + IMG), opaque(A.tb[1][1] + IMG)}};
-  auto load = [&](int ks, int m, Frag& f) {
-    const int c = m * R * 64 + ks * 1024;
-    put(f.h, 0, lds_tr(b[ks & 1][0] + c));
-    put(f.h, 2, lds_tr(b[ks & 1][1] + c + 512));
-    put(f.l, 0, lds_tr(b[ks & 1][0] + c + PLANE));
-    put(f.l, 2, lds_tr(b[ks & 1][1] + c + 512 + PLANE));
-  };
-  run_layer<NM, KS, F16>(load, in, acc);      // F16: fp16 planes (the 16-bit transpose read does not care which), x3h
-}
-
-template <int NM, int KS, int R, int IMG, int PLANE, typename SideF>
-__device__ __forceinline__ void layer_tr_mm(const LaneAddr& A, const Act<(KS + 1) / 2>& in, f32x16 (&acc)[NM], SideF side) {
-  const unsigned b[2][2] = {{opaque(A.tb[0][0] + IMG), opaque(A.tb[0][1] + IMG)}, {opaque(A.tb[1][0] + IMG), opaque(A.tb[1][1] + IMG)}};
-  auto load = [&](int ks, int m, Frag& f) {
-    const int c = m * R * 64 + ks * 1024;
-    put(f.h, 0, lds_tr(b[ks & 1][0] + c));
-    put(f.h, 2, lds_tr(b[ks & 1][1] + c + 512));
-    put(f.l, 0, lds_tr(b[ks & 1][0] + c + PLANE));
-    put(f.l, 2, lds_tr(b[ks & 1][1] + c + 512 + PLANE));
-  };
-  run_layer_mm<NM, KS>(load, in, acc, side);
-}
 
 // write a wave's packed activations (lane = point `row` of an R-row staging image, units of 4 features);
 // HI / LO: offsets of the two planes inside the staging buffer
@@ -382,21 +68,6 @@ __device__ __forceinline__ void stg_frag(unsigned sb0, unsigned sb1, int col0, i
 __device__ __forceinline__ f32x16 x3f(f32x16 acc, const Frag& a, const Frag& b) {
   return x3(acc, mk8(a.h[0], a.h[1], a.h[2], a.h[3]), mk8(a.l[0], a.l[1], a.l[2], a.l[3]),
             mk8(b.h[0], b.h[1], b.h[2], b.h[3]), mk8(b.l[0], b.l[1], b.l[2], b.l[3]));
-}
-
-// sin / cos for the backward: one multiply to revolutions, v_fract-style reduction, hardware sin/cos.
-// (|arg| is tens of radians: 3e-6 rad absolute, far inside the gradient tolerance; the exact-poly variant is
-// kept for trig_mode 0.)
-template <bool HW>
-__device__ __forceinline__ void bsincos(float x, float* s, float* c) {
-  if (HW) {
-    float rv = x * CIPS_INV_2PI;
-    rv = rv - rintf(rv);
-    *s = __builtin_amdgcn_sinf(rv);
-    *c = __builtin_amdgcn_cosf(rv);
-  } else {
-    sincos_reduced(reduce_2pi(x), s, c);
-  }
 }
 
 // B fragment of the aux image [point][8 columns] (16 B rows per plane, no swizzle): lane j supplies column
@@ -432,130 +103,10 @@ struct BwdX3Args {
   const int* count;  // [B] how many of them are defined (LIVE; EVEN reads its ranges from seg)
   const int* seg;    // EVEN instances only: [B*chunks][4] image (-1: idle), first slot, end slot, rounds per flat workgroup id
 };
-// how a workgroup of siren_bwd_x4_kernel finds its points (siren_bwd_x4.inc)
+// how a workgroup of siren_bwd_x4_kernel finds its points (MODE, below)
 enum { X3_DENSE = 0, X3_LIVE = 1, X3_EVEN = 2 };
 constexpr int GP_G1 = 0, GP_GC = H * H, GP_GF0 = GP_GC + HC * H, GP_GF1 = GP_GF0 + CF * HC, GPART = GP_GF1 + CF * HC;
 constexpr int SRED = 4 * 32 * 8 + 8;   // per wave a 32x8 tile of column sums, then 4 per-wave sums of dsigma (+ pad)
-
-// PRE: everything that only ever feeds a sine argument is stored divided by 2 pi — W1, Wc, the layer-0 packs and the FiLM
-// offsets c1 / cc — so that gain * (W h) + c comes out in REVOLUTIONS and the sine is v_fract + v_sin with no multiply
-// (the FiLM gains g1 / gc and ws stay as they are: the backward multiplies by them).  A backward that runs on these images
-// carries the factor through its linear chain and removes it where it writes its partial sums (siren_bwd_x4.inc).
-//
-// F16 (the forward kernels, round 5): the three weight images are fp16 hi / lo planes of  W * 2^k,  k per matrix such that
-// max |W| * 2^k lies in [2^13, 2^14) — every element down to 2^-17 of the largest keeps both planes normal, nothing
-// overflows (fp16 max 65504), and the products hi*hi, hi*lo, lo*hi are exact in the fp32 accumulator.  The scale leaves
-// through the consumers: G1 and GC hold gain * 2^-k (a power of two: exact), the colour head's 2^-k sits at O_AUX + 128
-// for the kernel's output fma.  Why: sigma = ws . sin(g1 (W1 h1) + c1) is the argument of two DISCONTINUOUS consumers —
-// relu(sigma + noise) in fancy_integration (pigan_utils.py:246-252) and the cdf search of sample_pdf (:164-209) — so its
-// rounding decides how many samples take another branch than the fp32 reference's.  bf16 planes carry W1 h1 to ~5e-6 of
-// its rms, fp16 planes to ~2e-7, the level of an fp32 fmaf chain, at the same three MFMAs per k-step.
-__device__ __forceinline__ float pow2_scale_for(float m, int& k) {
-  const unsigned u = __float_as_uint(m);
-  const int e = (int)((u >> 23) & 0xffu) - 127;
-  k = 13 - e;
-  if (!(m > 0.f) || e == 128) k = 0;           // all-zero, NaN or inf weights: no scaling (the result is theirs anyway)
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  return __uint_as_float((unsigned)(k + 127) << 23);
-}
-// SIG (siren_sigma_x3_kernel): only what the chain needs up to sigma, on the sigma carve — W1, the layer-0 packs, G1, C1, WS,
-// by the same arithmetic; w.wc, w.bc, w.wf, w.gc, w.pc are not read.
-template <bool PRE = false, bool F16 = false, bool SIG = false>
-__device__ __forceinline__ void stage_weights_x3(uchar* sm, const cips_siren_weights& w, int b) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const float pre = PRE ? CIPS_INV_2PI : 1.f;
-  float s1 = 1.f, sc = 1.f, sf = 1.f, i1 = 1.f, ic = 1.f, isf = 1.f;
-  if constexpr (F16) {
-    // per-matrix max |W|: lane-local, wave (DPP) and workgroup (LDS words at the start of the not yet written W1 image)
-    float m1 = 0.f, mc = 0.f, mf = 0.f;
-    for (int i = tid; i < H * 32; i += nt) {
-      const float4 v = *reinterpret_cast<const float4*>(w.w1 + 4 * i);
-      m1 = fmaxf(fmaxf(m1, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    }
-    if constexpr (!SIG) {
-    for (int i = tid; i < HC * 32; i += nt) {
-      const float4 v = *reinterpret_cast<const float4*>(w.wc + 4 * i);
-      mc = fmaxf(fmaxf(mc, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    }
-    for (int i = tid; i < CF * 16; i += nt) {
-      const float4 v = *reinterpret_cast<const float4*>(w.wf + 4 * i);
-      mf = fmaxf(fmaxf(mf, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    }
-    }
-    // NaN weights: fmaxf drops them here; they reach the planes (and every output) through the split below
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      m1 = fmaxf(m1, __shfl_xor(m1, o)); mc = fmaxf(mc, __shfl_xor(mc, o)); mf = fmaxf(mf, __shfl_xor(mf, o));
-    }
-    float* red = reinterpret_cast<float*>(sm + O_W1H);
-    const int wv = tid >> 6, nw = nt >> 6;
-    if ((tid & 63) == 0) { red[3 * wv] = m1; red[3 * wv + 1] = mc; red[3 * wv + 2] = mf; }
-    __syncthreads();
-    m1 = 0.f; mc = 0.f; mf = 0.f;
-    for (int i = 0; i < nw; ++i) { m1 = fmaxf(m1, red[3 * i]); mc = fmaxf(mc, red[3 * i + 1]); mf = fmaxf(mf, red[3 * i + 2]); }
-    __syncthreads();
-    int k1, kc, kf;
-    s1 = pow2_scale_for(m1 * pre, k1); sc = pow2_scale_for(mc * pre, kc); sf = pow2_scale_for(mf, kf);
-    i1 = __uint_as_float((unsigned)(127 - k1) << 23); ic = __uint_as_float((unsigned)(127 - kc) << 23);
-    isf = __uint_as_float((unsigned)(127 - kf) << 23);
-  }
-  for (int i = tid; i < H * 32; i += nt) {                  // W1: 128 rows x 32 units
-    const int row = i >> 5, u = i & 31;
-    float4 v = *reinterpret_cast<const float4*>(w.w1 + row * H + 4 * u);
-    if (PRE) { v.x *= pre; v.y *= pre; v.z *= pre; v.w *= pre; }
-    if (F16) { v.x *= s1; v.y *= s1; v.z *= s1; v.w *= s1; }
-    uint2 ph, pl;
-    split2t<F16>(v.x, v.y, ph.x, pl.x); split2t<F16>(v.z, v.w, ph.y, pl.y);
-    const int o = img_addr<2>(row, u, H);
-    *reinterpret_cast<uint2*>(sm + O_W1H + o) = ph;
-    *reinterpret_cast<uint2*>(sm + O_W1L + o) = pl;
-  }
-  if constexpr (!SIG) {
-  for (int i = tid; i < HC * 32; i += nt) {                 // Wc: 64 rows x 32 units
-    const int row = i >> 5, u = i & 31;
-    float4 v = *reinterpret_cast<const float4*>(w.wc + row * H + 4 * u);
-    if (PRE) { v.x *= pre; v.y *= pre; v.z *= pre; v.w *= pre; }
-    if (F16) { v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc; }
-    uint2 ph, pl;
-    split2t<F16>(v.x, v.y, ph.x, pl.x); split2t<F16>(v.z, v.w, ph.y, pl.y);
-    const int o = img_addr<2>(row, u, HC);
-    *reinterpret_cast<uint2*>(sm + O_WCH + o) = ph;
-    *reinterpret_cast<uint2*>(sm + O_WCL + o) = pl;
-  }
-  for (int i = tid; i < CF * 16; i += nt) {                 // Wf: 32 rows x 16 units
-    const int row = i >> 4, u = i & 15;
-    float4 v = *reinterpret_cast<const float4*>(w.wf + row * HC + 4 * u);
-    if (F16) { v.x *= sf; v.y *= sf; v.z *= sf; v.w *= sf; }
-    uint2 ph, pl;
-    split2t<F16>(v.x, v.y, ph.x, pl.x); split2t<F16>(v.z, v.w, ph.y, pl.y);
-    const int o = img_addr<2>(row, u, CF);
-    *reinterpret_cast<uint2*>(sm + O_WFH + o) = ph;
-    *reinterpret_cast<uint2*>(sm + O_WFL + o) = pl;
-  }
-  }
-  constexpr int VB = SIG ? SG_L0 - O_L0 : 0;                // the per-feature vectors keep their spacing on the sigma carve
-  float* L0 = reinterpret_cast<float*>(sm + VB + O_L0);
-  float* G1 = reinterpret_cast<float*>(sm + VB + O_G1); float* C1 = reinterpret_cast<float*>(sm + VB + O_C1);
-  float* WS = reinterpret_cast<float*>(sm + VB + O_WS);
-  for (int f = tid; f < H; f += nt) {
-    const float g0 = w.g0[b * H + f], gs = g0 * w.box_scale;
-    float4 pk;
-    pk.x = gs * w.w0[f * 3 + 0]; pk.y = gs * w.w0[f * 3 + 1]; pk.z = gs * w.w0[f * 3 + 2];
-    pk.w = fmaf(g0, w.b0[f], w.p0[b * H + f]);
-    if (PRE) { pk.x *= pre; pk.y *= pre; pk.z *= pre; pk.w *= pre; }
-    reinterpret_cast<float4*>(L0)[f] = pk;
-    const float g1 = w.g1[b * H + f];
-    G1[f] = F16 ? g1 * i1 : g1; C1[f] = fmaf(g1, w.b1[f], w.p1[b * H + f]) * pre; WS[f] = w.ws[f];
-  }
-  if constexpr (!SIG) {
-  float* GC = reinterpret_cast<float*>(sm + O_GC); float* CC = reinterpret_cast<float*>(sm + O_CC);
-  for (int f = tid; f < HC; f += nt) {
-    const float gc = w.gc[b * HC + f];
-    GC[f] = F16 ? gc * ic : gc; CC[f] = fmaf(gc, w.bc[f], w.pc[b * HC + f]) * pre;
-  }
-  if (F16 && tid == 0) *reinterpret_cast<float*>(sm + O_AUX + 128) = isf;
-  }
-}
 
 // phase timestamps for tuning (probe builds, -DCIPS_TUNING, with CIPS_X3_PROF set): workgroup (0,0), lane 0 of each wave,
 // first 8 rounds, s_memtime at each phase boundary.  The production build keeps the sched_barrier: it is part of the
@@ -694,375 +245,648 @@ __global__ __launch_bounds__(256) void siren_bwd_reduce_segments_kernel(const fl
   (g ? gpart_out : sred_out)[(long long)b * w4 + col] = acc;
 }
 
-#include "siren_bwd_x4.inc"
-#define X3F_TS(i)
-
-// cosine twins of sin_rev (siren_bwd_x4.inc), for siren_sigma_grad_chain.inc: the argument is in revolutions with HW, in radians
-// without.  sincos_rev's sine is sin_rev<HW>(x) expression for expression — the sigma of the gradient kernel is the sigma
-// kernel's bit for bit only while the two stay in step (tests/test_gpu_density_gradient.py asserts torch.equal).
-template <bool HW> __device__ __forceinline__ float cos_rev(float x) {
-  if (HW) return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(x));
-  float s_, c_; sincos_reduced(reduce_2pi(x), &s_, &c_); return c_;
-}
-template <bool HW> __device__ __forceinline__ void sincos_rev(float x, float* s, float* c) {
-  if (HW) { const float r = __builtin_amdgcn_fractf(x); *s = __builtin_amdgcn_sinf(r); *c = __builtin_amdgcn_cosf(r); }
-  else sincos_reduced(reduce_2pi(x), s, c);
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------
-// Forward on the same split-bf16 register chain (default; CIPS_SIREN_FWD=f32 selects siren.hip's exact fp32 MFMA
-// kernel): layer 0 on the VALU, W1 / Wc / Wf on v_mfma_f32_32x32x16_bf16 in three passes, sigma as a VALU
-// dot with one cross-half add.  No weight-gradient accumulators, so eight waves (two per SIMD) share the LDS images.
-struct FwdX3Args {
-  cips_siren_weights w;
-  const float* points;     // (B, P, 3) or NULL: generated from rg (point index = ray * S + s)
-  float* feat;
-  float* sigma;
-  float* zout;             // optional (B, P): the depth of every generated point
-  RayGen rg;
-  int B, P, chunk;
-};
+// siren_bwd_x4_kernel — the fused FiLM-SIREN backward in its round-4 schedule (the math, LDS images, staging windows,
+// accumulator ownership and partial-sum layout are the ones the head of this file describes; the reference is
+// exp/cips3d/models/generator.py:260-317 and exp/comm/models/film_layer.py:78-107).  What the schedule adds:
+//  * the five dense layers of the data chain run m-major with the PREVIOUS output tile's epilogue (FiLM, sine / cosine,
+//    hi / lo split) woven between the MFMAs of the current tile, five or six VALU instructions per MFMA
+//    (run_layer_mm; scripts/probe/issue_overlap_probe.hip is the measurement behind it);
+//  * with hardware trigonometry (HW) the sine arguments are in revolutions (stage_weights_x3<true>): v_fract + v_sin,
+//    no multiply, no rint / subtract.  The backward chain carries the factor: d h2, d a2 and d p2 are 1/(2 pi) of their
+//    values, d h1 and d a1 1/(2 pi)^2; the weight-gradient and column-sum accumulators they feed are multiplied back when the
+//    workgroup writes its partials (the partials keep their documented meaning).
+// Values computed in a slot are pinned there: sched_barrier(0) only binds the machine scheduler, and hipcc's IR-level sinking
+// otherwise moves the whole (side-effect-free) epilogue below the layer's MFMAs, next to its first use.
+__device__ __forceinline__ void pinf(float& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void pinf(float& a, float& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void pinf(float& a, float& b, float& c, float& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+__device__ __forceinline__ void pinu(unsigned& a, unsigned& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void pinu(unsigned& a, unsigned& b, unsigned& c, unsigned& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
 
-template <bool HW, bool F16>
-__global__ __launch_bounds__(512) void siren_fwd_x3_kernel(FwdX3Args a) {
+// MODE X3_LIVE: the workgroup walks a list of point indices instead of a contiguous range (cips_siren_bwd_x3_live in
+// cips3d_hip.h).  Image b's list is a.idx[b * P + 0 .. a.count[b]); workgroup (c, b) takes the slots
+// [c * len, min((c + 1) * len, count[b])), len = ceil(count[b] / chunks) rounded up to whole 128-point rounds.  cstart / cend /
+// pbase then count list SLOTS, and the three places that form a point index look it up; everything else in a round is the dense
+// kernel's.  The trip count comes from device memory, so a replayed graph follows the data.  With every point listed in order
+// the partition is the dense one whenever the dense chunk is a multiple of 128 that divides P, and the partials are
+// bit-identical.
+// MODE X3_EVEN: the same list walk, but image, first slot and end slot of the workgroup come from row (flat workgroup id) of the
+// table a.seg that cips_siren_bwd_x3_live_plan wrote (x3_even_plan above: every workgroup of the launch gets about the same
+// number of rounds, whatever its image's live share), and the partials go to row = flat id.  An idle id (image -1) leaves
+// before anything is staged; the table row is the same for every thread, so the workgroup leaves together.
+template <bool HW, int MODE>
+__global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
   extern __shared__ __attribute__((aligned(1024))) uchar smem[];
-  const int b = blockIdx.y;
-  stage_weights_x3<HW, F16>(smem, a.w, b);
-  if (threadIdx.x < CF) reinterpret_cast<float*>(smem + O_AUX)[threadIdx.x] = a.w.bf[threadIdx.x];   // bf[32] (aux image unused here)
+  constexpr bool LIVE = MODE != X3_DENSE;
+  int b_ = blockIdx.y, prow_ = 0, cs_ = 0, ce_ = 0;
+  if constexpr (MODE == X3_EVEN) {
+    prow_ = blockIdx.y * gridDim.x + blockIdx.x;
+    const int* const sg = a.seg + 4 * (long long)prow_;
+    b_ = __builtin_amdgcn_readfirstlane(sg[0]);
+    if (b_ < 0) return;
+    cs_ = __builtin_amdgcn_readfirstlane(sg[1]);
+    ce_ = __builtin_amdgcn_readfirstlane(sg[2]);
+  }
+  const int b = b_;
+  stage_weights_x3<HW>(smem, a.w, b);
   __syncthreads();
+  constexpr float TWO_PI = 6.283185307179586f;
+
   const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int cstart = blockIdx.x * a.chunk;
+  int cend = min(cstart + a.chunk, a.P);
+  if constexpr (MODE == X3_EVEN) {
+    cstart = cs_; cend = ce_;
+  } else if (LIVE) {
+    const int cnt = a.count[b];
+    const int len = ((cnt + a.chunks - 1) / a.chunks + 127) & ~127;
+    cstart = blockIdx.x * len;
+    cend = min(cstart + len, cnt);          // >= 1 unless the image has no live point at all
+  }
+  const int* const lidx = LIVE ? a.idx + (long long)b * a.P : nullptr;
   const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
-  const float bs = a.w.bs[0];
-  const float isf = F16 ? reinterpret_cast<const float*>(smem + O_AUX)[32] : 1.f;      // 2^-k of the colour head's weight image
-  const int cstart = blockIdx.x * a.chunk;
-  const int cend = min(cstart + a.chunk, a.P);
-  for (int pbase = cstart + wave * 32; pbase < cend; pbase += 8 * 32) {
+
+  // weight-gradient accumulators, owned per wave for the whole chunk; aS: column sums (see SRED)
+  f32x16 aG1[4], aGc[2], aGf[1], aS[1];
+  zero_acc(aG1); zero_acc(aGc); zero_acc(aGf); zero_acc(aS);
+  float r_dsg = 0.f;
+
+  // inputs of the first round
+  float px, py, pz, dsg;
+  {
+    const int slot = cstart + wave * 32 + (lane0 & 31);
+    const bool valid = slot < cend;
+    int p = valid ? slot : cend - 1;
+    if (LIVE) p = cend > 0 ? lidx[p] : 0;   // an image without live points: no list entry is defined, any point will do
+    const long long gp = (long long)b * a.P + p;
+    if (a.points) { px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2]; }
+    else gen_point(a.rg, b, p, px, py, pz);
+    dsg = valid ? a.dsigma[gp] : 0.f;
+  }
+
+  // The first NPRE of layer 0's 16 feature groups of the NEXT round's points are produced inside the dW1 phase of the current
+  // round, by the three waves that would otherwise wait at the barrier while the fourth stages its operands (a third each; the
+  // first round's come from this prologue); the rest is computed at the start of the round.  NPRE trades idle-slot use against
+  // the registers that carry the packed sines across the phase and the round boundary.  Measured (forward + backward at C2,
+  // one box each, profiles/r4_siren_bwd_ab_microbench.log): NPRE 16 -> 161 spilled VGPRs, 3.15 ms; 8 -> 94, 3.03 ms; 4 -> 61,
+  // 3.02 ms; 0 -> 39, 2.90 ms (2.97 with the dW1 loop rolled): the spill traffic lands in the layer-1 recompute and costs more
+  // than the idle slots give, so the shipped value is 0 — the mechanism stays for a chain with a smaller register footprint.
+  constexpr int NPRE = 0;
+  Act<4> h1n;
+  auto l0_groups = [&](auto G0c, auto G1c, float x, float y, float z) __attribute__((always_inline)) {
+    constexpr int G0 = decltype(G0c)::value, G1 = decltype(G1c)::value;
+    if (G0 >= G1) return;
+    int ln = lane0;
+    asm volatile("" : "+v"(ln));
+    const unsigned sbase_ = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
+    const unsigned v64 = opaque(sbase_ + O_L0 + 64 * (ln >> 5));
+    float4 pn[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pn[e] = lds_ld4(v64 + 128 * G0 + 16 * e);
+#pragma unroll
+    for (int grp = G0; grp < G1; ++grp) {          // grp = 4q + g: features 32q + 8g + 4hf + {0..3}
+      float4 pk[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pk[e] = pn[e];
+      if (grp + 1 < G1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pn[e] = lds_ld4(v64 + 128 * (grp + 1) + 16 * e);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      float s4[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s4[e] = sin_rev<HW>(fmaf(pk[e].x, x, fmaf(pk[e].y, y, fmaf(pk[e].z, z, pk[e].w))));
+      const int q = grp >> 2, g = grp & 3;
+      split2(s4[0], s4[1], h1n.hi[q][2 * g], h1n.lo[q][2 * g]);
+      split2(s4[2], s4[3], h1n.hi[q][2 * g + 1], h1n.lo[q][2 * g + 1]);
+      pinu(h1n.hi[q][2 * g], h1n.lo[q][2 * g], h1n.hi[q][2 * g + 1], h1n.lo[q][2 * g + 1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  using IC0 = std::integral_constant<int, 0>; using ICA = std::integral_constant<int, (NPRE + 2) / 3>;
+  using ICB = std::integral_constant<int, (2 * NPRE + 2) / 3>; using ICN = std::integral_constant<int, NPRE>;
+  using IC16 = std::integral_constant<int, 16>;
+  l0_groups(IC0{}, ICN{}, px, py, pz);
+
+  int rnd = -1;
+  for (int pbase = cstart; pbase < cend; pbase += 128) {
+    ++rnd;
+    X3_TS(0)
+    // every LDS address below is loop-invariant; laundering the lane id keeps hipcc from hoisting a few hundred
+    // of them out of the loop into live registers
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const int l31 = lane & 31, hf = lane >> 5;
     const LaneAddr LA = lane_addr(lane, sbase);
-    const int p = pbase + l31;
-    const bool valid = p < cend;
-    const long long gp = (long long)b * a.P + (valid ? p : cend - 1);
-    float px, py, pz, zpt = 0.f;
-    if (a.points) { px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2]; }
-    else gen_point(a.rg, b, valid ? p : cend - 1, px, py, pz, zpt);
+    const int prow = wave * 32 + l31;
+    const unsigned c7 = l31 & 7;
+    const unsigned m_d1 = c7 < 4 ? ~0u : 0u, m_d2 = c7 == 4 ? ~0u : 0u, m_h2 = c7 == 5 ? ~0u : 0u;
+    const unsigned m_dc = c7 == 6 ? ~0u : 0u, m_df = c7 == 7 ? ~0u : 0u;
 
-#include "siren_fwd_chain.inc"
-    if (valid) {
-      float* fo = a.feat + gp * CF + 4 * hf;
-      const float* bfv = reinterpret_cast<const float*>(smem + O_AUX);
+    // ---- upstream gradient of the 32 colour features: requested now, consumed after two layers ----
+    float4 df4[4];
+    {
+      const int slot = pbase + prow;
+      const bool valid = slot < cend;
+      int p = valid ? slot : cend - 1;
+      if (LIVE) p = lidx[p];
+      const float* dp = a.dfeat + ((long long)b * a.P + p) * CF + 4 * hf;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 v;
-        v.x = fmaf(accf[0][4 * g + 0], isf, bfv[8 * g + 4 * hf + 0]);
-        v.y = fmaf(accf[0][4 * g + 1], isf, bfv[8 * g + 4 * hf + 1]);
-        v.z = fmaf(accf[0][4 * g + 2], isf, bfv[8 * g + 4 * hf + 2]);
-        v.w = fmaf(accf[0][4 * g + 3], isf, bfv[8 * g + 4 * hf + 3]);
-        *reinterpret_cast<float4*>(fo + 8 * g) = v;
-      }
-      if (hf == 0) {
-        a.sigma[gp] = sig;
-        if (a.zout) a.zout[gp] = zpt;
-      }
+      for (int g = 0; g < 4; ++g) df4[g] = valid ? ld4(dp + 8 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Sigma-only forward (density volumes: cips_siren_sigma_x3, cips_siren_sigma_x3_grid): siren_fwd_x3_kernel's layout — lane =
-// point, a wave owns 32 points, the two lane halves split the features — running siren_sigma_chain.inc, the forward chain
-// up to sigma: 16 896 MAC per point instead of 27 136, 256 sines instead of 320, no operand split of h2, and one dword per
-// point to HBM instead of 132 B.  LDS: the sigma carve (67.5 KiB: W1 hi / lo, layer-0 packs, G1, C1, WS).
-// GRID: the point of index p = (i * ny + j) * nz + k is (gx[i], gy[j], gz[k]) — three host-built coordinate arrays READ by
-// the kernel, which does index arithmetic only: the lattice is whatever the host built, bit for bit.
-// Occupancy: two 512-thread workgroups fit a CU's LDS at 67.5 KiB each, and co-reside when the kernel stays at or below 128
-// VGPRs — which the chain does because it builds h1 one 32-feature tile at a time (siren_sigma_chain.inc).
-// __launch_bounds__' second argument is the minimum waves per SIMD asked of the register allocator: 4 = two workgroups of
-// 512 per CU.  profiles/density_grid.txt has this form timed against one workgroup per CU (bound 2, which also lets the
-// allocator use up to 256 VGPRs, and the launch's LDS request padded to 96 KiB): two per CU is 6.5 % faster.
-struct SigmaX3Args {
-  cips_siren_weights w;
-  const float* points;               // (B, P, 3); unused with GRID
-  const float *gx, *gy, *gz;         // GRID: the lattice's coordinates (nx), (ny), (nz)
-  float* sigma;                      // (B, P)
-  int ny, nz;
-  int B, P, chunk;
-};
-
-template <bool HW, bool F16, bool GRID>
-__global__ __launch_bounds__(512, 4) void siren_sigma_x3_kernel(SigmaX3Args a) {
-  extern __shared__ __attribute__((aligned(1024))) uchar smem[];
-  const int b = blockIdx.y;
-  stage_weights_x3<HW, F16, true>(smem, a.w, b);
-  __syncthreads();
-  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
-  const float bs = a.w.bs[0];
-  const int cstart = blockIdx.x * a.chunk;
-  const int cend = min(cstart + a.chunk, a.P);
-  for (int pbase = cstart + wave * 32; pbase < cend; pbase += 8 * 32) {
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    const int l31 = lane & 31, hf = lane >> 5;
-    LaneAddr LA = lane_addr(lane, sbase);
-    LA.v16 = opaque(sbase + SG_L0 + 16 * hf);
-    LA.v64 = opaque(sbase + SG_L0 + 64 * hf);
-    const int p = pbase + l31;
-    const bool valid = p < cend;
-    const int pc = valid ? p : cend - 1;           // ragged tail: the last valid point again, nothing stored
-    const long long gp = (long long)b * a.P + pc;
-    float px, py, pz;
-    if constexpr (GRID) {
-      const unsigned r = (unsigned)pc / (unsigned)a.nz, k = (unsigned)pc - r * (unsigned)a.nz;
-      const unsigned i = r / (unsigned)a.ny, j = r - i * (unsigned)a.ny;
-      px = a.gx[i]; py = a.gy[j]; pz = a.gz[k];
-    } else {
-      px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2];
+    // ---- aux row of this point: [1, x, y, z, 1, dsigma, 1, 1] ----
+    if (hf == 0) {
+      uint4 ah, al;
+      split2(1.f, px, ah.x, al.x); split2(py, pz, ah.y, al.y); split2(1.f, dsg, ah.z, al.z); split2(1.f, 1.f, ah.w, al.w);
+      const u32x4 vh = {ah.x, ah.y, ah.z, ah.w}, vl = {al.x, al.y, al.z, al.w};
+      *LDS_PTR(u32x4, sbase + O_AUX + prow * 16) = vh;
+      *LDS_PTR(u32x4, sbase + O_AUX + 2048 + prow * 16) = vl;
+      r_dsg += dsg;
     }
 
-#include "siren_sigma_chain.inc"
-    if (valid && hf == 0) a.sigma[gp] = sig;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
+    // ws * dsigma enters d h2, which this kernel carries as d h2 / (2 pi) when the images are pre-scaled
+    const float dsg_s = HW ? dsg * CIPS_INV_2PI : dsg;
 
-// ------------------------------------------------------------------------------------------------------------------
-// Sigma and its gradient w.r.t. the point (cips_siren_sigma_grad_x3, cips_siren_sigma_grad_x3_grid): the sigma kernel's layout,
-// LDS carve, staging, points sources and chunking, running siren_sigma_grad_chain.inc — the sigma chain, then
-//   dp1 = g1 * ws * cos(a1),  dh1 = W1^T dp1  (the W1 image read transposed: no second image),
-//   grad = box_scale * W0^T (g0 * cos(a0) * dh1) = sum_f pack[f].xyz * cos(a0[f]) * dh1[f]
-// — 16 896 + 16 384 MAC and 256 + 256 trigonometric evaluations per point.  sigma is the sigma kernel's bit for bit.
-// Two scale factors leave in fp32 at the output:
-//  * HW: the staging stores W1 and the layer-0 packs divided by 2 pi (the sines take revolutions), so both transposed factors
-//    carry 1 / (2 pi): the gradient is multiplied by (2 pi)^2;
-//  * F16: G1 holds g1 * 2^-k next to the W1 * 2^k image, so g1 * ws * cos can sit far below fp16's normal range.  Every wave
-//    takes  m = max_f |G1[f] * ws[f]|  of its image from LDS and multiplies dp1 by pow2_scale_for(m) — the staging rule: the
-//    largest |dp1| a point can have lies in [2^13, 2^14) — and the output by its inverse.  A power of two: exact to undo.
-// Registers: the packed dp1 (64) is live next to the 64 accumulators of dh1 plus the fragment ring, more than the 128 registers
-// two co-resident 512-thread workgroups would leave a wave, so the kernel asks for one workgroup per CU (bound 2: up to 256).
-struct SigmaGradX3Args {
-  cips_siren_weights w;
-  const float* points;               // (B, P, 3); unused with GRID
-  const float *gx, *gy, *gz;         // GRID: the lattice's coordinates (nx), (ny), (nz)
-  float* sigma;                      // (B, P) or NULL
-  float* grad;                       // (B, P, 3)
-  int ny, nz;
-  int B, P, chunk;
-};
-
-template <bool HW, bool F16, bool GRID>
-__global__ __launch_bounds__(512, 2) void siren_sigma_grad_x3_kernel(SigmaGradX3Args a) {
-  extern __shared__ __attribute__((aligned(1024))) uchar smem[];
-  const int b = blockIdx.y;
-  stage_weights_x3<HW, F16, true>(smem, a.w, b);
-  __syncthreads();
-  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
-  const float bs = a.w.bs[0];
-  float dscale = 1.f, oscale = HW ? 39.47841760435743f : 1.f;      // (2 pi)^2
-  if constexpr (F16) {
-    const float* G1 = reinterpret_cast<const float*>(smem + SG_L0 + (O_G1 - O_L0));
-    const float* WS = reinterpret_cast<const float*>(smem + SG_L0 + (O_WS - O_L0));
-    float m = fmaxf(fabsf(G1[lane0] * WS[lane0]), fabsf(G1[lane0 + 64] * WS[lane0 + 64]));
+    // ---- layer 0 (VALU); only the packed sines are kept, and only until layer 1 has consumed them ----
+    f32x16 acc[4];
+    zero_acc(acc);
+    float cs2[4][16];
+    Act<4> h2p;
+    // state of the woven epilogues (one group of 4 features at a time)
+    float rv[4], sn[4];
+    float4 gq, cq;
+    // FiLM + sine / cosine + split of features (q, g) of layer 1's output, in six slots of ~30 issue cycles
+    auto film2_slot = [&](int q, int g, int j) __attribute__((always_inline)) {
+      const float gg[4] = {gq.x, gq.y, gq.z, gq.w}, cc[4] = {cq.x, cq.y, cq.z, cq.w};
+      if (HW) {
+        if (j == 0) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    int k;
-    dscale = pow2_scale_for(m, k);
-    oscale *= __uint_as_float((unsigned)(127 - k) << 23);
-  }
-  const int cstart = blockIdx.x * a.chunk;
-  const int cend = min(cstart + a.chunk, a.P);
-  for (int pbase = cstart + wave * 32; pbase < cend; pbase += 8 * 32) {
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    const int l31 = lane & 31, hf = lane >> 5;
-    LaneAddr LA = lane_addr(lane, sbase);
-    LA.v16 = opaque(sbase + SG_L0 + 16 * hf);
-    LA.v64 = opaque(sbase + SG_L0 + 64 * hf);
-    const int p = pbase + l31;
-    const bool valid = p < cend;
-    const int pc = valid ? p : cend - 1;           // ragged tail: the last valid point again, nothing stored
-    const long long gp = (long long)b * a.P + pc;
-    float px, py, pz;
-    if constexpr (GRID) {
-      const unsigned r = (unsigned)pc / (unsigned)a.nz, k = (unsigned)pc - r * (unsigned)a.nz;
-      const unsigned i = r / (unsigned)a.ny, j = r - i * (unsigned)a.ny;
-      px = a.gx[i]; py = a.gy[j]; pz = a.gz[k];
-    } else {
-      px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2];
-    }
-
-#include "siren_sigma_grad_chain.inc"
-    if (valid && hf == 0) {
-      if (a.sigma) a.sigma[gp] = sig;
-      float* go = a.grad + gp * 3;
-      go[0] = gx * oscale; go[1] = gy * oscale; go[2] = gz * oscale;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Fused ray-march, non-hierarchical sampling (the headline configuration: num_steps samples per ray, no resampling):
-// ray set-up + FiLM-SIREN + alpha-composite (exp/comm/comm_utils.py:365-438, 584-679; exp/cips3d/models/
-// generator.py:260-317; exp/pigan/pigan_utils.py:212-273) in ONE kernel that walks the samples along the ray.
-// A wave owns 32 rays (lane & 31 = ray; the two lane halves hold 16 of the 32 feature channels each) and steps
-// s = 0..S-1: generate the sample point, run the register-chain MLP of siren_point_x3 (weights resident in LDS), and
-// fold the sample front-to-back into the ray's running transmittance / feature / depth accumulators — z is ascending by
-// construction (|jitter offset| <= half a bin), so the merge of the hierarchical path is the identity here and the
-// composite needs no cross-lane traffic at all.  HBM per ray: 4 B per sample of jitter (+ 4 B of noise when
-// nerf_noise > 0) in, 128 B feature + 4 B depth out = 4 S + 132 B; the (B, n, S, 3) points and the
-// (B, P, 32) per-sample features never exist in HBM unless the caller asks for them (feat / sigma / z outputs: the
-// training forward keeps them for the backward).  Transmittance runs in double like ATen's CPU cumprod.
-struct MarchArgs {
-  cips_siren_weights w;
-  RayGen rg;
-  const float* noise;        // (B, n, S) standard normals or NULL
-  float noise_std;
-  int clamp_mode, flags;     // flags: bit0 last_back, bit1 white_back
-  float *fea, *depth;        // (B, n, 32), (B, n)
-  float *weights;            // (B, n, S) or NULL
-  float *feat, *sigma, *zout;   // per-sample outputs (B, P, 32), (B, P), (B, P) or NULL
-  int B, rays_per_wg;
-  const unsigned char* clamp_pin;   // optional branch masks of the relu clamp (cips_march_fwd_x3's clamp_in / clamp_out):
-  unsigned char* clamp_rec;         // branch per (ray, sample) supplied / recorded; both NULL in production
-  int desync;                       // probe builds: shader cycles the second wave of every SIMD starts late (0 = together)
-  int one_wave;                     // probe builds: waves 4-7 leave at once (one wave per SIMD; half the rays are not marched)
-  unsigned long long* prof;         // probe builds: phase timestamps of workgroup (0,0), samples 8..11
-};
-
-
-#undef X3F_TS
-#ifdef CIPS_TUNING
-#define X3F_TS(i)                                                                                  \
-  __builtin_amdgcn_sched_barrier(0);                                                               \
-  if (a.prof && blockIdx.x == 0 && blockIdx.y == 0 && lane0 == 0 && (s >> 2) == 2)                 \
-    a.prof[(((s & 3) * 8 + wave) * 8) + (i)] = __builtin_amdgcn_s_memtime();                       \
-  __builtin_amdgcn_sched_barrier(0);
-#else
-#define X3F_TS(i)
-#endif
-template <bool HW, bool DBG, bool F16>
-__global__ __launch_bounds__(512) void siren_march_x3_kernel(MarchArgs a) {
-  extern __shared__ __attribute__((aligned(1024))) uchar smem[];
-  const int b = blockIdx.y;
-  stage_weights_x3<HW, F16>(smem, a.w, b);
-  if (threadIdx.x < CF) reinterpret_cast<float*>(smem + O_AUX)[threadIdx.x] = a.w.bf[threadIdx.x];
-  __syncthreads();
-  const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned sbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) uchar*)smem);
-  const float bs = a.w.bs[0];
-  const RayGen& g = a.rg;
-  const int S = g.S, n = g.n;
-  const int cstart = blockIdx.x * a.rays_per_wg;
-  const int cend = min(cstart + a.rays_per_wg, n);
-  const float* M = g.c2w + (long long)b * 16;
-  const float* bfv = reinterpret_cast<const float*>(smem + O_AUX);
-  const float isf = F16 ? bfv[32] : 1.f;        // 2^-k of the colour head's weight image
-  if (CIPS_TUNE(a.one_wave) && wave >= 4) return;
-  if (CIPS_TUNE(a.desync) > 0 && wave >= 4) {
-    const long long t0 = __builtin_readcyclecounter();
-    while (__builtin_readcyclecounter() - t0 < (long long)a.desync) __builtin_amdgcn_s_sleep(8);
-  }
-  for (int rbase = cstart + wave * 32; rbase < cend; rbase += 8 * 32) {
-    const int l31s = lane0 & 31, hfs = lane0 >> 5;
-    const int ray_raw = rbase + l31s;
-    const bool valid = ray_raw < cend;
-    const int ray = valid ? ray_raw : cend - 1;
-    const long long rs = ((long long)b * n + ray) * S;        // first sample of this ray in the (B, n, S) tensors
-    const RayDir d = ray_dir(g, ray);
-    const bool has_jit = g.jitter != nullptr;
-    float bias[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bias[r] = bfv[(r & 3) + 8 * (r >> 2) + 4 * hfs];
-    float F[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) F[r] = 0.f;
-    float flast[16];
-    double T = 1.0;
-    float depth = 0.f, wsum = 0.f, wlast = 0.f, zlast = 0.f;
-    // sample s: world point + depth; the depth of sample s+1 gives delta_s
-    float wx, wy, wz, zs;
-    ray_point(g, M, d, g.zg[0], has_jit ? g.jitter[rs] : 0.f, has_jit, wx, wy, wz, zs);
-    float u_next = (has_jit && S > 1) ? g.jitter[rs + 1] : 0.f;
-#pragma unroll 1
-    for (int s = 0; s < S; ++s) {
-      int lane = lane0;
-      asm volatile("" : "+v"(lane));
-      const int hf = lane >> 5;
-      const LaneAddr LA = lane_addr(lane, sbase);
-      // next sample's point now (its jitter was requested one step ago), the one after that requested now
-      float nx = 0.f, ny = 0.f, nz = 0.f, zn = 0.f;
-      if (s + 1 < S) ray_point(g, M, d, g.zg[s + 1], u_next, has_jit, nx, ny, nz, zn);
-      if (has_jit && s + 2 < S) u_next = g.jitter[rs + s + 2];
-      const float nse = a.noise ? a.noise[rs + s] : 0.f;
-
-      const float px = wx, py = wy, pz = wz;
-#include "siren_fwd_chain.inc"
-      float f[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) f[r] = fmaf(accf[0][r], isf, bias[r]);
-      // ---- composite (pigan_utils.py:239-258): alpha = 1 - exp(-delta * clamp(sigma + noise)), w = alpha * T ----
-      const float delta = (s + 1 < S) ? (zn - zs) : 1e10f;
-      const float sg = a.noise ? sig + nse * a.noise_std : sig;
-      float dens = (a.clamp_mode == 1) ? ((sg > 20.f) ? sg : log1pf(expf(sg))) : fmaxf(sg, 0.f);
-      if (DBG && a.clamp_mode == 0) {      // the debug instantiation only: the production kernel's code is untouched
-        bool pass = sg > 0.f;
-        if (a.clamp_pin) pass = a.clamp_pin[rs + s] != 0;
-        if (a.clamp_rec && valid && hf == 0) a.clamp_rec[rs + s] = pass ? 1 : 0;
-        dens = pass ? sg : 0.f;
-      }
-      const float alpha = 1.f - expf(-delta * dens);
-      const float w = alpha * (float)T;
-      T *= (double)(1.f - alpha + 1e-10f);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) F[r] = fmaf(w, f[r], F[r]);
-      depth = fmaf(w, zs, depth);
-      wsum += w;
-      if (s == S - 1) {
-        wlast = w; zlast = zs;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) flast[r] = f[r];
-      }
-      if (valid) {
-        if (a.feat) {
-          float* fo = a.feat + (rs + s) * CF + 4 * hf;
-#pragma unroll
-          for (int gq = 0; gq < 4; ++gq)
-            *reinterpret_cast<float4*>(fo + 8 * gq) = make_float4(f[4 * gq], f[4 * gq + 1], f[4 * gq + 2], f[4 * gq + 3]);
+          for (int e = 0; e < 4; ++e) rv[e] = fmaf(gg[e], acc[q][4 * g + e], cc[e]);
+          rv[0] = __builtin_amdgcn_fractf(rv[0]); rv[1] = __builtin_amdgcn_fractf(rv[1]);
+          pinf(rv[0], rv[1], rv[2], rv[3]);
+        } else if (j == 1) {
+          rv[2] = __builtin_amdgcn_fractf(rv[2]); rv[3] = __builtin_amdgcn_fractf(rv[3]);
+          sn[0] = __builtin_amdgcn_sinf(rv[0]); sn[1] = __builtin_amdgcn_sinf(rv[1]);
+          pinf(rv[2], rv[3], sn[0], sn[1]);
+        } else if (j == 2) {
+          cs2[q][4 * g + 0] = __builtin_amdgcn_cosf(rv[0]); cs2[q][4 * g + 1] = __builtin_amdgcn_cosf(rv[1]);
+          sn[2] = __builtin_amdgcn_sinf(rv[2]);
+          pinf(cs2[q][4 * g + 0], cs2[q][4 * g + 1]); pinf(sn[2]);
+        } else if (j == 3) {
+          sn[3] = __builtin_amdgcn_sinf(rv[3]);
+          cs2[q][4 * g + 2] = __builtin_amdgcn_cosf(rv[2]); cs2[q][4 * g + 3] = __builtin_amdgcn_cosf(rv[3]);
+          pinf(cs2[q][4 * g + 2], cs2[q][4 * g + 3]); pinf(sn[3]);
         }
-        if (hf == 0) {
-          if (a.sigma) a.sigma[rs + s] = sig;
-          if (a.zout) a.zout[rs + s] = zs;
-          if (a.weights && !(s == S - 1 && (a.flags & 1))) a.weights[rs + s] = w;
+      } else if (j == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sincos_rev<false>(fmaf(gg[e], acc[q][4 * g + e], cc[e]), &sn[e], &cs2[q][4 * g + e]);
+        pinf(sn[0], sn[1], sn[2], sn[3]);
+      }
+      if (j == 4) { split2(sn[0], sn[1], h2p.hi[q][2 * g], h2p.lo[q][2 * g]); pinu(h2p.hi[q][2 * g], h2p.lo[q][2 * g]); }
+      if (j == 5) {
+        split2(sn[2], sn[3], h2p.hi[q][2 * g + 1], h2p.lo[q][2 * g + 1]);
+        pinu(h2p.hi[q][2 * g + 1], h2p.lo[q][2 * g + 1]);
+        if (4 * q + g + 1 < 16) {               // next group's gains / offsets
+          gq = lds_ld4(LA.v16 + (O_G1 - O_L0) + 32 * (4 * q + g + 1)); cq = lds_ld4(LA.v16 + (O_C1 - O_L0) + 32 * (4 * q + g + 1));
         }
       }
-      wx = nx; wy = ny; wz = nz; zs = zn;
-      X3F_TS(7)
-      __builtin_amdgcn_sched_barrier(0);
+    };
+    {
+      l0_groups(ICN{}, IC16{}, px, py, pz);      // the groups the previous round's idle slots did not cover
+      gq = lds_ld4(LA.v16 + (O_G1 - O_L0)); cq = lds_ld4(LA.v16 + (O_C1 - O_L0));
+      // ---- recompute layer 1, m-major: the slots of tile m carry the epilogue of tile m - 1 ----
+      layer_fwd_mm<4, 4, H, O_W1H, O_W1L - O_W1H>(LA, h1n, acc, [&](int slot) __attribute__((always_inline)) {
+        const int m = slot / 24, j = slot % 24;
+        if (m >= 1) film2_slot(m - 1, j / 6, j % 6);
+      });
     }
-    if (a.flags & 1) {           // last_back: weights[:, :, -1] += 1 - weights_sum (pigan_utils.py:261-263)
-      const float extra = 1.f - wsum;
+    X3_TS(1)
+    // tile 3 of layer 1: its first group here, the other three under the colour layer's first six k-steps (which read h2 tiles
+    // 0..2; k-steps 6 and 7 read tile 3 and come after slot 17)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) F[r] = fmaf(extra, flast[r], F[r]);
-      depth = fmaf(extra, zlast, depth);
-      if (a.weights && valid && hfs == 0) a.weights[rs + S - 1] = wlast + extra;
-    }
-    if (a.flags & 2) {           // white_back: rgb + 1 - weights_sum (:266-268)
-      const float extra = 1.f - wsum;
+    for (int j = 0; j < 6; ++j) { film2_slot(3, 0, j); __builtin_amdgcn_sched_barrier(0); }
+
+    X3_TS(2)
+    // ---- recompute colour sine layer, m-major ----
+    f32x16 accc[2];
+    zero_acc(accc);
+    float csc[2][16];
+    Act<2> hcp;
+    float4 gcq, ccq;
+    auto filmc_slot = [&](int q, int g, int j) __attribute__((always_inline)) {
+      const float gg[4] = {gcq.x, gcq.y, gcq.z, gcq.w}, cc[4] = {ccq.x, ccq.y, ccq.z, ccq.w};
+      if (HW) {
+        if (j == 0) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) F[r] += extra;
-    }
-    if (valid) {
-      float* o = a.fea + ((long long)b * n + ray) * CF + 4 * hfs;
+          for (int e = 0; e < 4; ++e) rv[e] = fmaf(gg[e], accc[q][4 * g + e], cc[e]);
+          rv[0] = __builtin_amdgcn_fractf(rv[0]); rv[1] = __builtin_amdgcn_fractf(rv[1]);
+          pinf(rv[0], rv[1], rv[2], rv[3]);
+        } else if (j == 1) {
+          rv[2] = __builtin_amdgcn_fractf(rv[2]); rv[3] = __builtin_amdgcn_fractf(rv[3]);
+          sn[0] = __builtin_amdgcn_sinf(rv[0]); sn[1] = __builtin_amdgcn_sinf(rv[1]);
+          pinf(rv[2], rv[3], sn[0], sn[1]);
+        } else if (j == 2) {
+          csc[q][4 * g + 0] = __builtin_amdgcn_cosf(rv[0]); csc[q][4 * g + 1] = __builtin_amdgcn_cosf(rv[1]);
+          sn[2] = __builtin_amdgcn_sinf(rv[2]);
+          pinf(csc[q][4 * g + 0], csc[q][4 * g + 1]); pinf(sn[2]);
+        } else if (j == 3) {
+          sn[3] = __builtin_amdgcn_sinf(rv[3]);
+          csc[q][4 * g + 2] = __builtin_amdgcn_cosf(rv[2]); csc[q][4 * g + 3] = __builtin_amdgcn_cosf(rv[3]);
+          pinf(csc[q][4 * g + 2], csc[q][4 * g + 3]); pinf(sn[3]);
+        }
+      } else if (j == 0) {
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq)
-        *reinterpret_cast<float4*>(o + 8 * gq) = make_float4(F[4 * gq], F[4 * gq + 1], F[4 * gq + 2], F[4 * gq + 3]);
-      if (hfs == 0 && a.depth) a.depth[(long long)b * n + ray] = depth;
+        for (int e = 0; e < 4; ++e) sincos_rev<false>(fmaf(gg[e], accc[q][4 * g + e], cc[e]), &sn[e], &csc[q][4 * g + e]);
+        pinf(sn[0], sn[1], sn[2], sn[3]);
+      }
+      if (j == 4) { split2(sn[0], sn[1], hcp.hi[q][2 * g], hcp.lo[q][2 * g]); pinu(hcp.hi[q][2 * g], hcp.lo[q][2 * g]); }
+      if (j == 5) {
+        split2(sn[2], sn[3], hcp.hi[q][2 * g + 1], hcp.lo[q][2 * g + 1]);
+        pinu(hcp.hi[q][2 * g + 1], hcp.lo[q][2 * g + 1]);
+        if (4 * q + g + 1 < 8) {
+          gcq = lds_ld4(LA.v16 + (O_GC - O_L0) + 32 * (4 * q + g + 1)); ccq = lds_ld4(LA.v16 + (O_CC - O_L0) + 32 * (4 * q + g + 1));
+        }
+      }
+    };
+    gcq = lds_ld4(LA.v16 + (O_GC - O_L0)); ccq = lds_ld4(LA.v16 + (O_CC - O_L0));
+    layer_fwd_mm<2, 4, HC, O_WCH, O_WCL - O_WCH>(LA, h2p, accc, [&](int slot) __attribute__((always_inline)) {
+      if (slot < 18) film2_slot(3, 1 + slot / 6, slot % 6);
+      else if (slot >= 24) filmc_slot(0, (slot - 24) / 6, (slot - 24) % 6);
+    });
+#pragma unroll
+    for (int j = 0; j < 24; ++j) { filmc_slot(1, j / 6, j % 6); __builtin_amdgcn_sched_barrier(0); }
+
+    X3_TS(3)
+    Act<1> dfp;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      split2(df4[g].x, df4[g].y, dfp.hi[0][2 * g], dfp.lo[0][2 * g]);
+      split2(df4[g].z, df4[g].w, dfp.hi[0][2 * g + 1], dfp.lo[0][2 * g + 1]);
     }
+
+    // ---- dWf += dfeat^T hc over the workgroup's 128 points: wave -> (hc column tile w&1, point half w>>1);
+    //      waves 0 and 2 also take sum_p dfeat (aux column 7) ----
+    if (!CIPS_TUNE(a.dbg & 1)) {
+      constexpr int DFH = 0, DFL = 8192, HCH = 16384, HCL = 32768;
+      stage<1, 128, DFH, DFL>(sbase, prow, hf, dfp);
+      stage<2, 128, HCH, HCL>(sbase, prow, hf, hcp);
+      __syncthreads();
+      const int jt = wave & 1, kh = wave >> 1;
+      const unsigned mdf = jt == 0 ? m_df : 0u;          // waves 1 and 3 add zeros: no wave-dependent branches here
+      Frag fa[2], fb[2], fx[2];
+      // this wave's k-steps (4kh + k) and hc column block are folded into the lane bases
+      const unsigned d0 = opaque(LA.sb[0] + kh * 4096), d1 = opaque(LA.sb[1] + kh * 4096);      // dfeat: k-steps 4kh..
+      const unsigned h0 = opaque(d0 + jt * 8192), h1_ = opaque(d1 + jt * 8192);                  // hc: same k-steps, column block jt
+      const unsigned ax = opaque(LA.ab + kh * 1024);
+      stg_frag<128, DFH, DFL>(d0, d1, 0, 0, fa[0]);
+      stg_frag<128, HCH, HCL>(h0, h1_, 0, 0, fb[0]);
+      aux_frag(ax, 0, mdf, fx[0]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k + 1 < 4) {
+          stg_frag<128, DFH, DFL>(d0, d1, 0, k + 1, fa[(k + 1) & 1]);
+          stg_frag<128, HCH, HCL>(h0, h1_, 0, k + 1, fb[(k + 1) & 1]);
+          aux_frag(ax, k + 1, mdf, fx[(k + 1) & 1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        aGf[0] = x3f(aGf[0], fa[k & 1], fb[k & 1]);
+        aS[0] = x2f(aS[0], fa[k & 1], fx[k & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+    }
+
+    X3_TS(4)
+    // ---- d hc = Wf^T dfeat  (K = 32, M = 64);  dac = d hc * cos;  dpc = gc * dac ----
+    zero_acc(accc);
+    layer_tr<2, 2, CF, O_WFH, O_WFL - O_WFH>(LA, dfp, accc);
+    Act<2> dacp, dpcp;
+    {
+      float4 gn = lds_ld4(LA.v16 + (O_GC - O_L0));
+#pragma unroll
+      for (int grp = 0; grp < 8; ++grp) {
+        const float4 g4 = gn;
+        if (grp + 1 < 8) gn = lds_ld4(LA.v16 + (O_GC - O_L0) + 32 * (grp + 1));
+        __builtin_amdgcn_sched_barrier(0);
+        const int q = grp >> 2, g = grp & 3;
+        const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+        float v[4], w_[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = accc[q][4 * g + e] * csc[q][4 * g + e]; w_[e] = gg[e] * v[e]; }
+        split2(v[0], v[1], dacp.hi[q][2 * g], dacp.lo[q][2 * g]);
+        split2(v[2], v[3], dacp.hi[q][2 * g + 1], dacp.lo[q][2 * g + 1]);
+        split2(w_[0], w_[1], dpcp.hi[q][2 * g], dpcp.lo[q][2 * g]);
+        split2(w_[2], w_[3], dpcp.hi[q][2 * g + 1], dpcp.lo[q][2 * g + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+
+    pin(dacp); pin(h2p);
+    X3_TS(5)
+    // ---- dWc += dac^T h2: two sub-phases of 64 points; wave -> (dac row tile w&1, h2 column tiles 2(w>>1)+{0,1});
+    //      plus sum_p dsigma*h2 (h2 row tile w, aux column 5) and, on waves 0 and 1, sum_p dac (aux column 6).
+    //      Fragment reads run half a k-step ahead of their MFMAs. ----
+    if (!CIPS_TUNE(a.dbg & 2)) {
+      constexpr int DAH = 0, DAL = 8192, H2H = 16384, H2L = 32768;
+      const int it = wave & 1, jt0 = 2 * (wave >> 1);
+      const unsigned mdc = wave < 2 ? m_dc : 0u;         // waves 2 and 3 add zeros: no wave-dependent branches here
+      // wave-dependent column blocks folded into the lane bases (block stride of a 64-row image: 4096 B)
+      const unsigned i0 = opaque(LA.sb[0] + it * 4096), i1 = opaque(LA.sb[1] + it * 4096);
+      const unsigned j0 = opaque(LA.sb[0] + jt0 * 4096), j1 = opaque(LA.sb[1] + jt0 * 4096);
+      const unsigned w0 = opaque(LA.sb[0] + wave * 4096), w1 = opaque(LA.sb[1] + wave * 4096);
+#pragma unroll
+      for (int sp = 0; sp < 2; ++sp) {
+        if ((wave >> 1) == sp) {
+          stage<2, 64, DAH, DAL>(sbase, (wave & 1) * 32 + l31, hf, dacp);
+          stage<4, 64, H2H, H2L>(sbase, (wave & 1) * 32 + l31, hf, h2p);
+        }
+        __syncthreads();
+        Frag fa, fb0, fb1, fh, fx, fy;
+        stg_frag<64, DAH, DAL>(i0, i1, 0, 0, fa);
+        stg_frag<64, H2H, H2L>(j0, j1, 0, 0, fb0);
+        stg_frag<64, H2H, H2L>(j0, j1, 32, 0, fb1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          stg_frag<64, H2H, H2L>(w0, w1, 0, k, fh);
+          aux_frag(LA.ab, 4 * sp + k, m_h2, fx);
+          aux_frag(LA.ab, 4 * sp + k, mdc, fy);
+          __builtin_amdgcn_sched_barrier(0);
+          aGc[0] = x3f(aGc[0], fa, fb0);
+          aGc[1] = x3f(aGc[1], fa, fb1);
+          aS[0] = x2f(aS[0], fa, fy);
+          __builtin_amdgcn_sched_barrier(0);
+          if (k + 1 < 4) {
+            stg_frag<64, DAH, DAL>(i0, i1, 0, k + 1, fa);
+            stg_frag<64, H2H, H2L>(j0, j1, 0, k + 1, fb0);
+            stg_frag<64, H2H, H2L>(j0, j1, 32, k + 1, fb1);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          aS[0] = x3f(aS[0], fh, fx);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+      }
+    }
+
+    X3_TS(6)
+    // ---- d h2 = Wc^T dpc + ws * dsigma  (K = 64, M = 128), m-major;  da2 = d h2 * cos;  dp2 = g1 * da2.  A tile has only
+    //      12 MFMA slots here (4 k-steps) against ~36 VALU instructions per group: three slots per group, VALU-bound ----
+    zero_acc(acc);
+    Act<4> da2p;
+    Act<4> h1p;
+    Act<4> da1p;                         // consumed tile by tile inside the d h1 layer (da1_sums): never 64 live registers
+    float npx, npy, npz, ndsg;
+    {
+      Act<4> dp2p;
+      float v4[4], w4_[4];
+      float4 gq2, wq2;
+      auto dh2_slot = [&](int q, int g, int j) __attribute__((always_inline)) {
+        if (j == 0) {
+          const float gg[4] = {gq2.x, gq2.y, gq2.z, gq2.w}, ww[4] = {wq2.x, wq2.y, wq2.z, wq2.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v4[e] = fmaf(ww[e], dsg_s, acc[q][4 * g + e]) * cs2[q][4 * g + e];
+            w4_[e] = gg[e] * v4[e];
+          }
+          pinf(v4[0], v4[1], v4[2], v4[3]); pinf(w4_[0], w4_[1], w4_[2], w4_[3]);
+          if (4 * q + g + 1 < 16) {
+            gq2 = lds_ld4(LA.v16 + (O_G1 - O_L0) + 32 * (4 * q + g + 1)); wq2 = lds_ld4(LA.v16 + (O_WS - O_L0) + 32 * (4 * q + g + 1));
+          }
+        } else if (j == 1) {
+          split2(v4[0], v4[1], da2p.hi[q][2 * g], da2p.lo[q][2 * g]);
+          split2(v4[2], v4[3], da2p.hi[q][2 * g + 1], da2p.lo[q][2 * g + 1]);
+          pinu(da2p.hi[q][2 * g], da2p.lo[q][2 * g], da2p.hi[q][2 * g + 1], da2p.lo[q][2 * g + 1]);
+        } else {
+          split2(w4_[0], w4_[1], dp2p.hi[q][2 * g], dp2p.lo[q][2 * g]);
+          split2(w4_[2], w4_[3], dp2p.hi[q][2 * g + 1], dp2p.lo[q][2 * g + 1]);
+          pinu(dp2p.hi[q][2 * g], dp2p.lo[q][2 * g], dp2p.hi[q][2 * g + 1], dp2p.lo[q][2 * g + 1]);
+        }
+      };
+      gq2 = lds_ld4(LA.v16 + (O_G1 - O_L0)); wq2 = lds_ld4(LA.v16 + (O_WS - O_L0));
+      layer_tr_mm<4, 4, HC, O_WCH, O_WCL - O_WCH>(LA, dpcp, acc, [&](int slot) __attribute__((always_inline)) {
+        const int m = slot / 12, j = slot % 12;
+        if (m >= 1) dh2_slot(m - 1, j / 3, j % 3);
+      });
+#pragma unroll
+      for (int j = 0; j < 12; ++j) { dh2_slot(3, j / 3, j % 3); __builtin_amdgcn_sched_barrier(0); }
+
+      // ---- inputs of the next round: requested here, a whole layer before their first use (layer 0 of the next round inside
+      //      the dW1 phase below) ----
+      {
+        const int slot = pbase + 128 + prow;
+        const bool valid = slot < cend;
+        int p = valid ? slot : cend - 1;
+        if (LIVE) p = lidx[p];
+        const long long gp = (long long)b * a.P + p;
+        if (a.points) { npx = a.points[gp * 3 + 0]; npy = a.points[gp * 3 + 1]; npz = a.points[gp * 3 + 2]; }
+        else gen_point(a.rg, b, p, npx, npy, npz);
+        ndsg = valid ? a.dsigma[gp] : 0.f;
+      }
+      // ---- d h1 = W1^T dp2  (K = 128, M = 128), m-major;  da1 = d h1 * cos(layer-0 argument), the layer-0 sines recomputed
+      //      alongside for dW1: ~52 VALU instructions per group of 4 features in six slots ----
+      f32x16 acc1[4];
+      zero_acc(acc1);
+      float4 pq[4];
+      float ar[4], s1[4], c1[4], d1[4];
+      auto dh1_slot = [&](int q, int g, int j) __attribute__((always_inline)) {
+        if (j == 0) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ar[e] = fmaf(pq[e].x, px, fmaf(pq[e].y, py, fmaf(pq[e].z, pz, pq[e].w)));
+          pinf(ar[0], ar[1], ar[2], ar[3]);
+          if (4 * q + g + 1 < 16) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pq[e] = lds_ld4(LA.v64 + 128 * (4 * q + g + 1) + 16 * e);
+          }
+        } else if (j == 1) {
+          if (HW) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ar[e] = __builtin_amdgcn_fractf(ar[e]);
+            s1[0] = __builtin_amdgcn_sinf(ar[0]); s1[1] = __builtin_amdgcn_sinf(ar[1]);
+            pinf(ar[0], ar[1], ar[2], ar[3]); pinf(s1[0], s1[1]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sincos_rev<false>(ar[e], &s1[e], &c1[e]);
+            pinf(s1[0], s1[1], s1[2], s1[3]); pinf(c1[0], c1[1], c1[2], c1[3]);
+          }
+        } else if (j == 2) {
+          if (HW) {
+            s1[2] = __builtin_amdgcn_sinf(ar[2]); s1[3] = __builtin_amdgcn_sinf(ar[3]);
+            c1[0] = __builtin_amdgcn_cosf(ar[0]); c1[1] = __builtin_amdgcn_cosf(ar[1]);
+            pinf(s1[2], s1[3], c1[0], c1[1]);
+          }
+        } else if (j == 3) {
+          if (HW) { c1[2] = __builtin_amdgcn_cosf(ar[2]); c1[3] = __builtin_amdgcn_cosf(ar[3]); }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) d1[e] = acc1[q][4 * g + e] * c1[e];
+          pinf(d1[0], d1[1], d1[2], d1[3]);
+        } else if (j == 4) {
+          split2(s1[0], s1[1], h1p.hi[q][2 * g], h1p.lo[q][2 * g]);
+          split2(s1[2], s1[3], h1p.hi[q][2 * g + 1], h1p.lo[q][2 * g + 1]);
+          pinu(h1p.hi[q][2 * g], h1p.lo[q][2 * g], h1p.hi[q][2 * g + 1], h1p.lo[q][2 * g + 1]);
+        } else {
+          split2(d1[0], d1[1], da1p.hi[q][2 * g], da1p.lo[q][2 * g]);
+          split2(d1[2], d1[3], da1p.hi[q][2 * g + 1], da1p.lo[q][2 * g + 1]);
+          pinu(da1p.hi[q][2 * g], da1p.lo[q][2 * g], da1p.hi[q][2 * g + 1], da1p.lo[q][2 * g + 1]);
+        }
+      };
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pq[e] = lds_ld4(LA.v64 + 16 * e);
+      // sum_p da1 * [1, x, y, z] of feature tile q over this wave's OWN 32 points (round 4; was part of the dW1 phase: a third of
+      // its staging and 6 of its 34 MFMAs per sub-phase).  da1 tile q goes through a wave-private 4 KiB slot behind the (now
+      // 32 KiB) dW1 window and comes back feature-per-lane; the aux operand is masked to columns 0..3 AND to lane group q.  The
+      // column-sum tile aS has 32 columns of which the masks (functions of lane & 7) used only 8 — lane groups 1..3 were copies
+      // of group 0 — so tile q's sums land in columns 8 q + {0..3} of the SAME accumulator: no new registers; the waves' partial
+      // sums are added when the workgroup writes its partials.  Same-wave LDS traffic: the DS queue is in order, no barrier.
+      const unsigned prv = opaque(sbase + O_STG + 32768 + wave * 4096);
+      auto da1_put = [&](int q) __attribute__((always_inline)) {          // tile q -> the wave's private slot
+        const unsigned rb = opaque(prv + l31 * 64);
+        const int gsw = (l31 >> 1) & 7;
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const unsigned o = rb + (((2 * gg + hf) ^ gsw) << 3);
+          lds_st64(o, da1p.hi[q][2 * gg], da1p.hi[q][2 * gg + 1]);
+          lds_st64(o + 2048, da1p.lo[q][2 * gg], da1p.lo[q][2 * gg + 1]);
+        }
+      };
+      auto da1_sum = [&](int q) __attribute__((always_inline)) {          // read it back feature-per-lane, contract with aux
+        const unsigned mq = ((l31 >> 3) == q && c7 < 4) ? ~0u : 0u;
+        const unsigned p0 = opaque(LA.sb[0] + 32768 + wave * 4096), p1 = opaque(LA.sb[1] + 32768 + wave * 4096);
+        const unsigned axw = opaque(LA.ab + wave * 512);
+        Frag fd0, fd1, fy0, fy1;
+        stg_frag<32, 0, 2048>(p0, p1, 0, 0, fd0);
+        stg_frag<32, 0, 2048>(p0, p1, 0, 1, fd1);
+        aux_frag(axw, 0, mq, fy0);
+        aux_frag(axw, 1, mq, fy1);
+        __builtin_amdgcn_sched_barrier(0);
+        aS[0] = x3f(aS[0], fd0, fy0);
+        aS[0] = x3f(aS[0], fd1, fy1);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      // tile q's epilogue runs under tile q + 1's MFMAs; its slot is written at the first slot of tile q + 2 and read back eight
+      // slots later (the LDS round trip has long completed: the read costs its own latency only)
+      layer_tr_mm<4, 8, H, O_W1H, O_W1L - O_W1H>(LA, dp2p, acc1, [&](int slot) __attribute__((always_inline)) {
+        const int m = slot / 24, j = slot % 24;
+        if (m >= 2 && j == 0) da1_put(m - 2);
+        if (m >= 2 && j == 8) da1_sum(m - 2);
+        if (m >= 1) dh1_slot(m - 1, j / 6, j % 6);
+      });
+      X3_TS(7)
+      da1_put(2);
+#pragma unroll
+      for (int j = 0; j < 12; ++j) { dh1_slot(3, j / 6, j % 6); __builtin_amdgcn_sched_barrier(0); }
+      da1_sum(2);
+#pragma unroll
+      for (int j = 12; j < 24; ++j) { dh1_slot(3, j / 6, j % 6); __builtin_amdgcn_sched_barrier(0); }
+      da1_put(3);
+      da1_sum(3);
+    }
+
+    pin(da2p); pin(h1p);
+    X3_TS(8)
+    // ---- dW1 += da2^T h1: four sub-phases of 32 points; wave -> da2 row tile w, all four h1 column tiles;
+    //      plus sum_p da2 (aux column 4) and sum_p da1 * [1, x, y, z] (aux columns 0..3) for row tile w ----
+    if (!CIPS_TUNE(a.dbg & 4)) {
+      constexpr int DAH = 0, DAL = 8192, H1H = 16384, H1L = 24576;      // 32 KiB; the last 16 KiB hold the waves' private slots
+      const unsigned w0 = opaque(LA.sb[0] + wave * 2048), w1 = opaque(LA.sb[1] + wave * 2048);   // row tile w
+#pragma unroll
+      for (int sp = 0; sp < 4; ++sp) {
+        if (sp == 1) { X3_TS(10) }
+        if (wave == sp) {
+          stage<4, 32, DAH, DAL>(sbase, l31, hf, da2p);
+          stage<4, 32, H1H, H1L>(sbase, l31, hf, h1p);
+        } else if (NPRE > 0) {
+          // this wave's k-th idle sub-phase (k = sp for sp < wave, sp - 1 after its own turn): a third of the NPRE groups
+          const int k = sp - (sp > wave ? 1 : 0);
+          if (k == 0) l0_groups(IC0{}, ICA{}, npx, npy, npz);
+          else if (k == 1) l0_groups(ICA{}, ICB{}, npx, npy, npz);
+          else l0_groups(ICB{}, ICN{}, npx, npy, npz);
+        }
+        if (sp == 1) { X3_TS(11) }
+        __syncthreads();
+        if (sp == 1) { X3_TS(12) }
+        const unsigned ax = opaque(LA.ab + sp * 512);      // aux k-steps 2sp + k
+        Frag fa, fb0, fb1, fb2, fb3, fx;
+        stg_frag<32, DAH, DAL>(w0, w1, 0, 0, fa);
+        stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 0, 0, fb0);
+        stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 32, 0, fb1);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 64, k, fb2);
+          stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 96, k, fb3);
+          aux_frag(ax, k, m_d2, fx);
+          __builtin_amdgcn_sched_barrier(0);
+          aG1[0] = x3f(aG1[0], fa, fb0);
+          aG1[1] = x3f(aG1[1], fa, fb1);
+          __builtin_amdgcn_sched_barrier(0);
+          aG1[2] = x3f(aG1[2], fa, fb2);
+          aG1[3] = x3f(aG1[3], fa, fb3);
+          aS[0] = x2f(aS[0], fa, fx);
+          __builtin_amdgcn_sched_barrier(0);
+          if (k + 1 < 2) {
+            stg_frag<32, DAH, DAL>(w0, w1, 0, k + 1, fa);
+            stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 0, k + 1, fb0);
+            stg_frag<32, H1H, H1L>(LA.sb[0], LA.sb[1], 32, k + 1, fb1);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (sp == 1) { X3_TS(13) }
+        __syncthreads();
+        if (sp == 1) { X3_TS(14) }
+      }
+    }
+    px = npx; py = npy; pz = npz; dsg = ndsg;
+    X3_TS(9)
+  }
+
+  const int lane = lane0, l31 = lane & 31, hf = lane >> 5;
+  // ---- per-wave column sums and sum of dsigma.  Columns 4..7 of lane group 0 are this wave's row-tile sums as before; columns
+  //      8 q + {0..3} hold sum_p da1 * [1, x, y, z] of feature tile q over this wave's own points: the four waves' tiles meet in
+  //      the idle staging window and wave t adds tile t's four partials in wave order ----
+  {
+    float* part = reinterpret_cast<float*>(smem + O_STG);      // [wave][32 rows][32 columns] floats = 16 KiB
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[(wave * 32 + mfma_row(r, hf)) * 32 + l31] = aS[0][r];
+    __syncthreads();
+    float* sr = a.sred + (long long)(MODE == X3_EVEN ? prow_ : b * a.chunks + blockIdx.x) * SRED;
+    if (l31 < 8) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = mfma_row(r, hf);
+        // columns 0..3 are carried as 1/(2 pi)^2, column 4 (sum_p da2) as 1/(2 pi); 5..7 unscaled
+        float v = aS[0][r] * ((HW && l31 == 4) ? TWO_PI : 1.f);
+        if (l31 < 4) {
+          v = part[(0 * 32 + row) * 32 + 8 * wave + l31];
+          v += part[(1 * 32 + row) * 32 + 8 * wave + l31];
+          v += part[(2 * 32 + row) * 32 + 8 * wave + l31];
+          v += part[(3 * 32 + row) * 32 + 8 * wave + l31];
+          if (HW) v *= TWO_PI * TWO_PI;
+        }
+        sr[wave * 256 + row * 8 + l31] = v;
+      }
+    }
+    float t = r_dsg;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off);
+    if (lane == 0) sr[1024 + wave] = t;
+    if (lane == 1) sr[1028 + wave] = 0.f;
+  }
+  // ---- write the workgroup's partial weight gradients ----
+  {
+    float* gp_ = a.gpart + (long long)(MODE == X3_EVEN ? prow_ : b * a.chunks + blockIdx.x) * GPART;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gp_[GP_G1 + (32 * wave + mfma_row(r, hf)) * H + 32 * j + l31] = aG1[j][r] * (HW ? TWO_PI : 1.f);
+    const int it = wave & 1, jt0 = 2 * (wave >> 1);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gp_[GP_GC + (32 * it + mfma_row(r, hf)) * H + 32 * (jt0 + j) + l31] = aGc[j][r];
+    float* gf = gp_ + ((wave >> 1) ? GP_GF1 : GP_GF0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) gf[mfma_row(r, hf) * HC + 32 * (wave & 1) + l31] = aGf[0][r];
   }
 }
 
@@ -1178,12 +1002,6 @@ __global__ __launch_bounds__(128) void siren_bwd_finalize_kernel(FinArgs a) {
 
 }  // namespace
 
-// 4096-point chunks when that still fills the chip (>= 3 workgroups per CU on 256 CUs), else 2048 / 1024 / 512
-static int x3_chunk(int B, int P) {
-  int chunk = 4096;
-  while (chunk > 512 && (long long)B * ((P + chunk - 1) / chunk) < 768) chunk >>= 1;
-  return chunk;
-}
 extern "C" int cips_siren_bwd_x3_chunks(int B, int P) {
   const int chunk = x3_chunk(B, P);
   return (P + chunk - 1) / chunk;
@@ -1291,220 +1109,14 @@ static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points,
   a.chunk = x3_chunk(B, P);
   a.chunks = (P + a.chunk - 1) / a.chunk;
   dim3 grid(a.chunks, B);
-  static bool attr4 = false;
-  CIPS_PER_DEVICE(attr4, false);
-  if (!attr4) {
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_LIVE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_LIVE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<false, X3_EVEN>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    hipFuncSetAttribute((const void*)siren_bwd_x4_kernel<true, X3_EVEN>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    attr4 = true;
-  }
-  const bool hw = (w->trig_mode & 1) != 0;
-  if (seg) {
-    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_EVEN>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_EVEN>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-  } else if (idx) {
-    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_LIVE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_LIVE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-  } else {
-    if (hw) hipLaunchKernelGGL((siren_bwd_x4_kernel<true, X3_DENSE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((siren_bwd_x4_kernel<false, X3_DENSE>), grid, dim3(256), SMEM_BYTES, (hipStream_t)stream, a);
-  }
-  return CIPS_CHECK_LAUNCH();
-}
-
-static int siren_fwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays, float* feat,
-                               float* sigma, float* zout, int B, int P, cips_stream_t stream);
-
-extern "C" int cips_siren_fwd_x3(const cips_siren_weights* w, const float* points, float* feat, float* sigma, int B, int P,
-                                 cips_stream_t stream) {
-  if (!points) return (int)hipErrorInvalidValue;
-  return siren_fwd_x3_launch(w, points, nullptr, feat, sigma, nullptr, B, P, stream);
-}
-
-extern "C" int cips_siren_fwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, float* feat, float* sigma,
-                                      float* zout, int B, cips_stream_t stream) {
-  if (!rays) return (int)hipErrorInvalidValue;
-  return siren_fwd_x3_launch(w, nullptr, rays, feat, sigma, zout, B, rays->W * rays->H * rays->S, stream);
-}
-
-static int siren_fwd_x3_launch(const cips_siren_weights* w, const float* points, const cips_ray_params* rays, float* feat,
-                               float* sigma, float* zout, int B, int P, cips_stream_t stream) {
-  if (!w || !feat || !sigma || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
-  FwdX3Args a;
-  a.w = *w; a.points = points; a.feat = feat; a.sigma = sigma; a.zout = zout; a.B = B; a.P = P;
-  a.rg = RayGen{};
-  if (!points) { const int rc = fill_raygen(a.rg, rays); if (rc) return rc; }
-  a.chunk = 4096;
-  while (a.chunk > 512 && (long long)B * ((P + a.chunk - 1) / a.chunk) < 768) a.chunk >>= 1;
-  dim3 grid((P + a.chunk - 1) / a.chunk, B);
-  const int smem = O_STG;            // weight images + FiLM vectors + the 4 KiB slot reused for the output bias
-  // trig_mode bit 0: hardware sine; bit 1 (A/B runs only): the round-1..4 bf16 operand planes instead of fp16
-  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
-  auto go = [&](auto HW_, auto F16_) {
-    constexpr bool HW = decltype(HW_)::value, F16 = decltype(F16_)::value;
-    static bool attr_set = false;
-    CIPS_PER_DEVICE(attr_set, false);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)siren_fwd_x3_kernel<HW, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((siren_fwd_x3_kernel<HW, F16>), grid, dim3(512), smem, (hipStream_t)stream, a);
+  auto go = [&](auto HW_, auto MODE_) {
+    x3_launch<siren_bwd_x4_kernel<decltype(HW_)::value, decltype(MODE_)::value>>(grid, 256, SMEM_BYTES, stream, a);
   };
-  using T = std::true_type; using F = std::false_type;
-  if (hw) { if (f16) go(T{}, T{}); else go(T{}, F{}); }
-  else { if (f16) go(F{}, T{}); else go(F{}, F{}); }
-  return CIPS_CHECK_LAUNCH();
-}
-
-// Sigma-only forward: siren_fwd_x3_launch's chunking (at most 4096 points, halved while B * chunks < 768; a ragged tail is
-// clamped to the last valid point in-kernel).  grid == NULL: points (B, P, 3).
-static int siren_sigma_x3_launch(const cips_siren_weights* w, const float* points, const cips_grid_params* grid, float* sigma,
-                                 int B, int P, cips_stream_t stream) {
-  SigmaX3Args a;
-  a.w = *w; a.points = points; a.sigma = sigma; a.B = B; a.P = P;
-  a.gx = a.gy = a.gz = nullptr; a.ny = a.nz = 1;
-  if (grid) { a.gx = grid->gx; a.gy = grid->gy; a.gz = grid->gz; a.ny = grid->ny; a.nz = grid->nz; }
-  a.chunk = 4096;
-  while (a.chunk > 512 && (long long)B * ((P + a.chunk - 1) / a.chunk) < 768) a.chunk >>= 1;
-  dim3 g((P + a.chunk - 1) / a.chunk, B);
-  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
-  auto go = [&](auto HW_, auto F16_, auto GRID_) {
-    constexpr bool HW = decltype(HW_)::value, F16 = decltype(F16_)::value, GRID = decltype(GRID_)::value;
-    static bool attr_set = false;
-    CIPS_PER_DEVICE(attr_set, false);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)siren_sigma_x3_kernel<HW, F16, GRID>, hipFuncAttributeMaxDynamicSharedMemorySize, SG_SMEM_BYTES);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((siren_sigma_x3_kernel<HW, F16, GRID>), g, dim3(512), SG_SMEM_BYTES, (hipStream_t)stream, a);
-  };
-  using T = std::true_type; using F = std::false_type;
-  auto pick = [&](auto GRID_) {
-    if (hw) { if (f16) go(T{}, T{}, GRID_); else go(T{}, F{}, GRID_); }
-    else { if (f16) go(F{}, T{}, GRID_); else go(F{}, F{}, GRID_); }
-  };
-  if (grid) pick(T{}); else pick(F{});
-  return CIPS_CHECK_LAUNCH();
-}
-
-extern "C" int cips_siren_sigma_x3(const cips_siren_weights* w, const float* points, float* sigma, int B, int P,
-                                   cips_stream_t stream) {
-  if (!w || !points || !sigma || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
-  return siren_sigma_x3_launch(w, points, nullptr, sigma, B, P, stream);
-}
-
-extern "C" int cips_siren_sigma_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, int B,
-                                        cips_stream_t stream) {
-  if (!w || !grid || !sigma || B <= 0) return (int)hipErrorInvalidValue;
-  if (!grid->gx || !grid->gy || !grid->gz || grid->nx <= 0 || grid->ny <= 0 || grid->nz <= 0) return (int)hipErrorInvalidValue;
-  const long long nxy = (long long)grid->nx * grid->ny;               // < 2^62; times nz only once it is known to fit an int
-  if (nxy > INT_MAX || nxy * grid->nz > INT_MAX) return (int)hipErrorInvalidValue;
-  const long long P = nxy * grid->nz;
-  return siren_sigma_x3_launch(w, nullptr, grid, sigma, B, (int)P, stream);
-}
-
-// Sigma and its gradient: the sigma launcher's chunking and instance choice.
-static int siren_sigma_grad_x3_launch(const cips_siren_weights* w, const float* points, const cips_grid_params* grid, float* sigma,
-                                      float* grad, int B, int P, cips_stream_t stream) {
-  SigmaGradX3Args a;
-  a.w = *w; a.points = points; a.sigma = sigma; a.grad = grad; a.B = B; a.P = P;
-  a.gx = a.gy = a.gz = nullptr; a.ny = a.nz = 1;
-  if (grid) { a.gx = grid->gx; a.gy = grid->gy; a.gz = grid->gz; a.ny = grid->ny; a.nz = grid->nz; }
-  a.chunk = 4096;
-  while (a.chunk > 512 && (long long)B * ((P + a.chunk - 1) / a.chunk) < 768) a.chunk >>= 1;
-  dim3 g((P + a.chunk - 1) / a.chunk, B);
-  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
-  auto go = [&](auto HW_, auto F16_, auto GRID_) {
-    constexpr bool HW = decltype(HW_)::value, F16 = decltype(F16_)::value, GRID = decltype(GRID_)::value;
-    static bool attr_set = false;
-    CIPS_PER_DEVICE(attr_set, false);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)siren_sigma_grad_x3_kernel<HW, F16, GRID>, hipFuncAttributeMaxDynamicSharedMemorySize, SG_SMEM_BYTES);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((siren_sigma_grad_x3_kernel<HW, F16, GRID>), g, dim3(512), SG_SMEM_BYTES, (hipStream_t)stream, a);
-  };
-  using T = std::true_type; using F = std::false_type;
-  auto pick = [&](auto GRID_) {
-    if (hw) { if (f16) go(T{}, T{}, GRID_); else go(T{}, F{}, GRID_); }
-    else { if (f16) go(F{}, T{}, GRID_); else go(F{}, F{}, GRID_); }
-  };
-  if (grid) pick(T{}); else pick(F{});
-  return CIPS_CHECK_LAUNCH();
-}
-
-extern "C" int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, float* sigma, float* grad, int B, int P,
-                                        cips_stream_t stream) {
-  if (!w || !points || !grad || B <= 0 || P <= 0) return (int)hipErrorInvalidValue;
-  return siren_sigma_grad_x3_launch(w, points, nullptr, sigma, grad, B, P, stream);
-}
-
-extern "C" int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma, float* grad,
-                                             int B, cips_stream_t stream) {
-  if (!w || !grid || !grad || B <= 0) return (int)hipErrorInvalidValue;
-  if (!grid->gx || !grid->gy || !grid->gz || grid->nx <= 0 || grid->ny <= 0 || grid->nz <= 0) return (int)hipErrorInvalidValue;
-  const long long nxy = (long long)grid->nx * grid->ny;
-  if (nxy > INT_MAX || nxy * grid->nz > INT_MAX) return (int)hipErrorInvalidValue;
-  return siren_sigma_grad_x3_launch(w, nullptr, grid, sigma, grad, B, (int)(nxy * grid->nz), stream);
-}
-
-#ifdef CIPS_TUNING
-static unsigned long long* g_mprof = nullptr;
-extern "C" int cips_march_x3_prof(unsigned long long* host_out) {       // tuning aid: copies the 4x8x8 timestamps
-  if (!g_mprof) return (int)hipErrorNotReady;
-  return (int)hipMemcpy(host_out, g_mprof, 4 * 8 * 8 * 8, hipMemcpyDeviceToHost);
-}
-#endif
-extern "C" int cips_march_fwd_x3(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise,
-                                 float noise_std, int clamp_mode, int flags, float* fea, float* depth, float* weights,
-                                 float* feat, float* sigma, float* z, int B, const unsigned char* clamp_in,
-                                 unsigned char* clamp_out, cips_stream_t stream) {
-  if (!w || !fea || B <= 0) return (int)hipErrorInvalidValue;
-  MarchArgs a;
-  a.w = *w;
-  const int rc = fill_raygen(a.rg, rays);
-  if (rc) return rc;
-  a.noise = noise; a.noise_std = noise_std; a.clamp_mode = clamp_mode; a.flags = flags;
-  a.fea = fea; a.depth = depth; a.weights = weights; a.feat = feat; a.sigma = sigma; a.zout = z; a.B = B;
-  a.clamp_pin = clamp_in; a.clamp_rec = clamp_out;
-  a.desync = 0; a.one_wave = 0; a.prof = nullptr;
-#ifdef CIPS_TUNING
-  a.desync = cips_tune_env("CIPS_X3_MDESYNC", 0);
-  a.one_wave = cips_tune_env("CIPS_X3_MONE", 0);
-  if (cips_tune_env("CIPS_X3_MPROF", 0)) {
-    if (!g_mprof && hipMalloc(&g_mprof, 4 * 8 * 8 * 8) != hipSuccess) g_mprof = nullptr;
-    a.prof = g_mprof;
-  }
-#endif
-  // a workgroup's 8 waves take 32 rays each: 256-ray chunks keep all of them busy; halve only for small images
-  a.rays_per_wg = 256;
-  const int n = a.rg.n;
-  dim3 grid((n + a.rays_per_wg - 1) / a.rays_per_wg, B);
-  const int smem = O_STG;
-  const bool dbg = a.clamp_pin || a.clamp_rec;
-  const bool hw = (w->trig_mode & 1) != 0, f16 = (w->trig_mode & 2) == 0;
-  auto go = [&](auto HW_, auto DBG_, auto F16_) {
-    constexpr bool HW = decltype(HW_)::value, DBG = decltype(DBG_)::value, F16 = decltype(F16_)::value;
-    static bool attr_set = false;
-    CIPS_PER_DEVICE(attr_set, false);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)siren_march_x3_kernel<HW, DBG, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((siren_march_x3_kernel<HW, DBG, F16>), grid, dim3(512), smem, (hipStream_t)stream, a);
-  };
-  using T = std::true_type; using F = std::false_type;
-  if (hw) {
-    if (dbg) { if (f16) go(T{}, T{}, T{}); else go(T{}, T{}, F{}); }
-    else { if (f16) go(T{}, F{}, T{}); else go(T{}, F{}, F{}); }
-  } else {
-    if (dbg) { if (f16) go(F{}, T{}, T{}); else go(F{}, T{}, F{}); }
-    else { if (f16) go(F{}, F{}, T{}); else go(F{}, F{}, F{}); }
-  }
+  x3_pick([&](auto HW_) {
+    if (seg) go(HW_, std::integral_constant<int, X3_EVEN>{});
+    else if (idx) go(HW_, std::integral_constant<int, X3_LIVE>{});
+    else go(HW_, std::integral_constant<int, X3_DENSE>{});
+  }, (w->trig_mode & 1) != 0);
   return CIPS_CHECK_LAUNCH();
 }
 

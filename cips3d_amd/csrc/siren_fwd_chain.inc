@@ -1,4 +1,4 @@
-// siren_fwd_chain.inc — textually included by the forward kernels of siren_bwd_x3.hip (a shared __device__ function
+// siren_fwd_chain.inc — textually included by the forward kernels of siren_fwd_x3.hip (a shared __device__ function
 // changes hipcc's scheduling of this hand-pinned stream: 166 -> 256 VGPRs).
 // One wave-step of the forward chain.  Expects in scope: LaneAddr LA, int hf, float px, py, pz, bs and the template
 // flags HW (with HW the LDS images are stage_weights_x3<true, .>'s: every sine argument comes out in revolutions, sin_rev is

@@ -1,44 +1,13 @@
-// siren_sigma_grad_chain.inc — textually included by siren_sigma_grad_x3_kernel of siren_bwd_x3.hip: siren_sigma_chain.inc's
-// wave-step (that file is left alone, for the reason its header gives) carried on to the gradient of sigma w.r.t. the point.
-// In scope: LaneAddr LA (v16 / v64 pointing at this kernel's layer-0 packs), float px, py, pz, bs, float dscale (the power of two
+// siren_sigma_grad_chain.inc — textually included by siren_sigma_grad_x3_kernel (siren_sigma_x3.inc): siren_sigma_chain.inc's
+// wave-step carried on to the gradient of sigma w.r.t. the point.
+// In scope: what siren_sigma_w1.inc asks for (it opens the step: LA, hf, valid, gp, the point), float bs, float dscale (the power of two
 // the kernel puts on the layer-1 factor, 1 on bf16 planes) and the template flags HW and F16; defines `float sig` and
 // `float gx, gy, gz` (both lane halves), the gradient still times  dscale  and, with HW, divided by (2 pi)^2.
 //   sigma = ws . sin(a1) + bs,   dp1 = g1 * ws * cos(a1),   dh1 = W1^T dp1,   grad = sum_f pack[f].xyz cos(a0[f]) dh1[f]
-// sigma is siren_sigma_chain.inc's bit for bit: the first block is that file's, and the second evaluates the same fmaf chain per
-// feature in the same (grp, e) order; the sine of sincos_rev is sin_rev's expression.
-    f32x16 acc[4];
-    zero_acc(acc);
-    {
-      const unsigned wb[2][2] = {{opaque(LA.fb[0][0] + O_W1H), opaque(LA.fb[0][1] + O_W1H)},
-                                 {opaque(LA.fb[1][0] + O_W1H), opaque(LA.fb[1][1] + O_W1H)}};
-  #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        Act<1> h1q;
-  #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          float4 pk[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e) pk[e] = lds_ld4(LA.v64 + 128 * (4 * q + g) + 16 * e);
-          __builtin_amdgcn_sched_barrier(0);
-          float sn[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e) sn[e] = sin_rev<HW>(fmaf(pk[e].x, px, fmaf(pk[e].y, py, fmaf(pk[e].z, pz, pk[e].w))));
-          split2t<F16>(sn[0], sn[1], h1q.hi[0][2 * g], h1q.lo[0][2 * g]);
-          split2t<F16>(sn[2], sn[3], h1q.hi[0][2 * g + 1], h1q.lo[0][2 * g + 1]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        auto load = [&](int t, int m, Frag& f) {            // layer_fwd's fragment of k-step 2q + t, output tile m
-          const int c = q * H * 64 + m * 2048;
-          put(f.h, 0, lds_b64(wb[t][0] + c));
-          put(f.h, 2, lds_b64(wb[t][1] + c));
-          put(f.l, 0, lds_b64(wb[t][0] + c + (O_W1L - O_W1H)));
-          put(f.l, 2, lds_b64(wb[t][1] + c + (O_W1L - O_W1H)));
-        };
-        X3_PRIO(1);
-        run_layer<4, 2, F16>(load, h1q, acc);
-        X3_PRIO(0);
-      }
-    }
+// sigma is siren_sigma_chain.inc's bit for bit: the first block is the same text (siren_sigma_w1.inc).  The layer-1 epilogues stay
+// separate — this one takes the cosine next to every sine and packs dp1, the sigma chain keeps nothing but the dot — and agree
+// because both evaluate the same fmaf chain per feature in the same (grp, e) order; the sine of sincos_rev is sin_rev's expression.
+#include "siren_sigma_w1.inc"
     // layer-1 epilogue: the accumulator of feature f is consumed as sine for the sigma dot and as cosine for dp1, which is
     // packed to split planes — the B operand of the transposed layer, k order of the register chain
     float sig = 0.f;

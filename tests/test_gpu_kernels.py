@@ -143,7 +143,7 @@ def _siren_fp64(G, pts, style):
 @pytest.mark.parametrize("scale_w", [1.0, 37.0, 3e-4])
 def test_siren_forward_x3_sigma_is_fp32_class(scale_w, monkeypatch):
     """Round 5: the forward chain's dense layers run on fp16 hi / lo planes with per-matrix power-of-two weight scales
-    (siren_bwd_x3.hip: stage_weights_x3<., true>).  sigma feeds two discontinuities (the relu clamp, the cdf search), so its
+    (siren_x3_common.h: stage_weights_x3<., true>).  sigma feeds two discontinuities (the relu clamp, the cdf search), so its
     error is measured against an fp64 evaluation next to the fp32 oracle's own: the product has to be in the oracle's class
     (<= 2x its rms distance from fp64 + 2e-7), where the bf16 planes of rounds 1-4 sat 5-10x above it.  scale_w rescales
     W1 / Wc / Wf and compensates in the FiLM gains' biases so that the function stays in range: the images must not depend on
