@@ -133,6 +133,7 @@ SIGNATURES = {
     "cips_siren_bwd_x3_rays_live_even": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "cips_siren_bwd_x3_reduce_segments": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "cips_siren_bwd_x3_finalize": (i32, [C.POINTER(SirenWeights), vp, vp, i32, i32, C.POINTER(SirenGrads), vp]),
+    "cips_siren_bwd_x3_finalize_segments": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, C.POINTER(SirenGrads), vp]),
     "cips_march_fwd_x3": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "cips_siren_bwd_data": (i32, [C.POINTER(SirenWeights)] + [vp] * 14 + [i32, i32, vp]),
     "cips_siren_bwd_data_f32": (i32, [C.POINTER(SirenWeights)] + [vp] * 9 + [i32, i32, vp]),
@@ -141,6 +142,9 @@ SIGNATURES = {
     "cips_composite_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "cips_composite_bwd_live": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "cips_live_points": (i32, [vp, i32, i32, vp, vp, vp]),
+    "cips_composite_has_dead_samples": (i32, [i32]),
+    "cips_live_points_clamp": (i32, [vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "cips_composite_bwd_listed": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "cips_gemm_f32": (i32, [C.POINTER(GemmDesc), vp]),
     "cips_gemm_bf16x3": (i32, [C.POINTER(GemmX3Desc), vp]),
     "cips_gemm_bf16x3_fuses_torgb": (i32, [C.POINTER(GemmX3Desc)]),

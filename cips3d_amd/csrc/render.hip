@@ -60,6 +60,31 @@ __device__ __forceinline__ float clamp_density_grad(float x, int mode) {
   return x > 0.f ? 1.f : 0.f;
 }
 
+// The compositing backward's pre-activation of one sample, x = sigma + noise * noise_std (noise may be NULL): composite_bwd_kernel
+// and the list kernel behind cips_live_points_clamp form it here, so both see the same bits.
+__device__ __forceinline__ float comp_bwd_x(float sg, const float* noise, long long i, float noise_std) {
+  if (noise) sg += noise[i] * noise_std;
+  return sg;
+}
+
+// Can composite_bwd_kernel give the sample at sorted position k of a ray of E a non-zero feature row (w * G) or a non-zero
+// dsigma?  Known from x alone, i.e. at the end of the forward pass; never from dfea.  Read off that kernel:
+//   relu, x <= 0: dens = 0, alpha = 1 - exp(-delta * 0) = 0 exactly, w = alpha * T = 0, and the clamp's gradient is 0 in
+//     dsigma = dalpha * (delta * exp(-delta * dens)) * dgrad  -> dead.  (fmaxf(NaN, 0) = 0 makes a NaN x dead there as well; it
+//     counts as live here, which only lists more.)
+//   the ray's last sample under last_back (flags bit 0): w is topped up by 1 - sum w -> live whatever x is.
+//   softplus: dens > 0 at every x -> no sample is ever dead (comp_has_dead_samples: the caller keeps the mask path).
+// This is a superset of the kernel's own backward-time rule (w != 0) || (dsigma != 0) wherever z, the features and dfea are
+// finite.  A non-finite feature or dfea turns dalpha of every sample in front of it into NaN, and NaN * 0 = NaN makes the
+// backward-time rule list clamped samples too; this rule does not (their rows would carry nothing but that NaN, which the
+// ray's open samples carry as well).
+__device__ __forceinline__ bool comp_bwd_can_be_live(float x, int k, int E, int clamp_mode, int flags) {
+  if (clamp_mode != 0) return true;
+  if ((flags & 1) && k == E - 1) return true;
+  return !(x <= 0.f);
+}
+inline bool comp_has_dead_samples(int clamp_mode) { return clamp_mode == 0; }
+
 // ------------------------------------------------------------------------------------
 // H3a: coarse weights -> pdf -> cdf -> inverse-CDF samples -> fine points.
 // Follows exp/dev/nerf_inr/models/generator_nerf_inr.py:564-592 and
@@ -181,6 +206,8 @@ struct CompArgs {
   // optional (cips_composite_bwd_live): one byte per sample in the order of dfeat_* / dsig_*, 1 iff the sample's dfeat row or
   // its dsigma can be non-zero.  When given, the dfeat rows of the other samples are NOT written.
   unsigned char *live_c, *live_f;
+  // cips_composite_bwd_listed: the dfeat row and the dsigma of a sample are written iff comp_bwd_can_be_live holds for it
+  int listed;
   long long R;
   int S, E, clamp_mode, flags;
   // optional branch masks of the relu clamp per (ray, sorted position), see cips_composite_fwd in cips3d_hip.h:
@@ -334,9 +361,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
       zz = a.z_c[ray * S + i];
       sg = a.sig_c[ray * S + i];
     }
-    if (a.noise) sg += a.noise[ray * E + k] * a.noise_std;
     zall[k] = zz;   // sorted order
-    xs[k] = sg;
+    xs[k] = comp_bwd_x(sg, a.noise, ray * E + k, a.noise_std);
   }
   __syncthreads();
 
@@ -384,7 +410,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
       drow = a.dfeat_c + (ray * S + i) * 32;
       dsg = a.dsig_c + ray * S + i;
     }
-    if (active && !a.live_c) *reinterpret_cast<float4*>(drow + 4 * sub) = make_float4(w * G.x, w * G.y, w * G.z, w * G.w);
+    const bool wr = !a.listed || comp_bwd_can_be_live(xs[k], k, E, a.clamp_mode, a.flags);
+    if (active && !a.live_c && wr) *reinterpret_cast<float4*>(drow + 4 * sub) = make_float4(w * G.x, w * G.y, w * G.z, w * G.w);
     float dsv = 0.f;
     if ((k % SEG) == sub && active) {
       const float delta = (k + 1 < E) ? (zall[k + 1] - zall[k]) : 1e10f;
@@ -398,7 +425,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
       }
       // d alpha / d dens = delta * exp(-delta*dens)
       dsv = dalpha * (delta * expf(-delta * dens)) * dgrad;
-      *dsg = dsv;
+      if (wr) *dsg = dsv;
     }
     if (a.live_c) {
       // live: the weight that scales the row or the dsigma just stored is not zero (a NaN is not zero).  A relu-clamped sample
@@ -414,34 +441,23 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
   }
 }
 
-// Ascending indices of an image's non-zero mask bytes, and their number: one workgroup per image walks its P bytes in tiles
-// of 16 per thread; within a tile a thread's position is the block-wide exclusive scan of the per-thread counts, so the
-// order is the index order whatever the scheduling (no atomics).  Every write lands at a position <= its own index.
+// Ascending indices of an image's listed items, and their number: one workgroup per image walks its P items in tiles of 16
+// per thread; within a tile a thread's position is the block-wide exclusive scan of the per-thread counts, so the order is
+// the index order whatever the scheduling (no atomics).  Every write lands at a position <= its own index.
+// What "listed" means comes from Src: load(o) fetches the 16 items from o on (one tile ahead of their use), bits(tile) turns
+// them into 16 flags, bit j for item o + j, zero past the end.
 constexpr int LIVE_THREADS = 1024, LIVE_TILE = LIVE_THREADS * 16;
-__global__ __launch_bounds__(LIVE_THREADS) void live_points_kernel(const unsigned char* __restrict__ live, int P,
-                                                                   int* __restrict__ idx, int* __restrict__ count) {
+template <class Src>
+__device__ __forceinline__ void live_scan(const Src& src, int P, int* __restrict__ dst, int* __restrict__ count) {
   __shared__ int wsum[LIVE_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned char* src = live + (long long)b * P;
-  int* dst = idx + (long long)b * P;
-  const bool vec = (P & 15) == 0 && (reinterpret_cast<uintptr_t>(live) & 15) == 0;
-  auto load16 = [&](int o) {              // the 16 mask bytes from o on, zeros past the end
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (o >= P) return v;
-    if (vec) return *reinterpret_cast<const uint4*>(src + o);
-    unsigned wd[4] = {0u, 0u, 0u, 0u};
-    for (int j = 0; j < 16 && o + j < P; ++j) wd[j >> 2] |= (unsigned)src[o + j] << (8 * (j & 3));
-    return make_uint4(wd[0], wd[1], wd[2], wd[3]);
-  };
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int base = 0;
-  uint4 cur = load16(tid * 16);
+  auto cur = src.load(tid * 16);
   for (int t0 = 0; t0 < P; t0 += LIVE_TILE) {
     const int o = t0 + tid * 16;
-    const uint4 nxt = load16(o + LIVE_TILE);
-    const unsigned wd[4] = {cur.x, cur.y, cur.z, cur.w};
-    int n = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) n += ((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) ? 1 : 0;
+    const auto nxt = src.load(o + LIVE_TILE);
+    const unsigned m = src.bits(cur);
+    const int n = __popc(m);
     int incl = n;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -456,12 +472,63 @@ __global__ __launch_bounds__(LIVE_THREADS) void live_points_kernel(const unsigne
     int pos = base + before + incl - n;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if ((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) dst[pos++] = o + j;
+      if ((m >> j) & 1u) dst[pos++] = o + j;
     base += total;
     cur = nxt;
     __syncthreads();
   }
-  if (tid == 0) count[b] = base;
+  if (tid == 0) *count = base;
+}
+
+// listed = non-zero mask byte
+struct LiveBytes {
+  const unsigned char* src; int P; bool vec;
+  __device__ uint4 load(int o) const {      // the 16 mask bytes from o on, zeros past the end
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (o >= P) return v;
+    if (vec) return *reinterpret_cast<const uint4*>(src + o);
+    unsigned wd[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < 16 && o + j < P; ++j) wd[j >> 2] |= (unsigned)src[o + j] << (8 * (j & 3));
+    return make_uint4(wd[0], wd[1], wd[2], wd[3]);
+  }
+  __device__ unsigned bits(const uint4& t) const {
+    const unsigned wd[4] = {t.x, t.y, t.z, t.w};
+    unsigned m = 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m |= ((wd[j >> 2] >> (8 * (j & 3))) & 0xffu) ? 1u << j : 0u;
+    return m;
+  }
+};
+__global__ __launch_bounds__(LIVE_THREADS) void live_points_kernel(const unsigned char* __restrict__ live, int P,
+                                                                   int* __restrict__ idx, int* __restrict__ count) {
+  const int b = blockIdx.x;
+  const LiveBytes src{live + (long long)b * P, P, (P & 15) == 0 && (reinterpret_cast<uintptr_t>(live) & 15) == 0};
+  live_scan(src, P, idx + (long long)b * P, count + b);
+}
+
+// listed = comp_bwd_can_be_live of the flat path's sample (no fine set, identity order: item p of an image is position p % S
+// of ray p / S, and sigma / noise are indexed alike).  The flags are formed at the load; nothing here has to be fast.
+struct LiveClamp {
+  const float *sigma, *noise;     // the image's P values (noise may be NULL)
+  float noise_std;
+  int P, S, clamp_mode, flags;
+  __device__ unsigned load(int o) const {
+    unsigned m = 0u;
+    for (int j = 0; j < 16 && o + j < P; ++j) {
+      const float x = comp_bwd_x(sigma[o + j], noise, o + j, noise_std);
+      m |= comp_bwd_can_be_live(x, (o + j) % S, S, clamp_mode, flags) ? 1u << j : 0u;
+    }
+    return m;
+  }
+  __device__ unsigned bits(unsigned t) const { return t; }
+};
+__global__ __launch_bounds__(LIVE_THREADS) void live_points_clamp_kernel(const float* __restrict__ sigma,
+                                                                         const float* __restrict__ noise, float noise_std, int P,
+                                                                         int S, int clamp_mode, int flags, int* __restrict__ idx,
+                                                                         int* __restrict__ count) {
+  const int b = blockIdx.x;
+  const LiveClamp src{sigma + (long long)b * P, noise ? noise + (long long)b * P : nullptr, noise_std, P, S, clamp_mode, flags};
+  live_scan(src, P, idx + (long long)b * P, count + b);
 }
 
 inline int rays_per_block_for(size_t bytes_per_ray) {
@@ -539,6 +606,35 @@ extern "C" int cips_live_points(const unsigned char* live, int B, int P, int* id
   return CIPS_CHECK_LAUNCH();
 }
 
+extern "C" int cips_live_points_clamp(const float* sigma, const float* noise, float noise_std, int B, int n, int S, int clamp_mode,
+                                      int flags, int* idx, int* count, cips_stream_t stream) {
+  if (!sigma || !idx || !count || B <= 0 || n <= 0 || S <= 0 || (long long)n * S > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_points_clamp_kernel, dim3(B), dim3(LIVE_THREADS), 0, (hipStream_t)stream, sigma, noise, noise_std,
+                     n * S, S, clamp_mode, flags, idx, count);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_composite_has_dead_samples(int clamp_mode) { return comp_has_dead_samples(clamp_mode) ? 1 : 0; }
+
+static int composite_bwd_launch(CompArgs a, cips_stream_t stream) {
+  size_t per_ray = (size_t)6 * a.E * sizeof(float);
+  int rpb = rays_per_block_for(per_ray);
+  int blocks = (int)((a.R + rpb - 1) / rpb);
+  hipLaunchKernelGGL(composite_bwd_kernel, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_composite_bwd_listed(const float* feat, const float* sigma, const float* z, const float* noise,
+                                         float noise_std, const float* dfea, float* dfeat, float* dsigma, int R, int S,
+                                         int clamp_mode, int flags, cips_stream_t stream) {
+  if (R <= 0 || S <= 0 || !feat || !sigma || !z || !dfea || !dfeat || !dsigma) return (int)hipErrorInvalidValue;
+  CompArgs a = {};
+  a.feat_c = feat; a.sig_c = sigma; a.z_c = z; a.noise = noise; a.noise_std = noise_std; a.dfea = dfea;
+  a.dfeat_c = dfeat; a.dsig_c = dsigma; a.listed = 1;
+  a.R = R; a.S = S; a.E = S; a.clamp_mode = clamp_mode; a.flags = flags;
+  return composite_bwd_launch(a, stream);
+}
+
 extern "C" int cips_composite_bwd_live(const float* feat_c, const float* sig_c, const float* z_c,
                                        const float* feat_f, const float* sig_f, const float* z_f,
                                        const float* noise, float noise_std, const int* order, const float* dfea,
@@ -554,9 +650,5 @@ extern "C" int cips_composite_bwd_live(const float* feat_c, const float* sig_c, 
   a.live_c = live_c; a.live_f = live_f;
   a.R = R; a.S = S; a.E = feat_f ? 2 * S : S; a.clamp_mode = clamp_mode; a.flags = flags;
   a.clamp_pin = clamp_in; a.clamp_rec = nullptr;
-  size_t per_ray = (size_t)6 * a.E * sizeof(float);
-  int rpb = rays_per_block_for(per_ray);
-  int blocks = (R + rpb - 1) / rpb;
-  hipLaunchKernelGGL(composite_bwd_kernel, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
-  return CIPS_CHECK_LAUNCH();
+  return composite_bwd_launch(a, stream);
 }

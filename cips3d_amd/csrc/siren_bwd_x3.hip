@@ -898,22 +898,60 @@ __global__ __launch_bounds__(256, 1) void siren_bwd_x4_kernel(BwdX3Args a) {
 //   db = sum_b gain_b d phase_b.  Layer 0's input is box_scale * point.  Fixed summation order: chunks, then images.
 // One workgroup of 128 threads per output row: [0,128) rows of dW1 (+ layer 0 and the sigma head of feature f),
 // [128,192) rows of dWc, [192,224) rows of dWf (+ its bias), 224: the sigma bias.
+// SEGS (cips_siren_bwd_x3_finalize_segments): the partials are the EVEN launch's, image b's rows are first_b .. first_b + n_b - 1
+// of the img table, and every value the code below reads from "row b" is the sum of that column over those rows, formed here
+// in ascending row order — the value siren_bwd_reduce_segments_kernel would have stored, so the 16 gradients are the
+// two-launch sequence's bit for bit, without the per-image sums' round trip through HBM.
 struct FinArgs {
   cips_siren_weights w;
   const float* sred; const float* gpart;
+  const int* img;
   cips_siren_grads o;
   int B, chunks;
 };
 
+template <bool SEGS>
 __global__ __launch_bounds__(128) void siren_bwd_finalize_kernel(FinArgs a) {
   __shared__ float cols[8];
   __shared__ float red[128];
   const int task = blockIdx.x, j = threadIdx.x;
-  const int B = a.B, C = a.chunks;
+  const int B = a.B, C = SEGS ? 1 : a.chunks;
+  // SEGS: s0 / s1 = the sums of p0[w * W0] / p1[w * W1] over image b's rows w, ascending (p1 may be NULL).  The rows are loaded
+  // FIN_ROWS at a time before any is added: the walk costs a load latency per batch, not per row, and a thread that needs two
+  // columns (the SRED columns ride with threads 0..7) pays for one walk.
+  constexpr int FIN_ROWS = 16;
+  auto seg_sum = [&](int b, const float* p0, int W0, const float* p1, int W1, float& s0, float& s1) {
+    const int first = a.img[2 * b], n = a.img[2 * b + 1];
+    p0 += (long long)first * W0;
+    if (p1) p1 += (long long)first * W1;
+    float a0 = 0.f, a1 = 0.f;
+    for (int i = 0; i < n; i += FIN_ROWS) {
+      float v0[FIN_ROWS], v1[FIN_ROWS];
+#pragma unroll
+      for (int u = 0; u < FIN_ROWS; ++u) {
+        const int r = i + u < n ? i + u : n - 1;
+        v0[u] = p0[(long long)r * W0];
+        v1[u] = p1 ? p1[(long long)r * W1] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < FIN_ROWS; ++u)
+        if (i + u < n) { a0 = i + u ? a0 + v0[u] : v0[u]; a1 = i + u ? a1 + v1[u] : v1[u]; }
+    }
+    s0 = a0; s1 = a1;
+  };
+  // element `off` of row (b, c) of a partial array with rows of W floats (SEGS: c = 0, the image's row sum)
+  auto at = [&](const float* arr, int W, int b, int c, int off) {
+    if constexpr (!SEGS) return arr[((long long)b * C + c) * W + off];
+    else {
+      float s0, s1;
+      seg_sum(b, arr + off, W, nullptr, 0, s0, s1);
+      return s0;
+    }
+  };
+  auto colofs = [](int f, int col) { return (f >> 5) * 256 + (f & 31) * 8 + col; };
   auto colsum = [&](int b, int f, int col) {       // sum over chunks of column `col` of feature row f (SRED layout)
     float s = 0.f;
-    const float* p = a.sred + (long long)b * C * SRED + (f >> 5) * 256 + (f & 31) * 8 + col;
-    for (int c = 0; c < C; ++c) s += p[(long long)c * SRED];
+    for (int c = 0; c < C; ++c) s += at(a.sred, SRED, b, c, colofs(f, col));
     return s;
   };
   auto block_sum = [&](float v) {
@@ -938,12 +976,18 @@ __global__ __launch_bounds__(128) void siren_bwd_finalize_kernel(FinArgs a) {
     const float wj = Wrow[j];
     float acc_w = 0.f, acc_b = 0.f, acc_ws = 0.f, acc_b0 = 0.f, acc_w0[3] = {0.f, 0.f, 0.f};
     for (int b = 0; b < B; ++b) {
-      float v = 0.f;
-      const float* gp = a.gpart + (long long)b * C * GPART + goff + f * H + j;
-      for (int c = 0; c < C; ++c) v += gp[(long long)c * GPART];
+      float v = 0.f, cs = 0.f;
+      if constexpr (SEGS) {
+        float sv, sc;
+        seg_sum(b, a.gpart + goff + f * H + j, GPART, j < 8 ? a.sred + colofs(f, j) : nullptr, SRED, sv, sc);
+        v += sv; cs += sc;
+      } else {
+        for (int c = 0; c < C; ++c) v += at(a.gpart, GPART, b, c, goff + f * H + j);
+        if (j < 8) cs = colsum(b, f, j);
+      }
       const float gn = gain[b * gdim + f];
       acc_w = fmaf(gn, v, acc_w);
-      if (j < 8) cols[j] = colsum(b, f, j);
+      if (j < 8) cols[j] = cs;
       const float dot = block_sum(v * wj);           // (its barriers also publish cols)
       if (j == 0) {
         const float dph = l1 ? cols[4] : cols[6];
@@ -978,25 +1022,43 @@ __global__ __launch_bounds__(128) void siren_bwd_finalize_kernel(FinArgs a) {
       float v = 0.f;
       for (int b = 0; b < B; ++b) {
         float vb = 0.f;
-        const float* gp = a.gpart + (long long)b * C * GPART + ch * HC + j;
-        for (int c = 0; c < C; ++c) vb += gp[(long long)c * GPART + GP_GF0] + gp[(long long)c * GPART + GP_GF1];
+        if constexpr (SEGS) {
+          float s0, s1;
+          seg_sum(b, a.gpart + GP_GF0 + ch * HC + j, GPART, a.gpart + GP_GF1 + ch * HC + j, GPART, s0, s1);
+          vb += s0 + s1;
+        } else {
+          for (int c = 0; c < C; ++c) vb += at(a.gpart, GPART, b, c, GP_GF0 + ch * HC + j) + at(a.gpart, GPART, b, c, GP_GF1 + ch * HC + j);
+        }
         v += vb;
       }
       a.o.dwf[ch * HC + j] = v;
     }
-    if (j == 0) {
-      float s = 0.f;
-      for (int b = 0; b < B; ++b) s += colsum(b, ch, 7) + colsum(b, 64 + ch, 7);     // waves 0 and 2 hold the two halves
-      a.o.dbf[ch] = s;
-    }
-  } else if (j == 0) {
+    // the bias: one image's term per thread of the second wave (beside the first wave's walk above), added in image order
     float s = 0.f;
-    for (int b = 0; b < B; ++b)
-      for (int c = 0; c < C; ++c) {
-        const float* p = a.sred + ((long long)b * C + c) * SRED + 1024;
-        s += (p[0] + p[1]) + (p[2] + p[3]);
+    for (int b0 = 0; b0 < B; b0 += 64) {
+      const int b = b0 + j - 64;
+      if (j >= 64 && b < B) red[j - 64] = colsum(b, ch, 7) + colsum(b, 64 + ch, 7);     // waves 0 and 2 hold the two halves
+      __syncthreads();
+      if (j == 0)
+        for (int t = 0; t < 64 && b0 + t < B; ++t) s += red[t];
+      __syncthreads();
+    }
+    if (j == 0) a.o.dbf[ch] = s;
+  } else {
+    // the sigma bias: one row's term per thread, added in row order (images, then chunks)
+    float s = 0.f;
+    for (int i0 = 0; i0 < B * C; i0 += 128) {
+      const int it = i0 + j;
+      if (it < B * C) {
+        const int b = it / C, c = it % C;
+        red[j] = (at(a.sred, SRED, b, c, 1024) + at(a.sred, SRED, b, c, 1025)) + (at(a.sred, SRED, b, c, 1026) + at(a.sred, SRED, b, c, 1027));
       }
-    a.o.dbs[0] = s;
+      __syncthreads();
+      if (j == 0)
+        for (int t = 0; t < 128 && i0 + t < B * C; ++t) s += red[t];
+      __syncthreads();
+    }
+    if (j == 0) a.o.dbs[0] = s;
   }
 }
 
@@ -1120,13 +1182,25 @@ static int siren_bwd_x3_launch(const cips_siren_weights* w, const float* points,
   return CIPS_CHECK_LAUNCH();
 }
 
-extern "C" int cips_siren_bwd_x3_finalize(const cips_siren_weights* w, const float* sred, const float* gpart, int B,
-                                          int chunks, const cips_siren_grads* out, cips_stream_t stream) {
+static int siren_bwd_finalize_launch(const cips_siren_weights* w, const float* sred, const float* gpart, const int* img, int B,
+                                     int chunks, const cips_siren_grads* out, cips_stream_t stream) {
   if (!w || !sred || !gpart || !out || B <= 0 || chunks <= 0) return (int)hipErrorInvalidValue;
   const float* const* po = reinterpret_cast<const float* const*>(out);
   for (int i = 0; i < 16; ++i) if (!po[i]) return (int)hipErrorInvalidValue;
   FinArgs a;
-  a.w = *w; a.sred = sred; a.gpart = gpart; a.o = *out; a.B = B; a.chunks = chunks;
-  hipLaunchKernelGGL(siren_bwd_finalize_kernel, dim3(225), dim3(128), 0, (hipStream_t)stream, a);
+  a.w = *w; a.sred = sred; a.gpart = gpart; a.img = img; a.o = *out; a.B = B; a.chunks = chunks;
+  if (img) hipLaunchKernelGGL(siren_bwd_finalize_kernel<true>, dim3(225), dim3(128), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(siren_bwd_finalize_kernel<false>, dim3(225), dim3(128), 0, (hipStream_t)stream, a);
   return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_siren_bwd_x3_finalize(const cips_siren_weights* w, const float* sred, const float* gpart, int B,
+                                          int chunks, const cips_siren_grads* out, cips_stream_t stream) {
+  return siren_bwd_finalize_launch(w, sred, gpart, nullptr, B, chunks, out, stream);
+}
+
+extern "C" int cips_siren_bwd_x3_finalize_segments(const cips_siren_weights* w, const float* sred, const float* gpart,
+                                                   const int* img, int B, const cips_siren_grads* out, cips_stream_t stream) {
+  if (!img) return (int)hipErrorInvalidValue;
+  return siren_bwd_finalize_launch(w, sred, gpart, img, B, 1, out, stream);
 }

@@ -857,7 +857,9 @@ class GeneratorNerfINR(nn.Module):
         clamp = ops._CLAMP[s.clamp_mode]
         with _grad_ctx(nerf_grad):
             if g.form == "march":
-                geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled())
+                # (the last entry: the lists of the backward's live samples may be made in the forward — _head and
+                # _forward_styles join their stream, ops.live_forward_join)
+                geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled(), True)
                 return self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
                                         noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None)
             if g.form == "rays":
@@ -901,7 +903,11 @@ class GeneratorNerfINR(nn.Module):
         if not nerf_grad:
             pixels_fea = pixels_fea.detach()
         self._join_side()
-        return self.inr_net(pixels_fea, style_dict), aux
+        rgb = self.inr_net(pixels_fea, style_dict)
+        # the ray march's forward-time lists (ops.live_plan_forward) ran beside the head on a stream of their own: joined
+        # here, behind the head — in front of it the caller's stream would wait for them with nothing else to do
+        ops.live_forward_join(pixels_fea.device)
+        return rgb, aux
 
     def _part_grad(self, s, g, nerf_styles, style_dict, device):
         """part_grad_forward (generator.py:1536-1657): a `randperm(n)` splits the pixels of every image into `grad_points`
@@ -978,6 +984,7 @@ class GeneratorNerfINR(nn.Module):
             # hipGraph capture would end with an unjoined stream.  Nor may it leave the gradient ports _render opened
             # for the head pending: they hold the modulation graph, and the next forward() must not find them
             self._join_side()
+            ops.live_forward_join()         # likewise the ray march's list stream (no-op after _head's join)
             self.inr_net._tail = None
 
     def _density_styles(self, z_nerf, psi):

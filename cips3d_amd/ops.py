@@ -193,6 +193,15 @@ SIREN_BWD_LIVE = os.environ.get("CIPS_SIREN_BWD_LIVE", "1") != "0"
 # ... and deals the live samples evenly to the workgroups of that launch (cips_siren_bwd_x3_live_plan / *_live_even /
 # cips_siren_bwd_x3_reduce_segments) instead of giving every image the same number of workgroups.  "0": the *_live calls.
 SIREN_BWD_EVEN = os.environ.get("CIPS_SIREN_BWD_EVEN", "1") != "0"
+# ... and takes the lists and the EVEN plan from the FORWARD pass: what makes a sample dead under the relu clamp is known once the
+# march has written sigma, so a training forward builds both on a stream of their own, beside the INR head, and the backward goes
+# from the compositing backward (cips_composite_bwd_listed) straight into the SIREN backward.  Honoured only with the two
+# switches above on, backward "x3", no clamp pin and a clamp that has dead samples.  "0": the lists are made in the backward.
+SIREN_LIVE_FWD = os.environ.get("CIPS_SIREN_LIVE_FWD", "1") != "0"
+# True: with SIREN_LIVE_FWD the finalisation sums the EVEN launch's rows itself (cips_siren_bwd_x3_finalize_segments, same bits)
+# instead of reading the per-image sums of cips_siren_bwd_x3_reduce_segments.  Off: at the headline shape the row walk measured
+# 91 us against 51 + 18 us for the two launches (profiles/fwd_live_ab.txt).
+SIREN_FIN_SEGMENTS = False
 
 
 class SirenFunction(torch.autograd.Function):
@@ -323,7 +332,8 @@ def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None, live=None):
     in _SIREN_NAMES order.  The sample points are either given (B,P,3) or regenerated in-kernel from `rays` (a RayParams
     struct).  SIREN_BWD_MODE picks the form for given points; `rays` always takes the fused form, whatever the mode says
     (the staged data passes read a points tensor).  `live` (fused form only): (idx (B,P) int32, count (B) int32), the
-    points to process per image (cips_siren_bwd_x3_live); the rows of dfeat / dsigma at other points are never read."""
+    points to process per image (cips_siren_bwd_x3_live); the rows of dfeat / dsigma at other points are never read.  A
+    `live` of four, (idx, count, seg, img), brings the EVEN plan of those counts along (live_plan_forward)."""
     dev = t["w0"].device
     dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
     dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
@@ -344,6 +354,64 @@ def live_points(mask):
     return idx, count
 
 
+def _live_plan(count, B, P):
+    """(seg (B * chunks, 4) int32, img (B, 2) int32): the EVEN partition of lists with these counts (cips_siren_bwd_x3_live_plan)"""
+    lib = _lib.load()
+    seg = torch.empty(B * lib.cips_siren_bwd_x3_chunks(B, P), 4, dtype=torch.int32, device=count.device)
+    img = torch.empty(B, 2, dtype=torch.int32, device=count.device)
+    check(lib.cips_siren_bwd_x3_live_plan(_p(count), B, P, _p(seg), _p(img), _stream()), "cips_siren_bwd_x3_live_plan")
+    return seg, img
+
+
+# The stream the forward-time lists and plan run on, one per device: neither the caller's nor the generator's INR-mapping side
+# stream, which is joined in front of the head.  live_forward_join makes the caller's stream wait for it.
+_LIVE_STREAMS = {}
+_LIVE_PENDING = set()
+
+
+def live_forward_ok(clamp_mode, pin):
+    """the forward-time lists apply (see SIREN_LIVE_FWD)"""
+    return (SIREN_LIVE_FWD and SIREN_BWD_LIVE and SIREN_BWD_EVEN and SIREN_BWD_MODE == "x3" and pin is None
+            and bool(_lib.load().cips_composite_has_dead_samples(clamp_mode)))
+
+
+def live_plan_forward(sigma, noise, noise_std, B, n, S, clamp_mode, flags):
+    """(idx, count, seg, img) of the flat path's samples the compositing backward can give a non-zero gradient
+    (cips_live_points_clamp) and their EVEN plan, launched on the device's list stream behind the caller's.  Nothing waits for
+    them here: the consumer (RayMarchFunction.backward) does, and live_forward_join() joins the stream for callers that may
+    never run it."""
+    lib = _lib.load()
+    dev = sigma.device
+    P = n * S
+    idx = torch.empty(B, P, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    side = _LIVE_STREAMS.get(dev.index)
+    if side is None:
+        side = _LIVE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        check(lib.cips_live_points_clamp(_p(sigma), _p(noise), float(noise_std), B, n, S, clamp_mode, flags, _p(idx), _p(count),
+                                         _stream()), "cips_live_points_clamp")
+        seg, img = _live_plan(count, B, P)
+    for v in (sigma, noise, idx, count):
+        if v is not None:
+            v.record_stream(side)
+    for v in (seg, img):
+        v.record_stream(torch.cuda.current_stream(dev))
+    _LIVE_PENDING.add(dev.index)
+    return idx, count, seg, img
+
+
+def live_forward_join(device=None):
+    """the caller's stream waits for the forward-time lists of `device` (None: of every device); a no-op when none is pending.
+    The generator calls it behind the INR head's forward and on every exit of its forward, so that a captured forward
+    without a backward ends with no unjoined stream."""
+    for i in [torch.device(device).index] if device is not None else list(_LIVE_PENDING):
+        if i in _LIVE_PENDING:
+            _LIVE_PENDING.discard(i)
+            torch.cuda.current_stream(i).wait_stream(_LIVE_STREAMS[i])
+
+
 def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
     """one kernel: recompute + data gradients + weight-gradient contractions on split bf16, nothing staged in HBM"""
     lib = _lib.load()
@@ -354,14 +422,16 @@ def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
     sw_ = lib.cips_siren_bwd_x3_sred()
     sred = torch.empty(B * chunks, sw_, device=dev)
     gpart = torch.empty(B * chunks, gw, device=dev)
-    even = live is not None and SIREN_BWD_EVEN
+    planned = live is not None and len(live) == 4
+    even = planned or (live is not None and SIREN_BWD_EVEN)
     img = None
-    if even:
+    if planned:
+        idx, count, seg, img = live
+    elif even:
         # plan -> kernel -> segmented reduction: the partition follows the counts on the device, nothing is read back
         idx, count = live
-        seg = torch.empty(B * chunks, 4, dtype=torch.int32, device=dev)
-        img = torch.empty(B, 2, dtype=torch.int32, device=dev)
-        check(lib.cips_siren_bwd_x3_live_plan(_p(count), B, P, _p(seg), _p(img), _stream()), "cips_siren_bwd_x3_live_plan")
+        seg, img = _live_plan(count, B, P)
+    if even:
         if points is not None:
             check(lib.cips_siren_bwd_x3_live_even(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(idx), _p(count), _p(seg),
                                                   _p(sred), _p(gpart), B, P, _stream()), "cips_siren_bwd_x3_live_even")
@@ -390,6 +460,11 @@ def _siren_backward_fused(t, dfeat, dsigma, B, P, points, rays, live=None):
         setattr(sg, "d" + n, _p(v))
     # the partials are summed per image first (88 MB at C2: bandwidth-bound); the finalisation then walks B rows instead of
     # B * chunks
+    if planned and SIREN_FIN_SEGMENTS:
+        # ... or the finalisation walks an image's rows itself: no launch and no per-image sums in between
+        check(lib.cips_siren_bwd_x3_finalize_segments(C.byref(sw), _p(sred), _p(gpart), _p(img), B, C.byref(sg), _stream()),
+              "cips_siren_bwd_x3_finalize_segments")
+        return outs
     if even:
         # an image's rows are img[b] = (first, n) here, n from 1 to all of them: one launch sums both arrays
         SRr = torch.empty(B, sw_, device=dev)
@@ -746,12 +821,15 @@ class RayMarchFunction(torch.autograd.Function):
     samples along each ray (cips_march_fwd_x3).  Under no_grad nothing per-sample reaches HBM (4 S + 132 B per ray);
     a training forward also writes feat / sigma / z for the backward, which is cips_composite_bwd followed by the fused
     SIREN backward with the points regenerated in-kernel (cips_siren_bwd_x3_rays) — with SIREN_BWD_LIVE their *_live forms
-    and cips_live_points between them: the SIREN backward then runs over the samples with a non-zero upstream gradient."""
+    and cips_live_points between them: the SIREN backward then runs over the samples with a non-zero upstream gradient.
+    With SIREN_LIVE_FWD, for a caller that says so in geom and joins the list stream behind its next stage, the training
+    forward makes those lists and their EVEN plan itself, on another stream (live_plan_forward), and the backward is
+    cips_composite_bwd_listed followed by the SIREN backward."""
 
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
         lib = _lib.load()
-        B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom
+        B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom[:9]
         t = _siren_prep(siren)
         xg, yg, zg, cam2world, jitter, noise = _ray_prep(xg, yg, zg, cam2world, jitter, noise if noise_std != 0.0 else None)
         dev = cam2world.device
@@ -773,8 +851,11 @@ class RayMarchFunction(torch.autograd.Function):
         if rec is not None and CLAMP_REC is not None:
             CLAMP_REC.append(rec.reshape(B * n, S))
         ctx.clamp_mask = pin
+        # a tenth entry of geom, true: the caller joins the list stream (live_forward_join) whether or not a backward follows
+        ctx.live_fwd = train and len(geom) > 9 and bool(geom[9]) and live_forward_ok(clamp_mode, pin)
         if train:
-            ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values())
+            lists = live_plan_forward(sigma, noise, noise_std, B, n, S, clamp_mode, flags) if ctx.live_fwd else ()
+            ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values(), *lists)
         ctx.geom = geom
         ctx.mark_non_differentiable(depth)
         return fea, depth
@@ -783,15 +864,23 @@ class RayMarchFunction(torch.autograd.Function):
     def backward(ctx, dfea, _ddepth):
         lib = _lib.load()
         xg, yg, zg, cam2world, jitter, noise, feat, sigma, z = ctx.saved_tensors[:9]
-        t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[9:]))
-        B, H, W, S, zc, noise_std, clamp_mode, flags, _ = ctx.geom
+        t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[9:9 + len(_SIREN_NAMES)]))
+        B, H, W, S, zc, noise_std, clamp_mode, flags, _ = ctx.geom[:9]
         n = H * W
         R = B * n
         dfea = _c(dfea)
         dfeat = torch.empty_like(feat)
         dsig = torch.empty_like(sigma)
         use_live = SIREN_BWD_LIVE and SIREN_BWD_MODE == "x3"
-        if use_live:
+        live = None
+        if ctx.live_fwd:
+            live = ctx.saved_tensors[9 + len(_SIREN_NAMES):]
+            # the lists' stream, whether or not a live_forward_join has made some stream wait for it already
+            _LIVE_PENDING.discard(dfea.device.index)
+            torch.cuda.current_stream(dfea.device).wait_stream(_LIVE_STREAMS[dfea.device.index])
+            check(lib.cips_composite_bwd_listed(_p(feat), _p(sigma), _p(z), _p(noise), float(noise_std), _p(dfea), _p(dfeat),
+                                                _p(dsig), R, S, clamp_mode, flags, _stream()), "cips_composite_bwd_listed")
+        elif use_live:
             mask = torch.empty(B, n * S, dtype=torch.uint8, device=dfea.device)
             check(lib.cips_composite_bwd_live(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
                                               _p(dfea), _p(dfeat), _p(dsig), None, None, _p(mask), None, R, S, clamp_mode, flags,
@@ -802,7 +891,9 @@ class RayMarchFunction(torch.autograd.Function):
                                          _stream()), "cips_composite_bwd")
         _tail_gate_publish(dfea.device)
         rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
-        grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live_points(mask) if use_live else None)
+        if live is None and use_live:
+            live = live_points(mask)
+        grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live)
         return (None,) * 7 + grads
 
 

@@ -221,6 +221,11 @@ int cips_siren_bwd_x3_rays_live_even(const cips_siren_weights* w, const cips_ray
                                      float* gpart, int B, cips_stream_t stream);
 int cips_siren_bwd_x3_reduce_segments(const float* sred, const float* gpart, const int* img, int B, float* sred_out,
                                       float* gpart_out, cips_stream_t stream);
+/* cips_siren_bwd_x3_reduce_segments + cips_siren_bwd_x3_finalize (chunks = 1) in one launch: the finalisation sums image
+ * b's rows first_b .. first_b + n_b - 1 of sred / gpart itself, in ascending order.  The 16 gradients are those of the two
+ * calls bit for bit; the per-image sums never reach memory. */
+int cips_siren_bwd_x3_finalize_segments(const cips_siren_weights* w, const float* sred, const float* gpart, const int* img,
+                                        int B, const cips_siren_grads* out, cips_stream_t stream);
 
 /* Fused ray-march for NON-hierarchical sampling: ray set-up + FiLM-SIREN + alpha-composite in one kernel that walks
  * the samples along the ray (a wave owns 32 rays, one lane pair per ray; the running transmittance / feature / depth
@@ -312,6 +317,25 @@ int cips_composite_bwd_live(const float* feat_c, const float* sig_c, const float
  * its non-zero bytes, count[b] their number; idx entries from count[b] on are left as they were.  Deterministic (the order
  * is the index order, no atomics), one launch, one workgroup per image. */
 int cips_live_points(const unsigned char* live, int B, int P, int* idx, int* count, cips_stream_t stream);
+
+/* The live samples of the flat path (no fine set) decided from the FORWARD pass' values.  One rule, evaluated on
+ * x = sigma + noise * noise_std as cips_composite_bwd forms it: can that backward give sample k of a ray a non-zero dfeat
+ * row or a non-zero dsigma, whatever dfea is?  relu: !(x <= 0) (a NaN counts as live), and the ray's last sample under
+ * last_back (bit 0 of flags; white_back adds none); softplus: every sample.  On finite z, features and dfea this lists a
+ * superset of the samples cips_composite_bwd_live reports 1 (equal except where w or dsigma underflow to zero behind an open
+ * clamp).
+ * cips_composite_has_dead_samples(clamp_mode): 1 iff the rule can leave a sample out under that clamp (relu), else 0.
+ * cips_live_points_clamp: cips_live_points with the rule in place of a mask byte: sigma (B, n*S), noise (B, n*S) or NULL,
+ *   P = n*S points per image (must fit an int), sample k = p % S of ray p / S.  Same outputs and ordering guarantee.
+ * cips_composite_bwd_listed: cips_composite_bwd without a fine set, writing the dfeat row and the dsigma of exactly the
+ *   samples the rule lists (the same bits cips_composite_bwd stores there); the rows and dsigma of the others are NOT
+ *   written.  Every feature row is still read.  No clamp_in: a pinned clamp takes cips_composite_bwd_live. */
+int cips_composite_has_dead_samples(int clamp_mode);
+int cips_live_points_clamp(const float* sigma, const float* noise, float noise_std, int B, int n, int S, int clamp_mode,
+                           int flags, int* idx, int* count, cips_stream_t stream);
+int cips_composite_bwd_listed(const float* feat, const float* sigma, const float* z, const float* noise, float noise_std,
+                              const float* dfea, float* dfeat, float* dsigma, int R, int S, int clamp_mode, int flags,
+                              cips_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* generic batched fp32 GEMM on v_mfma_f32_32x32x2_f32 with fused epilogues */
