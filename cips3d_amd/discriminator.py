@@ -13,14 +13,19 @@ exp/comm/op/upfirdn2d.py) but backed by libcips3d_hip.so:
                                             so the R1 double-backward of train.py:387-394 works.
 """
 import collections
+import ctypes
+import functools
 import math
+import os
+import weakref
+from typing import NamedTuple
 
 import torch
 from torch import nn
 from torch.autograd import Function
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 
 
 # ------------------------------------------------------------------------------------------
@@ -53,23 +58,16 @@ class gate_debug:
         GATE_PIN, GATE_REC = self.old
 
 
-
-
 class FusedLeakyReLUFunctionBackward(Function):
     @staticmethod
     def forward(ctx, grad_output, out, negative_slope, scale, planes_only=False):
         ctx.save_for_backward(out)
         ctx.negative_slope, ctx.scale = negative_slope, scale
         if planes_only:
-            # the gated gradient as NHWC split planes ONLY (cips_lrelu_bwd_bias_nhwc): the tensor handed on is a stride-0 zero
-            # placeholder of the right shape that carries the planes (attribute `_cips_nhwc`); its consumers — the implicit-GEMM
-            # data and weight gradient of ONE convolution, chosen by ConvBiasActFunction.backward — read nothing else (_nhwc
-            # refuses a placeholder that lost its planes; _dense refuses to materialise one)
+            # the gated gradient as NHWC split planes ONLY (cips_lrelu_bwd_bias_nhwc): its consumers — the implicit-GEMM data and
+            # weight gradient of ONE convolution, chosen by ConvBiasActFunction.backward — read nothing else (_placeholder)
             P, gb = ops.lrelu_bwd_bias_nhwc(grad_output, out, negative_slope, scale)
-            ph = _zero1(grad_output).expand(grad_output.shape)
-            ph._cips_nhwc = (ph._version, ph.data_ptr(), {(): P})
-            ph._cips_planes_only = True
-            return ph, gb
+            return _placeholder(grad_output, P), gb
         if (grad_output.dim() == 4 and grad_output.dtype == torch.float32 and out.dtype == torch.float32
                 and grad_output.is_cuda and grad_output.is_contiguous() and out.is_contiguous()):
             return ops.lrelu_bwd_bias(grad_output, out, negative_slope, scale)     # one pass: gated gradient + bias sums
@@ -205,9 +203,8 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
-import os as _os
 CONV_MODES = ("bf16x3", "f32", "bf16")
-CONV_MODE = _os.environ.get("CIPS_D_CONV_MODE", "bf16x3")
+CONV_MODE = os.environ.get("CIPS_D_CONV_MODE", "bf16x3")
 
 
 def _conv_mode():
@@ -230,6 +227,17 @@ def _parity_channels_ok(C, O):
     return O % 32 == 0 and O >= 64 and C % 8 == 0
 
 
+def _parity_geometry(stride, pad, pre):
+    """the geometry of the parity data gradient: stride 2 without padding behind a Blur sampled at every pixel"""
+    return pre is not None and pre[3] == 1 and stride == 2 and pad == 0
+
+
+def _conv_planes(H, W, kh, kw, stride, pad, pre):
+    """(Hb, Wb, Ho, Wo): the blurred plane the convolution proper reads (the input's own without a Blur) and the output plane"""
+    Hb, Wb = _pre_shape(H, W, pre)
+    return Hb, Wb, (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
+
+
 def _single_pass(x_shape, w_shape, stride, pad, pre=None):
     """Which of the forward, the data gradient and the weight gradient of an "implicit" / "parity" convolution (_conv_forms)
     the single-pass kernels take -> three booleans, from the shapes alone (the mode is the caller's question).  The kernels walk
@@ -239,10 +247,9 @@ def _single_pass(x_shape, w_shape, stride, pad, pre=None):
     contraction keeps at least eight k-tiles per chunk (cips_conv2d_bf16_ksplit, ops.conv2d_x3_wgrad)."""
     B, C, H, W = x_shape
     O, _, kh, kw = w_shape
-    Hb, Wb = _pre_shape(H, W, pre)
-    Ho, Wo = (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
+    _, _, Ho, Wo = _conv_planes(H, W, kh, kw, stride, pad, pre)
     fwd = C % 64 == 0 and kh * kw * C >= 128
-    if pre is not None and pre[3] == 1 and stride == 2 and pad == 0:        # the parity form's geometry
+    if _parity_geometry(stride, pad, pre):
         dgrad = O % 64 == 0 and O >= 128
     else:
         dgrad = O % 64 == 0 and kh * kw * O >= 128
@@ -255,18 +262,17 @@ def _conv_forms(x_shape, w_shape, stride, pad, pre=None):
     (B, C, H, W) input under an (O, C, kh, kw) filter bank take -> three names out of "rgb" / "implicit" / "parity" / "f32".
     Shapes and CONV_MODE only.  `pre` is the folded Blur (see below; only its pads and its sampling stride are read): the
     convolution proper then runs on the blurred (Hb, Wb) map, and a data gradient that is not "parity" is the un-blurred
-    convolution's, followed by the Blur's transpose.  An "implicit" weight gradient is still declined by
-    ops.conv2d_x3_wgrad when ops.conv2d_x3_wgrad_declines(B, Ho * Wo), and is then computed in the f32 form."""
+    convolution's, followed by the Blur's transpose.  An "implicit" weight gradient is still declined where
+    ops.conv2d_x3_wgrad_declines(B, Ho * Wo), and is then computed in the f32 form (_ConvPlan.wgrad_declined)."""
     B, C, H, W = x_shape
     O, _, kh, kw = w_shape
     x3 = _conv_mode() != "f32"                    # "bf16": the same forms, single-pass where _single_pass allows
-    Hb, Wb = _pre_shape(H, W, pre)
-    Ho, Wo = (Hb + 2 * pad - kh) // stride + 1, (Wb + 2 * pad - kw) // stride + 1
+    Hb, Wb, Ho, Wo = _conv_planes(H, W, kh, kw, stride, pad, pre)
     planes8 = Ho > 0 and Wo > 0 and (Ho * Wo) % 8 == 0             # output planes in 8-pixel vectors
     rgb = kh == 1 and kw == 1 and stride == 1 and pad == 0 and C <= 4 and (Hb * Wb) % 4 == 0
     fallback = "rgb" if rgb else "f32"
     fwd = wgrad = "implicit" if x3 and _implicit_channels_ok(C, O) and planes8 else fallback
-    if pre is not None and pre[3] == 1 and stride == 2 and pad == 0 and x3 and _parity_channels_ok(C, O) and planes8:
+    if _parity_geometry(stride, pad, pre) and x3 and _parity_channels_ok(C, O) and planes8:
         dgrad = "parity"
     elif stride == 1 and kh - 1 - pad >= 0 and x3 and _implicit_channels_ok(O, C) and (Hb * Wb) % 8 == 0:
         dgrad = "implicit"            # dx = conv(dy, flipped weights with the channel roles swapped), padding kh - 1 - pad
@@ -275,66 +281,74 @@ def _conv_forms(x_shape, w_shape, stride, pad, pre=None):
     return fwd, dgrad, wgrad
 
 
-# NHWC planes of an activation / gradient are shared between the convolution ops that read the same tensor inside ONE
-# autograd node (dy feeds both the data and the weight gradient; the forward's planes of x feed its weight gradient):
-# a memo that only lives while that node's forward / backward runs.  It is per thread (autograd runs backward nodes
-# on its own threads) and every entry holds the SOURCE tensor as well as its planes: while the memo is alive the
-# source's storage cannot be freed and handed to another tensor of the same shape, so the (address, shape, version) key
-# cannot alias stale planes.
-import threading as _threading
-_tls = _threading.local()
+class _ConvPlan(NamedTuple):
+    """what follows from the shapes of one convolution call and CONV_MODE: the one place the functions below ask"""
+    blurred: tuple          # (Hb, Wb): the plane the convolution proper reads
+    out_shape: tuple        # (B, O, Ho, Wo)
+    forms: tuple            # _conv_forms: (forward, data gradient, weight gradient)
+    single: tuple           # the same three in one bf16 MFMA pass?  Mode "bf16", an "implicit" / "parity" form and _single_pass
+    wgrad_declined: bool    # an "implicit" weight gradient whose batch ops.conv2d_x3_wgrad declines: computed in the f32 form
+    planes_only: tuple      # may the gated gradient of a ConvBiasAct layer exist as NHWC planes only: [need_dx] (_planes_only_ok)
 
 
-def _memo():
-    if not hasattr(_tls, "shared"):
-        _tls.shared, _tls.depth = {}, 0
-    return _tls
+def _conv_plan(x_shape, w_shape, stride, pad, pre=None):
+    """the _ConvPlan of y = conv(Blur(x), w), memoised per mode, shapes (tuples or torch.Size) and the Blur's pads and sampling
+    stride — all of `pre` that is read.  The memo also holds what the rule helpers answered (_implicit_channels_ok,
+    _parity_channels_ok, ops.conv2d_*_wgrad_declines): whoever patches one of those calls _conv_plan_of.cache_clear()."""
+    return _conv_plan_of(_conv_mode(), x_shape, w_shape, stride, pad, pre and pre[1:])
 
 
-def _key(t):
-    return (t.data_ptr(), tuple(t.shape), t._version)
+@functools.lru_cache(maxsize=4096)
+def _conv_plan_of(mode, x_shape, w_shape, stride, pad, pads_down):
+    pre = pads_down and (None,) + tuple(pads_down)
+    (B, _, H, W), (O, _, kh, kw) = x_shape, w_shape
+    Hb, Wb, Ho, Wo = _conv_planes(H, W, kh, kw, stride, pad, pre)
+    forms = _conv_forms(x_shape, w_shape, stride, pad, pre)
+    single = tuple(mode == "bf16" and f in ("implicit", "parity") and s
+                   for f, s in zip(forms, _single_pass(x_shape, w_shape, stride, pad, pre)))
+    declined = forms[2] == "implicit" and ops.conv2d_x3_wgrad_declines(B, Ho * Wo)
+    # planes only: when BOTH consumers of the gated gradient — the convolution's weight gradient and, if asked for, its data
+    # gradient — take forms that read planes and nothing else (a weight gradient the single pass declines is the 3-pass kernel's)
+    po = forms[2] == "implicit" and not declined
+    return _ConvPlan((Hb, Wb), (B, O, Ho, Wo), forms, single, declined, (po, po and forms[1] in ("implicit", "parity")))
 
 
-class _Shared:
-    """dict-like view used by the Functions below: key -> planes"""
-
-    @staticmethod
-    def get(key_or_tensor):
-        m = _memo()
-        ent = m.shared.get(key_or_tensor)
-        return ent[1] if ent is not None else None
+# A FusedLeakyReLU backward may hand its gated gradient on as NHWC planes ONLY (PLANES_ONLY_GRADIENT): the tensor is then a
+# placeholder, a stride-0 expansion of a zero element that only placeholders expand, carrying the planes as `_cips_nhwc`.  Paths
+# that read planes take them from it (_grad_planes); every path that reads VALUES goes through _dense, which refuses it.
+_ZERO1 = {}                 # the element the _WeightGradPort handles expand (ordinary tensors: their values are zeros)
+_PLACEHOLDER_ZERO = {}      # the element planes-only placeholders expand ...
+_PLACEHOLDER_PTRS = set()   # ... and its address: what _is_planes_only recognises (the cached elements are never freed)
 
 
-_shared = _Shared()
+def _zero1(like, cache=_ZERO1, ptrs=None):
+    """one zero element per (device, dtype), made once (a fill launch per convolution call otherwise); never written"""
+    key = (like.device, like.dtype)
+    z = cache.get(key)
+    if z is None:
+        z = torch.zeros(1, device=like.device, dtype=like.dtype)
+        if like.is_cuda and torch.cuda.is_current_stream_capturing():
+            return z                                   # not cached: it lives in the capturing graph's pool
+        cache[key] = z
+        if ptrs is not None:
+            ptrs.add(z.data_ptr())
+    return z
 
 
-class _share_planes:
-    def __init__(self, *pairs):                 # (tensor, Planes or None) whose planes are already known
-        self.pairs = pairs
-
-    def __enter__(self):
-        m = _memo()
-        m.depth += 1
-        for ent in self.pairs:
-            t, p = ent[0], ent[1]
-            if p is not None:
-                m.shared[_key(t) + _pre_sig(ent[2] if len(ent) > 2 else None)] = (t, p)
-
-    def __exit__(self, *exc):
-        m = _memo()
-        m.depth -= 1
-        if m.depth == 0:
-            m.shared.clear()
+def _placeholder(like, planes):
+    """a planes-only gradient shaped like `like`: no values, `planes` are its NHWC split planes"""
+    ph = _zero1(like, _PLACEHOLDER_ZERO, _PLACEHOLDER_PTRS).expand(like.shape)
+    ph._cips_nhwc = (ph._version, ph.data_ptr(), {(): planes})
+    ph._cips_planes_only = True
+    return ph
 
 
 def _is_planes_only(t):
-    """a FusedLeakyReLU-backward placeholder: flagged, or — should the flag have been lost with the Python object — recognisable
-    by its storage: an expansion of THIS module's cached zero element (an ordinary stride-0 tensor, e.g. autograd's gradient of
-    a .sum(), is not one)"""
-    if getattr(t, "_cips_planes_only", False):
-        return True
-    z = _ZERO1.get((t.device, t.dtype))
-    return z is not None and t.dim() == 4 and t.numel() > 1 and t.data_ptr() == z.data_ptr()
+    """a placeholder: flagged, or — should the flag have been lost with the Python object (.detach(), a view) — recognisable by
+    its storage: an expansion of the placeholders' own zero element (a weight-port handle, or autograd's stride-0 gradient of a
+    .sum(), is not one).  The match is by address alone, whatever the device and dtype: the elements live as long as the process,
+    so no other tensor has their address.  The flag alone marks one made under hipGraph capture, whose element is not cached."""
+    return t.data_ptr() in _PLACEHOLDER_PTRS or getattr(t, "_cips_planes_only", False)
 
 
 def _dense(t):
@@ -361,17 +375,7 @@ def _nhwc(t, pre=None):
             return hit
     if _is_planes_only(t):
         raise RuntimeError("cips3d_amd: a planes-only gradient lost its planes")
-    m = _memo()
-    key = _key(t) + sig
-    ent = m.shared.get(key)
-    if ent is not None:
-        return ent[1]
-    if pre is None:
-        p = ops.split_planes_nhwc(t)
-    else:
-        p = ops.split_planes_nhwc(_pre_fp32(t, pre))
-    if m.depth:
-        m.shared[key] = (t, p)
+    p = ops.split_planes_nhwc(t if pre is None else _pre_fp32(t, pre))
     if att is not None and att[0] == t._version and att[1] == t.data_ptr():
         att[2][sig] = p
     else:
@@ -451,9 +455,23 @@ def _pre_adjoint(dxb, pre, in_shape):
 # through .data —, an optimiser step replayed from a hipGraph, a raw-pointer kernel) leaves stale planes in use: such
 # writers call invalidate_weight_cache(module_or_parameters) afterwards.  The cache lives in a weakly keyed table beside
 # the parameters, not in Parameter.__dict__: pickling / deepcopying a module does not carry GPU planes along.
-import weakref as _weakref
 _WCACHE = {}        # id(Parameter) -> (weakref to it, {(kind, scale): (version, data_ptr, operand)}); the weakref's callback
                     # drops the entry with the Parameter (a WeakKeyDictionary would compare tensor keys with ==)
+
+
+def _wcache_of(w):
+    """the {(kind, scale): (version, data_ptr, operand)} table of Parameter w, made on first use; it dies with the Parameter object"""
+    slot = _WCACHE.get(id(w))
+    if slot is None or slot[0]() is not w:
+        key_id = id(w)
+        slot = _WCACHE[key_id] = (weakref.ref(w, lambda _r, k=key_id: _WCACHE.pop(k, None)), {})
+    return slot[1]
+
+
+def _wcache_fresh(ent, w, key):
+    """the operand filed under `key` if the weight has not changed since (version counter, storage), else None"""
+    hit = ent.get(key)
+    return hit[2] if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr() else None
 
 
 def invalidate_weight_cache(what=None):
@@ -477,18 +495,12 @@ def _cached(w, scale, kind, build):
         # build them inside the capture (every replay rebuilds them from the current weights) and keep nothing
         with torch.no_grad():
             return build(w.detach() if scale == 1.0 else w.detach() * scale)
-    slot = _WCACHE.get(id(w))                              # entries die with the Parameter object
-    if slot is None or slot[0]() is not w:
-        key_id = id(w)
-        slot = _WCACHE[key_id] = (_weakref.ref(w, lambda _r, k=key_id: _WCACHE.pop(k, None)), {})
-    ent = slot[1]
-    key = (kind, float(scale))
-    hit = ent.get(key)
-    if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr():
-        return hit[2]
-    with torch.no_grad():
-        val = build(w.detach() if scale == 1.0 else w.detach() * scale)
-    ent[key] = (w._version, w.data_ptr(), val)
+    ent, key = _wcache_of(w), (kind, float(scale))
+    val = _wcache_fresh(ent, w, key)
+    if val is None:
+        with torch.no_grad():
+            val = build(w.detach() if scale == 1.0 else w.detach() * scale)
+        ent[key] = (w._version, w.data_ptr(), val)
     return val
 
 
@@ -511,9 +523,6 @@ def prepare_weight_planes(layers):
     are rebuilt by every replay: _cached handles that case per layer)."""
     if _conv_mode() == "f32" or torch.cuda.is_current_stream_capturing():
         return
-    import ctypes as C
-    from . import _lib
-    from ._lib import WPrepJob
     todo = []
     want_alt = torch.is_grad_enabled()
     for conv, alt in layers:
@@ -523,18 +532,10 @@ def prepare_weight_planes(layers):
         O, Cc, kh, kw = w.shape
         if not _implicit_channels_ok(Cc, O) or (alt == "s2banks" and not _parity_channels_ok(Cc, O)):
             continue                               # no implicit-GEMM form for these channel counts (_conv_forms): no planes
-        slot = _WCACHE.get(id(w))
-        if slot is None or slot[0]() is not w:
-            key_id = id(w)
-            slot = _WCACHE[key_id] = (_weakref.ref(w, lambda _r, k=key_id: _WCACHE.pop(k, None)), {})
-        ent = slot[1]
-        sc = float(conv.scale)
-
-        def stale(kind):
-            hit = ent.get((kind, sc))
-            return hit is None or hit[0] != w._version or hit[1] != w.data_ptr()
+        ent, sc = _wcache_of(w), float(conv.scale)
         # the alternate form serves the DATA gradient: needed whenever a backward may run, frozen weights included (the G step)
-        need_fwd, need_alt = stale("fwd"), bool(alt) and want_alt and stale(alt)
+        need_fwd = _wcache_fresh(ent, w, ("fwd", sc)) is None
+        need_alt = bool(alt) and want_alt and _wcache_fresh(ent, w, (alt, sc)) is None
         if need_fwd or need_alt:
             todo.append((w, ent, sc, alt if need_alt else None, need_fwd))
     if not todo:
@@ -545,7 +546,7 @@ def prepare_weight_planes(layers):
     with torch.no_grad(), torch.cuda.device(dev):
         for c0 in range(0, len(todo), mx):
             chunk = todo[c0:c0 + mx]
-            jobs = (WPrepJob * len(chunk))()
+            jobs = (_lib.WPrepJob * len(chunk))()
             made = []
             for j, (w, ent, sc, alt, need_fwd) in zip(jobs, chunk):
                 O, Cc, kh, kw = w.shape
@@ -567,7 +568,7 @@ def prepare_weight_planes(layers):
                         j.bank_off[i] = offs[i]
                     altv = (P, offs)
                 made.append((w, ent, sc, alt, fwd, altv))
-            _lib.check(lib.cips_conv_weight_prep_batch(jobs, len(chunk), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            _lib.check(lib.cips_conv_weight_prep_batch(jobs, len(chunk), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                        "cips_conv_weight_prep_batch")
             for w, ent, sc, alt, fwd, altv in made:
                 if fwd is not None:
@@ -611,11 +612,10 @@ def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
     B, C, H, W = x.shape
     O, _, kh, kw = w.shape
     x = x.contiguous()
-    form = _conv_forms(x.shape, w.shape, stride, pad, pre)[0]
+    plan = _conv_plan(x.shape, w.shape, stride, pad, pre)
+    form = plan.forms[0]
     if form == "implicit":
-        Hb, Wb = _pre_shape(H, W, pre)
-        single = CONV_MODE == "bf16" and _single_pass(x.shape, w.shape, stride, pad, pre)[0]
-        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, single=single)
+        return ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, *plan.blurred, O, kh, kw, stride, pad, single=plan.single[0])
     if pre is not None:
         x = _pre_fp32(x, pre)
     if form == "rgb":
@@ -638,10 +638,10 @@ def _conv_fwd(x, w, stride, pad, scale=1.0, pre=None):
 def _conv_bwd_data(dy, w, in_shape, stride, pad, scale=1.0, pre=None):
     B, C, H, W = in_shape
     O, _, kh, kw = w.shape
-    form = _conv_forms(in_shape, w.shape, stride, pad, pre)[1]
-    single = CONV_MODE == "bf16" and _single_pass(in_shape, w.shape, stride, pad, pre)[1]
+    plan = _conv_plan(in_shape, w.shape, stride, pad, pre)
+    form, single = plan.forms[1], plan.single[1]
     if pre is not None:
-        Hb, Wb = _pre_shape(H, W, pre)
+        Hb, Wb = plan.blurred
         if form == "parity":
             banks, w_off = _w_banks_s2(w, scale)
             dxp, out_off = ops.conv2d_x3_dgrad_s2(banks, w_off, _grad_planes(dy), B, C, Hb, Wb, O, kh, kw, single=single)
@@ -673,12 +673,13 @@ def _conv_bwd_weight(dy, x, w_shape, stride, pad, scale=1.0, pre=None):
     O, C, kh, kw = w_shape
     B = x.shape[0]
     x = x.contiguous()
-    form = _conv_forms(x.shape, w_shape, stride, pad, pre)[2]
+    plan = _conv_plan(x.shape, w_shape, stride, pad, pre)
+    form = plan.forms[2]
     if form == "implicit":
-        Hb, Wb = _pre_shape(x.shape[2], x.shape[3], pre)
-        single = CONV_MODE == "bf16" and _single_pass(x.shape, w_shape, stride, pad, pre)[2]      # else 3-pass, where that takes it
-        dw = ops.conv2d_x3_wgrad(_grad_planes(dy), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, scale, single=single)
-        if dw is not None:                # None: declined (ops.conv2d_x3_wgrad_declines), the f32 form below
+        dw = ops.conv2d_x3_wgrad(_grad_planes(dy), _nhwc(x, pre), B, C, *plan.blurred, O, kh, kw, stride, pad, scale,
+                                 single=plan.single[2])         # not single: 3-pass
+        assert (dw is None) == plan.wgrad_declined       # the launcher is still asked where it declines: the dispatch tests watch it there
+        if dw is not None:
             return dw
     if pre is not None:
         x = _pre_fp32(x, pre)
@@ -715,85 +716,59 @@ class _WeightGradPort(Function):
     @staticmethod
     def backward(ctx, g):
         w_shape, stride, pad, scale, pre = ctx.cfg
-        with _share_planes():
-            dw = Conv2dBwdWeightFunction.apply(g, ctx.x, w_shape, stride, pad, scale, pre)
-        return dw, None, None, None, None, None, None
+        return Conv2dBwdWeightFunction.apply(g, ctx.x, w_shape, stride, pad, scale, pre), None, None, None, None, None, None
 
 
-_ZERO1 = {}
-
-
-def _zero1(like):
-    """one zero element per (device, dtype), made once (a fill launch per convolution call otherwise); never written"""
-    key = (like.device, like.dtype)
-    z = _ZERO1.get(key)
-    if z is None:
-        z = torch.zeros(1, device=like.device, dtype=like.dtype)
-        if like.is_cuda and torch.cuda.is_current_stream_capturing():
-            return z                                   # not cached: it lives in the capturing graph's pool
-        _ZERO1[key] = z
-    return z
-
-
-def _weight_port(x, w, out_shape, stride, pad, scale, pre):
+def _weight_port(x, w, stride, pad, scale, pre):
     if torch.is_grad_enabled() and w.requires_grad:
-        return _WeightGradPort.apply(w, (x,), out_shape, stride, pad, scale, pre)
+        return _WeightGradPort.apply(w, (x,), _conv_plan(x.shape, w.shape, stride, pad, pre).out_shape, stride, pad, scale, pre)
     return None
-
-
-def _conv_out_shape(x, w, stride, pad, pre):
-    Hb, Wb = _pre_shape(x.shape[2], x.shape[3], pre)
-    return (x.shape[0], w.shape[0], (Hb + 2 * pad - w.shape[2]) // stride + 1, (Wb + 2 * pad - w.shape[3]) // stride + 1)
 
 
 class Conv2dFunction(Function):
     """y = conv(Blur(x), w * scale).  `scale` is EqualConv2d's constant 1/sqrt(C k^2) (discriminator.py:33, 44): keeping it
     out of the tensor lets the parameter itself arrive here, so that its operand planes can be cached (_cached).  `port`: the
-    weight's _WeightGradPort (or None): dy goes back through it, the weight gradient is that node's."""
+    weight's _WeightGradPort (or None): dy goes back through it, the weight gradient is that node's.  The backward refuses a
+    planes-only placeholder (_dense): only a ConvBiasActFunction hands one to its own convolution's gradients."""
 
     @staticmethod
     def forward(ctx, x, w, port, stride, pad, scale=1.0, pre=None):
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.scale, ctx.pre = stride, pad, scale, pre
         ctx.w_obj = w if isinstance(w, nn.Parameter) else None       # the Parameter object: the cache key
-        with _share_planes():
-            y = _conv_fwd(x, w, stride, pad, scale, pre)
-        return y
+        return _conv_fwd(x, w, stride, pad, scale, pre)
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         w = ctx.w_obj if ctx.w_obj is not None else w
         dx = None
-        dy = dy.contiguous()
-        with _share_planes():
-            if ctx.needs_input_grad[0]:
-                dx = Conv2dBwdDataFunction.apply(dy, w, x.shape, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
+        dy = _dense(dy)
+        if ctx.needs_input_grad[0]:
+            dx = Conv2dBwdDataFunction.apply(dy, w, x.shape, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
         return dx, None, (dy if ctx.needs_input_grad[2] else None), None, None, None, None
 
 
 def _conv_apply(x, w, stride, pad, scale=1.0, pre=None):
     x = x.contiguous()
-    return Conv2dFunction.apply(x, w, _weight_port(x, w, _conv_out_shape(x, w, stride, pad, pre), stride, pad, scale, pre),
-                                stride, pad, scale, pre)
+    return Conv2dFunction.apply(x, w, _weight_port(x, w, stride, pad, scale, pre), stride, pad, scale, pre)
 
 
 class ConvBiasActFunction(Function):
-    """out = leaky_relu(conv(x, w * scale) + bias, slope) * act_scale in ONE kernel (bias and activation in the epilogue
-    of the implicit-GEMM convolution): EqualConv2d followed by FusedLeakyReLU (discriminator.py:205-215).  The backward is
-    the composition of the two layers' own backward Functions, so every higher-order path (R1) is theirs; the weight
-    gradient is the port's (see _WeightGradPort)."""
+    """out = leaky_relu(conv(Blur(x), w * scale) + bias, slope) * act_scale in ONE kernel (bias and activation in the epilogue
+    of the implicit-GEMM convolution): EqualConv2d followed by FusedLeakyReLU (discriminator.py:205-215), for calls whose
+    forward is "implicit" (_conv_act_fusable).  The backward is the composition of the two layers' own backward Functions, so
+    every higher-order path (R1) is theirs; the weight gradient is the port's (see _WeightGradPort).  The gated gradient between
+    the two exists as NHWC planes only where _planes_only_ok; an incoming placeholder is refused (_dense)."""
 
     @staticmethod
     def forward(ctx, x, w, bias, port, stride, pad, scale, slope, act_scale, pre=None):
         B, C, H, W = x.shape
         O, _, kh, kw = w.shape
         x = x.contiguous()
-        Hb, Wb = _pre_shape(H, W, pre)
-        single = CONV_MODE == "bf16" and _single_pass(x.shape, w.shape, stride, pad, pre)[0]
-        with _share_planes():
-            out = ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, Hb, Wb, O, kh, kw, stride, pad, bias=bias.detach().contiguous(),
-                                act=True, slope=slope, act_scale=act_scale, single=single)
+        plan = _conv_plan(x.shape, w.shape, stride, pad, pre)
+        out = ops.conv2d_x3(_w_planes(w, scale), _nhwc(x, pre), B, C, *plan.blurred, O, kh, kw, stride, pad, bias=bias.detach().contiguous(),
+                            act=True, slope=slope, act_scale=act_scale, single=plan.single[0])
         ctx.save_for_backward(x, w, out)
         ctx.cfg = (stride, pad, scale, slope, act_scale, pre)
         ctx.w_obj = w if isinstance(w, nn.Parameter) else None
@@ -805,11 +780,10 @@ class ConvBiasActFunction(Function):
         w = ctx.w_obj if ctx.w_obj is not None else w
         stride, pad, scale, slope, act_scale, pre = ctx.cfg
         po = PLANES_ONLY_GRADIENT and _planes_only_ok(x.shape, w.shape, stride, pad, pre, ctx.needs_input_grad[0], dout)
-        dpre, dbias = FusedLeakyReLUFunctionBackward.apply(dout.contiguous(), out, slope, act_scale, po)
+        dpre, dbias = FusedLeakyReLUFunctionBackward.apply(_dense(dout), out, slope, act_scale, po)
         dx = None
-        with _share_planes():
-            if ctx.needs_input_grad[0]:
-                dx = Conv2dBwdDataFunction.apply(dpre, w, x.shape, stride, pad, scale, pre)
+        if ctx.needs_input_grad[0]:
+            dx = Conv2dBwdDataFunction.apply(dpre, w, x.shape, stride, pad, scale, pre)
         return (dx, None, (dbias if ctx.needs_input_grad[2] else None), (dpre if ctx.needs_input_grad[3] else None),
                 None, None, None, None, None, None)
 
@@ -818,20 +792,14 @@ PLANES_ONLY_GRADIENT = True      # False: FusedLeakyReLU's backward writes the f
 
 
 def _planes_only_ok(x_shape, w_shape, stride, pad, pre, need_dx, dout):
-    """may the gated gradient of this ConvBiasAct layer exist as NHWC planes only?  Yes when BOTH of its consumers — the
-    convolution's data gradient (if asked for) and weight gradient — take forms that read planes and nothing else"""
-    if not (dout.is_cuda and dout.dtype == torch.float32 and dout.dim() == 4):
-        return False
-    _, dgrad, wgrad = _conv_forms(x_shape, w_shape, stride, pad, pre)
-    if wgrad != "implicit" or ops.conv2d_x3_wgrad_declines(dout.shape[0], dout.shape[2] * dout.shape[3]):
-        return False
-    return not need_dx or dgrad in ("implicit", "parity")
+    """may the gated gradient of this ConvBiasAct layer exist as NHWC planes only?  The plan's answer, for a GPU fp32 batch"""
+    return (dout.is_cuda and dout.dtype == torch.float32 and dout.dim() == 4
+            and _conv_plan(x_shape, w_shape, stride, pad, pre).planes_only[bool(need_dx)])
 
 
 def _conv_bias_act_apply(x, w, bias, stride, pad, scale, slope, act_scale, pre=None):
     x = x.contiguous()
-    return ConvBiasActFunction.apply(x, w, bias, _weight_port(x, w, _conv_out_shape(x, w, stride, pad, pre), stride, pad, scale, pre),
-                                     stride, pad, scale, slope, act_scale, pre)
+    return ConvBiasActFunction.apply(x, w, bias, _weight_port(x, w, stride, pad, scale, pre), stride, pad, scale, slope, act_scale, pre)
 
 
 FOLD_BLUR = True            # False: Blur as its own upfirdn2d node in front of the convolution (the folding's parity test flips it)
@@ -844,10 +812,14 @@ def _conv_act_fusable(x, conv, act, pre=None):
         return False
     if GATE_PIN is not None or GATE_REC is not None:        # gate instrumentation works on the separate activation op
         return False
-    return _conv_forms(x.shape, conv.weight.shape, conv.stride, conv.padding, pre)[0] == "implicit"
+    return _conv_plan(x.shape, conv.weight.shape, conv.stride, conv.padding, pre).forms[0] == "implicit"
 
 
 class Conv2dBwdDataFunction(Function):
+    """dx of conv(Blur(x), w * scale) from dy, which may be a planes-only placeholder where the form reads planes (_conv_bwd_data
+    refuses it elsewhere).  Linear in dy and in w: its backward is the convolution of ggx (values: a placeholder is refused) and
+    the weight gradient of (dy, ggx)."""
+
     @staticmethod
     def forward(ctx, dy, w, in_shape, stride, pad, scale=1.0, pre=None):
         ctx.save_for_backward(dy, w)
@@ -860,12 +832,11 @@ class Conv2dBwdDataFunction(Function):
         dy, w = ctx.saved_tensors
         w = ctx.w_obj if ctx.w_obj is not None else w
         g_dy = g_w = None
-        ggx = ggx.contiguous()
-        with _share_planes():
-            if ctx.needs_input_grad[0]:
-                g_dy = _conv_apply(ggx, w, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
-            if ctx.needs_input_grad[1]:
-                g_w = Conv2dBwdWeightFunction.apply(dy, ggx, w.shape, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
+        ggx = _dense(ggx)
+        if ctx.needs_input_grad[0]:
+            g_dy = _conv_apply(ggx, w, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
+        if ctx.needs_input_grad[1]:
+            g_w = Conv2dBwdWeightFunction.apply(dy, ggx, w.shape, ctx.stride, ctx.pad, ctx.scale, ctx.pre)
         return g_dy, g_w, None, None, None, None, None
 
 
@@ -1034,8 +1005,6 @@ class ResBlock(nn.Module):
 
 def _eql(mode, a, b, s, B, K, O, bias=None, bias_scale=1.0):
     """cips_equal_linear: mode 0  s a b^T (+ bias * bias_scale) -> (B, O);  1  s a b -> (B, K);  2  s a^T b -> (O, K)"""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     a, b = a.contiguous().float(), b.contiguous().float()
     if not a.is_cuda:
@@ -1043,11 +1012,11 @@ def _eql(mode, a, b, s, B, K, O, bias=None, bias_scale=1.0):
     out = torch.empty({0: (B, O), 1: (B, K), 2: (O, K)}[mode], device=a.device)
     n = int(lib.cips_equal_linear_scratch(mode, B, K, O))
     scratch = torch.empty(n, device=a.device) if n else None
-    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(a.device):
         _lib.check(lib.cips_equal_linear(mode, P(a), P(b), P(bias.contiguous().float() if bias is not None else None),
                                          float(bias_scale), float(s), P(out), P(scratch), B, K, O,
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cips_equal_linear")
+                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "cips_equal_linear")
     return out
 
 
@@ -1135,19 +1104,17 @@ class _DiffAugFunction(Function):
 
     @staticmethod
     def forward(ctx, x, draws, adjoint, affine):
-        import ctypes as C
-        from . import _lib
         rb, rs, rc, tx, ty, ox, oy, (cut_h, cut_w, color) = draws
         x = x.contiguous().float()
         B, Cc, H, W = x.shape
         y = torch.empty_like(x)
         sums = torch.empty(33 * B, device=x.device)          # per-image sums + 32 slices of partials (cips_diffaug)
         lib = _lib.load()
-        P = lambda t: C.c_void_p(t.data_ptr())
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(x.device):
             _lib.check(lib.cips_diffaug(P(x), P(y), P(rb), P(rs), P(rc), P(tx), P(ty), P(ox), P(oy), P(sums), B, Cc, H, W,
                                         cut_h, cut_w, 1 if adjoint else 0, (1 if affine else 0) | (0 if color else 2),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cips_diffaug")
+                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "cips_diffaug")
         ctx.draws, ctx.adjoint = draws, adjoint
         return y
 
@@ -1215,10 +1182,8 @@ def DiffAugment(x, policy='', channels_first=True):
 
 
 def _hip_unary(name, *args):
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
-    _lib.check(getattr(lib, name)(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
+    _lib.check(getattr(lib, name)(*args, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
 
 
 class _AvgPool2Function(Function):
@@ -1226,13 +1191,12 @@ class _AvgPool2Function(Function):
 
     @staticmethod
     def forward(ctx, x, adjoint):
-        import ctypes as C
         x = x.contiguous().float()
         B, Cc, H, W = x.shape
         Ho, Wo = (H * 2, W * 2) if adjoint else (H // 2, W // 2)
         y = torch.empty(B, Cc, Ho, Wo, device=x.device)
         with torch.cuda.device(x.device):
-            _hip_unary("cips_avgpool2", C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), B * Cc, max(H, Ho), max(W, Wo),
+            _hip_unary("cips_avgpool2", ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), B * Cc, max(H, Ho), max(W, Wo),
                        1 if adjoint else 0)
         ctx.adjoint = adjoint
         return y
@@ -1247,13 +1211,12 @@ class _BlendFunction(Function):
 
     @staticmethod
     def forward(ctx, x, y, a, b):
-        import ctypes as C
         x = x.contiguous().float()
         y = y.contiguous().float() if y is not None else None
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _hip_unary("cips_axpby", C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
-                       C.c_void_p(out.data_ptr()), a, b, x.numel())
+            _hip_unary("cips_axpby", ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()) if y is not None else None,
+                       ctypes.c_void_p(out.data_ptr()), a, b, x.numel())
         ctx.ab, ctx.has_y = (a, b), y is not None
         return out
 

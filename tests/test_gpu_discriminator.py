@@ -644,6 +644,97 @@ def test_gated_gradient_as_planes_only(cfg, monkeypatch):
         dm._dense(ph)
     with pytest.raises(RuntimeError):
         dm._conv_bwd_data(ph, torch.randn(O, 3, 1, 1, device=d), (B, 3, 16, 16), 1, 0)
+    if cfg == (2, 64, 64, 32, False):
+        # a placeholder arriving as the upstream gradient of a convolution that did not ask for one is refused by the backward
+        # entry, before any launch: it used to be made dense, zeros, and give zero gradients
+        x16 = torch.randn(B, C, 16, 16, device=d, requires_grad=True)
+        y_plain = dm.conv2d(x16, layer.equal_conv.weight, padding=1)
+        assert type(y_plain.grad_fn).__name__ == "Conv2dFunctionBackward" and y_plain.shape == ph.shape
+        with pytest.raises(RuntimeError, match="planes-only"):
+            torch.autograd.grad(y_plain, x16, ph)
+        plain = dm.ConvLayer(C, O, 3).to(d)
+        y_fused = plain(x16)
+        assert type(y_fused.grad_fn).__name__ == "ConvBiasActFunctionBackward" and y_fused.shape == ph.shape
+        with pytest.raises(RuntimeError, match="planes-only"):
+            torch.autograd.grad(y_fused, x16, ph)
+        # ... and as the upstream gradient of a data gradient: its backward convolves the incoming ggx, values again
+        dy16 = torch.randn(B, O, 16, 16, device=d, requires_grad=True)
+        dx16 = dm.Conv2dBwdDataFunction.apply(dy16, layer.equal_conv.weight, (B, C, 16, 16), 1, 1)
+        assert type(dx16.grad_fn).__name__ == "Conv2dBwdDataFunctionBackward" and dx16.shape == ph.shape
+        with pytest.raises(RuntimeError, match="planes-only"):
+            torch.autograd.grad(dx16, dy16, ph)
+        # a weight-port handle is an ordinary tensor of zeros
+        handle = dm._zero1(x16).expand(ph.shape)
+        assert not dm._is_planes_only(handle) and not dm._dense(handle).any()
+
+
+def _resblock_r1_lib_calls(dm, mode):
+    """Library calls per symbol of one ResBlock(64, 64) on a (2, 64, 16, 16) input, from an empty weight-plane cache: forward,
+    autograd.grad(create_graph=True) w.r.t. the input, backward of (gx ** 2).sum() + (y ** 2).sum().  `dm`: the discriminator
+    module to run; every name of _lib.SIGNATURES is wrapped on the loaded library object for the duration."""
+    import collections
+    from cips3d_amd import _lib
+    lib = _lib.load()
+    d = torch.device("cuda:0")
+    torch.manual_seed(5)
+    blk = dm.ResBlock(64, 64).to(d)
+    x0 = torch.randn(2, 64, 16, 16, device=d)
+    up = torch.randn(2, 64, 8, 8, device=d)
+    counts = collections.Counter()
+    real = {n: getattr(lib, n) for n in _lib.SIGNATURES}
+
+    def counted(n, fn):
+        def call(*a):
+            counts[n] += 1
+            return fn(*a)
+        return call
+
+    def step():
+        dm.invalidate_weight_cache()
+        blk.zero_grad()
+        x = x0.clone().requires_grad_(True)
+        y = blk(x)
+        gx, = torch.autograd.grad((y * up).sum(), x, create_graph=True)
+        ((gx ** 2).sum() + (y ** 2).sum()).backward()
+        torch.cuda.synchronize()
+
+    old_mode = dm.CONV_MODE
+    dm.CONV_MODE = mode
+    try:
+        step()                              # whatever a first call sets up once is not counted
+        for n, fn in real.items():
+            setattr(lib, n, counted(n, fn))
+        step()
+    finally:
+        for n, fn in real.items():
+            setattr(lib, n, fn)
+        dm.CONV_MODE = old_mode
+    return dict(counts)
+
+
+# measured with this body on the module of commit 81dda42 (the parent of the change that introduced _conv_plan)
+_RESBLOCK_R1_COMMON = {
+    "cips_axpby": 3, "cips_conv2d_x3_dgrad_s2": 2, "cips_conv_wgrad_finish": 6, "cips_fused_bias_act": 2, "cips_lrelu_bwd_bias_finish": 4,
+    "cips_lrelu_bwd_bias_nhwc": 4, "cips_lrelu_bwd_bias_nhwc_tiles": 4, "cips_split_planes": 6, "cips_split_planes_nhwc": 8,
+    "cips_upfirdn2d": 6, "cips_upfirdn2d_parity": 2}
+RESBLOCK_R1_LIB_CALLS = {
+    "bf16x3": {**_RESBLOCK_R1_COMMON, "cips_conv2d_x3": 9, "cips_conv2d_x3_ksplit": 9, "cips_conv2d_x3_wgrad": 6},
+    # 3-pass in this mode too: the two parity data gradients (O = 64) and the three calls of the 1 x 1 skip convolution on 64
+    # channels (one 64-deep k-tile) — _single_pass
+    "bf16": {**_RESBLOCK_R1_COMMON, "cips_conv2d_x3": 3, "cips_conv2d_x3_ksplit": 3, "cips_conv2d_bf16": 6, "cips_conv2d_bf16_ksplit": 6,
+             "cips_conv2d_bf16_wgrad": 6},
+}
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+def test_resblock_r1_library_call_counts(mode):
+    """The host side of the convolution engine decides which library calls a step makes: the count per symbol is a constant of
+    the dispatch rule and the plane caches, compared for equality (a plane split twice, a plan that picks another form or a
+    cache that misses shows here as a count, long before it shows as a time)."""
+    from cips3d_amd import discriminator as dm
+    got = _resblock_r1_lib_calls(dm, mode)
+    print(mode, sorted(got.items()))
+    assert got == RESBLOCK_R1_LIB_CALLS[mode]
 
 
 def _shipped_conv_cases():
