@@ -821,8 +821,14 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__
 }
 __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, float a,
                                                     float b, long long n) {
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
-    out[t] = y ? __fadd_rn(__fmul_rn(a, x[t]), __fmul_rn(b, y[t])) : __fmul_rn(a, x[t]);
+  // the two products and the sum are rounded one by one, as the op-by-op blend rounds them.  (__fmul_rn / __fadd_rn do not say
+  // that to hipcc: they are inline `*` and `+` that it fused into out = fma(b, y, fl(a x)), one ulp off wherever b y is inexact;
+  // the pragma governs the operators written in this body.)
+#pragma clang fp contract(off)
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
+    const float ax = a * x[t];
+    out[t] = y ? ax + b * y[t] : ax;
+  }
 }
 
 extern "C" int cips_avgpool2(const float* x, float* y, long long planes, int H, int W, int adjoint, cips_stream_t stream) {
@@ -871,7 +877,7 @@ extern "C" int cips_image_to_u8(const float* x, unsigned char* out, int B, int C
   return CIPS_CHECK_LAUNCH();
 }
 
-extern "C" int cips_version(void) { return 8; }     // 8: - the im2col entry point that wrote split-bf16 planes (no caller left: its shapes take the fp32 form); 7: + cips_modfc_prep_bwd_batch_cores, cips_torgb_bwd_w_x3_batch_cores, cips_cores_colsum_parts (additive); 6: + cips_conv2d_x3_dgrad_s2, cips_upfirdn2d_parity, cips_lrelu_bwd_bias_finish / _nhwc, cips_conv_weight_prep_batch (additive)
+extern "C" int cips_version(void) { return 9; }     // 9: + cips_upfirdn2d_form (additive); 8: - the im2col entry point that wrote split-bf16 planes (no caller left: its shapes take the fp32 form); 7: + cips_modfc_prep_bwd_batch_cores, cips_torgb_bwd_w_x3_batch_cores, cips_cores_colsum_parts (additive); 6: + cips_conv2d_x3_dgrad_s2, cips_upfirdn2d_parity, cips_lrelu_bwd_bias_finish / _nhwc, cips_conv_weight_prep_batch (additive)
 extern "C" const char* cips_arch(void) { return "gfx950"; }
 
 extern "C" int cips_fused_bias_act(const float* x, const float* bias, const float* refer, float* y,
@@ -899,68 +905,116 @@ extern "C" int cips_fused_bias_act(const float* x, const float* bias, const floa
   return CIPS_CHECK_LAUNCH();
 }
 
+// The one dispatch rule of cips_upfirdn2d: which kernel instantiation a call runs (CIPS_UPFIRDN2D_* of include/cips3d_hip.h).
+// Host only, no device call; the entry point below switches on it.
+namespace {
+struct UfShape { int out_h, out_w; };
+inline bool uf_valid(int kernel_h, int kernel_w, int up_x, int up_y, int down_x, int down_y) {
+  return kernel_h * kernel_w <= 64 && up_x >= 1 && up_y >= 1 && down_x >= 1 && down_y >= 1;
+}
+inline UfShape uf_out(int in_h, int in_w, int kernel_h, int kernel_w, int up_x, int up_y, int down_x, int down_y, int pad_x0,
+                      int pad_x1, int pad_y0, int pad_y1) {
+  return {(in_h * up_y + pad_y0 + pad_y1 - kernel_h) / down_y + 1, (in_w * up_x + pad_x0 + pad_x1 - kernel_w) / down_x + 1};
+}
+// LDS band of upfirdn2d_blur_kernel: row width and output rows per band; false when even a one-row band does not fit
+inline bool uf_blur_plan(int in_w, int kernel_h, int down, int pad_x0, UfShape o, int* lds_w_, int* band_rows_) {
+  // LDS row: left padding + input + enough on the right for the last strip's reads (4 outputs past out_w at most)
+  int lds_w = ((o.out_w + 3) / 4 * 4 - 1) * down + 4 + 3 * down + 1;
+  if (lds_w < pad_x0 + in_w) lds_w = pad_x0 + in_w;
+  lds_w = (lds_w + 3) & ~3;
+  int band_rows = o.out_h;
+  while (band_rows > 1 && ((band_rows - 1) * down + kernel_h) * lds_w > UF_MAX_LDS_FLOATS) band_rows = (band_rows + 1) / 2;
+  *lds_w_ = lds_w; *band_rows_ = band_rows;
+  return ((band_rows - 1) * down + kernel_h) * lds_w <= UF_MAX_LDS_FLOATS;
+}
+}  // namespace
+
+extern "C" int cips_upfirdn2d_form(int in_h, int in_w, int minor, int kernel_h, int kernel_w, int up_x, int up_y, int down_x,
+                                   int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
+  if (!uf_valid(kernel_h, kernel_w, up_x, up_y, down_x, down_y)) return -1;
+  const UfShape o = uf_out(in_h, in_w, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+  if (minor <= 0 || o.out_h <= 0 || o.out_w <= 0) return CIPS_UPFIRDN2D_NONE;
+  if (minor == 1 && kernel_h == 4 && kernel_w == 4 && up_x == up_y && down_x == down_y) {
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    if (up_x == 1 && down_x == 2 && pad_x0 == 1 && in_w == 2 * o.out_w && pow2(o.out_w) && o.out_w >= 2 && pad_y0 >= 0)
+      return o.out_h < 48 ? CIPS_UPFIRDN2D_DOWN2_PAIRS_4 : CIPS_UPFIRDN2D_DOWN2_PAIRS_8;
+    if (up_x == 2 && down_x == 1 && pad_x0 == 2 && pad_y0 == 2 && o.out_w == 2 * in_w && pow2(in_w) && in_w >= 2 && o.out_h <= 2 * in_h)
+      return in_h < 24 ? CIPS_UPFIRDN2D_UP2_PAIRS_2 : CIPS_UPFIRDN2D_UP2_PAIRS_4;
+    // thread tile: 1 x 16 outputs with the lanes along x (fully coalesced loads; the 4 x 4 tile of round 2 put neighbouring
+    // lanes 16 B apart and moved 12.5x the output bytes through the texture path), 1 x 8 on short planes (fewer wasted rows)
+    if (up_x == 1 && down_x == 1) return o.out_h < 48 ? CIPS_UPFIRDN2D_DIRECT_1_8 : CIPS_UPFIRDN2D_DIRECT_1_16;
+    if (up_x == 1 && down_x == 2) return o.out_h < 48 ? CIPS_UPFIRDN2D_DIRECT_2_8 : CIPS_UPFIRDN2D_DIRECT_2_16;
+    if (up_x == 2 && down_x == 1) return CIPS_UPFIRDN2D_UP2_4;
+  }
+  if (up_x == 1 && up_y == 1 && minor == 1 && kernel_h <= 4 && kernel_w <= 4 && down_x == down_y && (down_x == 1 || down_x == 2) &&
+      pad_x0 >= 0 && pad_x1 >= 0 && pad_y0 >= 0 && pad_y1 >= 0) {
+    int lds_w, band_rows;
+    if (!uf_blur_plan(in_w, kernel_h, down_x, pad_x0, o, &lds_w, &band_rows)) return CIPS_UPFIRDN2D_BLUR_SPILL;
+    return down_x == 1 ? CIPS_UPFIRDN2D_BLUR_1 : CIPS_UPFIRDN2D_BLUR_2;
+  }
+  return CIPS_UPFIRDN2D_GENERIC;
+}
+
 extern "C" int cips_upfirdn2d(const float* input, const float* kernel, float* out, int major, int in_h,
                               int in_w, int minor, int kernel_h, int kernel_w, int up_x, int up_y, int down_x,
                               int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, cips_stream_t stream) {
-  if (kernel_h * kernel_w > 64 || up_x < 1 || up_y < 1 || down_x < 1 || down_y < 1) return (int)hipErrorInvalidValue;
+  const int form = cips_upfirdn2d_form(in_h, in_w, minor, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+  if (form < 0) return (int)hipErrorInvalidValue;
+  if (form == CIPS_UPFIRDN2D_NONE || major <= 0) return 0;
   UpfirArgs a;
   a.in = input; a.k = kernel; a.out = out; a.major = major; a.in_h = in_h; a.in_w = in_w; a.minor = minor;
   a.kh = kernel_h; a.kw = kernel_w; a.up_x = up_x; a.up_y = up_y; a.down_x = down_x; a.down_y = down_y;
   a.pad_x0 = pad_x0; a.pad_y0 = pad_y0;
-  a.out_h = (in_h * up_y + pad_y0 + pad_y1 - kernel_h) / down_y + 1;
-  a.out_w = (in_w * up_x + pad_x0 + pad_x1 - kernel_w) / down_x + 1;
-  long long total = (long long)major * a.out_h * a.out_w * minor;
-  if (total <= 0) return 0;
-  if (minor == 1 && kernel_h == 4 && kernel_w == 4 && up_x == up_y && down_x == down_y) {
-    hipStream_t st = (hipStream_t)stream;
-    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    if (up_x == 1 && down_x == 2 && pad_x0 == 1 && in_w == 2 * a.out_w && pow2(a.out_w) && a.out_w >= 2 && pad_y0 >= 0) {
-      const int th = a.out_h < 48 ? 4 : 8, bh = (a.out_h + th - 1) / th, seg = a.out_w < 64 ? a.out_w : 64;
-      const long long nthreads = (long long)major * a.out_w * bh;
-      const unsigned grid = (unsigned)((nthreads + 255) / 256 < 131072 ? (nthreads + 255) / 256 : 131072);
+  const UfShape o = uf_out(in_h, in_w, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+  a.out_h = o.out_h; a.out_w = o.out_w;
+  hipStream_t st = (hipStream_t)stream;
+  // grid of the register-tiled forms: one thread per (plane, column, tile of th rows), at most 131072 workgroups
+  auto tiles = [&](int cols, int bh) {
+    const long long nthreads = (long long)major * cols * bh;
+    return (unsigned)((nthreads + 255) / 256 < 131072 ? (nthreads + 255) / 256 : 131072);
+  };
+  switch (form) {
+    case CIPS_UPFIRDN2D_DOWN2_PAIRS_4:
+    case CIPS_UPFIRDN2D_DOWN2_PAIRS_8: {
+      const int th = form == CIPS_UPFIRDN2D_DOWN2_PAIRS_4 ? 4 : 8, bh = (a.out_h + th - 1) / th, seg = a.out_w < 64 ? a.out_w : 64;
+      const unsigned grid = tiles(a.out_w, bh);
       if (th == 4) hipLaunchKernelGGL(upfirdn2d_down2_pairs_kernel<4>, dim3(grid), dim3(256), 0, st, a, bh, seg);
       else hipLaunchKernelGGL(upfirdn2d_down2_pairs_kernel<8>, dim3(grid), dim3(256), 0, st, a, bh, seg);
       return CIPS_CHECK_LAUNCH();
     }
-    if (up_x == 2 && down_x == 1 && pad_x0 == 2 && pad_y0 == 2 && a.out_w == 2 * in_w && pow2(in_w) && in_w >= 2 && a.out_h <= 2 * in_h) {
-      const int tu = in_h < 24 ? 2 : 4, bh = (in_h + tu - 1) / tu, seg = in_w < 64 ? in_w : 64;
-      const long long nthreads = (long long)major * in_w * bh;
-      const unsigned grid = (unsigned)((nthreads + 255) / 256 < 131072 ? (nthreads + 255) / 256 : 131072);
+    case CIPS_UPFIRDN2D_UP2_PAIRS_2:
+    case CIPS_UPFIRDN2D_UP2_PAIRS_4: {
+      const int tu = form == CIPS_UPFIRDN2D_UP2_PAIRS_2 ? 2 : 4, bh = (in_h + tu - 1) / tu, seg = in_w < 64 ? in_w : 64;
+      const unsigned grid = tiles(in_w, bh);
       if (tu == 2) hipLaunchKernelGGL(upfirdn2d_up2_pairs_kernel<2>, dim3(grid), dim3(256), 0, st, a, bh, seg);
       else hipLaunchKernelGGL(upfirdn2d_up2_pairs_kernel<4>, dim3(grid), dim3(256), 0, st, a, bh, seg);
       return CIPS_CHECK_LAUNCH();
     }
-    if (up_x == 1 && (down_x == 1 || down_x == 2)) {
-      // thread tile: 1 x 16 outputs with the lanes along x (fully coalesced loads; the 4 x 4 tile of round 2 put neighbouring
-      // lanes 16 B apart and moved 12.5x the output bytes through the texture path), 1 x 8 on short planes (fewer wasted rows)
-      const int th = a.out_h < 48 ? 8 : 16;
+    case CIPS_UPFIRDN2D_DIRECT_1_8:
+    case CIPS_UPFIRDN2D_DIRECT_1_16:
+    case CIPS_UPFIRDN2D_DIRECT_2_8:
+    case CIPS_UPFIRDN2D_DIRECT_2_16: {
+      const int th = (form == CIPS_UPFIRDN2D_DIRECT_1_8 || form == CIPS_UPFIRDN2D_DIRECT_2_8) ? 8 : 16;
       const int bw = a.out_w, bh = (a.out_h + th - 1) / th;
-      const long long nthreads = (long long)major * bw * bh;
-      const unsigned grid = (unsigned)((nthreads + 255) / 256 < 131072 ? (nthreads + 255) / 256 : 131072);
+      const unsigned grid = tiles(bw, bh);
 #define CIPS_UF(D, TW_, TH_) hipLaunchKernelGGL((upfirdn2d_direct_kernel<D, TW_, TH_, false>), dim3(grid), dim3(256), 0, st, a, bw, bh, ParityIn())
-      if (down_x == 1) { if (th == 8) CIPS_UF(1, 1, 8); else CIPS_UF(1, 1, 16); }
-      else { if (th == 8) CIPS_UF(2, 1, 8); else CIPS_UF(2, 1, 16); }
+      if (form == CIPS_UPFIRDN2D_DIRECT_1_8) CIPS_UF(1, 1, 8);
+      else if (form == CIPS_UPFIRDN2D_DIRECT_1_16) CIPS_UF(1, 1, 16);
+      else if (form == CIPS_UPFIRDN2D_DIRECT_2_8) CIPS_UF(2, 1, 8);
+      else CIPS_UF(2, 1, 16);
 #undef CIPS_UF
       return CIPS_CHECK_LAUNCH();
     }
-    if (up_x == 2 && down_x == 1) {
+    case CIPS_UPFIRDN2D_UP2_4: {
       const int bh = (a.out_h + 3) / 4;
-      const long long nthreads = (long long)major * a.out_w * bh;
-      const unsigned grid = (unsigned)((nthreads + 255) / 256 < 131072 ? (nthreads + 255) / 256 : 131072);
-      hipLaunchKernelGGL(upfirdn2d_up2_kernel<4>, dim3(grid), dim3(256), 0, st, a, bh);
+      hipLaunchKernelGGL(upfirdn2d_up2_kernel<4>, dim3(tiles(a.out_w, bh)), dim3(256), 0, st, a, bh);
       return CIPS_CHECK_LAUNCH();
     }
-  }
-  if (up_x == 1 && up_y == 1 && minor == 1 && kernel_h <= 4 && kernel_w <= 4 && down_x == down_y && (down_x == 1 || down_x == 2) &&
-      pad_x0 >= 0 && pad_x1 >= 0 && pad_y0 >= 0 && pad_y1 >= 0) {
-    // LDS row: left padding + input + enough on the right for the last strip's reads (4 outputs past out_w at most)
-    const int down = down_x;
-    int lds_w = ((a.out_w + 3) / 4 * 4 - 1) * down + 4 + 3 * down + 1;
-    if (lds_w < pad_x0 + in_w) lds_w = pad_x0 + in_w;
-    lds_w = (lds_w + 3) & ~3;
-    int band_rows = a.out_h;
-    while (band_rows > 1 && ((band_rows - 1) * down + kernel_h) * lds_w > UF_MAX_LDS_FLOATS) band_rows = (band_rows + 1) / 2;
-    if (((band_rows - 1) * down + kernel_h) * lds_w <= UF_MAX_LDS_FLOATS) {
+    case CIPS_UPFIRDN2D_BLUR_1:
+    case CIPS_UPFIRDN2D_BLUR_2: {
+      const int down = down_x;
+      int lds_w, band_rows;
+      uf_blur_plan(in_w, kernel_h, down, pad_x0, o, &lds_w, &band_rows);
       const int bands = (a.out_h + band_rows - 1) / band_rows;
       const long long nwork = (long long)major * bands;
       const int strips = band_rows * ((a.out_w + 3) / 4);                 // 4-output strips per work item
@@ -968,13 +1022,16 @@ extern "C" int cips_upfirdn2d(const float* input, const float* kernel, float* ou
       const size_t lds_bytes = (size_t)(16 + ((band_rows - 1) * down + kernel_h) * lds_w) * sizeof(float);
       const long long cap = nthr == 64 ? 65536 : 16384;
       const unsigned grid = (unsigned)(nwork < cap ? nwork : cap);
-      if (down == 1) hipLaunchKernelGGL(upfirdn2d_blur_kernel<1>, dim3(grid), dim3(nthr), lds_bytes, (hipStream_t)stream, a, band_rows, bands, lds_w);
-      else hipLaunchKernelGGL(upfirdn2d_blur_kernel<2>, dim3(grid), dim3(nthr), lds_bytes, (hipStream_t)stream, a, band_rows, bands, lds_w);
+      if (down == 1) hipLaunchKernelGGL(upfirdn2d_blur_kernel<1>, dim3(grid), dim3(nthr), lds_bytes, st, a, band_rows, bands, lds_w);
+      else hipLaunchKernelGGL(upfirdn2d_blur_kernel<2>, dim3(grid), dim3(nthr), lds_bytes, st, a, band_rows, bands, lds_w);
+      return CIPS_CHECK_LAUNCH();
+    }
+    default: {                                     // CIPS_UPFIRDN2D_GENERIC, CIPS_UPFIRDN2D_BLUR_SPILL
+      const long long total = (long long)major * a.out_h * a.out_w * minor;
+      hipLaunchKernelGGL(upfirdn2d_kernel, dim3(grid_for(total)), dim3(256), 0, st, a);
       return CIPS_CHECK_LAUNCH();
     }
   }
-  hipLaunchKernelGGL(upfirdn2d_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, a);
-  return CIPS_CHECK_LAUNCH();
 }
 
 // Operand planes of the convolution WEIGHTS, all layers of a network in one launch (round 6): for every job the scaled weight

@@ -289,10 +289,24 @@ __global__ __launch_bounds__(64) void rownorm_bwd_kernel(const float* __restrict
   };
   if (mode & 4) {                     // y = x r: dx = r (dy - y mean(dy y))
     const float r = stats[2 * row + 1];
-    float s = 0.f;
-    for (int c = t; c < cols; c += 64) s = fmaf(gate(c), x[base + c] * r, s);
-    const float m = wave_sum_dpp(s) / (float)cols;
-    for (int c = t; c < cols; c += 64) dx[base + c] = r * (gate(c) - x[base + c] * r * m);
+    // Evaluated with each column's own term taken out of the two row sums P = sum dy y and S = sum x^2:
+    //   dy_c - y_c P / n = dy_c r^2 (1e-8 + (S - x_c^2) / n) - y_c (P - dy_c y_c) / n        (r^2 (S / n + 1e-8) = 1)
+    // The plain form loses dx wherever one column carries the row (y_c = +-1 to float32, dx = dy_c (1 - y_c^2) -> 0; with
+    // cols = 1 the true dx = dy 1e-8 r^3 came out as 0 or as rounding noise 100x its size); here those differences are between
+    // identically rounded products (hence the barriers: no contraction into fma(-dy, y, P)) and vanish exactly.
+    float s = 0.f, q = 0.f;
+    for (int c = t; c < cols; c += 64) {
+      const float xv = x[base + c];
+      s = fmaf(gate(c), xv * r, s);
+      q = fmaf(xv, xv, q);
+    }
+    const float P = wave_sum_dpp(s), S = wave_sum_dpp(q), n = (float)cols, r2 = r * r;
+    for (int c = t; c < cols; c += 64) {
+      const float xv = x[base + c], g = gate(c), yv = xv * r;
+      float gy = g * yv, x2 = xv * xv;
+      asm volatile("" : "+v"(gy), "+v"(x2));
+      dx[base + c] = r * (g * r2 * (1e-8f + (S - x2) / n) - yv * ((P - gy) / n));
+    }
     return;
   }
   if (!(mode & 1)) {                  // activation only
@@ -303,7 +317,9 @@ __global__ __launch_bounds__(64) void rownorm_bwd_kernel(const float* __restrict
   float s1 = 0.f, s2 = 0.f;
   for (int c = t; c < cols; c += 64) {
     const float g = gate(c);
-    const float gx = g * gamma[c];
+    float gx = g * gamma[c];
+    asm volatile("" : "+v"(gx));      // the ROUNDED product in both passes: hipcc contracts `gx - m1` below into fma(g, gamma, -m1), which
+                                      // leaves the product's rounding error where the terms cancel (cols = 1: dx = rstd * 1e-8 instead of 0)
     dyhat[base + c] = g;
     s1 += gx;
     s2 = fmaf(gx, (x[base + c] - mean) * rstd, s2);
@@ -311,7 +327,8 @@ __global__ __launch_bounds__(64) void rownorm_bwd_kernel(const float* __restrict
   const float m1 = wave_sum_dpp(s1) / (float)cols;
   const float m2 = wave_sum_dpp(s2) / (float)cols;
   for (int c = t; c < cols; c += 64) {
-    const float gx = dyhat[base + c] * gamma[c];
+    float gx = dyhat[base + c] * gamma[c];
+    asm volatile("" : "+v"(gx));
     dx[base + c] = rstd * (gx - m1 - (x[base + c] - mean) * rstd * m2);
   }
 }

@@ -2153,6 +2153,20 @@ def upfirdn2d_op(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_
     return out if input.dtype == torch.float32 else out.to(input.dtype)
 
 
+# cips_upfirdn2d_form's codes (CIPS_UPFIRDN2D_* of include/cips3d_hip.h), by kernel instantiation
+UPFIRDN2D_FORMS = ("none", "generic", "direct<1,8>", "direct<1,16>", "direct<2,8>", "direct<2,16>", "up2<4>", "down2_pairs<4>",
+                   "down2_pairs<8>", "up2_pairs<2>", "up2_pairs<4>", "blur<1>", "blur<2>", "blur_spill")
+
+
+def upfirdn2d_form(in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
+    """the kernel instantiation upfirdn2d_op runs for these arguments, as a name of UPFIRDN2D_FORMS (host only: no GPU needed);
+    ValueError for arguments the op refuses"""
+    code = _lib.load().cips_upfirdn2d_form(in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)
+    if code < 0:
+        raise ValueError("cips_upfirdn2d refuses these arguments (more than 64 taps, or an up / down factor below 1)")
+    return UPFIRDN2D_FORMS[code]
+
+
 def im2col(x, kh, kw, stride, pad):
     lib = _lib.load()
     B, Cc, H, W = x.shape

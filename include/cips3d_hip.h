@@ -679,6 +679,29 @@ int cips_upfirdn2d(const float* input, const float* kernel, float* out,
                    int major, int in_h, int in_w, int minor, int kernel_h, int kernel_w,
                    int up_x, int up_y, int down_x, int down_y,
                    int pad_x0, int pad_x1, int pad_y0, int pad_y1, cips_stream_t stream);
+/* Which kernel instantiation cips_upfirdn2d runs for these arguments (host only; the entry point switches on this very
+ * function, so the rule exists once): one code per instantiation, CIPS_UPFIRDN2D_NONE when the output is empty (the call
+ * launches nothing and returns 0), negative for arguments the call refuses.  Every form computes the generic kernel's
+ * values bit for bit; the query lets a test say which kernel a shape reached. */
+enum {
+  CIPS_UPFIRDN2D_NONE = 0,
+  CIPS_UPFIRDN2D_GENERIC = 1,          /* upfirdn2d_kernel: any up / down / minor, up to 64 taps */
+  CIPS_UPFIRDN2D_DIRECT_1_8 = 2,       /* upfirdn2d_direct_kernel<DOWN, 1, TH>: 4 x 4 taps, up 1, minor 1; */
+  CIPS_UPFIRDN2D_DIRECT_1_16 = 3,      /*   TH = 8 output rows per thread below out_h = 48, 16 from there on */
+  CIPS_UPFIRDN2D_DIRECT_2_8 = 4,
+  CIPS_UPFIRDN2D_DIRECT_2_16 = 5,
+  CIPS_UPFIRDN2D_UP2_4 = 6,            /* upfirdn2d_up2_kernel<4>: 4 x 4 taps, up 2, down 1, minor 1 */
+  CIPS_UPFIRDN2D_DOWN2_PAIRS_4 = 7,    /* upfirdn2d_down2_pairs_kernel<TH>: down 2, pad_x0 = 1, in_w = 2 out_w, out_w a power */
+  CIPS_UPFIRDN2D_DOWN2_PAIRS_8 = 8,    /*   of two, pad_y0 >= 0; TH = 4 below out_h = 48, else 8 */
+  CIPS_UPFIRDN2D_UP2_PAIRS_2 = 9,      /* upfirdn2d_up2_pairs_kernel<TU>: up 2, pad_x0 = pad_y0 = 2, out_w = 2 in_w, in_w a power */
+  CIPS_UPFIRDN2D_UP2_PAIRS_4 = 10,     /*   of two, out_h <= 2 in_h; TU = 2 below in_h = 24, else 4 */
+  CIPS_UPFIRDN2D_BLUR_1 = 11,          /* upfirdn2d_blur_kernel<DOWN> (LDS row bands): up 1, minor 1, at most 4 x 4 taps, */
+  CIPS_UPFIRDN2D_BLUR_2 = 12,          /*   pads >= 0, down 1 or 2, and no register-tiled form above applies */
+  CIPS_UPFIRDN2D_BLUR_SPILL = 13       /* a blur shape whose one-row band exceeds the 32 KiB of LDS: the generic kernel */
+};
+int cips_upfirdn2d_form(int in_h, int in_w, int minor, int kernel_h, int kernel_w,
+                        int up_x, int up_y, int down_x, int down_y,
+                        int pad_x0, int pad_x1, int pad_y0, int pad_y1);
 /* The same op for a 4 x 4 kernel, up = down = 1, on `major` planes of in_h x in_w that are stored as the four parity blocks
  * written by cips_conv2d_x3_dgrad_s2 (pixel (y, x) of plane m at dxp[blk_off[2(y&1) + (x&1)] + m * Np + (y>>1) * Ws + (x>>1)],
  * Ws = ceil((in_w - (x&1)) / 2), Np = Hs * Ws rounded up to 8): the transpose of the Blur of a down-sampling ConvLayer

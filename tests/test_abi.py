@@ -25,7 +25,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     lib = _lib.load()
     for s in syms:
         assert hasattr(lib, s), s
-    assert lib.cips_version() == 8
+    assert lib.cips_version() == 9
     assert lib.cips_arch() == b"gfx950"
 
 
@@ -174,6 +174,22 @@ def test_entry_points_validate_arguments_before_touching_the_device():
     assert lib.cips_conv1x1_smallk(None, None, None, 2, 5, 8, 64, None) == INVALID      # more than 4 input channels
     assert lib.cips_conv1x1_smallk(None, None, None, 2, 3, 8, 30, None) == INVALID      # pixels not a multiple of 4
     assert lib.cips_upfirdn2d(None, None, None, 1, 8, 8, 1, 9, 9, 1, 1, 1, 1, 0, 0, 0, 0, None) == INVALID   # > 64 taps
+    assert lib.cips_upfirdn2d_form(8, 8, 1, 9, 9, 1, 1, 1, 1, 0, 0, 0, 0) < 0           # the query refuses what the call refuses
+    assert lib.cips_upfirdn2d(None, None, None, 1, 8, 8, 1, 4, 4, 0, 1, 1, 1, 0, 0, 0, 0, None) == INVALID   # up_x 0
+    assert lib.cips_upfirdn2d_form(8, 8, 1, 4, 4, 0, 1, 1, 1, 0, 0, 0, 0) < 0 and lib.cips_upfirdn2d_form(8, 8, 1, 4, 4, 1, 1, 1, 0, 0, 0, 0, 0) < 0
+    assert lib.cips_upfirdn2d(None, None, None, 1, 2, 2, 1, 4, 4, 1, 1, 1, 1, 0, 0, 0, 0, None) == 0         # empty output: no-op
+    # the other streaming kernels of the discriminator and of the mapping networks (no launches)
+    assert lib.cips_conv1x1_smallk_bwd_data(None, None, None, 2, 5, 8, 64, None) == INVALID
+    assert lib.cips_conv1x1_smallk_bwd_data(None, None, None, 2, 3, 8, 30, None) == INVALID
+    assert lib.cips_conv1x1_smallk_bwd_weight(buf, buf, buf, 2, 5, 8, 64, None) == INVALID
+    assert lib.cips_conv1x1_smallk_bwd_weight(buf, buf, buf, 2, 3, 8, 30, None) == INVALID
+    assert lib.cips_avgpool2(buf, buf, 1, 3, 2, 0, None) == INVALID and lib.cips_avgpool2(buf, buf, 1, 2, 3, 1, None) == INVALID   # odd H / W
+    assert lib.cips_avgpool2(None, buf, 1, 2, 2, 0, None) == INVALID and lib.cips_axpby(buf, buf, buf, 1.0, 1.0, 0, None) == INVALID
+    assert lib.cips_rownorm_fwd(buf, buf, buf, buf, buf, 1, 1025, 1, 0.2, None) == INVALID               # more than 1024 columns
+    assert lib.cips_rownorm_fwd(buf, buf, buf, buf, buf, 1, 4, 5, 0.2, None) == INVALID                  # PixelNorm with LayerNorm
+    assert lib.cips_rownorm_fwd(buf, None, None, buf, buf, 1, 4, 1, 0.2, None) == INVALID                # LayerNorm without gamma
+    assert lib.cips_rownorm_bwd(buf, buf, buf, buf, buf, buf, buf, buf, buf, 1, 1025, 1, 0.2, None) == INVALID
+    assert lib.cips_rownorm_bwd(buf, buf, buf, buf, buf, buf, buf, buf, buf, 1, 4, 5, 0.2, None) == INVALID
     assert lib.cips_torgb_fwd(None, None, None, None, 16, 30, 0, None) == INVALID       # K not a multiple of 4
     assert lib.cips_fused_bias_act(None, buf, None, None, 16, 0, 1, 3, 0, 0.2, 1.0, None) == INVALID   # bias without its size
     assert lib.cips_fused_bias_act(None, None, None, None, 0, 0, 0, 3, 0, 0.2, 1.0, None) == 0          # empty tensor: no-op
@@ -195,3 +211,75 @@ def test_entry_points_validate_arguments_before_touching_the_device():
     assert lib.cips_gemm_bf16x3(ctypes.byref(e), None) == UNSUPPORTED
     e.addp_hi = None
     assert lib.cips_gemm_bf16x3_takes_addp(ctypes.byref(e)) == 0                                      # nothing to take
+
+
+# --------------------------------------------------------------------------------------
+# cips_upfirdn2d_form: the dispatch rule of cips_upfirdn2d, the very function the entry point switches on
+# --------------------------------------------------------------------------------------
+def _form(h, w, up, down, pad, minor=1, k=(4, 4)):
+    """pad = (x0, x1, y0, y1), the op's order"""
+    from cips3d_amd import ops
+    return ops.upfirdn2d_form(h, w, minor, k[0], k[1], up, up, down, down, *pad)
+
+
+def _backward_call(h, w, up, down, pad, k=(4, 4)):
+    """(in_h, in_w, up, down, pad) of the call UpFirDn2dBackward makes for this forward (UpFirDn2d.forward's g_pad formulas)"""
+    x0, x1, y0, y1 = pad
+    out_h = (h * up + y0 + y1 - k[0]) // down + 1
+    out_w = (w * up + x0 + x1 - k[1]) // down + 1
+    g_pad = (k[1] - x0 - 1, w * up - out_w * down + x0 - up + 1, k[0] - y0 - 1, h * up - out_h * down + y0 - up + 1)
+    return out_h, out_w, down, up, g_pad
+
+
+def test_upfirdn2d_form_codes_agree_with_the_header():
+    from cips3d_amd import ops
+    txt = open(os.path.join(ROOT, "include", "cips3d_hip.h")).read()
+    codes = {n.lower(): int(v) for n, v in re.findall(r"CIPS_UPFIRDN2D_([A-Z0-9_]+) = (\d+)", txt)}
+    assert sorted(codes.values()) == list(range(14))             # "none" + the thirteen kernel instantiations
+    norm = lambda s: s.replace("<", "_").replace(",", "_").replace(">", "")
+    assert [norm(n) for n in ops.UPFIRDN2D_FORMS] == sorted(codes, key=codes.get)
+    with pytest.raises(ValueError):
+        _form(8, 8, 1, 1, (0, 0, 0, 0), k=(9, 9))
+    assert _form(2, 2, 1, 1, (0, 0, 0, 0)) == "none"
+
+
+def test_upfirdn2d_form_of_the_skip_branch_blur_and_its_backward():
+    """ResBlock's skip: Blur pad (1, 1) + down 2 at the power-of-two stages -> the lanes-along-the-half-row kernels, forward
+    (TH 4 below out_h 48, else 8) and backward (TU 2 below in_h 24, else 4)"""
+    for n in (4, 8, 16, 32, 64, 128, 256):
+        assert _form(n, n, 1, 2, (1, 1, 1, 1)) == ("down2_pairs<4>" if n // 2 < 48 else "down2_pairs<8>"), n
+        h, w, up, down, g_pad = _backward_call(n, n, 1, 2, (1, 1, 1, 1))
+        assert (h, w, up, down, g_pad) == (n // 2, n // 2, 2, 1, (2, 1, 2, 1))
+        assert _form(h, w, up, down, g_pad) == ("up2_pairs<2>" if h < 24 else "up2_pairs<4>"), n
+    # both thresholds from either side (rows only: the width stays a power of two)
+    assert _form(94, 64, 1, 2, (1, 1, 1, 1)) == "down2_pairs<4>" and _form(96, 64, 1, 2, (1, 1, 1, 1)) == "down2_pairs<8>"   # out_h 47 | 48
+    assert _form(23, 32, 2, 1, (2, 1, 2, 1)) == "up2_pairs<2>" and _form(24, 32, 2, 1, (2, 1, 2, 1)) == "up2_pairs<4>"
+    # what the pairs kernels do not take: another low pad, a negative pad_y0, more output rows than 2 in_h
+    assert _form(16, 16, 1, 2, (2, 0, 1, 1)) == "direct<2,8>" and _form(16, 16, 1, 2, (1, 1, -1, 3)) == "direct<2,8>"
+    assert _form(8, 8, 2, 1, (2, 1, 1, 2)) == "up2<4>" and _form(8, 8, 2, 1, (2, 1, 2, 2)) == "up2<4>"
+
+
+def test_upfirdn2d_form_of_widths_that_are_no_power_of_two():
+    for n in (12, 24, 65):
+        out_h = (n + 2 - 4) // 2 + 1
+        assert _form(n, n, 1, 2, (1, 1, 1, 1)) == "direct<2,8>", n
+        h, w, up, down, g_pad = _backward_call(n, n, 1, 2, (1, 1, 1, 1))
+        assert (h, w) == (out_h, out_h) and _form(h, w, up, down, g_pad) == "up2<4>", n
+    assert _form(98, 98, 1, 2, (1, 1, 1, 1)) == "direct<2,16>" and _form(94, 98, 1, 2, (1, 1, 1, 1)) == "direct<2,8>"
+
+
+def test_upfirdn2d_form_of_the_conv_branch_blur_and_of_other_kernels():
+    for n in (4, 8, 16, 32, 46, 47, 48, 64, 65, 128, 256):       # pad (2, 2), down 1: out_h = n + 1
+        assert _form(n, n, 1, 1, (2, 2, 2, 2)) == ("direct<1,8>" if n + 1 < 48 else "direct<1,16>"), n
+    # its backward is the same blur with the pads of the flipped kernel
+    assert _backward_call(32, 32, 1, 1, (2, 2, 2, 2)) == (33, 33, 1, 1, (1, 1, 1, 1)) and _form(33, 33, 1, 1, (1, 1, 1, 1)) == "direct<1,8>"
+    # fewer than 4 x 4 taps: the LDS row-band kernel; a band that cannot hold one output row: the generic kernel
+    assert _form(17, 19, 1, 1, (1, 0, 1, 1), k=(3, 2)) == "blur<1>" and _form(17, 19, 1, 2, (1, 0, 1, 1), k=(3, 2)) == "blur<2>"
+    assert _form(17, 19, 1, 1, (1, 2, 0, 0), k=(1, 4)) == "blur<1>" and _form(200, 260, 1, 2, (1, 2, 0, 0), k=(1, 4)) == "blur<2>"
+    assert _form(4, 2100, 1, 1, (1, 1, 1, 1), k=(4, 3)) == "blur_spill" and _form(4, 2000, 1, 1, (1, 1, 1, 1), k=(4, 3)) == "blur<1>"
+    assert _form(17, 19, 1, 1, (-1, 2, 1, 1), k=(3, 2)) == "generic"                     # a negative pad
+    # interleaved channels, other factors, mixed factors
+    assert _form(6, 7, 2, 1, (2, 1, 2, 1), minor=2) == "generic" and _form(16, 16, 1, 2, (1, 1, 1, 1), minor=2) == "generic"
+    assert _form(9, 9, 3, 2, (2, 2, 2, 2)) == "generic" and _form(9, 9, 3, 2, (2, 2, 2, 2), k=(5, 3)) == "generic"
+    from cips3d_amd import _lib
+    assert _lib.load().cips_upfirdn2d_form(16, 16, 1, 4, 4, 1, 1, 2, 1, 1, 1, 1, 1) == 1     # down_x != down_y

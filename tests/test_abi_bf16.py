@@ -33,7 +33,7 @@ def test_entry_points_exist_in_header_ctypes_table_and_binary():
     for s in NEW:
         assert _l.SIGNATURES[s] == _l.SIGNATURES[s.replace("cips_gemm_bf16", "cips_gemm_bf16x3")], s
     # no struct layout and no existing signature changed
-    assert lib.cips_version() == 8
+    assert lib.cips_version() == 9
 
 
 def test_malformed_descriptors_get_the_three_pass_entry_points_codes():

@@ -40,7 +40,7 @@ def test_entry_points_exist_in_header_ctypes_table_and_binary():
     for s in NEW:
         assert protos[s].split() == protos[_twin(s)].split(), s
     # additive: no struct layout and no existing signature changed
-    assert lib.cips_version() == 8
+    assert lib.cips_version() == 9
 
 
 def _pv():

@@ -24,7 +24,7 @@ def test_density_symbols_are_exported_and_bound():
     assert _lib.SIGNATURES["cips_siren_sigma_x3_grid"] == (ctypes.c_int, [ctypes.POINTER(_lib.SirenWeights),
                                                                            ctypes.POINTER(_lib.GridParams), ctypes.c_void_p,
                                                                            ctypes.c_int, ctypes.c_void_p])
-    assert lib.cips_version() == 8           # purely additive: the ABI version stays
+    assert lib.cips_version() == 9           # unchanged by this entry point; 9 came with cips_upfirdn2d_form
 
 
 def test_grid_params_layout_matches_header_field_order():

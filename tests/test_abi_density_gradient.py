@@ -22,7 +22,7 @@ def test_density_gradient_symbols_are_exported_and_bound():
     assert _lib.SIGNATURES["cips_siren_sigma_grad_x3"] == (i32, [ctypes.POINTER(_lib.SirenWeights), vp, vp, vp, i32, i32, vp])
     assert _lib.SIGNATURES["cips_siren_sigma_grad_x3_grid"] == (i32, [ctypes.POINTER(_lib.SirenWeights),
                                                                        ctypes.POINTER(_lib.GridParams), vp, vp, i32, vp])
-    assert lib.cips_version() == 8           # purely additive: the ABI version stays
+    assert lib.cips_version() == 9           # unchanged by this entry point; 9 came with cips_upfirdn2d_form
 
 
 def test_density_gradient_entry_points_validate_arguments_before_touching_the_device():

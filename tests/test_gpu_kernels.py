@@ -974,8 +974,13 @@ def test_upfirdn2d_golden_and_fused_bias_act():
                                             ((700, 32, 32), 1, (2, 2)), ((300, 16, 16), 2, (1, 1)), ((513, 8, 8), 1, (2, 2)),
                                             ((100, 4, 4), 2, (1, 1)), ((70000, 4, 4), 1, (2, 2))])
 def test_upfirdn2d_blur_fast_path(shape, down, pad):
-    """The LDS-tiled form of upfirdn2d the Blur layers take (up 1, minor 1, 4x4 kernel, down 1 or 2): whole planes,
-    planes cut in row bands, odd sizes, asymmetric padding — against the oracle's restatement of upfirdn2d_native."""
+    """The up 1, minor 1, down 1 or 2 calls of the Blur layers against the oracle's restatement of upfirdn2d_native: whole
+    planes, many small planes, odd sizes, asymmetric padding.  Kernels reached (ops.upfirdn2d_form; the name is older than
+    the register-tiled forms): with the 4 x 4 blur kernel upfirdn2d_direct_kernel — <1,16> for the 64 x 64, 63 x 65 and
+    200 x 260 planes, <1,8> for the other down-1 cases, <2,16> for 130 x 258, <2,8> for 65 x 65 and 33 x 31 — and
+    upfirdn2d_down2_pairs_kernel<4> for the 16 x 16 and 4 x 4 planes at down 2, pad (1, 1); only the 3 x 2 kernel takes the
+    LDS row-band kernel upfirdn2d_blur_kernel<1 | 2> (cut in row bands for 200 x 260 and 130 x 258).
+    tests/test_gpu_stream_kernels.py reaches every instantiation by name."""
     from cips3d_amd import ops
     d = dev()
     g = torch.Generator().manual_seed(sum(shape) + down)
