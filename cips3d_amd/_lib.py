@@ -118,6 +118,9 @@ SIGNATURES = {
     "cips_siren_sigma_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, i32, vp]),
     "cips_siren_sigma_grad_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
     "cips_siren_sigma_grad_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, vp, i32, vp]),
+    "cips_siren_bwd_points_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, vp, i32, i32, vp]),
+    "cips_siren_bwd_points_x3_rays": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, vp, vp, i32, vp]),
+    "cips_rays_bwd_cam": (i32, [C.POINTER(RayParams), vp, vp, i32, vp]),
     "cips_siren_bwd_rows": (i32, [i32, i32]),
     "cips_siren_bwd_x3_chunks": (i32, [i32, i32]),
     "cips_siren_bwd_x3_gpart": (i32, []),

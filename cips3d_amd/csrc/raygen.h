@@ -62,6 +62,59 @@ __device__ __forceinline__ void gen_point(const RayGen& g, int b, int p, float& 
   gen_point(g, b, p, wx, wy, wz, z);
 }
 
+// gen_point with every rounding written out, for a kernel whose result is compared BIT FOR BIT with one computed at the points
+// cips_rays_fwd / cips_resample_fwd materialised (cips_siren_bwd_points_x3_rays).  "The same expressions in the same order" is not
+// enough for that: hipcc contracts a * b + c into an fma where it sees fit, differently from kernel to kernel (in rays_kernel the
+// x and y jitter offsets are fused and the z offset is not; each row of the matrix product rounds ONE of its products and fuses
+// the other two).  This is the sequence rays_kernel (points, directions) and resample_kernel (origin + direction * depth) are
+// built with — contraction is off in here and every fused operation is an explicit fmaf — so it does not move with its caller.
+// tests/test_gpu_points_gradient.py holds the two together: a compiler that builds those kernels otherwise shows there.
+__device__ __forceinline__ void gen_point_materialised(const RayGen& g, int b, int p, float& wx, float& wy, float& wz) {
+#pragma clang fp contract(off)
+  const int ray = p / g.S, s = p - ray * g.S;
+  const int row = ray / g.W, col = ray - row * g.W;
+  const float x = g.xg[col], y = g.yg[row];
+  const float nrm = sqrtf((x * x + y * y) + g.zc * g.zc);
+  const float dx = x / nrm, dy = y / nrm, dz = g.zc / nrm;
+  const float* M = g.c2w + (long long)b * 16;
+  if (g.zvals) {
+    const float z = g.zvals[(long long)b * g.n * g.S + p];
+    const float rx = __builtin_fmaf(dz, M[2], __builtin_fmaf(dy, M[1], dx * M[0]));
+    const float ry = __builtin_fmaf(dz, M[6], __builtin_fmaf(dx, M[4], dy * M[5]));
+    const float rz = __builtin_fmaf(dz, M[10], __builtin_fmaf(dx, M[8], dy * M[9]));
+    wx = __builtin_fmaf(rx, z, M[3]); wy = __builtin_fmaf(ry, z, M[7]); wz = __builtin_fmaf(rz, z, M[11]);
+    return;
+  }
+  const float z0 = g.zg[s];
+  float px = dx * z0, py = dy * z0, pz = dz * z0;
+  if (g.jitter) {
+    const float off = (g.jitter[(long long)b * g.n * g.S + p] - 0.5f) * (g.zg[1] - g.zg[0]);
+    px = __builtin_fmaf(dx, off, px); py = __builtin_fmaf(dy, off, py); pz = pz + dz * off;
+  }
+  wx = __builtin_fmaf(pz, M[2], __builtin_fmaf(py, M[1], px * M[0])) + M[3];
+  wy = __builtin_fmaf(pz, M[6], __builtin_fmaf(px, M[4], py * M[5])) + M[7];
+  wz = __builtin_fmaf(pz, M[10], __builtin_fmaf(px, M[8], py * M[9])) + M[11];
+}
+
+// point-major index p of image b -> the CAMERA-space sample q of gen_point's world point (world = R q + t with R, t of cam2world):
+// the px, py, pz ray_point forms before it applies the matrix, or direction * depth for the zvals form (where gen_point rotates
+// the direction first and scales after).  For the reduction of per-point gradients to the camera matrix (cips_rays_bwd_cam).
+__device__ __forceinline__ void gen_point_cam(const RayGen& g, int b, int p, float& qx, float& qy, float& qz) {
+  const int ray = p / g.S, s = p - ray * g.S;
+  const RayDir d = ray_dir(g, ray);
+  if (g.zvals) {
+    const float z = g.zvals[(long long)b * g.n * g.S + p];
+    qx = d.dx * z; qy = d.dy * z; qz = d.dz * z;
+    return;
+  }
+  const float z0 = g.zg[s];
+  qx = d.dx * z0; qy = d.dy * z0; qz = d.dz * z0;
+  if (g.jitter) {
+    const float off = (g.jitter[(long long)b * g.n * g.S + p] - 0.5f) * (g.zg[1] - g.zg[0]);
+    qx = qx + off * d.dx; qy = qy + off * d.dy; qz = qz + off * d.dz;
+  }
+}
+
 static inline int fill_raygen(RayGen& g, const cips_ray_params* r) {
   if (!r || !r->xg || !r->yg || !r->zg || !r->cam2world || r->W <= 0 || r->H <= 0 || r->S <= 1) return (int)hipErrorInvalidValue;
   g.xg = r->xg; g.yg = r->yg; g.zg = r->zg; g.c2w = r->cam2world; g.jitter = r->jitter; g.zvals = r->zvals; g.zc = r->zc;

@@ -692,16 +692,27 @@ def draw_part_randoms(s, b, device):
             (idx_rest, _draw_noise(s, ro, '_rest', b, idx_rest.numel(), device)))
 
 
-@torch.no_grad()
+def _wants_grad(*values):
+    return any(torch.is_tensor(v) and v.requires_grad for v in values)
+
+
 def camera_setup(s, theta, phi, b, device):
     """the camera draws of draw_randoms, or the explicit camera (theta is None; pitch / yaw are zeros) -> the origin of
-    every ray (b,3), cam2world (b,4,4), pitch_yaw (b,2).  O(b) host math."""
+    every ray (b,3), cam2world (b,4,4), pitch_yaw (b,2).  O(b) host math, under no_grad (the GAN step: the reference builds its
+    rays there) unless the caller's grad mode is on and camera_pos, camera_lookup, h_mean or v_mean is a tensor that requires
+    grad: then cam2world carries the graph to them (fitting a camera to an image)."""
+    with torch.set_grad_enabled(torch.is_grad_enabled() and _wants_grad(s.camera_pos, s.camera_lookup, s.h_mean, s.v_mean)):
+        return _camera_setup(s, theta, phi, b, device)
+
+
+def _camera_setup(s, theta, phi, b, device):
     if theta is None:
         origin, forward_vector = s.camera_pos, _normalize(s.camera_lookup)
         pitch = yaw = torch.zeros(b, 1, device=device)
     else:
         if s.sample_dist in _SIMPLE_CAMS:
-            if theta.is_cuda and not (s.staged and s.up_vector is not None):
+            # (the one-launch form takes the means as floats: a mean that requires grad goes op by op, which is differentiable)
+            if theta.is_cuda and not (s.staged and s.up_vector is not None) and not _wants_grad(s.h_mean, s.v_mean):
                 # draws -> pitch, yaw, origin, cam2world in one launch (the ~45 one-wave torch kernels of the op-by-op form
                 # below are 0.2 ms of a captured step)
                 pitch_yaw, origin, cam2world = ops.camera_pose(theta, phi, s.sample_dist == 'uniform', s.h_stddev, s.h_mean,
@@ -839,7 +850,18 @@ class GeneratorNerfINR(nn.Module):
         in_kernel = (not s.part) and ops.march_available() and self.siren.fused
         g = SimpleNamespace(form=("rays" if s.hierarchical_sample else "march") if in_kernel else "points", b=b, xg=xg, yg=yg,
                             zg=zg, zc=zc, origin=origin, cam2world=cam2world, jitter=jitter.reshape(b, s.n, S))
-        if g.form == "points":
+        # a camera that is being fitted: cam2world carries a graph and the NeRF path runs with gradients.  The in-kernel forms
+        # take the matrix as an input of their Functions; the "points" form applies it in torch
+        g.cam_grad = self.nerf_grad and torch.is_grad_enabled() and cam2world.requires_grad
+        if g.form == "points" and g.cam_grad:
+            with torch.no_grad():
+                # the camera-space samples and directions: the rays of the identity camera
+                eye = torch.eye(4, device=device).expand(b, 4, 4).contiguous()
+                q, g.z_vals, d_cam = ops.rays_fwd(xg, yg, zg, zc, eye, g.jitter, b, s.img_size, s.img_size, S)
+            Rt = cam2world[:, :3, :3].transpose(1, 2)
+            g.points = (q.view(b, s.n * S, 3) @ Rt + cam2world[:, None, :3, 3]).view(b, s.n, S, 3)
+            g.dirs = d_cam @ Rt
+        elif g.form == "points":
             with torch.no_grad():
                 g.points, g.z_vals, g.dirs = ops.rays_fwd(xg, yg, zg, zc, cam2world, g.jitter, b, s.img_size, s.img_size, S)
         return g
@@ -886,6 +908,10 @@ class GeneratorNerfINR(nn.Module):
                 if g.form == "rays":
                     feat_f, sig_f, _ = self.siren.evaluate_rays(*rays, zvals=fine_z.view(b, m * S))
                 else:
+                    if g.cam_grad and torch.is_grad_enabled():
+                        # origin + direction * depth outside no_grad: the depths are constants (as in the reference), the
+                        # origin and the directions carry the camera's graph
+                        fine_pts = (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * fine_z.view(b, m, S, 1)).reshape(b, m * S, 3)
                     feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, m * S, 3), nerf_styles)
                 feat_f, sig_f = feat_f.view(b * m, S, 32), sig_f.view(b * m, S)
             out = ops.CompositeFunction.apply(

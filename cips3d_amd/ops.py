@@ -11,6 +11,7 @@ import os
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import (ConvDgradS2Desc, ConvWgradDesc, ConvX3Desc, GemmDesc, GemmX3Desc, GlinJob, GridParams, ModfcBwdJob,
@@ -210,7 +211,8 @@ class SirenFunction(torch.autograd.Function):
     Mirrors NeRFNetwork.forward_with_frequencies_phase_shifts (generator.py:260-317); gains g*
     are already 15*gain_fc(style)+30 and phases p* = bias_fc(style) (film_layer.py:88-93), both
     computed by tiny torch Linears on the host side so autograd carries them to the mapping net.
-    No gradient w.r.t. points (the reference never needs it: points come from no_grad ray math).
+    The gradient w.r.t. the points is computed only when they require one (the GAN step's points come from no_grad ray
+    math): one extra launch, cips_siren_bwd_points_x3, behind whichever backward form ran.  Once differentiable.
     """
 
     @staticmethod
@@ -229,11 +231,17 @@ class SirenFunction(torch.autograd.Function):
         return feat, sigma
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dfeat, dsigma):
         points = ctx.saved_tensors[0]
         t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[1:]))
         B, P, _ = points.shape
-        return (None,) + _siren_backward(t, dfeat, dsigma, B, P, points=points)
+        if not ctx.needs_input_grad[0]:
+            return (None,) + _siren_backward(t, dfeat, dsigma, B, P, points=points)
+        _need_x3_points_grad()
+        dfeat, dsigma = _upstream(dfeat, dsigma, B, P, points.device)
+        grads = _siren_backward(t, dfeat, dsigma, B, P, points=points)
+        return (siren_bwd_points(t, dfeat, dsigma, B, P, points=points),) + grads
 
 
 def _siren_sigma_f32(t, points):
@@ -325,6 +333,45 @@ def siren_sigma_grad_grid(gx, gy, gz, *siren):
     check(_lib.load().cips_siren_sigma_grad_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), _p(grad), B, _stream()),
           "cips_siren_sigma_grad_x3_grid")
     return sigma, grad
+
+
+def _need_x3_points_grad():
+    if SIREN_FWD_MODE != "x3":
+        raise RuntimeError(f"the gradient w.r.t. the sample points / the camera runs on the split-operand SIREN chain only: "
+                           f"there is no exact-fp32 kernel for it (CIPS_SIREN_FWD={SIREN_FWD_MODE!r})")
+
+
+def _upstream(dfeat, dsigma, B, P, dev):
+    """the upstream gradients of a SIREN Function as contiguous fp32 tensors (None: zeros)"""
+    dfeat = _c(dfeat) if dfeat is not None else torch.zeros(B, P, 32, device=dev)
+    dsigma = _c(dsigma) if dsigma is not None else torch.zeros(B, P, device=dev)
+    return dfeat, dsigma
+
+
+def siren_bwd_points(t, dfeat, dsigma, B, P, points=None, rays=None):
+    """dpoints (B,P,3): the SIREN's vector-Jacobian product w.r.t. the sample points for the upstream gradients dfeat (B,P,32),
+    dsigma (B,P) — the points given (B,P,3) or regenerated in-kernel from `rays` (cips_siren_bwd_points_x3 / _rays).  Dense:
+    every row of dfeat / dsigma is read."""
+    _need_x3_points_grad()
+    _chk(dfeat, dsigma, points)
+    dpoints = torch.empty(B, P, 3, device=dfeat.device)
+    sw = _siren_struct(t)
+    if points is not None:
+        check(_lib.load().cips_siren_bwd_points_x3(C.byref(sw), _p(points), _p(dfeat), _p(dsigma), _p(dpoints), B, P, _stream()),
+              "cips_siren_bwd_points_x3")
+    else:
+        check(_lib.load().cips_siren_bwd_points_x3_rays(C.byref(sw), C.byref(rays), _p(dfeat), _p(dsigma), _p(dpoints), B,
+                                                        _stream()), "cips_siren_bwd_points_x3_rays")
+    return dpoints
+
+
+def rays_bwd_cam(rays, dpoints, B):
+    """per-point gradients (B, H*W*S, 3) of the points `rays` generates -> the gradient of cam2world (B,4,4), row 3 zeros
+    (cips_rays_bwd_cam: one launch, fixed summation order)"""
+    _chk(dpoints)
+    dcam = torch.empty(B, 4, 4, device=dpoints.device)
+    check(_lib.load().cips_rays_bwd_cam(C.byref(rays), _p(dpoints), _p(dcam), B, _stream()), "cips_rays_bwd_cam")
+    return dcam
 
 
 def _siren_backward(t, dfeat, dsigma, B, P, points=None, rays=None, live=None):
@@ -783,7 +830,9 @@ class SirenRaysFunction(torch.autograd.Function):
     """feat (B,P,32), sigma (B,P), z (B,P) = siren(points generated in-kernel) — SirenFunction without the (B,P,3)
     points tensor, for the two passes of the hierarchical path: the coarse pass generates its stratified samples from
     (grids, cam2world, jitter) (comm_utils.py:365-438, 584-679), the fine pass from the resampled depths
-    `zvals`: origin + direction * z (generator_nerf_inr.py:590-592).  Backward: cips_siren_bwd_x3_rays."""
+    `zvals`: origin + direction * z (generator_nerf_inr.py:590-592).  Backward: cips_siren_bwd_x3_rays; when cam2world requires a
+    gradient also the per-point gradients (cips_siren_bwd_points_x3_rays) and their reduction to the matrix (cips_rays_bwd_cam).
+    Grids, jitter and zvals get none.  Once differentiable."""
 
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, zvals, *siren):
@@ -806,12 +855,19 @@ class SirenRaysFunction(torch.autograd.Function):
         return feat, sigma, z
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dfeat, dsigma, _dz):
         xg, yg, zg, cam2world, jitter, zvals = ctx.saved_tensors[:6]
         t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[6:]))
         B, H, W, S, zc = ctx.geom
         rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S, zvals)
-        return (None,) * 7 + _siren_backward(t, dfeat, dsigma, B, H * W * S, rays=rp)
+        if not ctx.needs_input_grad[4]:
+            return (None,) * 7 + _siren_backward(t, dfeat, dsigma, B, H * W * S, rays=rp)
+        _need_x3_points_grad()
+        dfeat, dsigma = _upstream(dfeat, dsigma, B, H * W * S, cam2world.device)
+        grads = _siren_backward(t, dfeat, dsigma, B, H * W * S, rays=rp)
+        dcam = rays_bwd_cam(rp, siren_bwd_points(t, dfeat, dsigma, B, H * W * S, rays=rp), B)
+        return (None,) * 4 + (dcam,) + (None,) * 2 + grads
 
 
 class RayMarchFunction(torch.autograd.Function):
@@ -824,7 +880,10 @@ class RayMarchFunction(torch.autograd.Function):
     and cips_live_points between them: the SIREN backward then runs over the samples with a non-zero upstream gradient.
     With SIREN_LIVE_FWD, for a caller that says so in geom and joins the list stream behind its next stage, the training
     forward makes those lists and their EVEN plan itself, on another stream (live_plan_forward), and the backward is
-    cips_composite_bwd_listed followed by the SIREN backward."""
+    cips_composite_bwd_listed followed by the SIREN backward.
+    When cam2world requires a gradient the backward also runs the dense per-point kernel (cips_siren_bwd_points_x3_rays) and its
+    reduction (cips_rays_bwd_cam); the live forms of the compositing backward leave the rows of dead samples unwritten, so the
+    buffers are then allocated zero-filled — a dead sample's gradient is exactly zero.  Once differentiable."""
 
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
@@ -861,6 +920,7 @@ class RayMarchFunction(torch.autograd.Function):
         return fea, depth
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dfea, _ddepth):
         lib = _lib.load()
         xg, yg, zg, cam2world, jitter, noise, feat, sigma, z = ctx.saved_tensors[:9]
@@ -869,8 +929,12 @@ class RayMarchFunction(torch.autograd.Function):
         n = H * W
         R = B * n
         dfea = _c(dfea)
-        dfeat = torch.empty_like(feat)
-        dsig = torch.empty_like(sigma)
+        want_cam = ctx.needs_input_grad[4]
+        if want_cam:
+            _need_x3_points_grad()
+        # the camera gradient's kernel reads every row, the live forms below write only the live ones
+        dfeat = torch.zeros_like(feat) if want_cam else torch.empty_like(feat)
+        dsig = torch.zeros_like(sigma) if want_cam else torch.empty_like(sigma)
         use_live = SIREN_BWD_LIVE and SIREN_BWD_MODE == "x3"
         live = None
         if ctx.live_fwd:
@@ -894,7 +958,10 @@ class RayMarchFunction(torch.autograd.Function):
         if live is None and use_live:
             live = live_points(mask)
         grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live)
-        return (None,) * 7 + grads
+        if not want_cam:
+            return (None,) * 7 + grads
+        dcam = rays_bwd_cam(rp, siren_bwd_points(t, dfeat, dsig, B, n * S, rays=rp), B)
+        return (None,) * 4 + (dcam,) + (None,) * 2 + grads
 
 
 # --------------------------------------------------------------------------------------

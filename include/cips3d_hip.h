@@ -178,6 +178,23 @@ int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_p
 int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
                            const float* dsigma, float* sred, float* gpart, int B, cips_stream_t stream);
 
+/* Gradient w.r.t. the sample points: the vector-Jacobian product of cips_siren_fwd_x3 with the upstream gradients dfeat (B,P,32)
+ * and dsigma (B,P), dpoints (B,P,3) = J^T (dfeat, dsigma), row-major.  A data-only kernel (recompute + four transposed layers on
+ * three-pass split bf16, whatever trig_mode's bit 1 says); the weight gradients are cips_siren_bwd_x3's.  Every element of dpoints
+ * is written; a point whose dfeat row and dsigma are zero gets exact zeros.  All pointers are required; a NULL pointer or a
+ * non-positive size returns hipErrorInvalidValue before any HIP call. */
+int cips_siren_bwd_points_x3(const cips_siren_weights* w, const float* points, const float* dfeat, const float* dsigma,
+                             float* dpoints /* (B,P,3) */, int B, int P, cips_stream_t stream);
+/* the same with the points generated in-kernel from `rays` (coarse: grids + jitter; fine: zvals), P = H*W*S: the points form's
+ * result at cips_rays_fwd's points bit for bit. */
+int cips_siren_bwd_points_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat, const float* dsigma,
+                                  float* dpoints /* (B, H*W*S, 3) */, int B, cips_stream_t stream);
+/* Per-point gradients -> camera matrix.  The world point is R q + t with q the camera-space sample of `rays` (direction *
+ * (depth + jitter offset), or direction * zvals), so d cam2world[:3,:3] = sum_p dpoint q^T and d cam2world[:3,3] = sum_p dpoint.
+ * One launch, fixed summation order, no atomics: two calls on the same inputs give the same bits. */
+int cips_rays_bwd_cam(const cips_ray_params* rays, const float* dpoints /* (B, H*W*S, 3) */,
+                      float* dcam2world /* (B,4,4); row 3 written as zeros */, int B, cips_stream_t stream);
+
 /* The fused backward over a LIST of points per image instead of all P (the points whose upstream gradient is not exactly
  * zero: every output is linear in a point's (dfeat row, dsigma), so the others add nothing).  idx (B,P) int32: image b's
  * point indices, ascending, in idx[b*P + 0 .. count[b]); count (B) int32, 0 <= count[b] <= P; both device memory, read by
