@@ -96,6 +96,36 @@ def density_lattice(N, cube_length, center):
     return tuple(idx * (cube_length / (N - 1)) + (c - cube_length / 2) for c in center)
 
 
+def save_ply(path, vertices, faces, normals=None):
+    """One triangle mesh (GeneratorNerfINR.extract_mesh, ops.mesh_from_volume) as a binary little-endian PLY file: vertices
+    (V, 3) as float x y z, normals (V, 3) as float nx ny nz when given, faces (T, 3) as `list uchar int vertex_indices`.
+    Tensors on any device or arrays.  (No .mrc writer: see DESIGN.md section 6.)"""
+    import numpy as np
+
+    def host(t, dtype):
+        return np.ascontiguousarray((t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).astype(dtype))
+    v, f = host(vertices, "<f4"), host(faces, "<i4")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("save_ply takes vertices (V, 3) and faces (T, 3)")
+    cols = [v]
+    props = ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        n = host(normals, "<f4")
+        if n.shape != v.shape:
+            raise ValueError("save_ply: normals must have the vertices' shape")
+        cols.append(n)
+        props += ["property float nx", "property float ny", "property float nz"]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", *props, f"element face {len(f)}",
+              "property list uchar int vertex_indices", "end_header"]
+    rows = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    rows["n"] = 3
+    rows["i"] = f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(np.ascontiguousarray(np.concatenate(cols, 1)).tobytes())
+        fh.write(rows.tobytes())
+
+
 @torch.no_grad()
 def gen_images(rank, world_size, generator, G_kwargs, fake_dir, num_imgs, img_size, batch_size, forward_points=256 ** 2,
                progress=False):

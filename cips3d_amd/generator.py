@@ -1094,6 +1094,33 @@ class GeneratorNerfINR(nn.Module):
             return self.siren.density_gradient_lattice(gx, gy, gz, self._nerf_styles(style_dict))
         return self.siren.density_lattice(gx, gy, gz, self._nerf_styles(style_dict))
 
+    @torch.no_grad()
+    def extract_mesh(self, zs, level, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, normals=True):
+        """The surface sigma = level of density_grid's volume as one indexed triangle mesh per image -> a list of
+        SimpleNamespace(vertices (V, 3) fp32, faces (T, 3) int32, normals (V, 3) fp32 or None), all on the GPU; the volume never
+        leaves it (ops.mesh_from_volume: marching tetrahedra, one host synchronisation for the mesh sizes).  `level` has no
+        default: the right iso-value depends on the checkpoint.  The volume is density_grid's for the same arguments — same
+        styles, truncation and RNG draws (psi < 1 draws the 10 000 latents once).  Triangles are wound so that their geometric
+        normal points towards lower density; `normals` are -grad sigma / |grad sigma| at the vertices from
+        NeRFNetwork.density_gradient with that image's styles, exact zeros where the gradient is zero (as in geometry)."""
+        from .evaluation import density_lattice
+        device = zs['z_nerf'].device
+        nerf_styles = self._nerf_styles(self._density_styles(zs['z_nerf'], psi))
+        gx, gy, gz = (g.to(device) for g in density_lattice(resolution, cube_length, center))
+        sigma = self.siren.density_lattice(gx, gy, gz, nerf_styles)
+        meshes = []
+        for b, (vertices, faces) in enumerate(ops.mesh_from_volume(sigma.contiguous(), gx, gy, gz, level)):
+            n = None
+            if normals:
+                n = torch.zeros_like(vertices)
+                if vertices.shape[0]:
+                    styles_b = {name: style[b:b + 1] for name, style in nerf_styles.items()}
+                    grad = self.siren.density_gradient(vertices.unsqueeze(0), styles_b)[1][0]
+                    norm = grad.norm(dim=-1, keepdim=True)
+                    n = torch.where(norm > 0, -grad / norm, torch.zeros_like(grad))
+            meshes.append(SimpleNamespace(vertices=vertices, faces=faces, normals=n))
+        return meshes
+
     def forward_camera_pos_and_lookup(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                       h_mean, v_mean, hierarchical_sample, camera_pos, camera_lookup, psi=1,
                                       sample_dist=None, lock_view_dependence=False, clamp_mode='relu',

@@ -335,6 +335,66 @@ def siren_sigma_grad_grid(gx, gy, gz, *siren):
     return sigma, grad
 
 
+def mesh_from_volume(sigma, gx, gy, gz, level, out=None):
+    """Triangle meshes of the level set sigma = level: sigma (B, nx, ny, nz) on the lattice (gx[i], gy[j], gz[k]) of three
+    strictly increasing 1-D coordinate tensors -> a list of B pairs (vertices (V_b, 3) fp32, faces (T_b, 3) int32), all on the
+    GPU (cips_mesh_count / cips_mesh_emit: marching tetrahedra on the Kuhn decomposition, DESIGN.md section 3 "Meshes").  A
+    point is inside iff sigma > level; the triangles' normals (P1 - P0) x (P2 - P0) point towards lower density; faces index
+    their own image's vertices.  The pairs are views of two packed tensors; an image without a crossing gets (0, 3) tensors.
+    Two calls on the same input give the same bits.
+
+    ONE host synchronisation per call: the read of the per-image totals between the count and the emit launches, which sizes
+    the outputs (the check that the coordinates increase rides on the same read).  For that reason the function cannot be
+    captured in a hipGraph and raises under capture.  Inputs must be on the GPU, fp32 and contiguous; no gradient flows.
+    out: optional (vertices, faces) buffers to fill instead of new tensors, (>= sum V, 3) fp32 and (>= sum T, 3) int32,
+    contiguous; rows behind the totals are left untouched."""
+    sigma, gx, gy, gz = (t.detach() for t in (sigma, gx, gy, gz))
+    _chk(sigma, gx, gy, gz)
+    if any(t.dtype != torch.float32 for t in (sigma, gx, gy, gz)):
+        raise RuntimeError("mesh_from_volume takes fp32 tensors")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("mesh_from_volume reads the mesh sizes on the host between its launches: it cannot be captured in a hipGraph")
+    if sigma.dim() != 4 or gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
+        raise ValueError("mesh_from_volume takes sigma (B, nx, ny, nz) and three 1-D coordinate tensors")
+    B, nx, ny, nz = sigma.shape
+    if (gx.numel(), gy.numel(), gz.numel()) != (nx, ny, nz):
+        raise ValueError(f"coordinate tensors of {gx.numel()}, {gy.numel()}, {gz.numel()} points for a volume {nx} x {ny} x {nz}")
+    lib = _lib.load()
+    gp = GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz)
+    nbytes = lib.cips_mesh_scratch_bytes(C.byref(gp), B)
+    if nbytes < 0:
+        raise ValueError(f"mesh_from_volume: a lattice of {nx} x {ny} x {nz} points (B = {B}) is out of range: at least 2 points "
+                         "per axis, at most INT_MAX / 7 points and INT_MAX / 12 cells per image")
+    dev = sigma.device
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    level = float(level)
+    check(lib.cips_mesh_count(C.byref(gp), _p(sigma), level, B, _p(scratch), nbytes, _p(totals), _stream()), "cips_mesh_count")
+    increasing = torch.stack([(g[1:] > g[:-1]).all() for g in (gx, gy, gz)]).all()
+    *host, ok = torch.cat([totals.view(-1), increasing.to(torch.int64).view(1)]).tolist()       # the one synchronisation
+    if not ok:
+        raise ValueError("mesh_from_volume: the coordinate tensors must be strictly increasing")
+    V, T = host[0::2], host[1::2]
+    if out is None:
+        vertices = torch.empty(sum(V), 3, device=dev)
+        faces = torch.empty(sum(T), 3, dtype=torch.int32, device=dev)
+    else:
+        vertices, faces = out
+        _chk(vertices, faces)
+        if vertices.dtype != torch.float32 or faces.dtype != torch.int32 or vertices.dim() != 2 or faces.dim() != 2 \
+                or vertices.shape[1] != 3 or faces.shape[1] != 3 or vertices.shape[0] < sum(V) or faces.shape[0] < sum(T):
+            raise ValueError(f"mesh_from_volume: out must be (>= {sum(V)}, 3) fp32 and (>= {sum(T)}, 3) int32")
+    if sum(V) > 0 and sum(T) > 0:
+        check(lib.cips_mesh_emit(C.byref(gp), _p(sigma), level, B, _p(scratch), nbytes, _p(totals), _p(vertices), _p(faces),
+                                 _stream()), "cips_mesh_emit")
+    meshes, v0, t0 = [], 0, 0
+    for nv, nt in zip(V, T):
+        meshes.append((vertices[v0:v0 + nv], faces[t0:t0 + nt]))
+        v0 += nv
+        t0 += nt
+    return meshes
+
+
 def _need_x3_points_grad():
     if SIREN_FWD_MODE != "x3":
         raise RuntimeError(f"the gradient w.r.t. the sample points / the camera runs on the split-operand SIREN chain only: "

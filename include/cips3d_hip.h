@@ -174,6 +174,26 @@ int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, f
 int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma /* may be NULL */,
                                   float* grad, int B, cips_stream_t stream);
 
+/* Indexed triangle meshes of the level set sigma = level of a volume sigma (B, nx, ny, nz) on the lattice of cips_grid_params
+ * (strictly increasing coordinates; nx, ny, nz >= 2): marching tetrahedra on the Kuhn decomposition of every cell, no table of
+ * cube cases, watertight by construction (replaces the mcubes / skimage step of exp/pigan/scripts/extract_shapes.py on the host).
+ * A point is inside iff sigma > level (NaN: outside).  One vertex per lattice edge p -> p + d (d a non-zero 0/1 vector, edge
+ * class c = 4 dx + 2 dy + dz - 1 of its lower point p) whose ends differ, at g[a] + t (g[a + d_a] - g[a]) with
+ * t = (level - sigma_p) / (sigma_q - sigma_p), ordered by (p, c); triangles ordered by cell, tetrahedron, piece, wound so that
+ * (P1 - P0) x (P2 - P0) points towards lower density; faces index the vertices of their own image.  The rules in full: DESIGN.md
+ * section 3 "Meshes".  No atomics, fixed positions: two calls on the same input give the same bits.
+ * Scratch: device memory, 4-byte aligned, cips_mesh_scratch_bytes(grid, B) bytes (at most 8 per lattice point and image), filled
+ * by the count call and read by the emit call.  B <= 65535, 7 nx ny nz <= INT_MAX and 12 (nx-1)(ny-1)(nz-1) <= INT_MAX; anything
+ * else, a NULL pointer or a scratch that is too small returns hipErrorInvalidValue (the size query: -1) before any HIP call. */
+long long cips_mesh_scratch_bytes(const cips_grid_params* grid, int B);   /* host only: reads the three sizes */
+/* count + the two levels of the scan (three launches): totals (B, 2) int64 device memory receives (vertices, triangles) per image */
+int cips_mesh_count(const cips_grid_params* grid, const float* sigma, float level, int B, void* scratch, long long scratch_bytes,
+                    long long* totals, cips_stream_t stream);
+/* vertices + faces (two launches) behind a count call on the same grid, sigma, level, B, scratch and totals: the images' meshes
+ * packed one after the other, vertices (sum V, 3) fp32 and faces (sum T, 3) int32.  Nothing beyond the totals is ever written. */
+int cips_mesh_emit(const cips_grid_params* grid, const float* sigma, float level, int B, void* scratch, long long scratch_bytes,
+                   const long long* totals, float* vertices, int* faces, cips_stream_t stream);
+
 /* cips_siren_bwd_x3 with the points generated in-kernel from `rays` (P = H*W*S points per image). */
 int cips_siren_bwd_x3_rays(const cips_siren_weights* w, const cips_ray_params* rays, const float* dfeat,
                            const float* dsigma, float* sred, float* gpart, int B, cips_stream_t stream);
