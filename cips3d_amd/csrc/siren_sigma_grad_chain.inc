@@ -1,12 +1,13 @@
 // siren_sigma_grad_chain.inc — textually included by siren_sigma_grad_x3_kernel (siren_sigma_x3.inc): siren_sigma_chain.inc's
 // wave-step carried on to the gradient of sigma w.r.t. the point.
-// In scope: what siren_sigma_w1.inc asks for (it opens the step: LA, hf, valid, gp, the point), float bs, float dscale (the power of two
+// In scope: what siren_sigma_point.inc asks for (it opens the step: LA, hf, valid, gp, the point), float bs, float dscale (the power of two
 // the kernel puts on the layer-1 factor, 1 on bf16 planes) and the template flags HW and F16; defines `float sig` and
 // `float gx, gy, gz` (both lane halves), the gradient still times  dscale  and, with HW, divided by (2 pi)^2.
 //   sigma = ws . sin(a1) + bs,   dp1 = g1 * ws * cos(a1),   dh1 = W1^T dp1,   grad = sum_f pack[f].xyz cos(a0[f]) dh1[f]
 // sigma is siren_sigma_chain.inc's bit for bit: the first block is the same text (siren_sigma_w1.inc).  The layer-1 epilogues stay
 // separate — this one takes the cosine next to every sine and packs dp1, the sigma chain keeps nothing but the dot — and agree
 // because both evaluate the same fmaf chain per feature in the same (grp, e) order; the sine of sincos_rev is sin_rev's expression.
+#include "siren_sigma_point.inc"
 #include "siren_sigma_w1.inc"
     // layer-1 epilogue: the accumulator of feature f is consumed as sine for the sigma dot and as cosine for dp1, which is
     // packed to split planes — the B operand of the transposed layer, k order of the register chain

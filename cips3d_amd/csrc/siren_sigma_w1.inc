@@ -1,32 +1,10 @@
-// siren_sigma_w1.inc — textually included by siren_sigma_chain.inc and siren_sigma_grad_chain.inc: what the wave-steps of the sigma
-// and the sigma-gradient kernel have in common, as one text — the step's prologue (the laundered lane id, the LDS address bases
-// on the sigma carve, the ragged-tail clamp, the point from the points array or the GRID lattice), then layer 0 and the W1
-// product.  The sigma of the gradient kernel is the sigma kernel's bit for bit by construction up to here.  (Text and no
-// function: as a __device__ function the prologue alone changes the kernels' listings.)
-// In scope: the kernel's arguments a (points or gx / gy / gz, ny, nz, P), int b, lane0, pbase, cend, unsigned sbase and the template
-// flags HW, F16, GRID.  Defines LaneAddr LA (v16 / v64 pointing at the sigma carve's layer-0 packs), int hf, bool valid (false:
-// a lane past the chunk's end, working on the last valid point again; nothing is stored for it), long long gp (index of the point
-// in the (B, P) outputs), float px, py, pz and `f32x16 acc[4]`, the layer-1 pre-activations W1 h1 (before gain and offset) in
-// register-chain layout.
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    const int l31 = lane & 31, hf = lane >> 5;
-    LaneAddr LA = lane_addr(lane, sbase);
-    LA.v16 = opaque(sbase + SG_L0 + 16 * hf);
-    LA.v64 = opaque(sbase + SG_L0 + 64 * hf);
-    const int p = pbase + l31;
-    const bool valid = p < cend;
-    const int pc = valid ? p : cend - 1;           // ragged tail: the last valid point again, nothing stored
-    const long long gp = (long long)b * a.P + pc;
-    float px, py, pz;
-    if constexpr (GRID) {
-      const unsigned r = (unsigned)pc / (unsigned)a.nz, k = (unsigned)pc - r * (unsigned)a.nz;
-      const unsigned i = r / (unsigned)a.ny, j = r - i * (unsigned)a.ny;
-      px = a.gx[i]; py = a.gy[j]; pz = a.gz[k];
-    } else {
-      px = a.points[gp * 3 + 0]; py = a.points[gp * 3 + 1]; pz = a.points[gp * 3 + 2];
-    }
-
+// siren_sigma_w1.inc — textually included by siren_sigma_chain.inc and siren_sigma_grad_chain.inc behind siren_sigma_point.inc, and by
+// siren_surface_x3.hip behind a prologue of its own: what the wave-steps of the sigma, the sigma-gradient and the surface kernel have
+// in common, as one text — layer 0 and the W1 product.  The sigma of the gradient and of the surface kernel is the sigma kernel's
+// bit for bit by construction up to here.
+// In scope: what the prologue defines — LaneAddr LA (v16 / v64 pointing at the sigma carve's layer-0 packs) and the point, float
+// px, py, pz — and the template flags HW and F16.  Defines `f32x16 acc[4]`, the layer-1 pre-activations W1 h1 (before gain and
+// offset) in register-chain layout.
     f32x16 acc[4];
     zero_acc(acc);
     {

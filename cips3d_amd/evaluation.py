@@ -127,6 +127,22 @@ def save_ply(path, vertices, faces, normals=None):
 
 
 @torch.no_grad()
+def shade_surface(surface, light=(0., 0., 1.), ambient=0.2):
+    """A picture of GeneratorNerfINR.surface's result for save_image / save_images: Lambert shading of the normals,
+    ambient + (1 - ambient) * max(0, n . l) with l = light / |light| (world space), mapped to [-1, 1] and repeated over three
+    channels -> (b, 3, H, W); -1 (black) where mask == 0, the rays that cross no surface."""
+    if surface.normals is None:
+        raise ValueError("shade_surface needs normals (GeneratorNerfINR.surface(..., normals=True))")
+    n = surface.normals
+    l = torch.tensor(light, dtype=n.dtype, device=n.device)
+    l = l / l.norm()
+    lambert = (n * l.view(1, 3, 1, 1)).sum(1, keepdim=True).clamp(0., 1.)
+    shade = (ambient + (1. - ambient) * lambert) * 2. - 1.
+    shade = torch.where(surface.mask == 0, torch.full_like(shade, -1.), shade.clamp(-1., 1.))
+    return shade.expand(-1, 3, -1, -1).contiguous()
+
+
+@torch.no_grad()
 def gen_images(rank, world_size, generator, G_kwargs, fake_dir, num_imgs, img_size, batch_size, forward_points=256 ** 2,
                progress=False):
     """gen_images.py:30-69: `num_imgs` samples of `generator` (normally G_ema) at psi = 1 as

@@ -309,6 +309,21 @@ class NeRFNetwork(nn.Module):
                 return sigma.reshape(b, *n), grad.reshape(b, *n, 3)
             return ops.siren_sigma_grad_grid(gx, gy, gz, *self._siren_args(style_dict))
 
+    def surface_rays(self, style_dict, geom, xg, yg, zg, cam2world, level, refine):
+        """The iso-surface sigma = level along the unjittered camera rays -> depth (b,n), hit (b,n) uint8, sigma (b,n), points
+        (b,n,3), no gradient (the rule: ops.siren_surface).  The ray-cast HIP kernel for the shipped shape on the split-operand
+        chain; the same search composed from sigma evaluations (ops.siren_surface_composed) for the exact-fp32 forward
+        (CIPS_SIREN_FWD=f32) and, on tensor operations, for other widths / depths."""
+        with torch.no_grad():
+            style_dict = self._sigma_args(style_dict)
+            if not self.fused:
+                return ops.siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world,
+                                                  sigma_fn=lambda p: self._evaluate_unfused(p, style_dict)[1])
+            siren = self._siren_args(style_dict)
+            if ops.SIREN_FWD_MODE != "x3":
+                return ops.siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world, *siren)
+            return ops.siren_surface(level, refine, geom, xg, yg, zg, cam2world, *siren)
+
     def evaluate_rays(self, style_dict, geom, xg, yg, zg, cam2world, jitter=None, zvals=None):
         """evaluate() with the sample points generated in-kernel (coarse: from the jitter draw; fine: from the resampled
         depths `zvals`) -> feat (b,P,32), sigma (b,P), z (b,P)"""
@@ -1072,6 +1087,53 @@ class GeneratorNerfINR(nn.Module):
             return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
 
         return SimpleNamespace(depth=img(depth), points=img(points), sigma=img(sigma), normals=img(normals), pitch_yaw=pitch_yaw)
+
+    @torch.no_grad()
+    def surface(self, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean=math.pi * 0.5,
+                v_mean=math.pi * 0.5, psi=1, sample_dist=None, camera_pos=None, camera_lookup=None, up_vector=None, refine=8,
+                normals=True, rand_override=None):
+        """The surface sigma = level as the camera of forward() (or, with camera_pos / camera_lookup, of
+        forward_camera_pos_and_lookup()) sees it: every ray is walked through the density at the `num_steps` unjittered depths
+        from ray_start to ray_end, stopped at the first crossing of `level` and refined by `refine` bisection steps and a secant
+        step (NeRFNetwork.surface_rays; the rule: include/cips3d_hip.h, cips_siren_surface_x3) -> SimpleNamespace of
+          depth   (b,1,H,W)  the depth of the crossing — geometry()'s quantity; ray_start where the ray starts inside the
+                             surface, ray_end where it crosses nothing
+          mask    (b,1,H,W)  uint8: 1 crossing, 0 none (background), 2 the ray starts inside
+          points  (b,3,H,W)  origin + direction * depth, world space
+          sigma   (b,1,H,W)  the density at those points: level up to the residual of the refinement where mask == 1
+          normals (b,3,H,W)  -grad sigma / |grad sigma| at the points (NeRFNetwork.density_gradient); exact zeros where
+                             mask == 0 or the gradient is zero; None with normals=False
+          pitch_yaw (b,2)
+        `level` has no default (as in extract_mesh, whose mesh this is a view of).  Only the NeRF mapping network runs.  Random
+        numbers: as geometry() — the draws and the camera are draw_randoms / camera_setup on the RenderSettings of a
+        non-hierarchical forward() with nerf_noise = 0, so a seed gives the camera of the image it renders and the generators
+        are left where forward() leaves them; the jitter is drawn and not used."""
+        device = next(self.parameters()).device
+        if device.type != 'cuda':
+            raise RuntimeError("GeneratorNerfINR.surface runs on the GPU only (there is no CPU path)")
+        s = RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=False, sample_dist=sample_dist, nerf_noise=0.,
+            rand_override=rand_override, camera_pos=camera_pos, camera_lookup=camera_lookup, up_vector=up_vector)
+        nerf_styles = self._nerf_styles(self.siren._sigma_args(self._density_styles(zs['z_nerf'], psi)))
+        b, H = zs['z_nerf'].shape[0], img_size
+        d = draw_randoms(s, b, device)
+        _, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
+        xg, yg, zg = ops.pixel_grids(H, H, num_steps, ray_start, ray_end, device)
+        zc = float((-torch.ones(1) / np.tan((2 * math.pi * fov / 360) / 2)).item())
+        depth, hit, sigma, points = self.siren.surface_rays(nerf_styles, (b, H, H, num_steps, zc), xg, yg, zg, cam2world, level,
+                                                            refine)
+        nrm = None
+        if normals:
+            grad = self.siren.density_gradient(points, nerf_styles)[1]
+            norm = grad.norm(dim=-1, keepdim=True)
+            nrm = torch.where((norm > 0) & (hit != 0).unsqueeze(-1), -grad / norm, torch.zeros_like(grad))
+
+        def img(t):
+            return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
+
+        return SimpleNamespace(depth=img(depth), mask=img(hit), points=img(points), sigma=img(sigma),
+                               normals=img(nrm) if normals else None, pitch_yaw=pitch_yaw)
 
     @torch.no_grad()
     def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, return_gradient=False):

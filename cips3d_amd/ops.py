@@ -335,6 +335,76 @@ def siren_sigma_grad_grid(gx, gy, gz, *siren):
     return sigma, grad
 
 
+def siren_surface(level, refine, geom, xg, yg, zg, cam2world, *siren, trace=False):
+    """The iso-surface sigma = level as the camera rays of (geom = (B, H, W, S, zc), pixel grids, cam2world) see it
+    (cips_siren_surface_x3: one launch, about S + refine + 1 sigma evaluations per ray at most, no (B, n, S, 3) points and no
+    volume) -> depth (B, n) fp32, hit (B, n) uint8 (0 no crossing, 1 crossing, 2 the ray starts inside), sigma (B, n) the
+    density at the point of `depth`, points (B, n, 3) = origin + direction * depth; with trace=True also the debug trace
+    (B, n, S + refine, 2) of every (t, sigma) a ray's wave evaluated (NaN where it evaluated nothing).  The search rule:
+    include/cips3d_hip.h.  A plain function: inputs are detached, no gradient flows.  The rays are the unjittered ones.  With
+    SIREN_FWD_MODE other than "x3" it raises (siren_surface_composed is that mode's path)."""
+    t = _siren_prep(siren)
+    xg, yg, zg, cam2world, _, _ = _ray_prep(xg, yg, zg, cam2world, None, None)
+    if SIREN_FWD_MODE != "x3":
+        raise RuntimeError(f"the surface ray-cast kernel runs on the split-operand SIREN chain only (CIPS_SIREN_FWD="
+                           f"{SIREN_FWD_MODE!r}): use siren_surface_composed")
+    B, H, W, S, zc = geom
+    if not 0 <= int(refine) <= 32:
+        raise ValueError("siren_surface: refine must be in 0..32")
+    n, dev = H * W, cam2world.device
+    depth = torch.empty(B, n, device=dev)
+    hit = torch.empty(B, n, dtype=torch.uint8, device=dev)
+    sigma = torch.empty(B, n, device=dev)
+    points = torch.empty(B, n, 3, device=dev)
+    tr = torch.empty(B, n, S + int(refine), 2, device=dev) if trace else None
+    sw = _siren_struct(t)
+    rp = _ray_params(xg, yg, zg, zc, cam2world, None, H, W, S)
+    check(_lib.load().cips_siren_surface_x3(C.byref(sw), C.byref(rp), float(level), int(refine), _p(depth), _p(hit), _p(sigma),
+                                            _p(points), _p(tr), B, _stream()), "cips_siren_surface_x3")
+    return (depth, hit, sigma, points, tr) if trace else (depth, hit, sigma, points)
+
+
+def siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world, *siren, sigma_fn=None):
+    """siren_surface's search from existing pieces -> depth, hit, sigma, points: the world directions of cips_rays_fwd, one
+    sigma launch over all (ray, sample) points of the coarse walk (a (B, n, S, 3) tensor, no early exit), the first crossing by
+    tensor operations, then one sigma launch per bisection step and one for the final point.  sigma_fn(points (B, P, 3)) ->
+    (B, P) is siren_sigma on `siren` unless given (NeRFNetwork.surface_rays hands in the tensor-operation SIREN of other
+    widths).  The path of SIREN_FWD_MODE "f32" and the baseline of scripts/bench_surface.py; the same rule as the kernel, not
+    its roundings (the points are origin + direction * t in torch's arithmetic)."""
+    B, H, W, S, zc = geom
+    xg, yg, zg, cam2world, _, _ = _ray_prep(xg, yg, zg, cam2world, None, None)
+    if sigma_fn is None:
+        def sigma_fn(p):
+            return siren_sigma(p, *siren)
+    n = H * W
+    dirs = rays_fwd(xg, yg, zg, zc, cam2world, None, B, H, W, S)[2]                    # (B, n, 3) world directions
+    origin = cam2world[:, None, :3, 3]
+
+    def point(t):                                                                      # t (B, n, k) -> (B, n, k, 3)
+        return origin.unsqueeze(2) + dirs.unsqueeze(2) * t.unsqueeze(-1)
+
+    def sig_at(t):                                                                     # t (B, n) -> sigma (B, n)
+        return sigma_fn(point(t.unsqueeze(-1)).reshape(B, n, 3))
+    sig = sigma_fn(point(zg.view(1, 1, S).expand(B, n, S)).reshape(B, n * S, 3)).view(B, n, S)
+    inside = sig[..., 0] >= level
+    cross = (sig[..., :-1] < level) & (level <= sig[..., 1:])                          # crossing into step i + 1
+    # the walk stops at the first crossing; a crossing needs sigma[i] < level, so nothing crosses before an inside start is seen
+    first = cross.to(torch.uint8).argmax(-1)
+    hit = torch.where(inside, 2, torch.where(cross.any(-1), 1, 0)).to(torch.uint8)
+    one = hit == 1
+    lo, hi = zg[first].expand(B, n), zg[first + 1].expand(B, n)
+    slo, shi = sig.gather(-1, first.unsqueeze(-1)).squeeze(-1), sig.gather(-1, (first + 1).unsqueeze(-1)).squeeze(-1)
+    for _ in range(int(refine)):
+        mid = 0.5 * (lo + hi)
+        sm = sig_at(mid)
+        up = sm >= level
+        lo, hi = torch.where(up, lo, mid), torch.where(up, mid, hi)
+        slo, shi = torch.where(up, slo, sm), torch.where(up, sm, shi)
+    depth = torch.where(one, lo + (level - slo) / (shi - slo) * (hi - lo), torch.where(inside, zg[0], zg[S - 1]).expand(B, n))
+    points = point(depth.unsqueeze(-1)).reshape(B, n, 3).contiguous()
+    return depth, hit, sigma_fn(points), points
+
+
 def mesh_from_volume(sigma, gx, gy, gz, level, out=None):
     """Triangle meshes of the level set sigma = level: sigma (B, nx, ny, nz) on the lattice (gx[i], gy[j], gz[k]) of three
     strictly increasing 1-D coordinate tensors -> a list of B pairs (vertices (V_b, 3) fp32, faces (T_b, 3) int32), all on the

@@ -174,6 +174,27 @@ int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, f
 int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma /* may be NULL */,
                                   float* grad, int B, cips_stream_t stream);
 
+/* Ray casting of the iso-surface sigma = level: per camera ray of `rays` (n = H*W rays per image; rays->jitter and rays->zvals
+ * must be NULL, the walk is on the unjittered grid zg[0..S-1]) the depth of the first crossing, a hit mask, the surface point and
+ * the density there.  The point at depth t is camera origin + world ray direction * t (the zvals form of cips_ray_params: the
+ * direction rotated first, then scaled — the depth of cips_march_fwd_x3), sigma is cips_siren_sigma_x3's at that point bit for bit.
+ * The search, per ray, with s_i = sigma(point(zg[i])):
+ *   1. coarse walk i = 0, 1, ...: s_0 >= level -> hit = 2 (the ray starts inside), depth = zg[0]; else the first i >= 1 with
+ *      s_{i-1} < level <= s_i -> hit = 1 and the bracket [lo, hi] = [zg[i-1], zg[i]] with s_lo, s_hi; none -> hit = 0, depth = zg[S-1];
+ *   2. `refine` (0..32) bisection steps on a hit = 1 ray: mid = 0.5f * (lo + hi); sigma(mid) >= level -> hi = mid, s_hi = sigma(mid),
+ *      else lo = mid, s_lo = sigma(mid);
+ *   3. one secant step: depth = lo + ((level - s_lo) / (s_hi - s_lo)) * (hi - lo), every operation rounded on its own;
+ *   4. one more evaluation at point(depth) -> points (B,n,3) and sigma (B,n) (hit 0 / 2: at their zg[S-1] / zg[0] point).
+ * depth (B,n) fp32 and hit (B,n) uint8 are required; sigma, points and trace may be NULL.  Every element is written, nothing behind.
+ * trace (B, n, S + refine, 2): every (t, sigma) the ray's wave evaluated, slot i of the coarse walk and S + k of the refinement
+ * (a wave stops walking once none of its 32 rays is still searching, and skips the refinement without a hit = 1 ray); entries the
+ * wave never evaluated are NaN.  A debug output on an instantiation of its own.  Colour pointers of w are not read.
+ * A NULL w / rays / depth / hit / grid / camera, a non-NULL jitter / zvals, S <= 1, B <= 0, B > 65535, H*W > INT_MAX or refine
+ * outside 0..32 returns hipErrorInvalidValue before any HIP call. */
+int cips_siren_surface_x3(const cips_siren_weights* w, const cips_ray_params* rays, float level, int refine, float* depth,
+                          unsigned char* hit, float* sigma /* may be NULL */, float* points /* may be NULL */,
+                          float* trace /* may be NULL */, int B, cips_stream_t stream);
+
 /* Indexed triangle meshes of the level set sigma = level of a volume sigma (B, nx, ny, nz) on the lattice of cips_grid_params
  * (strictly increasing coordinates; nx, ny, nz >= 2): marching tetrahedra on the Kuhn decomposition of every cell, no table of
  * cube cases, watertight by construction (replaces the mcubes / skimage step of exp/pigan/scripts/extract_shapes.py on the host).
