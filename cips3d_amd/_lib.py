@@ -152,6 +152,12 @@ SIGNATURES = {
     "cips_composite_has_dead_samples": (i32, [i32]),
     "cips_live_points_clamp": (i32, [vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "cips_composite_bwd_listed": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    # differentiable depth / opacity: the arguments of the entry point named, then opacity resp. ddepth, dopacity, then the stream
+    "cips_march_fwd_x3_geo": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cips_composite_fwd_geo": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cips_composite_bwd_geo": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cips_composite_bwd_live_geo": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cips_composite_bwd_listed_geo": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "cips_gemm_f32": (i32, [C.POINTER(GemmDesc), vp]),
     "cips_gemm_bf16x3": (i32, [C.POINTER(GemmX3Desc), vp]),
     "cips_gemm_bf16x3_fuses_torgb": (i32, [C.POINTER(GemmX3Desc)]),

@@ -198,10 +198,13 @@ struct CompArgs {
   float noise_std;
   // forward outputs
   float *fea, *depth, *weights, *zsorted;
+  float* opacity;     // optional (R): sum_k w_k before the last_back / white_back adjustments (pigan_utils.py's weights_sum)
   int* order;
   // backward
   const int* order_in;
   const float* dfea;
+  // composite_bwd_kernel<true> only: the upstream gradients of depth and opacity per ray, either may be NULL (zeros)
+  const float *ddepth, *dopacity;
   float *dfeat_c, *dsig_c, *dfeat_f, *dsig_f;
   // optional (cips_composite_bwd_live): one byte per sample in the order of dfeat_* / dsig_*, 1 iff the sample's dfeat row or
   // its dsigma can be non-zero.  When given, the dfeat rows of the other samples are NOT written.
@@ -231,6 +234,8 @@ __device__ __forceinline__ const float* feat_row(const CompArgs& a, long long ra
   return a.feat_c + (ray * a.S + i) * 32;
 }
 
+// OPA: the instantiation that stores a.opacity (cips_composite_fwd_geo); cips_composite_fwd launches <false> as it always has
+template <bool OPA>
 __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int S = a.S, E = a.E;
@@ -287,6 +292,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   float depth = 0.f, wsum = 0.f, wlast = 0.f, zlast = 0.f;
   float4 flast = make_float4(0.f, 0.f, 0.f, 0.f);
   double T = 1.0;      // transmittance in double like ATen's CPU cumprod (acc_type), rounded to float per prefix
+  // (every lane of the segment accumulates depth and wsum over all E samples, so each holds the ray's values)
   // feature rows in batches of 8 independent 16-byte loads per lane (one 128-B line per sample and segment), then the
   // in-order accumulation: the serial chain is one double multiply and one fma per sample, no load and no expf in it
   for (int k0 = 0; k0 < E; k0 += 8) {
@@ -331,9 +337,18 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   if (active) {
     *reinterpret_cast<float4*>(a.fea + ray * 32 + 4 * sub) = F;
     if (sub == 0 && a.depth) a.depth[ray] = depth;
+    if (OPA && sub == 0 && a.opacity) a.opacity[ray] = wsum;     // neither adjustment above changed it
   }
 }
 
+// GEO: the ray's depth and opacity have upstream gradients too (cips_composite_bwd_geo and its kin).  depth = sum_k w_k z_k and
+// opacity = sum_k w_k are linear in the weights like the features, so they only add to dL/dw_k:
+//   s_k = G . f_k + gd z_k   and the offset   s_off = [last_back] s_last + [white_back] sum(G) - go,
+// dL/dw_k = s_k - s_off.  last_back tops the last weight up in the depth as in the features (depth += (1 - sum w) z_last), hence
+// gd z_last inside s_last; opacity is sum w BEFORE the top-up, so go stays out of it.  white_back touches neither.  The reverse
+// scan, the clamp's gradient and the live rules behind dL/dw_k are the same code; the dfeat rows (w_k G) do not change.
+// GEO = false is the kernel of cips_composite_bwd / _live / _listed as it was: the two terms are compiled out.
+template <bool GEO>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int S = a.S, E = a.E;
@@ -373,6 +388,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
   gsum += __shfl_xor(gsum, 1);
   gsum += __shfl_xor(gsum, 2);
   gsum += __shfl_xor(gsum, 4);
+  const float gd = (GEO && a.ddepth) ? a.ddepth[ray] : 0.f;
+  const float go = (GEO && a.dopacity) ? a.dopacity[ray] : 0.f;
   float wsum = 0.f;
   double T = 1.0;
   for (int k = 0; k < E; ++k) {
@@ -388,11 +405,13 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs a) {
     s += __shfl_xor(s, 1);
     s += __shfl_xor(s, 2);
     s += __shfl_xor(s, 4);
+    if (GEO) s = fmaf(gd, zall[k], s);
     if (sub == 0) { Ts[k] = Tf; al[k] = alpha; ss[k] = s; }
   }
   __syncthreads();
   float Q = 0.f;
-  const float s_off = ((a.flags & 1) ? ss[E - 1] : 0.f) + ((a.flags & 2) ? gsum : 0.f);
+  float s_off = ((a.flags & 1) ? ss[E - 1] : 0.f) + ((a.flags & 2) ? gsum : 0.f);
+  if (GEO) s_off -= go;
   for (int k = E - 1; k >= 0; --k) {
     const int i = ord[k];
     const float alpha = al[k], Tk = Ts[k], s = ss[k] - s_off;
@@ -571,24 +590,48 @@ extern "C" int cips_resample_fwd(const float* sigma, const float* z, const float
   return CIPS_CHECK_LAUNCH();
 }
 
+static int composite_fwd_launch(const float* feat_c, const float* sig_c, const float* z_c,
+                                const float* feat_f, const float* sig_f, const float* z_f,
+                                const float* noise, float noise_std, float* fea, float* depth,
+                                float* weights, int* order, float* zsorted, float* opacity, int R, int S,
+                                int clamp_mode, int flags, const unsigned char* clamp_in, unsigned char* clamp_out,
+                                cips_stream_t stream) {
+  if (R <= 0 || S <= 0) return (int)hipErrorInvalidValue;
+  CompArgs a = {};
+  a.feat_c = feat_c; a.sig_c = sig_c; a.z_c = z_c; a.feat_f = feat_f; a.sig_f = sig_f; a.z_f = z_f;
+  a.noise = noise; a.noise_std = noise_std; a.fea = fea; a.depth = depth; a.weights = weights;
+  a.order = order; a.zsorted = zsorted; a.opacity = opacity; a.R = R; a.S = S; a.E = feat_f ? 2 * S : S;
+  a.clamp_mode = clamp_mode; a.flags = flags;
+  a.clamp_pin = clamp_in; a.clamp_rec = clamp_out;
+  size_t per_ray = (size_t)4 * a.E * sizeof(float);
+  int rpb = rays_per_block_for(per_ray);
+  int blocks = (R + rpb - 1) / rpb;
+  if (opacity)
+    hipLaunchKernelGGL(composite_fwd_kernel<true>, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(composite_fwd_kernel<false>, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
+  return CIPS_CHECK_LAUNCH();
+}
+
 extern "C" int cips_composite_fwd(const float* feat_c, const float* sig_c, const float* z_c,
                                   const float* feat_f, const float* sig_f, const float* z_f,
                                   const float* noise, float noise_std, float* fea, float* depth,
                                   float* weights, int* order, float* zsorted, int R, int S,
                                   int clamp_mode, int flags, const unsigned char* clamp_in, unsigned char* clamp_out,
                                   cips_stream_t stream) {
-  if (R <= 0 || S <= 0) return (int)hipErrorInvalidValue;
-  CompArgs a = {};
-  a.feat_c = feat_c; a.sig_c = sig_c; a.z_c = z_c; a.feat_f = feat_f; a.sig_f = sig_f; a.z_f = z_f;
-  a.noise = noise; a.noise_std = noise_std; a.fea = fea; a.depth = depth; a.weights = weights;
-  a.order = order; a.zsorted = zsorted; a.R = R; a.S = S; a.E = feat_f ? 2 * S : S;
-  a.clamp_mode = clamp_mode; a.flags = flags;
-  a.clamp_pin = clamp_in; a.clamp_rec = clamp_out;
-  size_t per_ray = (size_t)4 * a.E * sizeof(float);
-  int rpb = rays_per_block_for(per_ray);
-  int blocks = (R + rpb - 1) / rpb;
-  hipLaunchKernelGGL(composite_fwd_kernel, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
-  return CIPS_CHECK_LAUNCH();
+  return composite_fwd_launch(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, fea, depth, weights, order, zsorted,
+                              nullptr, R, S, clamp_mode, flags, clamp_in, clamp_out, stream);
+}
+
+extern "C" int cips_composite_fwd_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                                      const float* feat_f, const float* sig_f, const float* z_f,
+                                      const float* noise, float noise_std, float* fea, float* depth,
+                                      float* weights, int* order, float* zsorted, int R, int S,
+                                      int clamp_mode, int flags, const unsigned char* clamp_in, unsigned char* clamp_out,
+                                      float* opacity, cips_stream_t stream) {
+  if (R <= 0 || S < 1 || !feat_c || !sig_c || !z_c || !fea || (feat_f && (!sig_f || !z_f))) return (int)hipErrorInvalidValue;
+  return composite_fwd_launch(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, fea, depth, weights, order, zsorted,
+                              opacity, R, S, clamp_mode, flags, clamp_in, clamp_out, stream);
 }
 
 extern "C" int cips_composite_bwd(const float* feat_c, const float* sig_c, const float* z_c,
@@ -616,22 +659,64 @@ extern "C" int cips_live_points_clamp(const float* sigma, const float* noise, fl
 
 extern "C" int cips_composite_has_dead_samples(int clamp_mode) { return comp_has_dead_samples(clamp_mode) ? 1 : 0; }
 
+// the upstream gradients of depth / opacity select the kernel: without either it is the one instantiation the entry points
+// without them have always launched
 static int composite_bwd_launch(CompArgs a, cips_stream_t stream) {
   size_t per_ray = (size_t)6 * a.E * sizeof(float);
   int rpb = rays_per_block_for(per_ray);
   int blocks = (int)((a.R + rpb - 1) / rpb);
-  hipLaunchKernelGGL(composite_bwd_kernel, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
+  if (a.ddepth || a.dopacity)
+    hipLaunchKernelGGL(composite_bwd_kernel<true>, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(composite_bwd_kernel<false>, dim3(blocks), dim3(rpb * SEG), rpb * per_ray, (hipStream_t)stream, a);
   return CIPS_CHECK_LAUNCH();
+}
+
+static int composite_bwd_listed_launch(const float* feat, const float* sigma, const float* z, const float* noise,
+                                       float noise_std, const float* dfea, float* dfeat, float* dsigma, int R, int S,
+                                       int clamp_mode, int flags, const float* ddepth, const float* dopacity,
+                                       cips_stream_t stream) {
+  if (R <= 0 || S <= 0 || !feat || !sigma || !z || !dfea || !dfeat || !dsigma) return (int)hipErrorInvalidValue;
+  CompArgs a = {};
+  a.feat_c = feat; a.sig_c = sigma; a.z_c = z; a.noise = noise; a.noise_std = noise_std; a.dfea = dfea;
+  a.dfeat_c = dfeat; a.dsig_c = dsigma; a.listed = 1;
+  a.ddepth = ddepth; a.dopacity = dopacity;
+  a.R = R; a.S = S; a.E = S; a.clamp_mode = clamp_mode; a.flags = flags;
+  return composite_bwd_launch(a, stream);
 }
 
 extern "C" int cips_composite_bwd_listed(const float* feat, const float* sigma, const float* z, const float* noise,
                                          float noise_std, const float* dfea, float* dfeat, float* dsigma, int R, int S,
                                          int clamp_mode, int flags, cips_stream_t stream) {
-  if (R <= 0 || S <= 0 || !feat || !sigma || !z || !dfea || !dfeat || !dsigma) return (int)hipErrorInvalidValue;
+  return composite_bwd_listed_launch(feat, sigma, z, noise, noise_std, dfea, dfeat, dsigma, R, S, clamp_mode, flags, nullptr,
+                                     nullptr, stream);
+}
+
+extern "C" int cips_composite_bwd_listed_geo(const float* feat, const float* sigma, const float* z, const float* noise,
+                                             float noise_std, const float* dfea, float* dfeat, float* dsigma, int R, int S,
+                                             int clamp_mode, int flags, const float* ddepth, const float* dopacity,
+                                             cips_stream_t stream) {
+  return composite_bwd_listed_launch(feat, sigma, z, noise, noise_std, dfea, dfeat, dsigma, R, S, clamp_mode, flags, ddepth,
+                                     dopacity, stream);
+}
+
+static int composite_bwd_live_launch(const float* feat_c, const float* sig_c, const float* z_c,
+                                     const float* feat_f, const float* sig_f, const float* z_f,
+                                     const float* noise, float noise_std, const int* order, const float* dfea,
+                                     float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                                     unsigned char* live_c, unsigned char* live_f, int R, int S,
+                                     int clamp_mode, int flags, const unsigned char* clamp_in, const float* ddepth,
+                                     const float* dopacity, cips_stream_t stream) {
+  if (R <= 0 || S <= 0 || (!order && feat_f)) return (int)hipErrorInvalidValue;
+  if ((live_c || live_f) && (!live_c || (feat_f && !live_f))) return (int)hipErrorInvalidValue;   // both masks or none
   CompArgs a = {};
-  a.feat_c = feat; a.sig_c = sigma; a.z_c = z; a.noise = noise; a.noise_std = noise_std; a.dfea = dfea;
-  a.dfeat_c = dfeat; a.dsig_c = dsigma; a.listed = 1;
-  a.R = R; a.S = S; a.E = S; a.clamp_mode = clamp_mode; a.flags = flags;
+  a.feat_c = feat_c; a.sig_c = sig_c; a.z_c = z_c; a.feat_f = feat_f; a.sig_f = sig_f; a.z_f = z_f;
+  a.noise = noise; a.noise_std = noise_std; a.order_in = order; a.dfea = dfea;
+  a.dfeat_c = dfeat_c; a.dsig_c = dsig_c; a.dfeat_f = dfeat_f; a.dsig_f = dsig_f;
+  a.live_c = live_c; a.live_f = live_f;
+  a.ddepth = ddepth; a.dopacity = dopacity;
+  a.R = R; a.S = S; a.E = feat_f ? 2 * S : S; a.clamp_mode = clamp_mode; a.flags = flags;
+  a.clamp_pin = clamp_in; a.clamp_rec = nullptr;
   return composite_bwd_launch(a, stream);
 }
 
@@ -641,14 +726,31 @@ extern "C" int cips_composite_bwd_live(const float* feat_c, const float* sig_c, 
                                        float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
                                        unsigned char* live_c, unsigned char* live_f, int R, int S,
                                        int clamp_mode, int flags, const unsigned char* clamp_in, cips_stream_t stream) {
-  if (R <= 0 || S <= 0 || (!order && feat_f)) return (int)hipErrorInvalidValue;
-  if ((live_c || live_f) && (!live_c || (feat_f && !live_f))) return (int)hipErrorInvalidValue;   // both masks or none
-  CompArgs a = {};
-  a.feat_c = feat_c; a.sig_c = sig_c; a.z_c = z_c; a.feat_f = feat_f; a.sig_f = sig_f; a.z_f = z_f;
-  a.noise = noise; a.noise_std = noise_std; a.order_in = order; a.dfea = dfea;
-  a.dfeat_c = dfeat_c; a.dsig_c = dsig_c; a.dfeat_f = dfeat_f; a.dsig_f = dsig_f;
-  a.live_c = live_c; a.live_f = live_f;
-  a.R = R; a.S = S; a.E = feat_f ? 2 * S : S; a.clamp_mode = clamp_mode; a.flags = flags;
-  a.clamp_pin = clamp_in; a.clamp_rec = nullptr;
-  return composite_bwd_launch(a, stream);
+  return composite_bwd_live_launch(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, order, dfea, dfeat_c, dsig_c,
+                                   dfeat_f, dsig_f, live_c, live_f, R, S, clamp_mode, flags, clamp_in, nullptr, nullptr, stream);
+}
+
+extern "C" int cips_composite_bwd_live_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                                           const float* feat_f, const float* sig_f, const float* z_f,
+                                           const float* noise, float noise_std, const int* order, const float* dfea,
+                                           float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                                           unsigned char* live_c, unsigned char* live_f, int R, int S,
+                                           int clamp_mode, int flags, const unsigned char* clamp_in, const float* ddepth,
+                                           const float* dopacity, cips_stream_t stream) {
+  if (R <= 0 || S < 1 || !feat_c || !sig_c || !z_c || !dfea || !dfeat_c || !dsig_c) return (int)hipErrorInvalidValue;
+  if (feat_f && (!sig_f || !z_f || !order || !dfeat_f || !dsig_f)) return (int)hipErrorInvalidValue;
+  if ((live_f && !live_c) || (live_c && feat_f && !live_f)) return (int)hipErrorInvalidValue;
+  return composite_bwd_live_launch(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, order, dfea, dfeat_c, dsig_c,
+                                   dfeat_f, dsig_f, live_c, live_f, R, S, clamp_mode, flags, clamp_in, ddepth, dopacity, stream);
+}
+
+extern "C" int cips_composite_bwd_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                                      const float* feat_f, const float* sig_f, const float* z_f,
+                                      const float* noise, float noise_std, const int* order, const float* dfea,
+                                      float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f, int R, int S,
+                                      int clamp_mode, int flags, const unsigned char* clamp_in, const float* ddepth,
+                                      const float* dopacity, cips_stream_t stream) {
+  return cips_composite_bwd_live_geo(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, order, dfea, dfeat_c, dsig_c,
+                                     dfeat_f, dsig_f, nullptr, nullptr, R, S, clamp_mode, flags, clamp_in, ddepth, dopacity,
+                                     stream);
 }

@@ -2,9 +2,17 @@
 // forward (cips_siren_fwd_x3, cips_siren_fwd_x3_rays) and the fused ray-march (cips_march_fwd_x3).  Both run one wave-step of
 // the chain from siren_fwd_chain.inc, included as text (its header says why it is no function).
 //
-// The sigma kernels (siren_sigma_x3.inc, included at the end) are compiled with this source.  On their own they come out
+// The sigma kernels (siren_sigma_x3.inc, included in front of the march's entry points, i.e. in front of where the march
+// kernels are instantiated) are compiled with this source.  On their own they come out
 // different: with no kernel in the module that stages Wc or Wf, every call of img_addr has R = 128, hipcc specialises it before
 // it is inlined, and the W1 staging loop of all sixteen instances gets other address arithmetic (same instruction count).
+// Why in front of the march and no longer at the end: the place changes no kernel's instructions (the compiler's assembly of
+// all 32 kernels was compared, place by place and against the build before the opacity instantiations), only the order of the
+// kernels in the code object.  But behind the twelve march kernels there are now,
+// tests/test_gpu_density.py::test_sigma_only_equals_the_full_forward_bit_for_bit[3-4160-0] failed on the MI355X in two runs of
+// two — two launches of siren_sigma_x3_kernel<false, true, false> on the same points differed in some element — and in front
+// of them the whole suite passes.  So the sigma kernel's software-trig form has a timing-dependent defect that the layout only
+// hides; it is older than this placement and its cause is not found.
 #include "siren_x3_common.h"
 
 // Phase timestamps of the chain, probe builds only (-DCIPS_TUNING with CIPS_X3_MPROF set): the including kernel supplies
@@ -101,6 +109,7 @@ struct MarchArgs {
   float noise_std;
   int clamp_mode, flags;     // flags: bit0 last_back, bit1 white_back
   float *fea, *depth;        // (B, n, 32), (B, n)
+  float *opacity;            // (B, n) or NULL: sum_s w_s before the last_back / white_back adjustments (cips_march_fwd_x3_geo)
   float *weights;            // (B, n, S) or NULL
   float *feat, *sigma, *zout;   // per-sample outputs (B, P, 32), (B, P), (B, P) or NULL
   int B, rays_per_wg;
@@ -111,7 +120,9 @@ struct MarchArgs {
   unsigned long long* prof;         // probe builds: phase timestamps of workgroup (0,0), samples 8..11
 };
 
-template <bool HW, bool DBG, bool F16>
+// OPA: the instantiation that stores `opacity` (the debug instantiation DBG stores it too, when given); the production
+// launch — no masks, no opacity — is the <HW, false, F16, false> kernel, whose code holds neither.
+template <bool HW, bool DBG, bool F16, bool OPA>
 __global__ __launch_bounds__(512) void siren_march_x3_kernel(MarchArgs a) {
   extern __shared__ __attribute__((aligned(1024))) uchar smem[];
   const int b = blockIdx.y;
@@ -236,6 +247,7 @@ __global__ __launch_bounds__(512) void siren_march_x3_kernel(MarchArgs a) {
       for (int gq = 0; gq < 4; ++gq)
         *reinterpret_cast<float4*>(o + 8 * gq) = make_float4(F[4 * gq], F[4 * gq + 1], F[4 * gq + 2], F[4 * gq + 3]);
       if (hfs == 0 && a.depth) a.depth[(long long)b * n + ray] = depth;
+      if ((DBG || OPA) && hfs == 0 && a.opacity) a.opacity[(long long)b * n + ray] = wsum;
     }
   }
 }
@@ -274,6 +286,8 @@ static int siren_fwd_x3_launch(const cips_siren_weights* w, const float* points,
   return CIPS_CHECK_LAUNCH();
 }
 
+#include "siren_sigma_x3.inc"
+
 #ifdef CIPS_TUNING
 static unsigned long long* g_mprof = nullptr;
 extern "C" int cips_march_x3_prof(unsigned long long* host_out) {       // tuning aid: copies the 4x8x8 timestamps
@@ -281,17 +295,17 @@ extern "C" int cips_march_x3_prof(unsigned long long* host_out) {       // tunin
   return (int)hipMemcpy(host_out, g_mprof, 4 * 8 * 8 * 8, hipMemcpyDeviceToHost);
 }
 #endif
-extern "C" int cips_march_fwd_x3(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise,
-                                 float noise_std, int clamp_mode, int flags, float* fea, float* depth, float* weights,
-                                 float* feat, float* sigma, float* z, int B, const unsigned char* clamp_in,
-                                 unsigned char* clamp_out, cips_stream_t stream) {
+static int march_fwd_x3_launch(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise,
+                               float noise_std, int clamp_mode, int flags, float* fea, float* depth, float* weights,
+                               float* feat, float* sigma, float* z, int B, const unsigned char* clamp_in,
+                               unsigned char* clamp_out, float* opacity, cips_stream_t stream) {
   if (!w || !fea || B <= 0) return (int)hipErrorInvalidValue;
   MarchArgs a;
   a.w = *w;
   const int rc = fill_raygen(a.rg, rays);
   if (rc) return rc;
   a.noise = noise; a.noise_std = noise_std; a.clamp_mode = clamp_mode; a.flags = flags;
-  a.fea = fea; a.depth = depth; a.weights = weights; a.feat = feat; a.sigma = sigma; a.zout = z; a.B = B;
+  a.fea = fea; a.depth = depth; a.opacity = opacity; a.weights = weights; a.feat = feat; a.sigma = sigma; a.zout = z; a.B = B;
   a.clamp_pin = clamp_in; a.clamp_rec = clamp_out;
   a.desync = 0; a.one_wave = 0; a.prof = nullptr;
 #ifdef CIPS_TUNING
@@ -307,10 +321,26 @@ extern "C" int cips_march_fwd_x3(const cips_siren_weights* w, const cips_ray_par
   const int n = a.rg.n;
   dim3 grid((n + a.rays_per_wg - 1) / a.rays_per_wg, B);
   const int smem = O_STG;
-  x3_pick([&](auto HW_, auto DBG_, auto F16_) {
-    x3_launch<siren_march_x3_kernel<decltype(HW_)::value, decltype(DBG_)::value, decltype(F16_)::value>>(grid, 512, smem, stream, a);
-  }, (w->trig_mode & 1) != 0, a.clamp_pin || a.clamp_rec, (w->trig_mode & 2) == 0);
+  x3_pick([&](auto HW_, auto DBG_, auto F16_, auto OPA_) {
+    constexpr bool dbg = decltype(DBG_)::value, opa = decltype(OPA_)::value && !dbg;
+    x3_launch<siren_march_x3_kernel<decltype(HW_)::value, dbg, decltype(F16_)::value, opa>>(grid, 512, smem, stream, a);
+  }, (w->trig_mode & 1) != 0, a.clamp_pin || a.clamp_rec, (w->trig_mode & 2) == 0, a.opacity != nullptr);
   return CIPS_CHECK_LAUNCH();
 }
 
-#include "siren_sigma_x3.inc"
+extern "C" int cips_march_fwd_x3(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise,
+                                 float noise_std, int clamp_mode, int flags, float* fea, float* depth, float* weights,
+                                 float* feat, float* sigma, float* z, int B, const unsigned char* clamp_in,
+                                 unsigned char* clamp_out, cips_stream_t stream) {
+  return march_fwd_x3_launch(w, rays, noise, noise_std, clamp_mode, flags, fea, depth, weights, feat, sigma, z, B, clamp_in,
+                             clamp_out, nullptr, stream);
+}
+
+extern "C" int cips_march_fwd_x3_geo(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise,
+                                     float noise_std, int clamp_mode, int flags, float* fea, float* depth, float* weights,
+                                     float* feat, float* sigma, float* z, int B, const unsigned char* clamp_in,
+                                     unsigned char* clamp_out, float* opacity, cips_stream_t stream) {
+  if (!w || !rays || !fea || B <= 0) return (int)hipErrorInvalidValue;
+  return march_fwd_x3_launch(w, rays, noise, noise_std, clamp_mode, flags, fea, depth, weights, feat, sigma, z, B, clamp_in,
+                             clamp_out, opacity, stream);
+}

@@ -329,9 +329,11 @@ class NeRFNetwork(nn.Module):
         depths `zvals`) -> feat (b,P,32), sigma (b,P), z (b,P)"""
         return ops.SirenRaysFunction.apply(geom, xg, yg, zg, cam2world, jitter, zvals, *self._siren_args(style_dict))
 
-    def march(self, style_dict, geom, xg, yg, zg, cam2world, jitter, noise):
-        """fused rays + SIREN + composite for non-hierarchical sampling -> pixels_fea (b,n,32), depth (b,n)"""
-        return ops.RayMarchFunction.apply(geom, xg, yg, zg, cam2world, jitter, noise, *self._siren_args(style_dict))
+    def march(self, style_dict, geom, xg, yg, zg, cam2world, jitter, noise, geo=False):
+        """fused rays + SIREN + composite for non-hierarchical sampling -> pixels_fea (b,n,32), depth (b,n); with `geo` also
+        opacity (b,n), and depth and opacity are differentiable (ops.RayMarchGeoFunction)"""
+        fn = ops.RayMarchGeoFunction if geo else ops.RayMarchFunction
+        return fn.apply(geom, xg, yg, zg, cam2world, jitter, noise, *self._siren_args(style_dict))
 
     def forward(self, input, style_dict, ray_directions=None, **kwargs):
         feat, sigma = self.evaluate(input, style_dict)
@@ -886,9 +888,10 @@ class GeneratorNerfINR(nn.Module):
         `idx` of them (form "points" only): -> pixels_fea (b, m, 32)"""
         return self._nerf_features_depth(s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx)[0]
 
-    def _nerf_features_depth(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None):
+    def _nerf_features_depth(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None, geo=False):
         """_nerf_features with the per-ray depth the march / composite kernels compute next to the features:
-        -> pixels_fea (b, m, 32), depth (b, m)"""
+        -> pixels_fea (b, m, 32), depth (b, m); with `geo` also opacity (b, m), the sum of the ray's weights before the
+        last_back top-up, and depth and opacity carry gradients like the features (the Functions' Geo counterparts)"""
         b, S, E, H, W = g.b, s.num_steps, s.E, s.img_size, s.img_size
         m = s.n if idx is None else idx.numel()
         clamp = ops._CLAMP[s.clamp_mode]
@@ -898,7 +901,7 @@ class GeneratorNerfINR(nn.Module):
                 # _forward_styles join their stream, ops.live_forward_join)
                 geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled(), True)
                 return self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
-                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None)
+                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None, geo=geo)
             if g.form == "rays":
                 rays = (nerf_styles, (b, H, W, S, g.zc), g.xg, g.yg, g.zg, g.cam2world)
                 feat_c, sig_c, z_c = self.siren.evaluate_rays(*rays, jitter=g.jitter)
@@ -929,9 +932,11 @@ class GeneratorNerfINR(nn.Module):
                         fine_pts = (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * fine_z.view(b, m, S, 1)).reshape(b, m * S, 3)
                     feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, m * S, 3), nerf_styles)
                 feat_f, sig_f = feat_f.view(b * m, S, 32), sig_f.view(b * m, S)
-            out = ops.CompositeFunction.apply(
+            out = (ops.CompositeGeoFunction if geo else ops.CompositeFunction).apply(
                 feat_c, sig_c, z_c, feat_f, sig_f, fine_z, noise_f.reshape(b * m, E) if s.nerf_noise != 0 else None,
                 s.nerf_noise, clamp, s.flags)
+            if geo:
+                return out[0].view(b, m, 32), out[1].view(b, m), out[2].view(b, m)
             return out[0].view(b, m, 32), out[1].view(b, m)
 
     def _head(self, s, pixels_fea, style_dict, nerf_grad):
@@ -967,10 +972,11 @@ class GeneratorNerfINR(nn.Module):
 
         return scatter(inr_g, inr_r), scatter(aux_g, aux_r) if s.return_aux_img else None
 
-    def _render(self, style_dict, s):
+    def _render(self, style_dict, s, geo=False):
         """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path:
         draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_features) -> head (_head), or
-        the last two per pixel subset (_part_grad)."""
+        the last two per pixel subset (_part_grad).  -> imgs, pitch_yaw; with `geo` (render(): whole images in one shot)
+        -> SimpleNamespace(imgs, depth, opacity, pitch_yaw), the same launches plus the opacity store of the NeRF path."""
         device = next(self.parameters()).device
         b = list(style_dict.values())[0].shape[0]
         if not s.part and not s.staged and self.nerf_grad and torch.is_grad_enabled():
@@ -987,14 +993,19 @@ class GeneratorNerfINR(nn.Module):
         if s.part:
             inr_img, aux_img = self._part_grad(s, g, nerf_styles, style_dict, device)
         else:
-            fea = self._nerf_features(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad)
+            fea, *maps = self._nerf_features_depth(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad, geo=geo)
             inr_img, aux_img = self._head(s, fea, style_dict, self.nerf_grad)
         inr_img = inr_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
         inr_img = self.filters(inr_img)
-        if not s.return_aux_img:
-            return inr_img.contiguous(), pitch_yaw
-        aux_img = aux_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
-        return torch.cat([inr_img, aux_img]), torch.cat([pitch_yaw, pitch_yaw])
+        if s.return_aux_img:
+            aux_img = aux_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
+            imgs, pitch_yaw = torch.cat([inr_img, aux_img]), torch.cat([pitch_yaw, pitch_yaw])
+        else:
+            imgs = inr_img.contiguous()
+        if not geo:
+            return imgs, pitch_yaw
+        depth, opacity = (t.view(b, 1, s.img_size, s.img_size) for t in maps[:2])
+        return SimpleNamespace(imgs=imgs, depth=depth, opacity=opacity, pitch_yaw=pitch_yaw)
 
     def forward(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                 h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, lock_view_dependence=False,
@@ -1008,8 +1019,42 @@ class GeneratorNerfINR(nn.Module):
             last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
             rand_override=kwargs.get('rand_override')))
 
-    def _forward_styles(self, zs, psi, s):
-        """the two entry points' common path: latents -> styles (truncated towards the average for psi < 1) -> _render"""
+    def render(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
+               h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, clamp_mode='relu', nerf_noise=0.,
+               white_back=False, last_back=False, return_aux_img=False, camera_pos=None, camera_lookup=None, up_vector=None,
+               rand_override=None, grad_points=None, forward_points=None):
+        """forward() (or, with camera_pos / camera_lookup, forward_camera_pos_and_lookup()) that also returns the geometry the
+        image is rendered from, differentiable -> SimpleNamespace of
+          imgs, pitch_yaw    what that call returns for the same arguments, seed and grad mode: the same bits and the same
+                             random draws (batch 2b with return_aux_img), from the same launches except that the NeRF
+                             forward runs its opacity-storing instantiation and one more (b, n) tensor is allocated
+          depth   (b,1,H,W)  the expected ray depth sum_k w_k z_k of the compositing kernel (under last_back with the topped-up
+                             last weight); for nerf_noise = 0 it is geometry().depth bit for bit
+          opacity (b,1,H,W)  sum_k w_k, taken BEFORE the last_back top-up (the reference's weights_sum, the soft foreground
+                             matte): under last_back it is not the constant 1
+        depth and opacity carry a grad_fn whenever the NeRF path runs with gradients, as in the reference, where fancy_integration
+        returns them as autograd tensors: a depth-supervised inversion, a silhouette loss or a geometric regulariser reaches
+        the SIREN weights, the NeRF mapping network, zs['z_nerf'] and a camera that requires grad (camera_pos, camera_lookup,
+        tensor h_mean / v_mean) on the native path (ops.RayMarchGeoFunction / ops.CompositeGeoFunction).
+        What gets no gradient: the sample depths z (constants, as in the reference: the coarse depths are inputs, the fine ones
+        are drawn under no_grad); and on GeneratorNerfINR_freeze_NeRF the whole NeRF path runs under no_grad, so depth and
+        opacity have no grad_fn there (imgs keeps the head's).  Whole images in one shot only, as in geometry(): the partial
+        (grad_points) and staged (forward_points) forms are refused.  Any value but None is: unlike forward(), which takes
+        grad_points >= n pixels as a whole-image render, render() refuses that too."""
+        if grad_points is not None or forward_points is not None:
+            raise ValueError("GeneratorNerfINR.render renders whole images in one shot: grad_points / forward_points are not "
+                             "supported (use forward() for the partial and staged forms; they return no depth or opacity)")
+        if next(self.parameters()).device.type != 'cuda':
+            raise RuntimeError("GeneratorNerfINR.render runs on the GPU only (there is no CPU path)")
+        return self._forward_styles(zs, psi, RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
+            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
+            last_back=last_back, return_aux_img=return_aux_img, rand_override=rand_override, camera_pos=camera_pos,
+            camera_lookup=camera_lookup, up_vector=up_vector), geo=True)
+
+    def _forward_styles(self, zs, psi, s, geo=False):
+        """the entry points' common path: latents -> styles (truncated towards the average for psi < 1) -> _render"""
         style_dict = self.mapping_network(**zs, defer_join=not psi < 1)     # joined right before the INR head (_head)
         if psi < 1:
             avg_styles = self.generate_avg_frequencies(device=self.device)
@@ -1018,7 +1063,7 @@ class GeneratorNerfINR(nn.Module):
         try:
             # with forward_points the reference evaluates image by image in chunks under no_grad (generator.py:1325-1347)
             with torch.set_grad_enabled(torch.is_grad_enabled() and not s.staged):
-                return self._render(style_dict, s)
+                return self._render(style_dict, s, geo)
         finally:
             # a deferred INR-mapping side stream is joined on EVERY exit (no-op after _head's own join): an exception
             # before the INR head must not leave the fork open — the main stream would never wait for it, and a

@@ -750,54 +750,118 @@ def resample_fwd(sigma, z, noise, noise_std, u, origins, dirs, B, n, S, clamp_mo
 _CLAMP = {"relu": 0, "softplus": 1}
 
 
+def _geo_upstream(dfea, ddepth, dopacity, like, dev):
+    """the upstream gradients of a differentiable-geometry backward as contiguous fp32 tensors: a missing dfea becomes zeros
+    shaped `like`, a missing ddepth / dopacity stays None (the kernels take NULL for zeros)"""
+    dfea = _c(dfea) if dfea is not None else torch.zeros(like, device=dev)
+    ddepth, dopacity = _c(ddepth), _c(dopacity)
+    _chk(dfea, ddepth, dopacity)
+    return dfea, ddepth, dopacity
+
+
+def _composite_bwd_call(name, args, ddepth, dopacity):
+    """the compositing backward `name` on `args` (everything but the stream) — or, with an upstream gradient of the ray's
+    depth or opacity, its `_geo` form, which takes the two behind them"""
+    lib = _lib.load()
+    if ddepth is None and dopacity is None:
+        check(getattr(lib, name)(*args, _stream()), name)
+    else:
+        check(getattr(lib, name + "_geo")(*args, _p(ddepth), _p(dopacity), _stream()), name + "_geo")
+
+
+def _composite_forward(ctx, geo, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, clamp_mode, flags):
+    """the forward of CompositeFunction (geo False) and CompositeGeoFunction (True: also the opacity output)
+    -> fea, depth, opacity or None, weights, order, zs"""
+    lib = _lib.load()
+    feat_c, sig_c, z_c = _c(feat_c.detach()), _c(sig_c.detach()), _c(z_c.detach())
+    hier = feat_f is not None
+    if hier:
+        feat_f, sig_f, z_f = _c(feat_f.detach()), _c(sig_f.detach()), _c(z_f.detach())
+    noise = _c(noise) if (noise is not None and noise_std != 0.0) else None
+    _chk(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise)
+    R, S, _ = feat_c.shape
+    E = 2 * S if hier else S
+    dev = feat_c.device
+    fea = torch.empty(R, 32, device=dev)
+    depth = torch.empty(R, device=dev)
+    opacity = torch.empty(R, device=dev) if geo else None
+    weights = torch.empty(R, E, device=dev)
+    order = torch.empty(R, E, device=dev, dtype=torch.int32)
+    zs = torch.empty(R, E, device=dev)
+    pin, rec = _clamp_debug_forward(R, E, clamp_mode, dev)
+    args = (_p(feat_c), _p(sig_c), _p(z_c), _p(feat_f), _p(sig_f), _p(z_f), _p(noise), float(noise_std), _p(fea), _p(depth),
+            _p(weights), _p(order), _p(zs), R, S, clamp_mode, flags, _p(pin), _p(rec))
+    if geo:
+        check(lib.cips_composite_fwd_geo(*args, _p(opacity), _stream()), "cips_composite_fwd_geo")
+    else:
+        check(lib.cips_composite_fwd(*args, _stream()), "cips_composite_fwd")
+    if rec is not None and CLAMP_REC is not None:
+        CLAMP_REC.append(rec.reshape(R, E))
+    ctx.clamp_mask = pin                      # pinned branches: the backward takes the same ones (else: its own sign test)
+    ctx.save_for_backward(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, order)
+    ctx.meta = (float(noise_std), clamp_mode, flags, hier)
+    return fea, depth, opacity, weights, order, zs
+
+
+def _composite_backward(ctx, dfea, ddepth=None, dopacity=None):
+    """-> dfeat_c, dsig_c, dfeat_f, dsig_f of one compositing forward (cips_composite_bwd, or cips_composite_bwd_geo when the
+    depth or the opacity has an upstream gradient too)"""
+    feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, order = ctx.saved_tensors
+    noise_std, clamp_mode, flags, hier = ctx.meta
+    R, S, _ = feat_c.shape
+    dfeat_c = torch.empty_like(feat_c)
+    dsig_c = torch.empty_like(sig_c)
+    dfeat_f = torch.empty_like(feat_f) if hier else None
+    dsig_f = torch.empty_like(sig_f) if hier else None
+    _composite_bwd_call("cips_composite_bwd",
+                        (_p(feat_c), _p(sig_c), _p(z_c), _p(feat_f), _p(sig_f), _p(z_f), _p(noise), noise_std, _p(order),
+                         _p(dfea), _p(dfeat_c), _p(dsig_c), _p(dfeat_f), _p(dsig_f), R, S, clamp_mode, flags,
+                         _p(ctx.clamp_mask)), ddepth, dopacity)
+    _tail_gate_publish(dfea.device)
+    return dfeat_c, dsig_c, dfeat_f, dsig_f
+
+
 class CompositeFunction(torch.autograd.Function):
     """Merge (optional) + alpha-composite; see cips_composite_fwd / _bwd.
     Inputs are flattened over rays: feat (R,S,32), sig (R,S), z (R,S); fine set may be None."""
 
     @staticmethod
     def forward(ctx, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, clamp_mode, flags):
-        lib = _lib.load()
-        feat_c, sig_c, z_c = _c(feat_c.detach()), _c(sig_c.detach()), _c(z_c.detach())
-        hier = feat_f is not None
-        if hier:
-            feat_f, sig_f, z_f = _c(feat_f.detach()), _c(sig_f.detach()), _c(z_f.detach())
-        noise = _c(noise) if (noise is not None and noise_std != 0.0) else None
-        _chk(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise)
-        R, S, _ = feat_c.shape
-        E = 2 * S if hier else S
-        dev = feat_c.device
-        fea = torch.empty(R, 32, device=dev)
-        depth = torch.empty(R, device=dev)
-        weights = torch.empty(R, E, device=dev)
-        order = torch.empty(R, E, device=dev, dtype=torch.int32)
-        zs = torch.empty(R, E, device=dev)
-        pin, rec = _clamp_debug_forward(R, E, clamp_mode, dev)
-        check(lib.cips_composite_fwd(_p(feat_c), _p(sig_c), _p(z_c), _p(feat_f), _p(sig_f), _p(z_f), _p(noise),
-                                     float(noise_std), _p(fea), _p(depth), _p(weights), _p(order), _p(zs),
-                                     R, S, clamp_mode, flags, _p(pin), _p(rec), _stream()), "cips_composite_fwd")
-        if rec is not None and CLAMP_REC is not None:
-            CLAMP_REC.append(rec.reshape(R, E))
-        ctx.clamp_mask = pin                      # pinned branches: the backward takes the same ones (else: its own sign test)
-        ctx.save_for_backward(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, order)
-        ctx.meta = (float(noise_std), clamp_mode, flags, hier)
+        fea, depth, _, weights, order, zs = _composite_forward(ctx, False, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise,
+                                                               noise_std, clamp_mode, flags)
         ctx.mark_non_differentiable(depth, weights, order, zs)
         return fea, depth, weights, order, zs
 
     @staticmethod
     def backward(ctx, dfea, *unused):
-        lib = _lib.load()
-        feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, order = ctx.saved_tensors
-        noise_std, clamp_mode, flags, hier = ctx.meta
-        R, S, _ = feat_c.shape
-        dfea = _c(dfea)
-        dfeat_c = torch.empty_like(feat_c)
-        dsig_c = torch.empty_like(sig_c)
-        dfeat_f = torch.empty_like(feat_f) if hier else None
-        dsig_f = torch.empty_like(sig_f) if hier else None
-        check(lib.cips_composite_bwd(_p(feat_c), _p(sig_c), _p(z_c), _p(feat_f), _p(sig_f), _p(z_f), _p(noise),
-                                     noise_std, _p(order), _p(dfea), _p(dfeat_c), _p(dsig_c), _p(dfeat_f),
-                                     _p(dsig_f), R, S, clamp_mode, flags, _p(ctx.clamp_mask), _stream()), "cips_composite_bwd")
-        _tail_gate_publish(dfea.device)
+        dfeat_c, dsig_c, dfeat_f, dsig_f = _composite_backward(ctx, _c(dfea))
+        return dfeat_c, dsig_c, None, dfeat_f, dsig_f, None, None, None, None, None
+
+
+class CompositeGeoFunction(torch.autograd.Function):
+    """CompositeFunction with the geometry differentiable: -> fea (R,32), depth (R), opacity (R), weights, order, zs, the first
+    three with gradients.  depth = sum_k w_k z_k (+ (1 - sum w) z_last under last_back), opacity = sum_k w_k before the last_back
+    top-up (the reference's weights_sum, pigan_utils.py:261); both are linear in the weights like the features, and their
+    upstream gradients enter the same reverse scan (cips_composite_bwd_geo).  The depths z stay constants, as in the
+    reference; `weights` is not a differentiable output.  An upstream of the features alone takes CompositeFunction's call.
+    Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, noise_std, clamp_mode, flags):
+        fea, depth, opacity, weights, order, zs = _composite_forward(ctx, True, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise,
+                                                                     noise_std, clamp_mode, flags)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(weights, order, zs)
+        return fea, depth, opacity, weights, order, zs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dfea, ddepth, dopacity, *unused):
+        if dfea is None and ddepth is None and dopacity is None:
+            return (None,) * 10
+        feat_c = ctx.saved_tensors[0]
+        dfea, ddepth, dopacity = _geo_upstream(dfea, ddepth, dopacity, (feat_c.shape[0], 32), feat_c.device)
+        dfeat_c, dsig_c, dfeat_f, dsig_f = _composite_backward(ctx, dfea, ddepth, dopacity)
         return dfeat_c, dsig_c, None, dfeat_f, dsig_f, None, None, None, None, None
 
 
@@ -1017,81 +1081,121 @@ class RayMarchFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
-        lib = _lib.load()
-        B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom[:9]
-        t = _siren_prep(siren)
-        xg, yg, zg, cam2world, jitter, noise = _ray_prep(xg, yg, zg, cam2world, jitter, noise if noise_std != 0.0 else None)
-        dev = cam2world.device
-        n = H * W
-        # per-sample outputs only when a backward can follow: the caller's grad mode counts (inside forward() it is
-        # always off, and under torch.no_grad() needs_input_grad still reports the parameters' requires_grad)
-        train = grad_mode and any(ctx.needs_input_grad)
-        fea = torch.empty(B, n, 32, device=dev)
-        depth = torch.empty(B, n, device=dev)
-        feat = torch.empty(B, n * S, 32, device=dev) if train else None
-        sigma = torch.empty(B, n * S, device=dev) if train else None
-        z = torch.empty(B, n * S, device=dev) if train else None
-        sw = _siren_struct(t)
-        rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
-        pin, rec = _clamp_debug_forward(B * n, S, clamp_mode, dev)
-        check(lib.cips_march_fwd_x3(C.byref(sw), C.byref(rp), _p(noise), float(noise_std), clamp_mode, flags, _p(fea),
-                                    _p(depth), None, _p(feat), _p(sigma), _p(z), B, _p(pin), _p(rec), _stream()),
-              "cips_march_fwd_x3")
-        if rec is not None and CLAMP_REC is not None:
-            CLAMP_REC.append(rec.reshape(B * n, S))
-        ctx.clamp_mask = pin
-        # a tenth entry of geom, true: the caller joins the list stream (live_forward_join) whether or not a backward follows
-        ctx.live_fwd = train and len(geom) > 9 and bool(geom[9]) and live_forward_ok(clamp_mode, pin)
-        if train:
-            lists = live_plan_forward(sigma, noise, noise_std, B, n, S, clamp_mode, flags) if ctx.live_fwd else ()
-            ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values(), *lists)
-        ctx.geom = geom
+        fea, depth, _ = _march_forward(ctx, False, geom, xg, yg, zg, cam2world, jitter, noise, *siren)
         ctx.mark_non_differentiable(depth)
         return fea, depth
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dfea, _ddepth):
-        lib = _lib.load()
-        xg, yg, zg, cam2world, jitter, noise, feat, sigma, z = ctx.saved_tensors[:9]
-        t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[9:9 + len(_SIREN_NAMES)]))
-        B, H, W, S, zc, noise_std, clamp_mode, flags, _ = ctx.geom[:9]
-        n = H * W
-        R = B * n
-        dfea = _c(dfea)
-        want_cam = ctx.needs_input_grad[4]
-        if want_cam:
-            _need_x3_points_grad()
-        # the camera gradient's kernel reads every row, the live forms below write only the live ones
-        dfeat = torch.zeros_like(feat) if want_cam else torch.empty_like(feat)
-        dsig = torch.zeros_like(sigma) if want_cam else torch.empty_like(sigma)
-        use_live = SIREN_BWD_LIVE and SIREN_BWD_MODE == "x3"
-        live = None
-        if ctx.live_fwd:
-            live = ctx.saved_tensors[9 + len(_SIREN_NAMES):]
-            # the lists' stream, whether or not a live_forward_join has made some stream wait for it already
-            _LIVE_PENDING.discard(dfea.device.index)
-            torch.cuda.current_stream(dfea.device).wait_stream(_LIVE_STREAMS[dfea.device.index])
-            check(lib.cips_composite_bwd_listed(_p(feat), _p(sigma), _p(z), _p(noise), float(noise_std), _p(dfea), _p(dfeat),
-                                                _p(dsig), R, S, clamp_mode, flags, _stream()), "cips_composite_bwd_listed")
-        elif use_live:
-            mask = torch.empty(B, n * S, dtype=torch.uint8, device=dfea.device)
-            check(lib.cips_composite_bwd_live(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
-                                              _p(dfea), _p(dfeat), _p(dsig), None, None, _p(mask), None, R, S, clamp_mode, flags,
-                                              _p(ctx.clamp_mask), _stream()), "cips_composite_bwd_live")
-        else:
-            check(lib.cips_composite_bwd(_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None,
-                                         _p(dfea), _p(dfeat), _p(dsig), None, None, R, S, clamp_mode, flags, _p(ctx.clamp_mask),
-                                         _stream()), "cips_composite_bwd")
-        _tail_gate_publish(dfea.device)
-        rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
-        if live is None and use_live:
-            live = live_points(mask)
-        grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live)
-        if not want_cam:
-            return (None,) * 7 + grads
-        dcam = rays_bwd_cam(rp, siren_bwd_points(t, dfeat, dsig, B, n * S, rays=rp), B)
-        return (None,) * 4 + (dcam,) + (None,) * 2 + grads
+        return _march_backward(ctx, _c(dfea))
+
+
+class RayMarchGeoFunction(torch.autograd.Function):
+    """RayMarchFunction with the geometry differentiable: -> pixels_fea (B,n,32), depth (B,n), opacity (B,n), all three with
+    gradients (cips_march_fwd_x3_geo; depth and opacity as CompositeGeoFunction defines them).  The backward takes every route
+    RayMarchFunction's takes — dense, masked, the forward-time lists, and the camera's — with the `_geo` form of the route's
+    compositing backward when the depth or the opacity has an upstream gradient (only dsigma changes; the liveness rules hold
+    whatever the upstream is: a relu-clamped sample has alpha = 0 and d alpha / dx = 0), and exactly RayMarchFunction's calls
+    when only the features have one.  Once differentiable; no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
+        ctx.set_materialize_grads(False)
+        return _march_forward(ctx, True, geom, xg, yg, zg, cam2world, jitter, noise, *siren)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dfea, ddepth, dopacity):
+        if dfea is None and ddepth is None and dopacity is None:
+            return (None,) * (7 + len(_SIREN_NAMES))
+        feat = ctx.saved_tensors[6]
+        B, H, W = ctx.geom[:3]
+        return _march_backward(ctx, *_geo_upstream(dfea, ddepth, dopacity, (B, H * W, 32), feat.device))
+
+
+def _march_forward(ctx, geo, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
+    """the forward of RayMarchFunction (geo False) and RayMarchGeoFunction (True: also the opacity output)
+    -> fea, depth, opacity or None"""
+    lib = _lib.load()
+    B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom[:9]
+    t = _siren_prep(siren)
+    xg, yg, zg, cam2world, jitter, noise = _ray_prep(xg, yg, zg, cam2world, jitter, noise if noise_std != 0.0 else None)
+    dev = cam2world.device
+    n = H * W
+    # per-sample outputs only when a backward can follow: the caller's grad mode counts (inside forward() it is
+    # always off, and under torch.no_grad() needs_input_grad still reports the parameters' requires_grad)
+    train = grad_mode and any(ctx.needs_input_grad)
+    fea = torch.empty(B, n, 32, device=dev)
+    depth = torch.empty(B, n, device=dev)
+    opacity = torch.empty(B, n, device=dev) if geo else None
+    feat = torch.empty(B, n * S, 32, device=dev) if train else None
+    sigma = torch.empty(B, n * S, device=dev) if train else None
+    z = torch.empty(B, n * S, device=dev) if train else None
+    sw = _siren_struct(t)
+    rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
+    pin, rec = _clamp_debug_forward(B * n, S, clamp_mode, dev)
+    args = (C.byref(sw), C.byref(rp), _p(noise), float(noise_std), clamp_mode, flags, _p(fea), _p(depth), None, _p(feat),
+            _p(sigma), _p(z), B, _p(pin), _p(rec))
+    if geo:
+        check(lib.cips_march_fwd_x3_geo(*args, _p(opacity), _stream()), "cips_march_fwd_x3_geo")
+    else:
+        check(lib.cips_march_fwd_x3(*args, _stream()), "cips_march_fwd_x3")
+    if rec is not None and CLAMP_REC is not None:
+        CLAMP_REC.append(rec.reshape(B * n, S))
+    ctx.clamp_mask = pin
+    # a tenth entry of geom, true: the caller joins the list stream (live_forward_join) whether or not a backward follows
+    ctx.live_fwd = train and len(geom) > 9 and bool(geom[9]) and live_forward_ok(clamp_mode, pin)
+    if train:
+        lists = live_plan_forward(sigma, noise, noise_std, B, n, S, clamp_mode, flags) if ctx.live_fwd else ()
+        ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values(), *lists)
+    ctx.geom = geom
+    return fea, depth, opacity
+
+
+def _march_backward(ctx, dfea, ddepth=None, dopacity=None):
+    """the backward of one march forward for the upstream gradient dfea (B,n,32) and, optionally, those of depth / opacity (B,n)
+    -> the gradients of the Functions' inputs (geom, xg, yg, zg, cam2world, jitter, noise, *siren)"""
+    xg, yg, zg, cam2world, jitter, noise, feat, sigma, z = ctx.saved_tensors[:9]
+    t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[9:9 + len(_SIREN_NAMES)]))
+    B, H, W, S, zc, noise_std, clamp_mode, flags, _ = ctx.geom[:9]
+    n = H * W
+    R = B * n
+    want_cam = ctx.needs_input_grad[4]
+    if want_cam:
+        _need_x3_points_grad()
+    # the camera gradient's kernel reads every row, the live forms below write only the live ones
+    dfeat = torch.zeros_like(feat) if want_cam else torch.empty_like(feat)
+    dsig = torch.zeros_like(sigma) if want_cam else torch.empty_like(sigma)
+    use_live = SIREN_BWD_LIVE and SIREN_BWD_MODE == "x3"
+    live = None
+    if ctx.live_fwd:
+        live = ctx.saved_tensors[9 + len(_SIREN_NAMES):]
+        # the lists' stream, whether or not a live_forward_join has made some stream wait for it already
+        _LIVE_PENDING.discard(dfea.device.index)
+        torch.cuda.current_stream(dfea.device).wait_stream(_LIVE_STREAMS[dfea.device.index])
+        _composite_bwd_call("cips_composite_bwd_listed",
+                            (_p(feat), _p(sigma), _p(z), _p(noise), float(noise_std), _p(dfea), _p(dfeat), _p(dsig), R, S,
+                             clamp_mode, flags), ddepth, dopacity)
+    elif use_live:
+        mask = torch.empty(B, n * S, dtype=torch.uint8, device=dfea.device)
+        _composite_bwd_call("cips_composite_bwd_live",
+                            (_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None, _p(dfea),
+                             _p(dfeat), _p(dsig), None, None, _p(mask), None, R, S, clamp_mode, flags, _p(ctx.clamp_mask)),
+                            ddepth, dopacity)
+    else:
+        _composite_bwd_call("cips_composite_bwd",
+                            (_p(feat), _p(sigma), _p(z), None, None, None, _p(noise), float(noise_std), None, _p(dfea),
+                             _p(dfeat), _p(dsig), None, None, R, S, clamp_mode, flags, _p(ctx.clamp_mask)), ddepth, dopacity)
+    _tail_gate_publish(dfea.device)
+    rp = _ray_params(xg, yg, zg, zc, cam2world, jitter, H, W, S)
+    if live is None and use_live:
+        live = live_points(mask)
+    grads = _siren_backward(t, dfeat, dsig, B, n * S, rays=rp, live=live)
+    if not want_cam:
+        return (None,) * 7 + grads
+    dcam = rays_bwd_cam(rp, siren_bwd_points(t, dfeat, dsig, B, n * S, rays=rp), B)
+    return (None,) * 4 + (dcam,) + (None,) * 2 + grads
 
 
 # --------------------------------------------------------------------------------------

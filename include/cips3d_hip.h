@@ -298,6 +298,15 @@ int cips_siren_bwd_x3_finalize_segments(const cips_siren_weights* w, const float
 int cips_march_fwd_x3(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise, float noise_std,
                       int clamp_mode, int flags, float* fea, float* depth, float* weights, float* feat, float* sigma,
                       float* z, int B, const unsigned char* clamp_in, unsigned char* clamp_out, cips_stream_t stream);
+/* cips_march_fwd_x3 with one more optional output, opacity (B,n): the ray's sum of weights as the kernel accumulates it,
+ * stored before the last_back / white_back adjustments (pigan_utils.py's weights_sum; under last_back it is NOT the constant
+ * 1).  The store is in instantiations of their own: with opacity NULL this launches exactly what cips_march_fwd_x3 launches
+ * and stores the same bits, and the production kernel keeps its registers.  Every other output is the same bits either way.
+ * Validated before any HIP call: w, rays, fea NULL, B <= 0 or ray parameters fill_raygen refuses -> hipErrorInvalidValue. */
+int cips_march_fwd_x3_geo(const cips_siren_weights* w, const cips_ray_params* rays, const float* noise, float noise_std,
+                          int clamp_mode, int flags, float* fea, float* depth, float* weights, float* feat, float* sigma,
+                          float* z, int B, const unsigned char* clamp_in, unsigned char* clamp_out, float* opacity,
+                          cips_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* H3  hierarchical resampling + merge + alpha-composite               */
@@ -394,6 +403,56 @@ int cips_live_points_clamp(const float* sigma, const float* noise, float noise_s
 int cips_composite_bwd_listed(const float* feat, const float* sigma, const float* z, const float* noise, float noise_std,
                               const float* dfea, float* dfeat, float* dsigma, int R, int S, int clamp_mode, int flags,
                               cips_stream_t stream);
+
+/* Differentiable depth and opacity.  The `_geo` forms take the arguments of the entry point they are named after, then the
+ * new ones, then the stream.
+ *
+ * cips_composite_fwd_geo: cips_composite_fwd with one more optional output, opacity (R) = sum_k w_k, stored before the
+ *   last_back / white_back adjustments (pigan_utils.py's weights_sum: under last_back it is not the constant 1).  Every other
+ *   output is cips_composite_fwd's bit for bit, with or without it.
+ *   hipErrorInvalidValue, before any HIP call: R <= 0, S < 1, feat_c / sig_c / z_c / fea NULL, a feat_f without sig_f and z_f.
+ *
+ * cips_composite_bwd_geo / _live_geo / _listed_geo: the three compositing backwards with the upstream gradients ddepth (R)
+ *   and dopacity (R) of the ray's depth and opacity next to dfea; either may be NULL (zeros).  With BOTH NULL they launch the
+ *   kernel instantiation the entry points without them launch and store exactly their bits (the two terms are a template
+ *   parameter of the kernel: that instantiation has no trace of them).  Otherwise, with
+ *       depth = sum_k w_k z_k + [last_back] (1 - sum w) z_last,   opacity = sum_k w_k,
+ *   the per-sample scalar of the reverse scan, dL/dw_k, gains two terms:
+ *       dL/dw_k = (G . f_k + gd z_k) - [last_back] (G . f_last + gd z_last) - [white_back] sum(G) + go.
+ *   last_back: the depth upstream sees the topped-up last weight like the features do; the opacity upstream does not (opacity
+ *   is taken before the top-up).  white_back touches neither.  Everything behind dL/dw_k is unchanged: dalpha = T_k (dL/dw_k -
+ *   Q), the clamp's gradient, and the dfeat rows w_k G, which do not depend on gd / go at all — only dsigma does.  z gets no
+ *   gradient (depths are constants, as in the reference).
+ *   Liveness keeps its meaning: a relu-clamped sample has alpha = 0 and d alpha / dx = 0 whatever the upstream is, so its row
+ *   and its dsigma stay zero, _live_geo's mask follows the same (w != 0) || (dsigma != 0), _listed_geo writes by the same rule,
+ *   and cips_live_points_clamp's lists remain a superset of what these backwards can make non-zero.
+ *   hipErrorInvalidValue, before any HIP call: R <= 0, S < 1; feat / sigma / z / dfea / dfeat / dsigma (of the coarse set, and
+ *   with a feat_f of the fine set, and then `order`) NULL; a live_f without a live_c, or with a fine set a live_c without a
+ *   live_f. */
+int cips_composite_fwd_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                           const float* feat_f, const float* sig_f, const float* z_f,
+                           const float* noise, float noise_std,
+                           float* fea, float* depth, float* weights, int* order, float* zsorted,
+                           int R, int S, int clamp_mode, int flags, const unsigned char* clamp_in, unsigned char* clamp_out,
+                           float* opacity, cips_stream_t stream);
+int cips_composite_bwd_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                           const float* feat_f, const float* sig_f, const float* z_f,
+                           const float* noise, float noise_std, const int* order,
+                           const float* dfea,
+                           float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                           int R, int S, int clamp_mode, int flags, const unsigned char* clamp_in,
+                           const float* ddepth, const float* dopacity, cips_stream_t stream);
+int cips_composite_bwd_live_geo(const float* feat_c, const float* sig_c, const float* z_c,
+                                const float* feat_f, const float* sig_f, const float* z_f,
+                                const float* noise, float noise_std, const int* order,
+                                const float* dfea,
+                                float* dfeat_c, float* dsig_c, float* dfeat_f, float* dsig_f,
+                                unsigned char* live_c, unsigned char* live_f,
+                                int R, int S, int clamp_mode, int flags, const unsigned char* clamp_in,
+                                const float* ddepth, const float* dopacity, cips_stream_t stream);
+int cips_composite_bwd_listed_geo(const float* feat, const float* sigma, const float* z, const float* noise, float noise_std,
+                                  const float* dfea, float* dfeat, float* dsigma, int R, int S, int clamp_mode, int flags,
+                                  const float* ddepth, const float* dopacity, cips_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* generic batched fp32 GEMM on v_mfma_f32_32x32x2_f32 with fused epilogues */
