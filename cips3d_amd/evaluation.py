@@ -208,3 +208,20 @@ def saved_models(model_dict, info_msg, G, G_ema, G_kwargs, fixed_z, img_size, sa
     from .checkpoint import save_models
     save_models(saved_dir, model_dict, info_msg=info_msg)
     save_images(saved_dir, G, G_ema, G_kwargs, fixed_z, img_size)
+
+
+@torch.no_grad()
+def render_views(G, styles, yaws, pitches=None, **render_kw):
+    """The multi-view strip of the reference's Projector (exp/cips3d/models/st_web.py:66-186): the styles of
+    cips3d_amd.projection.project (or of G.styles) rendered from a list of angles -> a list with one (b, 3, H, W) image
+    batch per angle, each what G.forward_styles(styles, h_mean=yaw, v_mean=pitch, **render_kw) returns under no_grad.
+    `pitches`: one per yaw, default pi / 2.  render_kw: forward_styles' arguments; img_size is required, the others default to
+    the projection loop's camera (fov 12, rays 0.88..1.12, 24 steps, no hierarchical sampling, a fixed camera)."""
+    yaws = [float(y) for y in yaws]
+    pitches = [math.pi * 0.5] * len(yaws) if pitches is None else [float(p) for p in pitches]
+    if len(pitches) != len(yaws):
+        raise ValueError(f"render_views: {len(yaws)} yaws but {len(pitches)} pitches")
+    kw = dict(fov=12, ray_start=0.88, ray_end=1.12, num_steps=24, h_stddev=0., v_stddev=0., hierarchical_sample=False,
+              sample_dist='gaussian')
+    kw.update(render_kw)
+    return [G.forward_styles(styles, h_mean=yaw, v_mean=pitch, **kw)[0] for yaw, pitch in zip(yaws, pitches)]

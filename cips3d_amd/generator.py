@@ -728,8 +728,10 @@ def _camera_setup(s, theta, phi, b, device):
         pitch = yaw = torch.zeros(b, 1, device=device)
     else:
         if s.sample_dist in _SIMPLE_CAMS:
-            # (the one-launch form takes the means as floats: a mean that requires grad goes op by op, which is differentiable)
-            if theta.is_cuda and not (s.staged and s.up_vector is not None) and not _wants_grad(s.h_mean, s.v_mean):
+            # (the one-launch form takes the means as floats: a mean that requires grad goes op by op, which is differentiable,
+            # and so does a per-image (b, 1) mean, e.g. the fitted angles of projection.project)
+            per_image = any(torch.is_tensor(v) and v.numel() > 1 for v in (s.h_mean, s.v_mean))
+            if theta.is_cuda and not (s.staged and s.up_vector is not None) and not _wants_grad(s.h_mean, s.v_mean) and not per_image:
                 # draws -> pitch, yaw, origin, cam2world in one launch (the ~45 one-wave torch kernels of the op-by-op form
                 # below are 0.2 ms of a captured step)
                 pitch_yaw, origin, cam2world = ops.camera_pose(theta, phi, s.sample_dist == 'uniform', s.h_stddev, s.h_mean,
@@ -1060,6 +1062,53 @@ class GeneratorNerfINR(nn.Module):
             avg_styles = self.generate_avg_frequencies(device=self.device)
             style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles,
                                                        raw_lambda=psi)
+        return self._render_styles(style_dict, s, geo)
+
+    # ---- style-space entry points: what fitting, interpolation and per-layer mixing work on ----
+    def _style_dims(self):
+        """name -> width of every style forward() renders from, in the order of its style dictionary (mapping_network: the
+        NeRF mapping network's heads, then the INR one's).  The width is the consumer's: the FiLM layers' resp. the modulated
+        FCs' style_dim."""
+        dims = {f'{self.siren.name_prefix}_w{i}': lay.style_dim for i, lay in enumerate(self.siren.network)}
+        dims[f'{self.siren.name_prefix}_rgb'] = self.siren.color_layer_sine.style_dim
+        dims.update(self.inr_net.style_dim_dict)
+        names = tuple(self.mapping_network_nerf.head_dim_dict) + tuple(self.mapping_network_inr.head_dim_dict)
+        return OrderedDict((name, dims[name]) for name in names)
+
+    @property
+    def style_names(self):
+        """the keys of the style dictionary forward() renders from, in its order"""
+        return tuple(self._style_dims())
+
+    def styles(self, zs, psi=1.0):
+        """zs -> {name: (b, dim)}: the dictionary forward(zs, psi=psi) renders from — both mapping networks, and for psi < 1
+        the truncation towards the average of the same 10 000 draws.  Returned joined: the INR mapping network's side stream
+        is not pending.  Under grad mode it is differentiable with respect to zs and the mapping networks."""
+        style_dict = self.mapping_network(**zs)
+        if psi < 1:
+            avg_styles = self.generate_avg_frequencies(device=self.device)
+            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles, raw_lambda=psi)
+        return style_dict
+
+    def _check_styles(self, styles, what):
+        """the style dictionary of a caller -> a dict in forward()'s order (the same tensors), or ValueError"""
+        dims = self._style_dims()
+        missing = [name for name in dims if name not in styles]
+        unknown = [name for name in styles if name not in dims]
+        if missing or unknown:
+            raise ValueError(f"{what}: styles must hold exactly G.style_names; missing {missing}, unknown {unknown}")
+        b = styles[next(iter(dims))].shape[0] if styles[next(iter(dims))].dim() == 2 else None
+        for name, dim in dims.items():
+            t = styles[name]
+            if t.dim() != 2 or t.shape[0] != b or t.shape[1] != dim:
+                raise ValueError(f"{what}: style {name!r} must be ({b if b is not None else 'b'}, {dim}), got {tuple(t.shape)}")
+        if next(self.parameters()).device.type != 'cuda':
+            raise RuntimeError(f"GeneratorNerfINR.{what} runs on the GPU only (there is no CPU path)")
+        return {name: styles[name] for name in dims}
+
+    def _render_styles(self, style_dict, s, geo=False):
+        """the entry points' common path behind the mapping networks: styles (the latent entry points', possibly with the INR
+        mapping network's side stream still pending, or a caller's) -> _render, with the clean-up every exit needs"""
         try:
             # with forward_points the reference evaluates image by image in chunks under no_grad (generator.py:1325-1347)
             with torch.set_grad_enabled(torch.is_grad_enabled() and not s.staged):
@@ -1072,6 +1121,40 @@ class GeneratorNerfINR(nn.Module):
             self._join_side()
             ops.live_forward_join()         # likewise the ray march's list stream (no-op after _head's join)
             self.inr_net._tail = None
+
+    def forward_styles(self, styles, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
+                       h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, sample_dist=None, lock_view_dependence=False,
+                       clamp_mode='relu', nerf_noise=0., white_back=False, last_back=False, return_aux_img=False,
+                       grad_points=None, forward_points=None, camera_pos=None, camera_lookup=None, up_vector=None, **kwargs):
+        """forward() (or, with camera_pos / camera_lookup, forward_camera_pos_and_lookup()) from a style dictionary instead of
+        latents: `styles` holds one (b, dim) tensor per name of G.style_names — styles(zs, psi), or anything made from such
+        dictionaries (a fitted offset, an interpolation, a per-layer mix).  The other arguments are forward()'s without zs
+        and psi; forward_styles(styles(zs, psi), ...) returns what forward(zs, psi=psi, ...) returns for the same seed, bit
+        for bit, and the same parameter gradients.  Every key may be its own tensor, and a leaf: the gradient of an image loss
+        reaches it (on the freeze variant only the INR-side keys, the NeRF path runs under no_grad there)."""
+        return self._render_styles(self._check_styles(styles, "forward_styles"), RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
+            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
+            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
+            rand_override=kwargs.get('rand_override'), camera_pos=camera_pos, camera_lookup=camera_lookup,
+            up_vector=up_vector))
+
+    def render_styles(self, styles, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
+                      h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, sample_dist=None, clamp_mode='relu', nerf_noise=0.,
+                      white_back=False, last_back=False, return_aux_img=False, camera_pos=None, camera_lookup=None,
+                      up_vector=None, rand_override=None, grad_points=None, forward_points=None):
+        """render() from a style dictionary (forward_styles' `styles`): -> SimpleNamespace(imgs, depth, opacity, pitch_yaw),
+        what render(zs, psi=psi, ...) returns for styles(zs, psi).  Whole images in one shot only, as render()."""
+        if grad_points is not None or forward_points is not None:
+            raise ValueError("GeneratorNerfINR.render_styles renders whole images in one shot: grad_points / forward_points "
+                             "are not supported (use forward_styles() for the partial and staged forms)")
+        return self._render_styles(self._check_styles(styles, "render_styles"), RenderSettings(
+            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
+            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
+            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
+            last_back=last_back, return_aux_img=return_aux_img, rand_override=rand_override, camera_pos=camera_pos,
+            camera_lookup=camera_lookup, up_vector=up_vector), geo=True)
 
     def _density_styles(self, z_nerf, psi):
         """z_nerf -> the NeRF styles of the density entry points: only the NeRF mapping network runs; for psi < 1 the styles are

@@ -2483,3 +2483,70 @@ def col2im(col, B, Cc, H, W, kh, kw, stride, pad):
     dx = torch.empty(B, Cc, H, W, device=col.device)
     check(lib.cips_col2im(_p(col), _p(dx), B, Cc, H, W, kh, kw, stride, pad, _stream()), "cips_col2im")
     return dx
+
+
+# --------------------------------------------------------------------------------------
+# Pyramid fit loss (csrc/fit_loss.hip): the loss of the projection loop
+# --------------------------------------------------------------------------------------
+FIT_LOSS_KINDS = ("mse", "charbonnier")
+
+
+class PyramidLossFunction(torch.autograd.Function):
+    """(pred, target, weight or None) -> loss (b,): cips_pyramid_loss_fwd writes the loss and d loss / d pred in one pass; the
+    backward scales that stored gradient by the upstream value of each image (one launch, nothing recomputed)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, level_weights, kind, eps):
+        lib = _lib.load()
+        b, Cc, H, W = pred.shape
+        L = len(level_weights)
+        loss = torch.empty(b, device=pred.device)
+        grad = torch.empty_like(pred)
+        nscr = lib.cips_pyramid_loss_scratch(b, Cc, H, W, L)
+        scratch = torch.empty(max(nscr, 1), device=pred.device)
+        lw = (C.c_double * L)(*level_weights)
+        check(lib.cips_pyramid_loss_fwd(_p(pred), _p(target), _p(weight), lw, L, kind, eps, _p(loss), _p(grad), _p(scratch),
+                                        nscr, b, Cc, H, W, _stream()), "cips_pyramid_loss_fwd")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        grad, = ctx.saved_tensors
+        dloss = _c(dloss)
+        out = torch.empty_like(grad)
+        check(_lib.load().cips_pyramid_loss_bwd(_p(grad), _p(dloss), _p(out), grad.shape[0], grad[0].numel(), _stream()),
+              "cips_pyramid_loss_bwd")
+        return out, None, None, None, None, None
+
+
+def pyramid_loss(pred, target, weight=None, level_weights=(1.,), kind="mse", eps=1e-3):
+    """Per-image multi-scale fit loss -> (b,), differentiable with respect to `pred` only.
+    pred, target (b,C,H,W); weight (b,1,H,W) or None (= 1).  With d_0 = pred - target, w_0 = weight and level l+1 the 2x2 mean
+    of level l (of both),   loss_b = sum_l level_weights[l] / (C H_l W_l) * sum_{c,y,x} w_l rho(d_l),
+    rho(x) = x^2 (kind "mse") or sqrt(x^2 + eps^2) - eps ("charbonnier").  1 <= len(level_weights) <= 8, H and W multiples of
+    2^(levels - 1).  level_weights=(1.,), "mse", no weight: nn.MSELoss per image (the reference Projector's loss).
+    Deterministic: fixed summation order, no atomics; an image's result does not depend on its batch."""
+    level_weights = tuple(float(v) for v in level_weights)
+    L = len(level_weights)
+    if kind not in FIT_LOSS_KINDS:
+        raise ValueError(f"pyramid_loss: kind {kind!r} (one of {FIT_LOSS_KINDS})")
+    if not 1 <= L <= 8 or any(not math.isfinite(v) or v < 0 for v in level_weights):
+        raise ValueError("pyramid_loss: 1 to 8 finite, non-negative level weights")
+    if pred.dim() != 4 or pred.shape != target.shape or pred.numel() == 0:
+        raise ValueError(f"pyramid_loss: pred and target (b,C,H,W) of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    b, Cc, H, W = pred.shape
+    if H % (1 << (L - 1)) or W % (1 << (L - 1)):
+        raise ValueError(f"pyramid_loss: {L} levels need H and W to be multiples of {1 << (L - 1)}, got {H} x {W}")
+    if weight is not None and tuple(weight.shape) != (b, 1, H, W):
+        raise ValueError(f"pyramid_loss: weight ({b},1,{H},{W}) expected, got {tuple(weight.shape)}")
+    if kind == "charbonnier" and not eps > 0:
+        raise ValueError("pyramid_loss: charbonnier needs eps > 0")
+    for t in (pred, target, weight):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("pyramid_loss needs fp32 tensors on the GPU (no CPU fallback)")
+    target = target.detach().contiguous()
+    weight = weight.detach().contiguous() if weight is not None else None
+    _chk(target, weight)
+    return PyramidLossFunction.apply(pred.contiguous(), target, weight, level_weights, FIT_LOSS_KINDS.index(kind), float(eps))

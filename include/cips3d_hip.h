@@ -923,6 +923,29 @@ int cips_opt_step(const cips_opt_tensor* table_dev, const int* chunk_tensor_dev,
                   float beta1, float beta2, float eps, float ema_decay, int write_grad,
                   long long* steps_dev, cips_stream_t stream);
 
+/* ------------------------------------------------------------------ */
+/* Pyramid fit loss (csrc/fit_loss.hip): what fitting styles or a camera to an image minimises.  Replaces, per step, the
+ * reference Projector's nn.MSELoss (exp/cips3d/models/st_web.py:144-186) and the ATen chain a multi-scale version of it
+ * would be (sub, avg_pool2d per level, mul, pow / sqrt, mean, and their autograd backward).
+ * pred, target (B,C,H,W), weight (B,1,H,W) or NULL (= 1), all fp32 contiguous on the device:
+ *   d_0 = pred - target, d_{l+1} = 2x2 mean of d_l;   w_0 = weight, w_{l+1} = 2x2 mean of w_l
+ *   loss[b] = sum_{l<L} level_weights[l] / (C H_l W_l) * sum_{c,y,x} w_l rho(d_l)
+ *   rho(x) = x^2 (kind 0)  or  sqrt(x^2 + eps^2) - eps (kind 1, Charbonnier; eps > 0)
+ * 1 <= L <= 8; H and W multiples of 2^(L-1).  level_weights_host: L doubles in HOST memory (read during the call); they and
+ * eps are doubles because the gradient is formed in fp64 and rounded once: for L <= 6 it is the correctly rounded gradient.
+ * The forward writes loss (B) and grad (B,C,H,W) = d loss[b] / d pred in one pass over pred / target: two launches, three
+ * for L > 6.  scratch: cips_pyramid_loss_scratch(B,C,H,W,L) floats of device memory (-1: invalid shape), overwritten.
+ * No atomics and a fixed summation order: equal inputs give equal bits, and image b's loss and gradient do not depend on
+ * the other images of the batch.  cips_pyramid_loss_bwd: out[b] = grad[b] * upstream[b] (per_image = C*H*W elements each).
+ * Invalid arguments (NULL required pointer, a size <= 0, L outside 1..8, H or W not a multiple of 2^(L-1), eps <= 0 with
+ * kind 1, a scratch that is too small) return hipErrorInvalidValue before any HIP call. */
+long long cips_pyramid_loss_scratch(int B, int C, int H, int W, int L);
+int cips_pyramid_loss_fwd(const float* pred, const float* target, const float* weight, const double* level_weights_host,
+                          int L, int kind, double eps, float* loss, float* grad, float* scratch, long long scratch_floats,
+                          int B, int C, int H, int W, cips_stream_t stream);
+int cips_pyramid_loss_bwd(const float* grad, const float* upstream, float* out, int B, long long per_image,
+                          cips_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
