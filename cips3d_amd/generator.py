@@ -258,26 +258,26 @@ class NeRFNetwork(nn.Module):
             style_dict = {**style_dict, key: style_dict[f'{self.name_prefix}_w0'].new_zeros(b, self.color_layer_sine.style_dim)}
         return style_dict
 
-    def density(self, points, style_dict):
-        """points (b,P,3) -> sigma (b,P), no gradient: the sigma-only HIP kernel for the shipped shape (the forward's sigma bit
-        for bit, without the colour branch), tensor operations for other widths / depths."""
+    def _density_call(self, style_dict, fused, unfused):
+        """the frame of the density family: no gradient, the styles completed by _sigma_args, then fused(*the 16 SIREN
+        tensors) for the shipped shape or unfused(styles) on tensor operations for other widths / depths"""
         with torch.no_grad():
             style_dict = self._sigma_args(style_dict)
             if not self.fused:
-                return self._evaluate_unfused(points, style_dict)[1]
-            return ops.siren_sigma(points, *self._siren_args(style_dict))
+                return unfused(style_dict)
+            return fused(*self._siren_args(style_dict))
+
+    def density(self, points, style_dict):
+        """points (b,P,3) -> sigma (b,P), no gradient: the sigma-only HIP kernel for the shipped shape (the forward's sigma bit
+        for bit, without the colour branch), tensor operations for other widths / depths."""
+        return self._density_call(style_dict, lambda *siren: ops.siren_sigma(points, *siren),
+                                  lambda styles: self._evaluate_unfused(points, styles)[1])
 
     def density_lattice(self, gx, gy, gz, style_dict):
         """density() over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> (b, nx, ny, nz); the fused kernel
         reads the coordinates themselves, no points tensor is built"""
-        with torch.no_grad():
-            style_dict = self._sigma_args(style_dict)
-            if not self.fused:
-                n = (len(gx), len(gy), len(gz))
-                pts = torch.stack([gx.view(-1, 1, 1).expand(n), gy.view(1, -1, 1).expand(n), gz.view(1, 1, -1).expand(n)], -1)
-                b = style_dict[f'{self.name_prefix}_w0'].shape[0]
-                return self._evaluate_unfused(pts.reshape(1, -1, 3).expand(b, -1, 3), style_dict)[1].reshape(b, *n)
-            return ops.siren_sigma_grid(gx, gy, gz, *self._siren_args(style_dict))
+        return self._density_call(style_dict, lambda *siren: ops.siren_sigma_grid(gx, gy, gz, *siren),
+                                  lambda styles: self._unfused_lattice(gx, gy, gz, styles, False))
 
     def _unfused_gradient(self, points, style_dict):
         """sigma and d sigma / d points of _evaluate_unfused by autograd (the tensor-operation path of other widths / depths)"""
@@ -287,42 +287,37 @@ class NeRFNetwork(nn.Module):
             grad, = torch.autograd.grad(sigma.sum(), pts)
         return sigma.detach(), grad
 
+    def _unfused_lattice(self, gx, gy, gz, style_dict, gradient):
+        """the lattice forms on tensor operations: the points are materialised (ops.lattice_points)"""
+        b, n = style_dict[f'{self.name_prefix}_w0'].shape[0], (len(gx), len(gy), len(gz))
+        pts = ops.lattice_points(gx, gy, gz, b)
+        if not gradient:
+            return self._evaluate_unfused(pts, style_dict)[1].reshape(b, *n)
+        sigma, grad = self._unfused_gradient(pts, style_dict)
+        return sigma.reshape(b, *n), grad.reshape(b, *n, 3)
+
     def density_gradient(self, points, style_dict):
         """points (b,P,3) -> sigma (b,P), d sigma / d points (b,P,3); the outputs carry no grad_fn.  The fused HIP kernel for
         the shipped shape (ops.siren_sigma_grad: sigma is density()'s bit for bit), autograd through the tensor operations for
         other widths / depths."""
-        with torch.no_grad():
-            style_dict = self._sigma_args(style_dict)
-            if not self.fused:
-                return self._unfused_gradient(points, style_dict)
-            return ops.siren_sigma_grad(points, *self._siren_args(style_dict))
+        return self._density_call(style_dict, lambda *siren: ops.siren_sigma_grad(points, *siren),
+                                  lambda styles: self._unfused_gradient(points, styles))
 
     def density_gradient_lattice(self, gx, gy, gz, style_dict):
         """density_gradient() over the lattice (gx[i], gy[j], gz[k]) -> (b, nx, ny, nz), (b, nx, ny, nz, 3)"""
-        with torch.no_grad():
-            style_dict = self._sigma_args(style_dict)
-            if not self.fused:
-                n = (len(gx), len(gy), len(gz))
-                pts = torch.stack([gx.view(-1, 1, 1).expand(n), gy.view(1, -1, 1).expand(n), gz.view(1, 1, -1).expand(n)], -1)
-                b = style_dict[f'{self.name_prefix}_w0'].shape[0]
-                sigma, grad = self._unfused_gradient(pts.reshape(1, -1, 3).expand(b, -1, 3), style_dict)
-                return sigma.reshape(b, *n), grad.reshape(b, *n, 3)
-            return ops.siren_sigma_grad_grid(gx, gy, gz, *self._siren_args(style_dict))
+        return self._density_call(style_dict, lambda *siren: ops.siren_sigma_grad_grid(gx, gy, gz, *siren),
+                                  lambda styles: self._unfused_lattice(gx, gy, gz, styles, True))
 
     def surface_rays(self, style_dict, geom, xg, yg, zg, cam2world, level, refine):
         """The iso-surface sigma = level along the unjittered camera rays -> depth (b,n), hit (b,n) uint8, sigma (b,n), points
         (b,n,3), no gradient (the rule: ops.siren_surface).  The ray-cast HIP kernel for the shipped shape on the split-operand
         chain; the same search composed from sigma evaluations (ops.siren_surface_composed) for the exact-fp32 forward
         (CIPS_SIREN_FWD=f32) and, on tensor operations, for other widths / depths."""
-        with torch.no_grad():
-            style_dict = self._sigma_args(style_dict)
-            if not self.fused:
-                return ops.siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world,
-                                                  sigma_fn=lambda p: self._evaluate_unfused(p, style_dict)[1])
-            siren = self._siren_args(style_dict)
-            if ops.SIREN_FWD_MODE != "x3":
-                return ops.siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world, *siren)
-            return ops.siren_surface(level, refine, geom, xg, yg, zg, cam2world, *siren)
+        rays = (level, refine, geom, xg, yg, zg, cam2world)
+        return self._density_call(
+            style_dict,
+            lambda *siren: (ops.siren_surface if ops.SIREN_FWD_MODE == "x3" else ops.siren_surface_composed)(*rays, *siren),
+            lambda styles: ops.siren_surface_composed(*rays, sigma_fn=lambda p: self._evaluate_unfused(p, styles)[1]))
 
     def evaluate_rays(self, style_dict, geom, xg, yg, zg, cam2world, jitter=None, zvals=None):
         """evaluate() with the sample points generated in-kernel (coarse: from the jitter draw; fine: from the resampled
@@ -600,7 +595,7 @@ def create_cam2world_matrix(forward_vector, origin, up_vector=None):
 # ------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class RenderSettings:
-    """What forward() / forward_camera_pos_and_lookup() were asked for, built once there and handed down."""
+    """What an entry point of GeneratorNerfINR was asked for, built once there (RenderSettings.of) and handed down."""
     img_size: int
     fov: float
     ray_start: float
@@ -630,6 +625,24 @@ class RenderSettings:
     # generator.py:1325-1347: fewer grad_points than pixels is part_grad_forward, which is not handed forward_points
     part = property(lambda s: s.grad_points is not None and s.grad_points < s.n)
     staged = property(lambda s: s.forward_points is not None and not s.part)
+
+    @classmethod
+    def of(cls, args, **fixed):
+        """The settings of an entry point: the fields it has a parameter for, picked by name out of `args` (its locals():
+        whatever else is in there is not a field and is dropped), then `fixed` on top; a field it has no parameter for keeps
+        the default above.  What differs between the entry points, all of it:
+
+          entry point                    camera_pos, camera_lookup, up_vector     rand_override    grad_points, forward_points
+          forward                        no parameter: never set                  from **kwargs    passed
+          forward_camera_pos_and_lookup  set (generator_v1's drops an up_vector)  from **kwargs    passed
+          forward_styles                 optional                                 from **kwargs    passed
+          render, render_styles          optional                                 named parameter  any value but None: ValueError
+          geometry                       optional                                 named parameter  no parameter
+          surface                        optional                                 named parameter  no parameter
+
+        Fixed fields: geometry nerf_noise=0. (and it has no return_aux_img parameter); surface hierarchical_sample=False and
+        nerf_noise=0. (and no clamp_mode, white_back, last_back or return_aux_img parameter: the defaults)."""
+        return cls(**{**{k: v for k, v in args.items() if k in cls.__dataclass_fields__}, **fixed})
 
 
 def _grad_ctx(nerf_grad):
@@ -749,6 +762,23 @@ def _camera_setup(s, theta, phi, b, device):
     return cam2world[:, :3, 3].contiguous(), cam2world, torch.cat([pitch, yaw], -1)       # every ray starts at the camera
 
 
+def _zc(fov):
+    """the camera-space z of the image plane for a field of view in degrees (get_initial_rays_trig, comm_utils.py:365-438)"""
+    return float((-torch.ones(1) / np.tan((2 * math.pi * fov / 360) / 2)).item())
+
+
+def _unit_normals(grad, mask=None):
+    """-grad / |grad| over the last dimension; exact zeros where the gradient is zero or `mask` (grad's leading shape) is 0"""
+    norm = grad.norm(dim=-1, keepdim=True)
+    keep = norm > 0 if mask is None else (norm > 0) & (mask != 0).unsqueeze(-1)
+    return torch.where(keep, -grad / norm, torch.zeros_like(grad))
+
+
+def _maps(t, b, H):
+    """per-ray values (b, H * H) or (b, H * H, k) -> maps (b, 1 or k, H, H)"""
+    return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
+
+
 # ------------------------------------------------------------------------------------------
 # generator
 # ------------------------------------------------------------------------------------------
@@ -865,7 +895,7 @@ class GeneratorNerfINR(nn.Module):
           "points"  everything else (pixel subsets, other SIREN shapes): the points are materialised here, once"""
         S = s.num_steps
         xg, yg, zg = ops.pixel_grids(s.img_size, s.img_size, S, s.ray_start, s.ray_end, device)
-        zc = float((-torch.ones(1) / np.tan((2 * math.pi * s.fov / 360) / 2)).item())
+        zc = _zc(s.fov)
         in_kernel = (not s.part) and ops.march_available() and self.siren.fused
         g = SimpleNamespace(form=("rays" if s.hierarchical_sample else "march") if in_kernel else "points", b=b, xg=xg, yg=yg,
                             zg=zg, zc=zc, origin=origin, cam2world=cam2world, jitter=jitter.reshape(b, s.n, S))
@@ -885,27 +915,28 @@ class GeneratorNerfINR(nn.Module):
                 g.points, g.z_vals, g.dirs = ops.rays_fwd(xg, yg, zg, zc, cam2world, g.jitter, b, s.img_size, s.img_size, S)
         return g
 
-    def _nerf_features(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None):
+    def _nerf_stage(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None, geo=False):
         """points_forward (generator.py:1659-1746) up to the composite, for all n rays of every image or for the subset
-        `idx` of them (form "points" only): -> pixels_fea (b, m, 32)"""
-        return self._nerf_features_depth(s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx)[0]
-
-    def _nerf_features_depth(self, s, g, nerf_styles, noise_c, u, noise_f, nerf_grad, idx=None, geo=False):
-        """_nerf_features with the per-ray depth the march / composite kernels compute next to the features:
-        -> pixels_fea (b, m, 32), depth (b, m); with `geo` also opacity (b, m), the sum of the ray's weights before the
-        last_back top-up, and depth and opacity carry gradients like the features (the Functions' Geo counterparts)"""
+        `idx` of them (form "points" only): -> pixels_fea (b, m, 32), the per-ray depth (b, m) the march / composite kernels
+        compute next to the features, opacity.  opacity is None unless `geo`: then it is (b, m), the sum of the ray's weights
+        before the last_back top-up, and depth and opacity carry gradients like the features (the Functions' Geo counterparts)"""
         b, S, E, H, W = g.b, s.num_steps, s.E, s.img_size, s.img_size
         m = s.n if idx is None else idx.numel()
         clamp = ops._CLAMP[s.clamp_mode]
+
+        def along_rays(dirs, z):        # origin + direction * depth (generator_nerf_inr.py:537-598) -> points (b, m * S, 3)
+            return (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * z.view(b, m, S, 1)).reshape(b, m * S, 3)
+
         with _grad_ctx(nerf_grad):
             if g.form == "march":
-                # (the last entry: the lists of the backward's live samples may be made in the forward — _head and
-                # _forward_styles join their stream, ops.live_forward_join)
-                geom = (b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled(), True)
-                return self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
-                                        noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None, geo=geo)
+                # (live_fwd: the lists of the backward's live samples may be made in the forward — _head and _render_styles
+                # join their stream, ops.live_forward_join)
+                geom = ops.MarchGeom(b, H, W, S, g.zc, float(s.nerf_noise), clamp, s.flags, torch.is_grad_enabled(), live_fwd=True)
+                out = self.siren.march(nerf_styles, geom, g.xg, g.yg, g.zg, g.cam2world, g.jitter,
+                                       noise_f.reshape(b, m, S) if s.nerf_noise != 0 else None, geo=geo)
+                return out[0], out[1], out[2] if geo else None
             if g.form == "rays":
-                rays = (nerf_styles, (b, H, W, S, g.zc), g.xg, g.yg, g.zg, g.cam2world)
+                rays = (nerf_styles, ops.RayGeom(b, H, W, S, g.zc), g.xg, g.yg, g.zg, g.cam2world)
                 feat_c, sig_c, z_c = self.siren.evaluate_rays(*rays, jitter=g.jitter)
                 dirs = None
             else:
@@ -923,23 +954,20 @@ class GeneratorNerfINR(nn.Module):
                         dirs.reshape(b * m, 3) if dirs is not None else None, b, m, S, clamp, rays=rp)
                     fine_z = ops.fine_z_debug(drawn_z)
                     if fine_z is not drawn_z and g.form == "points":
-                        # pinned depths, materialised points: origin + direction * depth (generator_nerf_inr.py:537-598)
-                        fine_pts = (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * fine_z.view(b, m, S, 1)).reshape(b, m * S, 3).contiguous()
+                        fine_pts = along_rays(dirs, fine_z)        # pinned depths, materialised points
                 if g.form == "rays":
                     feat_f, sig_f, _ = self.siren.evaluate_rays(*rays, zvals=fine_z.view(b, m * S))
                 else:
                     if g.cam_grad and torch.is_grad_enabled():
-                        # origin + direction * depth outside no_grad: the depths are constants (as in the reference), the
-                        # origin and the directions carry the camera's graph
-                        fine_pts = (g.origin.view(b, 1, 1, 3) + dirs.reshape(b, m, 1, 3) * fine_z.view(b, m, S, 1)).reshape(b, m * S, 3)
+                        # again outside no_grad: the depths are constants (as in the reference), the origin and the
+                        # directions carry the camera's graph
+                        fine_pts = along_rays(dirs, fine_z)
                     feat_f, sig_f = self.siren.evaluate(fine_pts.view(b, m * S, 3), nerf_styles)
                 feat_f, sig_f = feat_f.view(b * m, S, 32), sig_f.view(b * m, S)
             out = (ops.CompositeGeoFunction if geo else ops.CompositeFunction).apply(
                 feat_c, sig_c, z_c, feat_f, sig_f, fine_z, noise_f.reshape(b * m, E) if s.nerf_noise != 0 else None,
                 s.nerf_noise, clamp, s.flags)
-            if geo:
-                return out[0].view(b, m, 32), out[1].view(b, m), out[2].view(b, m)
-            return out[0].view(b, m, 32), out[1].view(b, m)
+            return out[0].view(b, m, 32), out[1].view(b, m), out[2].view(b, m) if geo else None
 
     def _head(self, s, pixels_fea, style_dict, nerf_grad):
         """the tail of points_forward (generator.py:1747-1762) on features of any form: -> inr rgb (b,m,3), aux rgb or None.
@@ -962,10 +990,10 @@ class GeneratorNerfINR(nn.Module):
         rendered with gradients and a rest rendered under no_grad, each with its own noise draws; the two are scattered
         back (int64 bookkeeping of comm_utils.py:240-282) -> inr rgb (b,n,3), aux rgb or None"""
         (idx_grad, noise_grad), (idx_rest, noise_rest) = draw_part_randoms(s, g.b, device)
-        fea = self._nerf_features(s, g, nerf_styles, *noise_grad, self.nerf_grad, idx_grad)
+        fea, _, _ = self._nerf_stage(s, g, nerf_styles, *noise_grad, self.nerf_grad, idx_grad)
         inr_g, aux_g = self._head(s, fea, style_dict, self.nerf_grad)
         with torch.no_grad():
-            fea = self._nerf_features(s, g, nerf_styles, *noise_rest, False, idx_rest)
+            fea, _, _ = self._nerf_stage(s, g, nerf_styles, *noise_rest, False, idx_rest)
             inr_r, aux_r = self._head(s, fea, style_dict, False)
 
         def scatter(pg, pr):       # comm_utils.scatter_points: rows idx_grad <- pg (with grad), idx_rest <- pr
@@ -976,7 +1004,7 @@ class GeneratorNerfINR(nn.Module):
 
     def _render(self, style_dict, s, geo=False):
         """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path:
-        draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_features) -> head (_head), or
+        draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_stage) -> head (_head), or
         the last two per pixel subset (_part_grad).  -> imgs, pitch_yaw; with `geo` (render(): whole images in one shot)
         -> SimpleNamespace(imgs, depth, opacity, pitch_yaw), the same launches plus the opacity store of the NeRF path."""
         device = next(self.parameters()).device
@@ -995,7 +1023,7 @@ class GeneratorNerfINR(nn.Module):
         if s.part:
             inr_img, aux_img = self._part_grad(s, g, nerf_styles, style_dict, device)
         else:
-            fea, *maps = self._nerf_features_depth(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad, geo=geo)
+            fea, depth, opacity = self._nerf_stage(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad, geo=geo)
             inr_img, aux_img = self._head(s, fea, style_dict, self.nerf_grad)
         inr_img = inr_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
         inr_img = self.filters(inr_img)
@@ -1006,7 +1034,7 @@ class GeneratorNerfINR(nn.Module):
             imgs = inr_img.contiguous()
         if not geo:
             return imgs, pitch_yaw
-        depth, opacity = (t.view(b, 1, s.img_size, s.img_size) for t in maps[:2])
+        depth, opacity = (t.view(b, 1, s.img_size, s.img_size) for t in (depth, opacity))
         return SimpleNamespace(imgs=imgs, depth=depth, opacity=opacity, pitch_yaw=pitch_yaw)
 
     def forward(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
@@ -1014,12 +1042,7 @@ class GeneratorNerfINR(nn.Module):
                 clamp_mode='relu', nerf_noise=0., white_back=False, last_back=False, return_aux_img=False,
                 grad_points=None, forward_points=None, **kwargs):
         """generator.py:1256-1370.  Returns (imgs (b or 2b,3,H,W), pitch_yaw (b or 2b,2))."""
-        return self._forward_styles(zs, psi, RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
-            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
-            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
-            rand_override=kwargs.get('rand_override')))
+        return self._forward_styles(zs, psi, RenderSettings.of(locals(), rand_override=kwargs.get('rand_override')))
 
     def render(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, clamp_mode='relu', nerf_noise=0.,
@@ -1043,26 +1066,35 @@ class GeneratorNerfINR(nn.Module):
         opacity have no grad_fn there (imgs keeps the head's).  Whole images in one shot only, as in geometry(): the partial
         (grad_points) and staged (forward_points) forms are refused.  Any value but None is: unlike forward(), which takes
         grad_points >= n pixels as a whole-image render, render() refuses that too."""
+        self._whole_images_only('render', 'forward', grad_points, forward_points)
+        self._gpu_only('render')
+        return self._forward_styles(zs, psi, RenderSettings.of(locals()), geo=True)
+
+    def _whole_images_only(self, name, other, grad_points, forward_points):
+        """the refusal of render() / render_styles(): any value but None, unlike `other`, the entry point that takes them"""
         if grad_points is not None or forward_points is not None:
-            raise ValueError("GeneratorNerfINR.render renders whole images in one shot: grad_points / forward_points are not "
-                             "supported (use forward() for the partial and staged forms; they return no depth or opacity)")
-        if next(self.parameters()).device.type != 'cuda':
-            raise RuntimeError("GeneratorNerfINR.render runs on the GPU only (there is no CPU path)")
-        return self._forward_styles(zs, psi, RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
-            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
-            last_back=last_back, return_aux_img=return_aux_img, rand_override=rand_override, camera_pos=camera_pos,
-            camera_lookup=camera_lookup, up_vector=up_vector), geo=True)
+            raise ValueError(f"GeneratorNerfINR.{name} renders whole images in one shot: grad_points / forward_points are not "
+                             f"supported (use {other}() for the partial and staged forms; they return no depth or opacity)")
+
+    def _gpu_only(self, name):
+        """the refusal of the entry points that have no CPU path -> the parameters' device"""
+        device = next(self.parameters()).device
+        if device.type != 'cuda':
+            raise RuntimeError(f"GeneratorNerfINR.{name} runs on the GPU only (there is no CPU path)")
+        return device
+
+    def _truncate(self, style_dict, psi, avg_styles=None):
+        """styles -> the same, for psi < 1 lerped towards the average styles: avg_styles(), by default the average of 10 000
+        draws through both mapping networks (generate_avg_frequencies), made only then"""
+        if psi < 1:
+            avg = avg_styles() if avg_styles is not None else self.generate_avg_frequencies(device=self.device)
+            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg, raw_lambda=psi)
+        return style_dict
 
     def _forward_styles(self, zs, psi, s, geo=False):
         """the entry points' common path: latents -> styles (truncated towards the average for psi < 1) -> _render"""
-        style_dict = self.mapping_network(**zs, defer_join=not psi < 1)     # joined right before the INR head (_head)
-        if psi < 1:
-            avg_styles = self.generate_avg_frequencies(device=self.device)
-            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles,
-                                                       raw_lambda=psi)
-        return self._render_styles(style_dict, s, geo)
+        # (defer_join: joined right before the INR head, _head)
+        return self._render_styles(self._truncate(self.mapping_network(**zs, defer_join=not psi < 1), psi), s, geo)
 
     # ---- style-space entry points: what fitting, interpolation and per-layer mixing work on ----
     def _style_dims(self):
@@ -1084,11 +1116,7 @@ class GeneratorNerfINR(nn.Module):
         """zs -> {name: (b, dim)}: the dictionary forward(zs, psi=psi) renders from — both mapping networks, and for psi < 1
         the truncation towards the average of the same 10 000 draws.  Returned joined: the INR mapping network's side stream
         is not pending.  Under grad mode it is differentiable with respect to zs and the mapping networks."""
-        style_dict = self.mapping_network(**zs)
-        if psi < 1:
-            avg_styles = self.generate_avg_frequencies(device=self.device)
-            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg_styles, raw_lambda=psi)
-        return style_dict
+        return self._truncate(self.mapping_network(**zs), psi)
 
     def _check_styles(self, styles, what):
         """the style dictionary of a caller -> a dict in forward()'s order (the same tensors), or ValueError"""
@@ -1102,8 +1130,7 @@ class GeneratorNerfINR(nn.Module):
             t = styles[name]
             if t.dim() != 2 or t.shape[0] != b or t.shape[1] != dim:
                 raise ValueError(f"{what}: style {name!r} must be ({b if b is not None else 'b'}, {dim}), got {tuple(t.shape)}")
-        if next(self.parameters()).device.type != 'cuda':
-            raise RuntimeError(f"GeneratorNerfINR.{what} runs on the GPU only (there is no CPU path)")
+        self._gpu_only(what)
         return {name: styles[name] for name in dims}
 
     def _render_styles(self, style_dict, s, geo=False):
@@ -1132,13 +1159,8 @@ class GeneratorNerfINR(nn.Module):
         and psi; forward_styles(styles(zs, psi), ...) returns what forward(zs, psi=psi, ...) returns for the same seed, bit
         for bit, and the same parameter gradients.  Every key may be its own tensor, and a leaf: the gradient of an image loss
         reaches it (on the freeze variant only the INR-side keys, the NeRF path runs under no_grad there)."""
-        return self._render_styles(self._check_styles(styles, "forward_styles"), RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
-            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
-            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
-            rand_override=kwargs.get('rand_override'), camera_pos=camera_pos, camera_lookup=camera_lookup,
-            up_vector=up_vector))
+        return self._render_styles(self._check_styles(styles, "forward_styles"),
+                                   RenderSettings.of(locals(), rand_override=kwargs.get('rand_override')))
 
     def render_styles(self, styles, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                       h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, sample_dist=None, clamp_mode='relu', nerf_noise=0.,
@@ -1146,26 +1168,17 @@ class GeneratorNerfINR(nn.Module):
                       up_vector=None, rand_override=None, grad_points=None, forward_points=None):
         """render() from a style dictionary (forward_styles' `styles`): -> SimpleNamespace(imgs, depth, opacity, pitch_yaw),
         what render(zs, psi=psi, ...) returns for styles(zs, psi).  Whole images in one shot only, as render()."""
-        if grad_points is not None or forward_points is not None:
-            raise ValueError("GeneratorNerfINR.render_styles renders whole images in one shot: grad_points / forward_points "
-                             "are not supported (use forward_styles() for the partial and staged forms)")
-        return self._render_styles(self._check_styles(styles, "render_styles"), RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
-            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
-            last_back=last_back, return_aux_img=return_aux_img, rand_override=rand_override, camera_pos=camera_pos,
-            camera_lookup=camera_lookup, up_vector=up_vector), geo=True)
+        self._whole_images_only('render_styles', 'forward_styles', grad_points, forward_points)
+        return self._render_styles(self._check_styles(styles, "render_styles"), RenderSettings.of(locals()), geo=True)
 
     def _density_styles(self, z_nerf, psi):
         """z_nerf -> the NeRF styles of the density entry points: only the NeRF mapping network runs; for psi < 1 the styles are
         truncated towards the average of 10 000 draws as in forward() (the same draws from the RNG as
-        generate_avg_frequencies)"""
-        style_dict = self._map_nerf(z_nerf)
-        if psi < 1:
-            avg = self._map_nerf(self.get_zs(10000)['z_nerf'])
-            avg = {name: style.mean(0, keepdim=True) for name, style in avg.items()}
-            style_dict = self.get_truncated_freq_phase(raw_style_dict=style_dict, avg_style_dict=avg, raw_lambda=psi)
-        return style_dict
+        generate_avg_frequencies: get_zs draws both latents), an average of its own that leaves self.avg_styles alone"""
+        def avg_styles():
+            return {name: style.mean(0, keepdim=True) for name, style in self._map_nerf(self.get_zs(10000)['z_nerf']).items()}
+
+        return self._truncate(self._map_nerf(z_nerf), psi, avg_styles)
 
     @torch.no_grad()
     def density_gradient(self, zs, points, psi=1.0):
@@ -1190,31 +1203,26 @@ class GeneratorNerfINR(nn.Module):
         whole images in one shot (no grad_points / forward_points), which is all this entry point offers: every draw of a
         forward, the noise tensors included, is made before the NeRF path starts and nothing after it draws.  For psi < 1 the
         10 000 latents of the average styles are drawn as get_zs draws them (both z_nerf and z_inr), as in forward()."""
-        device = next(self.parameters()).device
-        if device.type != 'cuda':
-            raise RuntimeError("GeneratorNerfINR.geometry runs on the GPU only (there is no CPU path)")
-        s = RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample, sample_dist=sample_dist,
-            clamp_mode=clamp_mode, nerf_noise=0., white_back=white_back, last_back=last_back, rand_override=rand_override,
-            camera_pos=camera_pos, camera_lookup=camera_lookup, up_vector=up_vector)
-        style_dict = self.siren._sigma_args(self._density_styles(zs['z_nerf'], psi))
-        b, H = zs['z_nerf'].shape[0], img_size
-        d = draw_randoms(s, b, device)
-        origin, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
+        device = self._gpu_only('geometry')
+        s, b, H = RenderSettings.of(locals(), nerf_noise=0.), zs['z_nerf'].shape[0], img_size
+        nerf_styles, d, origin, cam2world, pitch_yaw = self._density_camera(s, zs, psi, device)
         g = self._ray_geometry(s, b, device, origin, cam2world, d.jitter)
-        nerf_styles = self._nerf_styles(style_dict)
-        depth = self._nerf_features_depth(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, False)[1]
+        _, depth, _ = self._nerf_stage(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, False)
         dirs = g.dirs if g.form == "points" else ops.rays_fwd(g.xg, g.yg, g.zg, g.zc, cam2world, g.jitter, b, H, H, s.num_steps)[2]
         points = origin.view(b, 1, 3) + dirs * depth.view(b, s.n, 1)
         sigma, grad = self.siren.density_gradient(points, nerf_styles)
-        norm = grad.norm(dim=-1, keepdim=True)
-        normals = torch.where(norm > 0, -grad / norm, torch.zeros_like(grad))
+        normals = _unit_normals(grad)
+        return SimpleNamespace(depth=_maps(depth, b, H), points=_maps(points, b, H), sigma=_maps(sigma, b, H),
+                               normals=_maps(normals, b, H), pitch_yaw=pitch_yaw)
 
-        def img(t):
-            return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
-
-        return SimpleNamespace(depth=img(depth), points=img(points), sigma=img(sigma), normals=img(normals), pitch_yaw=pitch_yaw)
+    def _density_camera(self, s, zs, psi, device):
+        """what geometry() and surface() start from, in the order forward() consumes the generator in: the NeRF styles of the
+        density entry points (for psi < 1 the 10 000 latents are drawn here, before the draws of the forward), then the draws
+        and the camera of settings s -> nerf_styles, draws, origin, cam2world, pitch_yaw"""
+        nerf_styles = self._nerf_styles(self.siren._sigma_args(self._density_styles(zs['z_nerf'], psi)))
+        b = zs['z_nerf'].shape[0]
+        d = draw_randoms(s, b, device)
+        return (nerf_styles, d) + camera_setup(s, d.theta, d.phi, b, device)
 
     @torch.no_grad()
     def surface(self, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean=math.pi * 0.5,
@@ -1236,32 +1244,15 @@ class GeneratorNerfINR(nn.Module):
         numbers: as geometry() — the draws and the camera are draw_randoms / camera_setup on the RenderSettings of a
         non-hierarchical forward() with nerf_noise = 0, so a seed gives the camera of the image it renders and the generators
         are left where forward() leaves them; the jitter is drawn and not used."""
-        device = next(self.parameters()).device
-        if device.type != 'cuda':
-            raise RuntimeError("GeneratorNerfINR.surface runs on the GPU only (there is no CPU path)")
-        s = RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=False, sample_dist=sample_dist, nerf_noise=0.,
-            rand_override=rand_override, camera_pos=camera_pos, camera_lookup=camera_lookup, up_vector=up_vector)
-        nerf_styles = self._nerf_styles(self.siren._sigma_args(self._density_styles(zs['z_nerf'], psi)))
-        b, H = zs['z_nerf'].shape[0], img_size
-        d = draw_randoms(s, b, device)
-        _, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
+        device = self._gpu_only('surface')
+        s, b, H = RenderSettings.of(locals(), hierarchical_sample=False, nerf_noise=0.), zs['z_nerf'].shape[0], img_size
+        nerf_styles, _, _, cam2world, pitch_yaw = self._density_camera(s, zs, psi, device)
         xg, yg, zg = ops.pixel_grids(H, H, num_steps, ray_start, ray_end, device)
-        zc = float((-torch.ones(1) / np.tan((2 * math.pi * fov / 360) / 2)).item())
-        depth, hit, sigma, points = self.siren.surface_rays(nerf_styles, (b, H, H, num_steps, zc), xg, yg, zg, cam2world, level,
-                                                            refine)
-        nrm = None
-        if normals:
-            grad = self.siren.density_gradient(points, nerf_styles)[1]
-            norm = grad.norm(dim=-1, keepdim=True)
-            nrm = torch.where((norm > 0) & (hit != 0).unsqueeze(-1), -grad / norm, torch.zeros_like(grad))
-
-        def img(t):
-            return t.reshape(b, H, H, -1).permute(0, 3, 1, 2).contiguous()
-
-        return SimpleNamespace(depth=img(depth), mask=img(hit), points=img(points), sigma=img(sigma),
-                               normals=img(nrm) if normals else None, pitch_yaw=pitch_yaw)
+        depth, hit, sigma, points = self.siren.surface_rays(nerf_styles, ops.RayGeom(b, H, H, num_steps, _zc(fov)), xg, yg, zg,
+                                                            cam2world, level, refine)
+        nrm = _unit_normals(self.siren.density_gradient(points, nerf_styles)[1], hit) if normals else None
+        return SimpleNamespace(depth=_maps(depth, b, H), mask=_maps(hit, b, H), points=_maps(points, b, H),
+                               sigma=_maps(sigma, b, H), normals=_maps(nrm, b, H) if normals else None, pitch_yaw=pitch_yaw)
 
     @torch.no_grad()
     def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, return_gradient=False):
@@ -1305,9 +1296,7 @@ class GeneratorNerfINR(nn.Module):
                 n = torch.zeros_like(vertices)
                 if vertices.shape[0]:
                     styles_b = {name: style[b:b + 1] for name, style in nerf_styles.items()}
-                    grad = self.siren.density_gradient(vertices.unsqueeze(0), styles_b)[1][0]
-                    norm = grad.norm(dim=-1, keepdim=True)
-                    n = torch.where(norm > 0, -grad / norm, torch.zeros_like(grad))
+                    n = _unit_normals(self.siren.density_gradient(vertices.unsqueeze(0), styles_b)[1][0])
             meshes.append(SimpleNamespace(vertices=vertices, faces=faces, normals=n))
         return meshes
 
@@ -1317,13 +1306,7 @@ class GeneratorNerfINR(nn.Module):
                                       nerf_noise=0., white_back=False, last_back=False, return_aux_img=False,
                                       grad_points=None, forward_points=None, up_vector=None, **kwargs):
         """generator.py:1828-1951 (explicit camera; pitch/yaw are zeros)."""
-        return self._forward_styles(zs, psi, RenderSettings(
-            img_size=img_size, fov=fov, ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, h_stddev=h_stddev,
-            v_stddev=v_stddev, h_mean=h_mean, v_mean=v_mean, hierarchical_sample=hierarchical_sample,
-            sample_dist=sample_dist, clamp_mode=clamp_mode, nerf_noise=nerf_noise, white_back=white_back,
-            last_back=last_back, return_aux_img=return_aux_img, grad_points=grad_points, forward_points=forward_points,
-            rand_override=kwargs.get('rand_override'), camera_pos=camera_pos, camera_lookup=camera_lookup,
-            up_vector=up_vector))
+        return self._forward_styles(zs, psi, RenderSettings.of(locals(), rand_override=kwargs.get('rand_override')))
 
 
 class GeneratorNerfINR_freeze_NeRF(GeneratorNerfINR):

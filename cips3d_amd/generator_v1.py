@@ -9,7 +9,7 @@ keys, the reference's initialisation draw order) and three overrides:
 
   _map_inr       the INR mapping network followed by nerf_rgb_mapping on the grouped-linear kernel: both run on the INR
                  mapping side stream, their backward next to the NeRF path's;
-  _nerf_styles   _render calls it ahead of its NeRF stage (_nerf_features): the caller's stream joins that side stream before
+  _nerf_styles   _render calls it ahead of its NeRF stage (_nerf_stage): the caller's stream joins that side stream before
                  the first SIREN launch, whose colour FiLM reads nerf_rgb (v0 joins in _head, right before the INR head;
                  DESIGN.md §3, "generator_v1");
   forward_camera_pos_and_lookup   takes no up_vector (generator_v1.py:1845): the keyword lands in **kwargs and is ignored,

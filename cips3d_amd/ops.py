@@ -9,6 +9,7 @@ import ctypes as C
 import math
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -83,6 +84,15 @@ def pixel_grids(W, H, S, ray_start, ray_end, device):
             _GRIDS.clear()
         _GRIDS[key] = g
     return g
+
+
+# The `geom` of the Functions and functions that generate rays in-kernel, and the longer one of RayMarchFunction /
+# RayMarchGeoFunction (a plain tuple in this order is taken too).  grad_mode: the caller's torch.is_grad_enabled(), inside a
+# Function's forward it is always off; live_fwd: the caller joins the list stream (live_forward_join) whether or not a
+# backward follows.
+RayGeom = namedtuple("RayGeom", "B H W S zc")
+MarchGeom = namedtuple("MarchGeom", RayGeom._fields + ("noise_std", "clamp_mode", "flags", "grad_mode", "live_fwd"), defaults=(False,))
+
 
 def rays_fwd(xg, yg, zg, zc, cam2world, jitter, B, H, W, S):
     """-> points (B,n,S,3), z (B,n,S), dirs (B,n,3); see cips_rays_fwd."""
@@ -254,16 +264,40 @@ def _siren_sigma_f32(t, points):
     return sigma
 
 
+def lattice_points(gx, gy, gz, B):
+    """the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors as points (B, nx * ny * nz, 3), x slowest: what the
+    lattice kernels never build, for the paths that have no such kernel.  An expanded view over the batch."""
+    n = (gx.numel(), gy.numel(), gz.numel())
+    pts = torch.stack([gx.view(-1, 1, 1).expand(n), gy.view(1, -1, 1).expand(n), gz.view(1, 1, -1).expand(n)], -1)
+    return pts.reshape(1, -1, 3).expand(B, -1, 3)
+
+
+def _sigma_prep(points, siren):
+    """the inputs of the points forms of the sigma family, detached, contiguous and checked -> t, points, (B, P)"""
+    t = _siren_prep(siren)
+    points = _c(points.detach())
+    _chk(points)
+    return t, points, points.shape[:2]
+
+
+def _sigma_grid_prep(who, gx, gy, gz, siren):
+    """... of the lattice forms -> t, (gx, gy, gz), GridParams over them, (B, nx, ny, nz)"""
+    t = _siren_prep(siren)
+    gx, gy, gz = (_c(v.detach()) for v in (gx, gy, gz))
+    _chk(gx, gy, gz)
+    if gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
+        raise ValueError(f"{who} takes three 1-D coordinate tensors")
+    nx, ny, nz = gx.numel(), gy.numel(), gz.numel()
+    return t, (gx, gy, gz), GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz), (t["g0"].shape[0], nx, ny, nz)
+
+
 def siren_sigma(points, *siren):
     """sigma (B,P) of SirenFunction at points (B,P,3) without the colour branch (cips_siren_sigma_x3: 4 B per point written
     instead of 132, bit for bit the forward kernel's sigma).  A plain function: inputs are detached, no gradient flows.  With
     SIREN_FWD_MODE "f32" the exact-fp32 forward runs and its sigma is returned."""
-    t = _siren_prep(siren)
-    points = _c(points.detach())
-    _chk(points)
+    t, points, (B, P) = _sigma_prep(points, siren)
     if SIREN_FWD_MODE != "x3":
         return _siren_sigma_f32(t, points)
-    B, P, _ = points.shape
     sigma = torch.empty(B, P, device=points.device)
     sw = _siren_struct(t)
     check(_lib.load().cips_siren_sigma_x3(C.byref(sw), _p(points), _p(sigma), B, P, _stream()), "cips_siren_sigma_x3")
@@ -274,21 +308,13 @@ def siren_sigma_grid(gx, gy, gz, *siren):
     """sigma (B, nx, ny, nz) over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors (cips_siren_sigma_x3_grid:
     the kernel reads the coordinates and computes none, no (B,P,3) tensor exists).  Same value as siren_sigma on the
     materialised points, bit for bit.  With SIREN_FWD_MODE "f32" the points are materialised for the exact-fp32 forward."""
-    t = _siren_prep(siren)
-    gx, gy, gz = (_c(v.detach()) for v in (gx, gy, gz))
-    _chk(gx, gy, gz)
-    if gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
-        raise ValueError("siren_sigma_grid takes three 1-D coordinate tensors")
-    B = t["g0"].shape[0]
-    nx, ny, nz = gx.numel(), gy.numel(), gz.numel()
+    t, (gx, gy, gz), gp, shape = _sigma_grid_prep("siren_sigma_grid", gx, gy, gz, siren)
     if SIREN_FWD_MODE != "x3":
-        pts = torch.stack([gx.view(nx, 1, 1).expand(nx, ny, nz), gy.view(1, ny, 1).expand(nx, ny, nz),
-                           gz.view(1, 1, nz).expand(nx, ny, nz)], -1).reshape(1, -1, 3).expand(B, -1, 3)
-        return _siren_sigma_f32(t, pts.contiguous()).view(B, nx, ny, nz)
-    sigma = torch.empty(B, nx, ny, nz, device=gx.device)
+        return _siren_sigma_f32(t, lattice_points(gx, gy, gz, shape[0]).contiguous()).view(shape)
+    sigma = torch.empty(shape, device=gx.device)
     sw = _siren_struct(t)
-    gp = GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz)
-    check(_lib.load().cips_siren_sigma_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), B, _stream()), "cips_siren_sigma_x3_grid")
+    check(_lib.load().cips_siren_sigma_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), shape[0], _stream()),
+          "cips_siren_sigma_x3_grid")
     return sigma
 
 
@@ -302,11 +328,8 @@ def siren_sigma_grad(points, *siren):
     """sigma (B,P) and its gradient w.r.t. the points, grad (B,P,3), at points (B,P,3) (cips_siren_sigma_grad_x3).  sigma is
     siren_sigma's bit for bit.  A plain function: inputs are detached, the outputs carry no grad_fn.  With SIREN_FWD_MODE
     other than "x3" it raises: the exact-fp32 forward has no gradient kernel."""
-    t = _siren_prep(siren)
-    points = _c(points.detach())
-    _chk(points)
+    t, points, (B, P) = _sigma_prep(points, siren)
     _need_x3_sigma_grad()
-    B, P, _ = points.shape
     sigma = torch.empty(B, P, device=points.device)
     grad = torch.empty(B, P, 3, device=points.device)
     sw = _siren_struct(t)
@@ -318,19 +341,12 @@ def siren_sigma_grad(points, *siren):
 def siren_sigma_grad_grid(gx, gy, gz, *siren):
     """siren_sigma_grad over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> sigma (B, nx, ny, nz),
     grad (B, nx, ny, nz, 3) (cips_siren_sigma_grad_x3_grid: no points tensor exists).  The points form's values bit for bit."""
-    t = _siren_prep(siren)
-    gx, gy, gz = (_c(v.detach()) for v in (gx, gy, gz))
-    _chk(gx, gy, gz)
-    if gx.dim() != 1 or gy.dim() != 1 or gz.dim() != 1:
-        raise ValueError("siren_sigma_grad_grid takes three 1-D coordinate tensors")
+    t, (gx, gy, gz), gp, shape = _sigma_grid_prep("siren_sigma_grad_grid", gx, gy, gz, siren)
     _need_x3_sigma_grad()
-    B = t["g0"].shape[0]
-    nx, ny, nz = gx.numel(), gy.numel(), gz.numel()
-    sigma = torch.empty(B, nx, ny, nz, device=gx.device)
-    grad = torch.empty(B, nx, ny, nz, 3, device=gx.device)
+    sigma = torch.empty(shape, device=gx.device)
+    grad = torch.empty(*shape, 3, device=gx.device)
     sw = _siren_struct(t)
-    gp = GridParams(_p(gx), _p(gy), _p(gz), nx, ny, nz)
-    check(_lib.load().cips_siren_sigma_grad_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), _p(grad), B, _stream()),
+    check(_lib.load().cips_siren_sigma_grad_x3_grid(C.byref(sw), C.byref(gp), _p(sigma), _p(grad), shape[0], _stream()),
           "cips_siren_sigma_grad_x3_grid")
     return sigma, grad
 
@@ -348,7 +364,7 @@ def siren_surface(level, refine, geom, xg, yg, zg, cam2world, *siren, trace=Fals
     if SIREN_FWD_MODE != "x3":
         raise RuntimeError(f"the surface ray-cast kernel runs on the split-operand SIREN chain only (CIPS_SIREN_FWD="
                            f"{SIREN_FWD_MODE!r}): use siren_surface_composed")
-    B, H, W, S, zc = geom
+    B, H, W, S, zc = RayGeom(*geom)
     if not 0 <= int(refine) <= 32:
         raise ValueError("siren_surface: refine must be in 0..32")
     n, dev = H * W, cam2world.device
@@ -371,7 +387,7 @@ def siren_surface_composed(level, refine, geom, xg, yg, zg, cam2world, *siren, s
     (B, P) is siren_sigma on `siren` unless given (NeRFNetwork.surface_rays hands in the tensor-operation SIREN of other
     widths).  The path of SIREN_FWD_MODE "f32" and the baseline of scripts/bench_surface.py; the same rule as the kernel, not
     its roundings (the points are origin + direction * t in torch's arithmetic)."""
-    B, H, W, S, zc = geom
+    B, H, W, S, zc = RayGeom(*geom)
     xg, yg, zg, cam2world, _, _ = _ray_prep(xg, yg, zg, cam2world, None, None)
     if sigma_fn is None:
         def sigma_fn(p):
@@ -1031,7 +1047,7 @@ class SirenRaysFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, geom, xg, yg, zg, cam2world, jitter, zvals, *siren):
         lib = _lib.load()
-        B, H, W, S, zc = geom
+        B, H, W, S, zc = geom = RayGeom(*geom)
         t = _siren_prep(siren)
         xg, yg, zg, cam2world, jitter, zvals = _ray_prep(xg, yg, zg, cam2world, jitter, zvals)
         dev = cam2world.device
@@ -1110,15 +1126,15 @@ class RayMarchGeoFunction(torch.autograd.Function):
         if dfea is None and ddepth is None and dopacity is None:
             return (None,) * (7 + len(_SIREN_NAMES))
         feat = ctx.saved_tensors[6]
-        B, H, W = ctx.geom[:3]
-        return _march_backward(ctx, *_geo_upstream(dfea, ddepth, dopacity, (B, H * W, 32), feat.device))
+        g = ctx.geom
+        return _march_backward(ctx, *_geo_upstream(dfea, ddepth, dopacity, (g.B, g.H * g.W, 32), feat.device))
 
 
 def _march_forward(ctx, geo, geom, xg, yg, zg, cam2world, jitter, noise, *siren):
     """the forward of RayMarchFunction (geo False) and RayMarchGeoFunction (True: also the opacity output)
     -> fea, depth, opacity or None"""
     lib = _lib.load()
-    B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode = geom[:9]
+    B, H, W, S, zc, noise_std, clamp_mode, flags, grad_mode, live_fwd = geom = MarchGeom(*geom)
     t = _siren_prep(siren)
     xg, yg, zg, cam2world, jitter, noise = _ray_prep(xg, yg, zg, cam2world, jitter, noise if noise_std != 0.0 else None)
     dev = cam2world.device
@@ -1144,8 +1160,7 @@ def _march_forward(ctx, geo, geom, xg, yg, zg, cam2world, jitter, noise, *siren)
     if rec is not None and CLAMP_REC is not None:
         CLAMP_REC.append(rec.reshape(B * n, S))
     ctx.clamp_mask = pin
-    # a tenth entry of geom, true: the caller joins the list stream (live_forward_join) whether or not a backward follows
-    ctx.live_fwd = train and len(geom) > 9 and bool(geom[9]) and live_forward_ok(clamp_mode, pin)
+    ctx.live_fwd = train and bool(live_fwd) and live_forward_ok(clamp_mode, pin)
     if train:
         lists = live_plan_forward(sigma, noise, noise_std, B, n, S, clamp_mode, flags) if ctx.live_fwd else ()
         ctx.save_for_backward(xg, yg, zg, cam2world, jitter, noise, feat, sigma, z, *t.values(), *lists)
@@ -1158,7 +1173,7 @@ def _march_backward(ctx, dfea, ddepth=None, dopacity=None):
     -> the gradients of the Functions' inputs (geom, xg, yg, zg, cam2world, jitter, noise, *siren)"""
     xg, yg, zg, cam2world, jitter, noise, feat, sigma, z = ctx.saved_tensors[:9]
     t = dict(zip(_SIREN_NAMES, ctx.saved_tensors[9:9 + len(_SIREN_NAMES)]))
-    B, H, W, S, zc, noise_std, clamp_mode, flags, _ = ctx.geom[:9]
+    B, H, W, S, zc, noise_std, clamp_mode, flags, _, _ = ctx.geom
     n = H * W
     R = B * n
     want_cam = ctx.needs_input_grad[4]

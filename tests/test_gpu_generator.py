@@ -505,7 +505,7 @@ def test_weight_gradient_tail_on_the_side_stream_gives_the_same_gradients(tag):
             torch.cuda.synchronize()
             # (a frozen NeRF has no backward to run beside: the generator keeps the plain form there)
             assert (len(calls) - n0 == 1) == (mode == "side" and not fix["freeze"])
-            # opened by _render ahead of its NeRF stage (_nerf_features), the ports ran behind the compositing backward and waited for its event
+            # opened by _render ahead of its NeRF stage (_nerf_stage), the ports ran behind the compositing backward and waited for its event
             assert all(ports.waited for ports in calls[n0:])
             assert not ops._TAIL_GATE
             out.setdefault(mode, []).append((imgs.detach().clone(), {n: p.grad.clone() for n, p in G.named_parameters() if p.grad is not None}))
