@@ -56,134 +56,6 @@ __global__ __launch_bounds__(256) void modfc_prep_kernel(const float* __restrict
   }
 }
 
-// bf16x3 operand planes of Wb [in][out] and Wbt [out][in] (hi/lo each), in two launches:
-//   (1) demod[b][n] = rsqrt(sum_k (W[k][n] (s[b][k]+1))^2 + eps)          grid (out/32, B)
-//   (2) 32x32 tiles of v = W (s+1) demod, split to hi/lo, written row-major and (through LDS) transposed,
-//       both with coalesced accesses                                            grid (out/32, in/32, B)
-__global__ __launch_bounds__(256) void modfc_demod_kernel(const float* __restrict__ W, const float* __restrict__ s,
-                                                          float* __restrict__ demod, int in_dim, int out_dim, float eps) {
-  __shared__ float red[8][33];
-  const int b = blockIdx.y;
-  const int c = threadIdx.x & 31, kg = threadIdx.x >> 5;
-  const int n = blockIdx.x * 32 + c;
-  const float* sb = s + (long long)b * in_dim;
-  float q = 0.f;
-  if (n < out_dim)
-    for (int k = kg; k < in_dim; k += 8) {
-      float u = W[(long long)k * out_dim + n] * (sb[k] + 1.f);
-      q = fmaf(u, u, q);
-    }
-  red[kg][c] = q;
-  __syncthreads();
-  if (kg == 0 && n < out_dim) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) t += red[g][c];
-    demod[(long long)b * out_dim + n] = rsqrtf(t + eps);
-  }
-}
-__global__ __launch_bounds__(256) void modfc_planes_kernel(const float* __restrict__ W, const float* __restrict__ s,
-                                                           const float* __restrict__ demod,
-                                                           unsigned short* __restrict__ wbh, unsigned short* __restrict__ wbl,
-                                                           unsigned short* __restrict__ wth, unsigned short* __restrict__ wtl,
-                                                           int in_dim, int out_dim) {
-  __shared__ unsigned short th[32][33], tl[32][33];
-  const int b = blockIdx.z;
-  const int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const long long base = (long long)b * in_dim * out_dim;
-  for (int kk = ty; kk < 32; kk += 8) {
-    const int k = k0 + kk, n = n0 + tx;
-    unsigned short h = 0, l = 0;
-    if (k < in_dim && n < out_dim) {
-      const float v = W[(long long)k * out_dim + n] * (s[(long long)b * in_dim + k] + 1.f) * demod[(long long)b * out_dim + n];
-      h = f2bf(v);
-      l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
-      wbh[base + (long long)k * out_dim + n] = h;
-      wbl[base + (long long)k * out_dim + n] = l;
-    }
-    th[kk][tx] = h; tl[kk][tx] = l;
-  }
-  __syncthreads();
-  for (int nn = ty; nn < 32; nn += 8) {
-    const int n = n0 + nn, k = k0 + tx;
-    if (k < in_dim && n < out_dim) {
-      wth[base + (long long)n * in_dim + k] = th[tx][nn];
-      wtl[base + (long long)n * in_dim + k] = tl[tx][nn];
-    }
-  }
-}
-
-// ---- prep backward -------------------------------------------------------------------
-// u = W*(s+1), q_n = sum_k u^2 + eps, d = q^-1/2, Wb = u*d.  With G = dL/dWb:
-//   c_n  = sum_k G_kn u_kn
-//   du   = d_n * (G_kn - d_n^2 u_kn c_n)
-//   dW_kn = sum_b (s_bk+1) du_bkn ;  ds_bk = sum_n W_kn du_bkn
-__global__ __launch_bounds__(256) void modfc_prep_bwd_c_kernel(const float* __restrict__ W, const float* __restrict__ s,
-                                                               const float* __restrict__ G, float* __restrict__ cbuf,
-                                                               int in_dim, int out_dim) {
-  __shared__ float red[8][33];
-  const int b = blockIdx.y;
-  const int c = threadIdx.x & 31, kg = threadIdx.x >> 5;
-  const int n = blockIdx.x * 32 + c;
-  const float* sb = s + (long long)b * in_dim;
-  const float* Gb = G + (long long)b * in_dim * out_dim;
-  float q = 0.f;
-  if (n < out_dim)
-    for (int k = kg; k < in_dim; k += 8)
-      q = fmaf(Gb[(long long)k * out_dim + n], W[(long long)k * out_dim + n] * (sb[k] + 1.f), q);
-  red[kg][c] = q;
-  __syncthreads();
-  if (kg == 0 && n < out_dim) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) t += red[g][c];
-    cbuf[(long long)b * out_dim + n] = t;
-  }
-}
-
-__global__ __launch_bounds__(256) void modfc_prep_bwd_w_kernel(const float* __restrict__ W, const float* __restrict__ s,
-                                                               const float* __restrict__ demod, const float* __restrict__ G,
-                                                               const float* __restrict__ cbuf, float* __restrict__ dW,
-                                                               int B, int in_dim, int out_dim) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long long)in_dim * out_dim) return;
-  const int k = (int)(idx / out_dim), n = (int)(idx % out_dim);
-  const float w = W[idx];
-  float acc = 0.f;
-  for (int b = 0; b < B; ++b) {   // fixed order: deterministic
-    const float m = s[(long long)b * in_dim + k] + 1.f;
-    const float d = demod[(long long)b * out_dim + n];
-    const float g = G[((long long)b * in_dim + k) * out_dim + n];
-    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
-    acc = fmaf(m, du, acc);
-  }
-  dW[idx] = acc;
-}
-
-// one wave per (b, k): lanes stride over n
-__global__ __launch_bounds__(256) void modfc_prep_bwd_s_kernel(const float* __restrict__ W, const float* __restrict__ s,
-                                                               const float* __restrict__ demod, const float* __restrict__ G,
-                                                               const float* __restrict__ cbuf, float* __restrict__ ds,
-                                                               int B, int in_dim, int out_dim) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)B * in_dim) return;
-  const int b = (int)(row / in_dim), k = (int)(row % in_dim);
-  const float m = s[row] + 1.f;
-  float acc = 0.f;
-  for (int n = lane; n < out_dim; n += 64) {
-    const float w = W[(long long)k * out_dim + n];
-    const float d = demod[(long long)b * out_dim + n];
-    const float g = G[row * out_dim + n];
-    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
-    acc = fmaf(w, du, acc);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  if (lane == 0) ds[row] = acc;
-}
-
 // ---- ToRGB --------------------------------------------------------------------------
 // load 4 consecutive activations either from fp32 or from bf16 hi/lo planes
 template <bool X3>
@@ -373,7 +245,6 @@ __global__ __launch_bounds__(256) void torgb_bwd_w_partial_kernel(const void* __
   const long long m1 = (m0 + TORGB_ROWS < M) ? m0 + TORGB_ROWS : M;
   float* out = partial + (long long)blockIdx.x * 4 * K;
   const int nk4 = K / 4;                       // float4 columns
-  const int groups = 256 / (nk4 < 256 ? nk4 : 256) > 0 ? 256 / (nk4 < 256 ? nk4 : 256) : 1;
   for (int kb = 0; kb < nk4; kb += 256) {
     const int cols = (nk4 - kb) < 256 ? (nk4 - kb) : 256;     // float4 columns handled this pass
     const int grp = 256 / cols;                               // row-interleave groups
@@ -409,7 +280,6 @@ __global__ __launch_bounds__(256) void torgb_bwd_w_partial_kernel(const void* __
     }
     __syncthreads();
   }
-  (void)groups;
   if (threadIdx.x < 3) {
     float sacc = 0.f;
     for (long long m = m0; m < m1; ++m) sacc += drgb[m * 3 + threadIdx.x];
@@ -475,7 +345,7 @@ __global__ __launch_bounds__(256) void torgb_bwd_x_kernel(const float* __restric
 
 // Split-plane form of the same: P (hi, lo planes) = (drgb @ w) * (gate bit ? 1 : slope), gate as a BIT plane (bit k&7 of byte
 // [m][k>>3]; NULL: no gate), optional fp32 copy before gating.  One lane = 8 consecutive columns: 3 scalars of drgb, one gate
-// byte, two 16-byte stores — a pure 4-bytes-per-element write stream (the round-2 path ran this rank-3 product as a K = 32
+// byte, two 16-byte stores — a pure 4-bytes-per-element write stream (the GEMM path ran this rank-3 product as a K = 32
 // zero-padded bf16x3 GEMM: 138 us + two padding kernels for 268 MB of output at C2; the sums here are exact fp32).
 __global__ __launch_bounds__(256) void torgb_bwd_x_x3_kernel(const float* __restrict__ drgb, const float* __restrict__ w,
                                                              const unsigned char* __restrict__ gate, float slope,
@@ -522,30 +392,60 @@ __global__ __launch_bounds__(256) void torgb_bwd_x_x3_kernel(const float* __rest
 }
 
 
-// ---- batched forms: every modulated-FC layer of the CIPS head in ONE launch --------------------------------
-// The per-layer kernels above are a few microseconds of work each; 18 layers x (2 + 3) launches per step cost more
-// in launch tails and idle CUs than in arithmetic.  The weights and styles of all layers are known before the
-// head's forward starts, and every dL/dWb is known once its backward is through, so both directions batch.
+// ---- split-plane prep and its backward: job tables, every modulated-FC layer of the CIPS head in ONE launch ---
+// One layer is a few microseconds of work; 18 layers x (2 + 3) launches per step cost more in launch tails and idle
+// CUs than in arithmetic.  The weights and styles of all layers are known before the head's forward starts, and
+// every dL/dWb is known once its backward is through, so both directions run on tables of up to MAXJOBS layers
+// (a block finds its layer in blockIdx, the grid covers the largest one).  Forward, bf16x3 operand planes of
+// Wb [in][out] and Wbt [out][in] (hi/lo each) in two launches:
+//   (1) demod[b][n] = rsqrt(sum_k (W[k][n] (s[b][k]+1))^2 + eps)
+//   (2) tiles of v = W (s+1) demod, split to hi/lo, written row-major and (through LDS) transposed, both coalesced
+// Backward: u = W*(s+1), q_n = sum_k u^2 + eps, d = q^-1/2, Wb = u*d.  With G = dL/dWb:
+//   c_n  = sum_k G_kn u_kn
+//   du   = d_n * (G_kn - d_n^2 u_kn c_n)
+//   dW_kn = sum_b (s_bk+1) du_bkn ;  ds_bk = sum_n W_kn du_bkn
+// The forms, and the rule that selects them (the entry points at the end of the file):
+//   scalar batch   32-column reductions, 32 x 32 plane tiles, one pass each for c, dW and ds: every shape.
+//   16-byte batch  4 columns per lane; dW and ds in ONE pass.  Column sums and planes each when every job's shape
+//                  allows (out_dim % 4 == 0; planes also in_dim % 8 == 0), the fused pass for B <= 64, out_dim <= 1024.
+//   co-resident    no LDS, <= 40 VGPRs, for the side stream beside the fused SIREN backward: asked for by entry point.
+//   single-job     cips_modfc_prep_x3 / cips_modfc_prep_bwd: a one-job table on the scalar batch kernels, whatever
+//                  the shape — their bits do not depend on what a batch of layers would have selected.
 constexpr int MAXJOBS = 24;
 struct PrepJobs {
   const float* W[MAXJOBS]; const float* s[MAXJOBS]; float* demod[MAXJOBS];
   unsigned short *wbh[MAXJOBS], *wbl[MAXJOBS], *wth[MAXJOBS], *wtl[MAXJOBS];
   int in_dim[MAXJOBS], out_dim[MAXJOBS];
 };
-__global__ __launch_bounds__(256) void modfc_demod_batch_kernel(PrepJobs J, int B, float eps) {
+struct ColJobs {                       // the column reductions of both directions: G == nullptr selects the demodulation sums
+  const float* W[MAXJOBS]; const float* s[MAXJOBS]; const float* G[MAXJOBS]; float* out[MAXJOBS];
+  int in_dim[MAXJOBS], out_dim[MAXJOBS];
+};
+struct BwdJobs {
+  const float* W[MAXJOBS]; const float* s[MAXJOBS]; const float* demod[MAXJOBS]; const float* G[MAXJOBS];
+  float *cbuf[MAXJOBS], *dW[MAXJOBS], *ds[MAXJOBS];
+  int in_dim[MAXJOBS], out_dim[MAXJOBS];
+};
+
+// ---- scalar batch forms ---------------------------------------------------------------------------------------
+// out[b][n] = WITH_G ? c_n = sum_k G_kn u_kn : demod = rsqrt(sum_k u_kn^2 + eps);  grid (out/32, B, jobs),
+// 256 threads = 32 columns x 8 k-groups, combined in group order through LDS
+template <bool WITH_G>
+__global__ __launch_bounds__(256) void modfc_colsum_batch_kernel(ColJobs J, float eps) {
   __shared__ float red[8][33];
   const int job = blockIdx.z, b = blockIdx.y;
   const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
   if (blockIdx.x * 32 >= out_dim) return;
   const float* __restrict__ W = J.W[job];
   const float* __restrict__ sb = J.s[job] + (long long)b * in_dim;
+  const float* __restrict__ Gb = WITH_G ? J.G[job] + (long long)b * in_dim * out_dim : nullptr;
   const int c = threadIdx.x & 31, kg = threadIdx.x >> 5;
   const int n = blockIdx.x * 32 + c;
   float q = 0.f;
   if (n < out_dim)
     for (int k = kg; k < in_dim; k += 8) {
-      float u = W[(long long)k * out_dim + n] * (sb[k] + 1.f);
-      q = fmaf(u, u, q);
+      const float u = W[(long long)k * out_dim + n] * (sb[k] + 1.f);
+      q = WITH_G ? fmaf(Gb[(long long)k * out_dim + n], u, q) : fmaf(u, u, q);
     }
   red[kg][c] = q;
   __syncthreads();
@@ -553,9 +453,10 @@ __global__ __launch_bounds__(256) void modfc_demod_batch_kernel(PrepJobs J, int 
     float t = 0.f;
 #pragma unroll
     for (int g = 0; g < 8; ++g) t += red[g][c];
-    J.demod[job][(long long)b * out_dim + n] = rsqrtf(t + eps);
+    J.out[job][(long long)b * out_dim + n] = WITH_G ? t : rsqrtf(t + eps);
   }
 }
+// 32 x 32 tiles of the planes; grid (out/32, in/32, B * jobs)
 __global__ __launch_bounds__(256) void modfc_planes_batch_kernel(PrepJobs J, int B) {
   __shared__ unsigned short th[32][33], tl[32][33];
   const int job = blockIdx.z / B, b = blockIdx.z % B;
@@ -590,7 +491,52 @@ __global__ __launch_bounds__(256) void modfc_planes_batch_kernel(PrepJobs J, int
   }
 }
 
-// The same planes in 64 x 64 tiles: float4 reads of W along n, 8-byte plane stores along n straight from registers,
+// dW and ds, one pass over G each; grids (in*out/256, jobs) and (B*in/4, jobs): one wave per (b, k), lanes stride over n
+__global__ __launch_bounds__(256) void modfc_prep_bwd_w_batch_kernel(BwdJobs J, int B) {
+  const int job = blockIdx.y;
+  const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)in_dim * out_dim) return;
+  const float* __restrict__ s = J.s[job]; const float* __restrict__ demod = J.demod[job];
+  const float* __restrict__ G = J.G[job]; const float* __restrict__ cbuf = J.cbuf[job];
+  const int k = (int)(idx / out_dim), n = (int)(idx % out_dim);
+  const float w = J.W[job][idx];
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {   // fixed order: deterministic
+    const float m = s[(long long)b * in_dim + k] + 1.f;
+    const float d = demod[(long long)b * out_dim + n];
+    const float g = G[((long long)b * in_dim + k) * out_dim + n];
+    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
+    acc = fmaf(m, du, acc);
+  }
+  J.dW[job][idx] = acc;
+}
+__global__ __launch_bounds__(256) void modfc_prep_bwd_s_batch_kernel(BwdJobs J, int B) {
+  const int job = blockIdx.y;
+  const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long long)B * in_dim) return;
+  const float* __restrict__ W = J.W[job]; const float* __restrict__ demod = J.demod[job];
+  const float* __restrict__ G = J.G[job]; const float* __restrict__ cbuf = J.cbuf[job];
+  const int b = (int)(row / in_dim), k = (int)(row % in_dim);
+  const float m = J.s[job][row] + 1.f;
+  float acc = 0.f;
+  for (int n = lane; n < out_dim; n += 64) {
+    const float w = W[(long long)k * out_dim + n];
+    const float d = demod[(long long)b * out_dim + n];
+    const float g = G[row * out_dim + n];
+    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
+    acc = fmaf(w, du, acc);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+  if (lane == 0) J.ds[job][row] = acc;
+}
+
+
+// ---- 16-byte batch forms: the column reductions, the planes and the fused dW / ds pass ----------------------------
+// The planes in 64 x 64 tiles: float4 reads of W along n, 8-byte plane stores along n straight from registers,
 // 16-byte stores of the transposed planes along k through LDS (the 32 x 32 form above writes 64-byte segments of 2-byte
 // elements: 3.4 TB/s on the 1.2 GB of per-sample weight planes of a C2 step).  Needs out_dim % 4 == 0, in_dim % 8 == 0.
 __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, int B) {
@@ -647,85 +593,11 @@ __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, i
   }
 }
 
-struct BwdJobs {
-  const float* W[MAXJOBS]; const float* s[MAXJOBS]; const float* demod[MAXJOBS]; const float* G[MAXJOBS];
-  float *cbuf[MAXJOBS], *dW[MAXJOBS], *ds[MAXJOBS];
-  int in_dim[MAXJOBS], out_dim[MAXJOBS];
-};
-__global__ __launch_bounds__(256) void modfc_prep_bwd_c_batch_kernel(BwdJobs J) {
-  __shared__ float red[8][33];
-  const int job = blockIdx.z, b = blockIdx.y;
-  const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
-  if (blockIdx.x * 32 >= out_dim) return;
-  const float* __restrict__ W = J.W[job];
-  const float* __restrict__ sb = J.s[job] + (long long)b * in_dim;
-  const float* __restrict__ Gb = J.G[job] + (long long)b * in_dim * out_dim;
-  const int c = threadIdx.x & 31, kg = threadIdx.x >> 5;
-  const int n = blockIdx.x * 32 + c;
-  float q = 0.f;
-  if (n < out_dim)
-    for (int k = kg; k < in_dim; k += 8)
-      q = fmaf(Gb[(long long)k * out_dim + n], W[(long long)k * out_dim + n] * (sb[k] + 1.f), q);
-  red[kg][c] = q;
-  __syncthreads();
-  if (kg == 0 && n < out_dim) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) t += red[g][c];
-    J.cbuf[job][(long long)b * out_dim + n] = t;
-  }
-}
-__global__ __launch_bounds__(256) void modfc_prep_bwd_w_batch_kernel(BwdJobs J, int B) {
-  const int job = blockIdx.y;
-  const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long long)in_dim * out_dim) return;
-  const float* __restrict__ s = J.s[job]; const float* __restrict__ demod = J.demod[job];
-  const float* __restrict__ G = J.G[job]; const float* __restrict__ cbuf = J.cbuf[job];
-  const int k = (int)(idx / out_dim), n = (int)(idx % out_dim);
-  const float w = J.W[job][idx];
-  float acc = 0.f;
-  for (int b = 0; b < B; ++b) {   // fixed order: deterministic
-    const float m = s[(long long)b * in_dim + k] + 1.f;
-    const float d = demod[(long long)b * out_dim + n];
-    const float g = G[((long long)b * in_dim + k) * out_dim + n];
-    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
-    acc = fmaf(m, du, acc);
-  }
-  J.dW[job][idx] = acc;
-}
-__global__ __launch_bounds__(256) void modfc_prep_bwd_s_batch_kernel(BwdJobs J, int B) {
-  const int job = blockIdx.y;
-  const int in_dim = J.in_dim[job], out_dim = J.out_dim[job];
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)B * in_dim) return;
-  const float* __restrict__ W = J.W[job]; const float* __restrict__ demod = J.demod[job];
-  const float* __restrict__ G = J.G[job]; const float* __restrict__ cbuf = J.cbuf[job];
-  const int b = (int)(row / in_dim), k = (int)(row % in_dim);
-  const float m = J.s[job][row] + 1.f;
-  float acc = 0.f;
-  for (int n = lane; n < out_dim; n += 64) {
-    const float w = W[(long long)k * out_dim + n];
-    const float d = demod[(long long)b * out_dim + n];
-    const float g = G[row * out_dim + n];
-    const float du = d * (g - d * d * (w * m) * cbuf[(long long)b * out_dim + n]);
-    acc = fmaf(w, du, acc);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  if (lane == 0) J.ds[job][row] = acc;
-}
-
-// ---- vector forms of the column reductions and the fused dW / ds pass (round 3) ------------------------------------
-// The per-image gradient G = dL/dWb of the 18 head layers is 604 MB at C2.  The three-pass backward above reads it
+// The per-image gradient G = dL/dWb of the 18 head layers is 604 MB at C2.  The three-pass scalar backward reads it
 // three times (c, dW, ds); here the column sums c read it once with 16-byte lanes and ONE further pass produces both
 // dW (sum over images, registers) and ds (sum over columns, one wave reduction per image) — two reads instead of three.
-// A block is 64 columns x 16 row groups, every lane owns 4 consecutive columns.
-struct ColJobs {                       // one table for both uses: G == nullptr selects the demodulation sums
-  const float* W[MAXJOBS]; const float* s[MAXJOBS]; const float* G[MAXJOBS]; float* out[MAXJOBS];
-  int in_dim[MAXJOBS], out_dim[MAXJOBS];
-};
+// The column sums (the 16-byte twin of modfc_colsum_batch_kernel): a block is 64 columns x 16 row groups, every lane
+// owns 4 consecutive columns.
 template <bool WITH_G>
 __global__ __launch_bounds__(256) void modfc_colsum4_batch_kernel(ColJobs J, int B, float eps) {
   __shared__ float4 red[16][17];
@@ -813,7 +685,7 @@ __global__ __launch_bounds__(256) void modfc_prep_bwd_ws_batch_kernel(BwdJobs J,
 }
 
 
-// ---- co-resident forms (round 6) ----------------------------------------------------------------------------------
+// ---- co-resident forms --------------------------------------------------------------------------------------------
 // The fused SIREN backward holds every CU for 2.4 ms with the whole LDS (160 KiB) and 472 of the 512 registers of each SIMD
 // lane: a kernel that uses NO LDS and at most 40 VGPRs still gets a wave slot beside it (profiles/r6_coresidency_probe.txt:
 // LDS-free launches on a side stream complete at their usual latency while it runs, LDS users wait for it to end).  The
@@ -981,6 +853,67 @@ __global__ __launch_bounds__(64) void torgb_bwd_w_reduce_cores_kernel(const floa
   }
 }
 
+// ---- job tables from the callers' job lists: one fill per table (validation, pointers, dimensions, maxima) ------
+struct JobDims {
+  int max_in = 0, max_out = 0;
+  long long max_nw = 0;                  // largest in_dim * out_dim
+  bool out4 = true, in8 = true;          // every out_dim % 4 == 0, every in_dim % 8 == 0: what the 16-byte forms need
+  void add(int in_dim, int out_dim) {
+    max_in = in_dim > max_in ? in_dim : max_in; max_out = out_dim > max_out ? out_dim : max_out;
+    const long long nw = (long long)in_dim * out_dim;
+    max_nw = nw > max_nw ? nw : max_nw;
+    out4 = out4 && out_dim % 4 == 0; in8 = in8 && in_dim % 8 == 0;
+  }
+};
+
+int fill_prep_jobs(const cips_modfc_prep_job* jobs, int njobs, int B, PrepJobs& J, ColJobs& Cj, JobDims& D) {
+  if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < njobs; ++i) {
+    const cips_modfc_prep_job& j = jobs[i];
+    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
+    J.W[i] = Cj.W[i] = j.weight; J.s[i] = Cj.s[i] = j.s; J.demod[i] = Cj.out[i] = j.demod;
+    J.wbh[i] = (unsigned short*)j.wb_hi; J.wbl[i] = (unsigned short*)j.wb_lo;
+    J.wth[i] = (unsigned short*)j.wbt_hi; J.wtl[i] = (unsigned short*)j.wbt_lo;
+    J.in_dim[i] = Cj.in_dim[i] = j.in_dim; J.out_dim[i] = Cj.out_dim[i] = j.out_dim;
+    D.add(j.in_dim, j.out_dim);
+  }
+  return (int)hipSuccess;
+}
+
+// need_out4: an out_dim that is no multiple of 4 is refused (the co-resident kernels have no scalar form)
+int fill_bwd_jobs(const cips_modfc_bwd_job* jobs, int njobs, int B, bool need_out4, BwdJobs& J, ColJobs& Cj, JobDims& D) {
+  if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < njobs; ++i) {
+    const cips_modfc_bwd_job& j = jobs[i];
+    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
+    if (need_out4 && j.out_dim % 4) return (int)hipErrorNotSupported;
+    J.W[i] = Cj.W[i] = j.weight; J.s[i] = Cj.s[i] = j.s; J.demod[i] = j.demod; J.G[i] = Cj.G[i] = j.gwb;
+    J.cbuf[i] = Cj.out[i] = j.cbuf; J.dW[i] = j.dweight; J.ds[i] = j.ds;
+    J.in_dim[i] = Cj.in_dim[i] = j.in_dim; J.out_dim[i] = Cj.out_dim[i] = j.out_dim;
+    D.add(j.in_dim, j.out_dim);
+  }
+  return (int)hipSuccess;
+}
+
+int fill_torgb_jobs(const void* const* x_hi, const void* const* x_lo, int njobs, long long M, int K, TorgbJobs& J) {
+  if (!x_hi || !x_lo || njobs <= 0 || M <= 0) return (int)hipErrorInvalidValue;
+  if (njobs > TORGB_MAXJOBS || K != 512) return (int)hipErrorNotSupported;
+  for (int i = 0; i < njobs; ++i) {
+    if (!x_hi[i] || !x_lo[i]) return (int)hipErrorInvalidValue;
+    J.xh[i] = (const u16*)x_hi[i]; J.xl[i] = (const u16*)x_lo[i];
+  }
+  return (int)hipSuccess;
+}
+
+// the scalar three-pass backward: what the batch entry launches when a shape rules out the 16-byte forms, and what the
+// single-job entry always launches
+int launch_bwd_scalar(const BwdJobs& J, const ColJobs& Cj, const JobDims& D, int njobs, int B, hipStream_t st) {
+  hipLaunchKernelGGL(modfc_colsum_batch_kernel<true>, dim3((D.max_out + 31) / 32, B, njobs), dim3(256), 0, st, Cj, 0.f);
+  hipLaunchKernelGGL(modfc_prep_bwd_w_batch_kernel, dim3((unsigned)((D.max_nw + 255) / 256), njobs), dim3(256), 0, st, J, B);
+  hipLaunchKernelGGL(modfc_prep_bwd_s_batch_kernel, dim3((unsigned)(((long long)B * D.max_in + 3) / 4), njobs), dim3(256), 0, st, J, B);
+  return CIPS_CHECK_LAUNCH();
+}
+
 }  // namespace
 
 extern "C" int cips_modfc_prep(const float* weight, const float* s, float* wb, float* wbt, float* demod,
@@ -996,16 +929,12 @@ extern "C" int cips_modfc_prep_bwd(const float* weight, const float* s, const fl
                                    float* cbuf, float* dweight, float* ds, int B, int in_dim, int out_dim,
                                    cips_stream_t stream) {
   if (B <= 0 || in_dim <= 0 || out_dim <= 0) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(modfc_prep_bwd_c_kernel, dim3((out_dim + 31) / 32, B), dim3(256), 0, st, weight, s, gwb,
-                     cbuf, in_dim, out_dim);
-  long long nw = (long long)in_dim * out_dim;
-  hipLaunchKernelGGL(modfc_prep_bwd_w_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, weight, s,
-                     demod, gwb, cbuf, dweight, B, in_dim, out_dim);
-  long long rows = (long long)B * in_dim;
-  hipLaunchKernelGGL(modfc_prep_bwd_s_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, weight, s,
-                     demod, gwb, cbuf, ds, B, in_dim, out_dim);
-  return CIPS_CHECK_LAUNCH();
+  const cips_modfc_bwd_job job = {weight, s, demod, gwb, cbuf, dweight, ds, in_dim, out_dim};
+  BwdJobs J = {};
+  ColJobs Cj = {};
+  JobDims D;
+  if (const int rc = fill_bwd_jobs(&job, 1, B, false, J, Cj, D)) return rc;
+  return launch_bwd_scalar(J, Cj, D, 1, B, (hipStream_t)stream);      // the scalar form whatever the shape
 }
 
 extern "C" int cips_torgb_fwd(const float* x, const float* w, const float* bias, float* rgb, long long M,
@@ -1062,12 +991,14 @@ extern "C" int cips_modfc_prep_x3(const float* weight, const float* s, void* wb_
                                   void* wbt_lo, float* demod, int B, int in_dim, int out_dim, float eps,
                                   cips_stream_t stream) {
   if (B <= 0 || in_dim <= 0 || out_dim <= 0) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(modfc_demod_kernel, dim3((out_dim + 31) / 32, B), dim3(256), 0, st, weight, s, demod, in_dim,
-                     out_dim, eps);
-  hipLaunchKernelGGL(modfc_planes_kernel, dim3((out_dim + 31) / 32, (in_dim + 31) / 32, B), dim3(256), 0, st, weight,
-                     s, demod, (unsigned short*)wb_hi, (unsigned short*)wb_lo, (unsigned short*)wbt_hi,
-                     (unsigned short*)wbt_lo, in_dim, out_dim);
+  const cips_modfc_prep_job job = {weight, s, wb_hi, wb_lo, wbt_hi, wbt_lo, demod, in_dim, out_dim};
+  PrepJobs J = {};
+  ColJobs Cj = {};
+  JobDims D;
+  if (const int rc = fill_prep_jobs(&job, 1, B, J, Cj, D)) return rc;
+  hipStream_t st = (hipStream_t)stream;                               // the scalar forms whatever the shape
+  hipLaunchKernelGGL(modfc_colsum_batch_kernel<false>, dim3((out_dim + 31) / 32, B, 1), dim3(256), 0, st, Cj, eps);
+  hipLaunchKernelGGL(modfc_planes_batch_kernel, dim3((out_dim + 31) / 32, (in_dim + 31) / 32, B), dim3(256), 0, st, J, B);
   return CIPS_CHECK_LAUNCH();
 }
 
@@ -1089,15 +1020,11 @@ extern "C" int cips_torgb_bwd_w(const float* x, const float* drgb, float* partia
 extern "C" int cips_torgb_bwd_w_x3(const void* x_hi, const void* x_lo, const float* drgb, float* partials,
                                    float* dw, float* dbias, long long M, int K, cips_stream_t stream) {
   if (M <= 0 || K <= 0 || (K & 3) || K > 512) return (int)hipErrorInvalidValue;
+  if (K == 512) return cips_torgb_bwd_w_x3_batch(&x_hi, &x_lo, 1, drgb, partials, dw, dbias, M, K, stream);   // its one-job case
   int chunks = cips_torgb_bwd_partials(M);
   hipStream_t st = (hipStream_t)stream;
-  if (K == 512) {
-    TorgbJobs J = {};
-    J.xh[0] = (const u16*)x_hi; J.xl[0] = (const u16*)x_lo;
-    hipLaunchKernelGGL(torgb_bwd_w_partial_x3_k512_kernel, dim3(chunks), dim3(256), 0, st, J, drgb, partials, M);
-  } else
-    hipLaunchKernelGGL(torgb_bwd_w_partial_kernel<true>, dim3(chunks), dim3(256), 0, st, x_hi, x_lo, drgb, partials,
-                       M, K);
+  hipLaunchKernelGGL(torgb_bwd_w_partial_kernel<true>, dim3(chunks), dim3(256), 0, st, x_hi, x_lo, drgb, partials,
+                     M, K);
   hipLaunchKernelGGL(torgb_bwd_w_reduce_kernel, dim3((3 * K + 3 + 7) / 8), dim3(256), 0, st, partials, dw,
                      dbias, chunks, K);
   return CIPS_CHECK_LAUNCH();
@@ -1107,13 +1034,8 @@ extern "C" int cips_torgb_bwd_w_x3(const void* x_hi, const void* x_lo, const flo
 // dw (njobs, 3, K), dbias (njobs, 3)
 extern "C" int cips_torgb_bwd_w_x3_batch(const void* const* x_hi, const void* const* x_lo, int njobs, const float* drgb,
                                          float* partials, float* dw, float* dbias, long long M, int K, cips_stream_t stream) {
-  if (!x_hi || !x_lo || njobs <= 0 || M <= 0) return (int)hipErrorInvalidValue;
-  if (njobs > TORGB_MAXJOBS || K != 512) return (int)hipErrorNotSupported;
   TorgbJobs J = {};
-  for (int i = 0; i < njobs; ++i) {
-    if (!x_hi[i] || !x_lo[i]) return (int)hipErrorInvalidValue;
-    J.xh[i] = (const u16*)x_hi[i]; J.xl[i] = (const u16*)x_lo[i];
-  }
+  if (const int rc = fill_torgb_jobs(x_hi, x_lo, njobs, M, K, J)) return rc;
   const int chunks = cips_torgb_bwd_partials(M);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(torgb_bwd_w_partial_x3_k512_kernel, dim3(chunks, njobs), dim3(256), 0, st, J, drgb, partials, M);
@@ -1127,36 +1049,22 @@ extern "C" int cips_cores_colsum_parts(void) { return CS_KS; }
 extern "C" int cips_modfc_prep_bwd_batch_cores(const cips_modfc_bwd_job* jobs, int njobs, int B, cips_stream_t stream) {
   if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
   if (B > 64) return (int)hipErrorNotSupported;
-  BwdJobs J;
+  BwdJobs J = {};
   ColJobs Cj = {};
-  int max_in = 0, max_out = 0;
-  for (int i = 0; i < njobs; ++i) {
-    const cips_modfc_bwd_job& j = jobs[i];
-    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
-    if (j.out_dim % 4) return (int)hipErrorNotSupported;
-    J.W[i] = j.weight; J.s[i] = j.s; J.demod[i] = j.demod; J.G[i] = j.gwb;
-    J.cbuf[i] = j.cbuf; J.dW[i] = j.dweight; J.ds[i] = j.ds;
-    J.in_dim[i] = j.in_dim; J.out_dim[i] = j.out_dim;
-    Cj.W[i] = j.weight; Cj.s[i] = j.s; Cj.G[i] = j.gwb; Cj.out[i] = j.cbuf; Cj.in_dim[i] = j.in_dim; Cj.out_dim[i] = j.out_dim;
-    max_in = j.in_dim > max_in ? j.in_dim : max_in; max_out = j.out_dim > max_out ? j.out_dim : max_out;
-  }
+  JobDims D;
+  if (const int rc = fill_bwd_jobs(jobs, njobs, B, true, J, Cj, D)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(modfc_colsum4_cores_kernel, dim3((max_out + 255) / 256, B, njobs * CS_KS), dim3(64), 0, st, Cj, B);
-  hipLaunchKernelGGL(modfc_colsum_fold_cores_kernel, dim3((B * max_out / 4 + 255) / 256, njobs), dim3(256), 0, st, Cj, B);
-  hipLaunchKernelGGL(modfc_prep_bwd_ws_cores_kernel, dim3((max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
+  hipLaunchKernelGGL(modfc_colsum4_cores_kernel, dim3((D.max_out + 255) / 256, B, njobs * CS_KS), dim3(64), 0, st, Cj, B);
+  hipLaunchKernelGGL(modfc_colsum_fold_cores_kernel, dim3((B * D.max_out / 4 + 255) / 256, njobs), dim3(256), 0, st, Cj, B);
+  hipLaunchKernelGGL(modfc_prep_bwd_ws_cores_kernel, dim3((D.max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
   return CIPS_CHECK_LAUNCH();
 }
 
 // co-resident form of cips_torgb_bwd_w_x3_batch: same arguments, layouts and partial scratch
 extern "C" int cips_torgb_bwd_w_x3_batch_cores(const void* const* x_hi, const void* const* x_lo, int njobs, const float* drgb,
                                                float* partials, float* dw, float* dbias, long long M, int K, cips_stream_t stream) {
-  if (!x_hi || !x_lo || njobs <= 0 || M <= 0) return (int)hipErrorInvalidValue;
-  if (njobs > TORGB_MAXJOBS || K != 512) return (int)hipErrorNotSupported;
   TorgbJobs J = {};
-  for (int i = 0; i < njobs; ++i) {
-    if (!x_hi[i] || !x_lo[i]) return (int)hipErrorInvalidValue;
-    J.xh[i] = (const u16*)x_hi[i]; J.xl[i] = (const u16*)x_lo[i];
-  }
+  if (const int rc = fill_torgb_jobs(x_hi, x_lo, njobs, M, K, J)) return rc;
   const int chunks = cips_torgb_bwd_partials(M);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(torgb_bwd_w_partial_cores_kernel, dim3((chunks + 1) / 2, njobs), dim3(256), 0, st, J, drgb, partials, M, chunks);
@@ -1189,68 +1097,34 @@ extern "C" int cips_torgb_bwd_x_x3(const float* drgb, const float* w, const void
 extern "C" int cips_modfc_max_jobs(void) { return MAXJOBS; }
 
 extern "C" int cips_modfc_prep_x3_batch(const cips_modfc_prep_job* jobs, int njobs, int B, float eps, cips_stream_t stream) {
-  if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
-  PrepJobs J;
-  int max_in = 0, max_out = 0;
-  for (int i = 0; i < njobs; ++i) {
-    const cips_modfc_prep_job& j = jobs[i];
-    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
-    J.W[i] = j.weight; J.s[i] = j.s; J.demod[i] = j.demod;
-    J.wbh[i] = (unsigned short*)j.wb_hi; J.wbl[i] = (unsigned short*)j.wb_lo;
-    J.wth[i] = (unsigned short*)j.wbt_hi; J.wtl[i] = (unsigned short*)j.wbt_lo;
-    J.in_dim[i] = j.in_dim; J.out_dim[i] = j.out_dim;
-    max_in = j.in_dim > max_in ? j.in_dim : max_in; max_out = j.out_dim > max_out ? j.out_dim : max_out;
-  }
+  PrepJobs J = {};
+  ColJobs Cj = {};
+  JobDims D;
+  if (const int rc = fill_prep_jobs(jobs, njobs, B, J, Cj, D)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  bool wide = true;                              // 64 x 64 tiles with vector accesses when every job's shape allows
-  bool vec4 = true;                              // 16-byte lanes in the column reductions
-  for (int i = 0; i < njobs; ++i) {
-    wide = wide && (jobs[i].out_dim % 4 == 0) && (jobs[i].in_dim % 8 == 0);
-    vec4 = vec4 && (jobs[i].out_dim % 4 == 0);
-  }
-  if (vec4) {
-    ColJobs Cj = {};
-    for (int i = 0; i < njobs; ++i) { Cj.W[i] = J.W[i]; Cj.s[i] = J.s[i]; Cj.out[i] = J.demod[i]; Cj.in_dim[i] = J.in_dim[i]; Cj.out_dim[i] = J.out_dim[i]; }
-    hipLaunchKernelGGL(modfc_colsum4_batch_kernel<false>, dim3((max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, eps);
-  } else
-    hipLaunchKernelGGL(modfc_demod_batch_kernel, dim3((max_out + 31) / 32, B, njobs), dim3(256), 0, st, J, B, eps);
-  if (wide)
-    hipLaunchKernelGGL(modfc_planes_batch64_kernel, dim3((max_out + 63) / 64, (max_in + 63) / 64, B * njobs), dim3(256), 0, st, J, B);
+  if (D.out4)                                    // 16-byte lanes in the column reductions
+    hipLaunchKernelGGL(modfc_colsum4_batch_kernel<false>, dim3((D.max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, eps);
   else
-    hipLaunchKernelGGL(modfc_planes_batch_kernel, dim3((max_out + 31) / 32, (max_in + 31) / 32, B * njobs), dim3(256), 0, st, J, B);
+    hipLaunchKernelGGL(modfc_colsum_batch_kernel<false>, dim3((D.max_out + 31) / 32, B, njobs), dim3(256), 0, st, Cj, eps);
+  if (D.out4 && D.in8)                           // 64 x 64 tiles with vector accesses when every job's shape allows
+    hipLaunchKernelGGL(modfc_planes_batch64_kernel, dim3((D.max_out + 63) / 64, (D.max_in + 63) / 64, B * njobs), dim3(256), 0, st, J, B);
+  else
+    hipLaunchKernelGGL(modfc_planes_batch_kernel, dim3((D.max_out + 31) / 32, (D.max_in + 31) / 32, B * njobs), dim3(256), 0, st, J, B);
   return CIPS_CHECK_LAUNCH();
 }
 
 extern "C" int cips_modfc_prep_bwd_batch(const cips_modfc_bwd_job* jobs, int njobs, int B, cips_stream_t stream) {
-  if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
-  BwdJobs J;
-  int max_in = 0, max_out = 0;
-  long long max_nw = 0;
-  for (int i = 0; i < njobs; ++i) {
-    const cips_modfc_bwd_job& j = jobs[i];
-    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
-    J.W[i] = j.weight; J.s[i] = j.s; J.demod[i] = j.demod; J.G[i] = j.gwb;
-    J.cbuf[i] = j.cbuf; J.dW[i] = j.dweight; J.ds[i] = j.ds;
-    J.in_dim[i] = j.in_dim; J.out_dim[i] = j.out_dim;
-    max_in = j.in_dim > max_in ? j.in_dim : max_in; max_out = j.out_dim > max_out ? j.out_dim : max_out;
-    const long long nw = (long long)j.in_dim * j.out_dim;
-    max_nw = nw > max_nw ? nw : max_nw;
-  }
+  BwdJobs J = {};
+  ColJobs Cj = {};
+  JobDims D;
+  if (const int rc = fill_bwd_jobs(jobs, njobs, B, false, J, Cj, D)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  bool vec4 = B <= 64 && max_out <= 1024;        // two reads of G instead of three (see modfc_prep_bwd_ws_batch_kernel)
-  for (int i = 0; i < njobs; ++i) vec4 = vec4 && (jobs[i].out_dim % 4 == 0);
-  if (vec4) {
-    ColJobs Cj = {};
-    for (int i = 0; i < njobs; ++i) { Cj.W[i] = J.W[i]; Cj.s[i] = J.s[i]; Cj.G[i] = J.G[i]; Cj.out[i] = J.cbuf[i]; Cj.in_dim[i] = J.in_dim[i]; Cj.out_dim[i] = J.out_dim[i]; }
-    hipLaunchKernelGGL(modfc_colsum4_batch_kernel<true>, dim3((max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, 0.f);
-    if (max_out <= 512)
-      hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<2>, dim3((max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
-    else
-      hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<4>, dim3((max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
-    return CIPS_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(modfc_prep_bwd_c_batch_kernel, dim3((max_out + 31) / 32, B, njobs), dim3(256), 0, st, J);
-  hipLaunchKernelGGL(modfc_prep_bwd_w_batch_kernel, dim3((unsigned)((max_nw + 255) / 256), njobs), dim3(256), 0, st, J, B);
-  hipLaunchKernelGGL(modfc_prep_bwd_s_batch_kernel, dim3((unsigned)(((long long)B * max_in + 3) / 4), njobs), dim3(256), 0, st, J, B);
+  if (!(D.out4 && B <= 64 && D.max_out <= 1024)) return launch_bwd_scalar(J, Cj, D, njobs, B, st);
+  // two reads of G instead of three (see modfc_prep_bwd_ws_batch_kernel)
+  hipLaunchKernelGGL(modfc_colsum4_batch_kernel<true>, dim3((D.max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, 0.f);
+  if (D.max_out <= 512)
+    hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<2>, dim3((D.max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
+  else
+    hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<4>, dim3((D.max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
   return CIPS_CHECK_LAUNCH();
 }

@@ -32,30 +32,11 @@ from . import _lib, ops
 # fused bias + leaky relu  (mirrors exp/comm/op/fused_act.py:19-86)
 # ------------------------------------------------------------------------------------------
 # LeakyReLU gate instrumentation (parity tests; never set in production) — the discriminator's counterpart of
-# ops.GATE_PIN / ops.GATE_REC: GATE_PIN is an iterator of bool tensors shaped like the activations, one per
-# fused_leaky_relu call in call order; the op then applies `gate ? 1 : slope` from the tensor (cips_fused_bias_act
-# in its gradient form: y = (refer > 0 ? x + b : (x + b) * slope) * scale) and every backward order uses the same
-# gate.  GATE_REC receives the bool gates actually used.
-GATE_PIN = None
-GATE_REC = None
-
-
-class gate_debug:
-    def __init__(self, pin=None, rec=None):
-        self.pin, self.rec = pin, rec
-
-    def __enter__(self):
-        global GATE_PIN, GATE_REC
-        self.old = (GATE_PIN, GATE_REC)
-        GATE_PIN = iter(self.pin) if self.pin is not None else None
-        GATE_REC = self.rec
-        return self
-
-    def __exit__(self, *exc):
-        global GATE_PIN, GATE_REC
-        if exc[0] is None and GATE_PIN is not None:
-            assert next(GATE_PIN, None) is None, "pinned gates left over"
-        GATE_PIN, GATE_REC = self.old
+# ops.gate_debug, a hook of its own: pin holds bool tensors shaped like the activations, one per fused_leaky_relu
+# call in call order; the op then applies `gate ? 1 : slope` from the tensor (cips_fused_bias_act in its gradient
+# form: y = (refer > 0 ? x + b : (x + b) * slope) * scale) and every backward order uses the same gate.  rec receives
+# the bool gates actually used.
+gate_debug = ops.DebugHook(leftover="pinned gates left over")
 
 
 class FusedLeakyReLUFunctionBackward(Function):
@@ -88,15 +69,15 @@ class FusedLeakyReLUFunction(Function):
     @staticmethod
     def forward(ctx, input, bias, negative_slope, scale):
         empty = input.new_empty(0)
-        if GATE_PIN is not None:
-            gate = next(GATE_PIN).to(input.device).reshape(input.shape)
+        if gate_debug.pin is not None:
+            gate = next(gate_debug.pin).to(input.device).reshape(input.shape)
             refer = torch.where(gate, 1.0, -1.0).to(input.dtype)       # only its sign is read
             out = ops.fused_bias_act(input, bias, refer, 3, 1, negative_slope, scale)
         else:
             out = ops.fused_bias_act(input, bias, empty, 3, 0, negative_slope, scale)
             refer = out                                                    # sign(out) = sign(input + bias)
-        if GATE_REC is not None:
-            GATE_REC.append((refer > 0).clone())
+        if gate_debug.rec is not None:
+            gate_debug.rec.append((refer > 0).clone())
         ctx.save_for_backward(refer)
         ctx.negative_slope, ctx.scale = negative_slope, scale
         return out
@@ -810,7 +791,7 @@ def _conv_act_fusable(x, conv, act, pre=None):
     """EqualConv2d (no bias of its own) + FusedLeakyReLU on a GPU batch whose forward takes the implicit-GEMM form"""
     if not (_CONV_ACT_FUSED and x.is_cuda and x.dtype == torch.float32 and conv.bias is None and isinstance(act, FusedLeakyReLU)):
         return False
-    if GATE_PIN is not None or GATE_REC is not None:        # gate instrumentation works on the separate activation op
+    if gate_debug.active:        # gate instrumentation works on the separate activation op
         return False
     return _conv_plan(x.shape, conv.weight.shape, conv.stride, conv.padding, pre).forms[0] == "implicit"
 

@@ -5,6 +5,7 @@ PyTorch is used for device memory, streams and autograd bookkeeping only; every 
 kernel on the hot path is a hand-written HIP kernel in libcips3d_hip.so.  There is no CPU
 fallback: tensors must live on a ROCm device and the extension must be built.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -811,8 +812,8 @@ def _composite_forward(ctx, geo, feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, 
         check(lib.cips_composite_fwd_geo(*args, _p(opacity), _stream()), "cips_composite_fwd_geo")
     else:
         check(lib.cips_composite_fwd(*args, _stream()), "cips_composite_fwd")
-    if rec is not None and CLAMP_REC is not None:
-        CLAMP_REC.append(rec.reshape(R, E))
+    if rec is not None:
+        clamp_debug.rec.append(rec.reshape(R, E))
     ctx.clamp_mask = pin                      # pinned branches: the backward takes the same ones (else: its own sign test)
     ctx.save_for_backward(feat_c, sig_c, z_c, feat_f, sig_f, z_f, noise, order)
     ctx.meta = (float(noise_std), clamp_mode, flags, hier)
@@ -1157,8 +1158,8 @@ def _march_forward(ctx, geo, geom, xg, yg, zg, cam2world, jitter, noise, *siren)
         check(lib.cips_march_fwd_x3_geo(*args, _p(opacity), _stream()), "cips_march_fwd_x3_geo")
     else:
         check(lib.cips_march_fwd_x3(*args, _stream()), "cips_march_fwd_x3")
-    if rec is not None and CLAMP_REC is not None:
-        CLAMP_REC.append(rec.reshape(B * n, S))
+    if rec is not None:
+        clamp_debug.rec.append(rec.reshape(B * n, S))
     ctx.clamp_mask = pin
     ctx.live_fwd = train and bool(live_fwd) and live_forward_ok(clamp_mode, pin)
     if train:
@@ -1276,116 +1277,81 @@ def torgb_bwd_x(drgb2d, w, add, mask, out_unmasked, out):
                                _stream()), "cips_torgb_bwd_x")
 
 
-# ---- LeakyReLU gate instrumentation of the head (parity tests; never set in production) --------------------------
+# ---- instrumentation of the path's discontinuities (parity tests; never set in production) -----------------------
+class DebugHook:
+    """A pin / record hook: `pin` is an iterator the instrumented op draws its decisions from in call order instead of taking
+    them itself (None: not pinned), `rec` a list that receives the decisions it took (None: not recorded).
+    `with hook(pin=[...] or None, rec=list or None): ...` sets both and restores the outer values on exit, so uses nest.
+    leftover: the message of the assertion that every pin was drawn when the block ends without an exception (None: not
+    asserted)."""
+
+    def __init__(self, leftover=None):
+        self.pin, self.rec, self.leftover = None, None, leftover
+
+    @property
+    def active(self):
+        return self.pin is not None or self.rec is not None
+
+    @contextlib.contextmanager
+    def __call__(self, pin=None, rec=None):
+        old = (self.pin, self.rec)
+        self.pin, self.rec = (iter(pin) if pin is not None else None), rec
+        try:
+            yield self
+            if self.leftover is not None and self.pin is not None:
+                assert next(self.pin, None) is None, self.leftover
+        finally:
+            self.pin, self.rec = old
+
+
 # A LeakyReLU gate (pre-activation > 0) is the one discontinuity of the head: two fp32 evaluations of the same layer
 # may disagree on it for pre-activations within rounding of zero, and each disagreement moves the gradients by a
 # finite amount.  Gradient parity is therefore stated for a GIVEN set of gates:
-#   GATE_PIN: iterator of uint8 bit planes (B, n, C/8) (bit c&7 of byte c>>3 = gate of column c), one per modulated-FC
-#             layer in call order; the forward epilogues then apply `gate ? 1 : slope` from the plane instead of
-#             deciding by the sign they computed, and the backward uses the same plane.
-#   GATE_REC: list that receives the bit plane every layer actually used, in call order.
-GATE_PIN = None
-GATE_REC = None
+#   pin: uint8 bit planes (B, n, C/8) (bit c&7 of byte c>>3 = gate of column c), one per modulated-FC layer in call
+#        order; the forward epilogues then apply `gate ? 1 : slope` from the plane instead of deciding by the sign
+#        they computed, and the backward uses the same plane.
+#   rec: receives the bit plane every layer actually used, in call order.
+gate_debug = DebugHook(leftover="pinned gate planes left over")
 # The other discontinuity of the path: importance resampling places the fine samples by a searchsorted over the coarse
 # weights' cdf (pigan_utils.py:164-273); a cdf value within rounding of the uniform draw puts a sample in the
-# neighbouring bin.  FINE_Z_REC collects the depths every hierarchical forward resampled (b*n, S); FINE_Z_PIN (an
-# iterator of such tensors) replaces them — parity tests compare gradients for the SAME sample placement.
-FINE_Z_PIN = None
-FINE_Z_REC = None
-
-
+# neighbouring bin.  rec collects the depths every hierarchical forward resampled (b*n, S); pin (such tensors)
+# replaces them — parity tests compare gradients for the SAME sample placement.
+resample_debug = DebugHook()
 # The third discontinuity: relu(sigma + nerf_noise * eps) in fancy_integration (pigan_utils.py:246-252).  The reference trains
 # its first 5 000 steps with nerf_noise 1 -> 0 (train.py:325-327); a pre-activation within rounding of 0 takes either
 # branch, and the two gradients of the sigma head (sums of d sigma with heavy cancellation) move by a finite amount per
-# flipped sample.  CLAMP_PIN: iterator of uint8 tensors (R, E) (R rays, E sorted positions; 0 = clamped, else the linear
-# branch), one per composite / fused-march forward in call order — forward AND backward then take the branch from it.
-# CLAMP_REC: list receiving the branches each forward actually took.
-CLAMP_PIN = None
-CLAMP_REC = None
-
-
-class clamp_debug:
-    """with clamp_debug(pin=[mask, ...] or None, rec=list or None): ...   (tests only)"""
-
-    def __init__(self, pin=None, rec=None):
-        self.pin, self.rec = pin, rec
-
-    def __enter__(self):
-        global CLAMP_PIN, CLAMP_REC
-        self.old = (CLAMP_PIN, CLAMP_REC)
-        CLAMP_PIN = iter(self.pin) if self.pin is not None else None
-        CLAMP_REC = self.rec
-        return self
-
-    def __exit__(self, *exc):
-        global CLAMP_PIN, CLAMP_REC
-        CLAMP_PIN, CLAMP_REC = self.old
+# flipped sample.  pin: uint8 tensors (R, E) (R rays, E sorted positions; 0 = clamped, else the linear branch), one per
+# composite / fused-march forward in call order — forward AND backward then take the branch from it.  rec: receives the
+# branches each forward actually took.
+clamp_debug = DebugHook()
 
 
 def _clamp_debug_forward(R, E, clamp_mode, dev):
     """-> (pin, rec) for one composite forward of R rays x E positions: both None outside clamp_debug / for softplus"""
-    if (CLAMP_PIN is None and CLAMP_REC is None) or clamp_mode != 0:
+    if not clamp_debug.active or clamp_mode != 0:
         return None, None
     pin = None
-    if CLAMP_PIN is not None:
-        pin = next(CLAMP_PIN).to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
+    if clamp_debug.pin is not None:
+        pin = next(clamp_debug.pin).to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
         if pin.numel() != R * E:
             raise ValueError(f"clamp_debug: pinned mask of {pin.numel()} entries for {R} rays x {E} positions")
-    return pin, (torch.empty(R * E, dtype=torch.uint8, device=dev) if CLAMP_REC is not None else None)
-
-
-class resample_debug:
-    """with resample_debug(pin=[fine_z, ...] or None, rec=list or None): ...   (tests only)"""
-
-    def __init__(self, pin=None, rec=None):
-        self.pin, self.rec = pin, rec
-
-    def __enter__(self):
-        global FINE_Z_PIN, FINE_Z_REC
-        self.old = (FINE_Z_PIN, FINE_Z_REC)
-        FINE_Z_PIN = iter(self.pin) if self.pin is not None else None
-        FINE_Z_REC = self.rec
-        return self
-
-    def __exit__(self, *exc):
-        global FINE_Z_PIN, FINE_Z_REC
-        FINE_Z_PIN, FINE_Z_REC = self.old
+    return pin, (torch.empty(R * E, dtype=torch.uint8, device=dev) if clamp_debug.rec is not None else None)
 
 
 def fine_z_debug(fine_z):
     """-> the depths one hierarchical forward is to use: `fine_z` itself (recorded under resample_debug(rec=...)), or the next
     pinned tensor in its shape — a different object, so a caller that materialised points from `fine_z` can tell"""
-    if FINE_Z_REC is not None:
-        FINE_Z_REC.append(fine_z.detach().clone())
-    if FINE_Z_PIN is None:
+    if resample_debug.rec is not None:
+        resample_debug.rec.append(fine_z.detach().clone())
+    if resample_debug.pin is None:
         return fine_z
-    return next(FINE_Z_PIN).to(fine_z.device).reshape(fine_z.shape).contiguous()
-
-
-class gate_debug:
-    """with gate_debug(pin=planes or None, rec=list or None): ..."""
-
-    def __init__(self, pin=None, rec=None):
-        self.pin, self.rec = pin, rec
-
-    def __enter__(self):
-        global GATE_PIN, GATE_REC
-        self.old = (GATE_PIN, GATE_REC)
-        GATE_PIN = iter(self.pin) if self.pin is not None else None
-        GATE_REC = self.rec
-        return self
-
-    def __exit__(self, *exc):
-        global GATE_PIN, GATE_REC
-        if exc[0] is None and GATE_PIN is not None:
-            assert next(GATE_PIN, None) is None, "pinned gate planes left over"
-        GATE_PIN, GATE_REC = self.old
+    return next(resample_debug.pin).to(fine_z.device).reshape(fine_z.shape).contiguous()
 
 
 def _next_pin(B, n, C, dev):
-    if GATE_PIN is None:
+    if gate_debug.pin is None:
         return None
-    p = next(GATE_PIN)
+    p = next(gate_debug.pin)
     assert p.dtype == torch.uint8 and tuple(p.shape) == (B, n, C // 8), (tuple(p.shape), (B, n, C // 8))
     return p.to(dev).contiguous()
 
@@ -1401,6 +1367,19 @@ def _sign_to_bits(a):
     """fp32 (..., C) -> uint8 bit plane (..., C/8) of a > 0"""
     w = (1 << torch.arange(8, device=a.device)).to(torch.int32)
     return ((a > 0).reshape(*a.shape[:-1], a.shape[-1] // 8, 8).to(torch.int32) * w).sum(-1).to(torch.uint8)
+
+
+def _head_params(nblocks, params):
+    """the head's parameter layout: (W1, s1, W2, s2) per block, then (T, tau) of the ToRGB tap of every block k >= 3 — what
+    follows them are the handles of gradient ports -> blocks (list of 4-tuples), rgbp (flat list), detached and contiguous"""
+    blocks = [tuple(_c(p.detach()) for p in params[4 * k:4 * k + 4]) for k in range(nblocks)]
+    rgbp = [_c(p.detach()) for p in params[4 * nblocks:4 * nblocks + 2 * max(nblocks - 3, 0)]]
+    return blocks, rgbp
+
+
+def _head_grads(dx0, grads_blocks, grads_rgb):
+    """the head's gradients in autograd order: (nblocks, grad_mode, ports, x0), then the layout of _head_params"""
+    return (None, None, None, dx0) + tuple(g for gb in grads_blocks for g in gb) + tuple(grads_rgb)
 
 
 class InrHeadFunction(torch.autograd.Function):
@@ -1419,11 +1398,7 @@ class InrHeadFunction(torch.autograd.Function):
         x0 = _c(x0.detach())
         B, n, _ = x0.shape
         dev = x0.device
-        blocks = []
-        for k in range(nblocks):
-            W1, s1, W2, s2 = [_c(p.detach()) for p in params[4 * k:4 * k + 4]]
-            blocks.append((W1, s1, W2, s2))
-        rgbp = [_c(p.detach()) for p in params[4 * nblocks:]]
+        blocks, rgbp = _head_params(nblocks, params)
         _chk(x0, *[t for blk in blocks for t in blk], *rgbp)
         saved = []
         x = x0
@@ -1447,9 +1422,9 @@ class InrHeadFunction(torch.autograd.Function):
             else:
                 a2 = bmm_nn(a1, wb2, **e2)
                 out = a2
-            if GATE_REC is not None:
-                GATE_REC.append(pin1 if pin1 is not None else _sign_to_bits(a1))
-                GATE_REC.append(pin2 if pin2 is not None else _sign_to_bits(a2))
+            if gate_debug.rec is not None:
+                gate_debug.rec.append(pin1 if pin1 is not None else _sign_to_bits(a1))
+                gate_debug.rec.append(pin2 if pin2 is not None else _sign_to_bits(a2))
             if k >= 3:
                 T, tau = rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1]
                 torgb_fwd(out.view(B * n, -1), T, tau, rgb.view(B * n, 3), accumulate=not first_rgb)
@@ -1516,11 +1491,7 @@ class InrHeadFunction(torch.autograd.Function):
                     epi["rgb_w"] = rgbp[2 * (k - 1 - 3)]
                 g2 = bmm_nn(g1, wbt1, out=torch.empty(B, n, width, device=dev), **epi)
                 Dout = newD
-        flat = [None, None, None, dx0]
-        for gb in grads_blocks:
-            flat.extend(gb)
-        flat.extend(grads_rgb)
-        return tuple(flat)
+        return _head_grads(dx0, grads_blocks, grads_rgb)
 
 
 # --------------------------------------------------------------------------------------
@@ -1564,24 +1535,31 @@ X3_KERNEL = 0        # descriptor field `kernel` of every split-bf16 GEMM issued
                      # (production); 1 / 2 / 3 force a kernel (cips3d_hip.h) — set by the kernel parity tests and microbenchmarks
 
 
-def _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C=None, P=None, T=None, ldt=0, strideT=0,
-             mask_out=None, add=None, rgb_g=None, rgb_w=None, C_unmasked=None, mask=None, act=0, res=None, gate_bits=0,
-             torgb=None, addp=None):
-    d = GemmX3Desc()
+def _x3_operands(d, A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C):
+    """the fields every split-bf16 GEMM descriptor sets: operand planes, shape, strides, the fp32 output C (M, N) and the
+    constants -> d"""
     d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
     d.M, d.N, d.K, d.lda, d.ldb = M, N, K, lda, ldb
     d.strideA, d.strideB, d.batch = strideA, strideB, batch
     d.C, d.ldc, d.strideC = _p(C), N, M * N
+    d.slope = LRELU_SLOPE
+    d.kernel = X3_KERNEL
+    return d
+
+
+def _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C=None, P=None, T=None, ldt=0, strideT=0,
+             mask_out=None, add=None, rgb_g=None, rgb_w=None, C_unmasked=None, mask=None, act=0, res=None, gate_bits=0,
+             torgb=None, addp=None):
+    d = _x3_operands(GemmX3Desc(), A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C)
     d.P_hi, d.P_lo = (_p(P.hi), _p(P.lo)) if P is not None else (None, None)
     d.ldp, d.strideP = N, M * N
     d.T_hi, d.T_lo = (_p(T.hi), _p(T.lo)) if T is not None else (None, None)
     d.ldt, d.strideT = ldt, strideT
     d.mask_out, d.add, d.rgb_g, d.rgb_w = _p(mask_out), _p(add), _p(rgb_g), _p(rgb_w)
     d.C_unmasked, d.mask = _p(C_unmasked), _p(mask)
-    d.act, d.slope = act, LRELU_SLOPE
+    d.act = act
     d.res_hi, d.res_lo = (_p(res.hi), _p(res.lo)) if res is not None else (None, None)
     d.gate_bits = gate_bits        # bit 0: `mask` is a uint8 bit plane (M, N/8); bit 1: `mask_out` is written as one
-    d.kernel = X3_KERNEL
     if torgb is not None:          # (T (3, N), partials (N/128, batch*M, 4)): ToRGB forward folded into the epilogue
         d.torgb_w, d.torgb_part = _p(torgb[0]), _p(torgb[1])
     if addp is not None:           # (Planes of a gated tensor, bit plane of that gate): the addend, un-gated on the fly
@@ -1639,13 +1617,7 @@ def gemm_x3_torgb(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, P, rgb_w, r
 def gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, Cm, single=False):
     """C[b][m][n] = sum_k A[b][k][m] * B[b][k][n]; A, B: Planes stored [K][ld] (k-major), C fp32 (M,N)."""
     name, fn = _x3_entry(single, "_km")
-    d = GemmX3Desc()
-    d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
-    d.M, d.N, d.K, d.lda, d.ldb = M, N, K, lda, ldb
-    d.strideA, d.strideB, d.batch = strideA, strideB, batch
-    d.C, d.ldc, d.strideC = _p(Cm), N, M * N
-    d.slope = LRELU_SLOPE
-    d.kernel = X3_KERNEL
+    d = _x3_operands(GemmX3Desc(), A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, Cm)
     check(fn(C.byref(d), _stream()), name)
 
 
@@ -1654,17 +1626,12 @@ def gemm_x3_km_grouped(problems, M, N, K, lda, ldb, batch, strideA, strideB, sin
     (256x256 tiles), else one K-major GEMM per problem."""
     name, fn = _x3_entry(single, "_km_grouped")
     descs = (GemmX3Desc * len(problems))()
-    for d, (A, Bm, C) in zip(descs, problems):
-        d.A_hi, d.A_lo, d.B_hi, d.B_lo = _p(A.hi), _p(A.lo), _p(Bm.hi), _p(Bm.lo)
-        d.M, d.N, d.K, d.lda, d.ldb = M, N, K, lda, ldb
-        d.strideA, d.strideB, d.batch = strideA, strideB, batch
-        d.C, d.ldc, d.strideC = _p(C), N, M * N
-        d.slope = LRELU_SLOPE
-        d.kernel = X3_KERNEL
+    for d, (A, Bm, Cm) in zip(descs, problems):
+        _x3_operands(d, A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, Cm)
     rc = fn(descs, len(problems), _stream())
     if rc == 801:      # hipErrorNotSupported
-        for (A, Bm, C) in problems:
-            gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C, single=single)
+        for (A, Bm, Cm) in problems:
+            gemm_x3_km(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, Cm, single=single)
         return
     check(rc, name)
 
@@ -1887,14 +1854,19 @@ def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nc
     return dw
 
 
+def _modfc_prep_x3_out(W, B):
+    """what one layer's split-plane prep writes: wb Planes (B,in,out), wbt Planes (B,out,in), demod (B,out)"""
+    in_dim, out_dim = W.shape
+    return (Planes.empty(B, in_dim, out_dim, device=W.device), Planes.empty(B, out_dim, in_dim, device=W.device),
+            torch.empty(B, out_dim, device=W.device))
+
+
 def modfc_prep_x3(W, s, eps=1e-8):
+    """one layer through the single-job entry: the scalar kernels whatever the shape"""
     lib = _lib.load()
     in_dim, out_dim = W.shape
     B = s.shape[0]
-    dev = W.device
-    wb = Planes.empty(B, in_dim, out_dim, device=dev)
-    wbt = Planes.empty(B, out_dim, in_dim, device=dev)
-    demod = torch.empty(B, out_dim, device=dev)
+    wb, wbt, demod = _modfc_prep_x3_out(W, B)
     check(lib.cips_modfc_prep_x3(_p(W), _p(s), _p(wb.hi), _p(wb.lo), _p(wbt.hi), _p(wbt.lo), _p(demod), B, in_dim,
                                  out_dim, eps, _stream()), "cips_modfc_prep_x3")
     return wb, wbt, demod
@@ -1911,14 +1883,10 @@ def modfc_prep_x3_batch(layers, eps=1e-8):
         jobs = (ModfcPrepJob * len(chunk))()
         B = chunk[0][1].shape[0]
         for j, (W, s) in zip(jobs, chunk):
-            in_dim, out_dim = W.shape
-            dev = W.device
-            wb = Planes.empty(B, in_dim, out_dim, device=dev)
-            wbt = Planes.empty(B, out_dim, in_dim, device=dev)
-            demod = torch.empty(B, out_dim, device=dev)
+            wb, wbt, demod = _modfc_prep_x3_out(W, B)
             j.weight, j.s, j.demod = _p(W), _p(s), _p(demod)
             j.wb_hi, j.wb_lo, j.wbt_hi, j.wbt_lo = _p(wb.hi), _p(wb.lo), _p(wbt.hi), _p(wbt.lo)
-            j.in_dim, j.out_dim = in_dim, out_dim
+            j.in_dim, j.out_dim = W.shape
             out.append((wb, wbt, demod))
         check(lib.cips_modfc_prep_x3_batch(jobs, len(chunk), B, eps, _stream()), "cips_modfc_prep_x3_batch")
     return out
@@ -2091,16 +2059,14 @@ class InrHeadX3Function(torch.autograd.Function):
             raise RuntimeError("bf16x3 INR path needs pixels per image and feature width to be multiples of 32")
         dev = x0.device
         sp = ctx.single = INR_MODE == "bf16"
-        blocks = [tuple(_c(p.detach()) for p in params[4 * k:4 * k + 4]) for k in range(nblocks)]
-        # (T, tau) of the ToRGB tap of every block k >= 3; what follows them are the ports' handles
-        rgbp = [_c(p.detach()) for p in params[4 * nblocks:4 * nblocks + 2 * max(nblocks - 3, 0)]]
+        blocks, rgbp = _head_params(nblocks, params)
         _chk(x0, *[t for blk in blocks for t in blk], *rgbp)
         train = grad_mode and any(ctx.needs_input_grad)       # no-grad / inference: nothing kept
         x0P, _ = split_planes(x0, want_t=False)
         rgb = torch.empty(B, n, 3, device=dev)
         # modulate / demodulate / split every layer's weights up front, in one batch
         prepped = modfc_prep_x3_batch([(W, s_) for (W1, s1, W2, s2) in blocks for (W, s_) in ((W1, s1), (W2, s2))])
-        dbg = GATE_PIN is not None or GATE_REC is not None          # gate instrumentation (tests): bit planes always
+        dbg = gate_debug.active                                     # gate instrumentation (tests): bit planes always
         # every buffer is allocated here, before the first GEMM
         layers = []
         xP = x0P
@@ -2112,7 +2078,7 @@ class InrHeadX3Function(torch.autograd.Function):
             bits = (train or dbg) and cout % 32 == 0
             pin1 = _next_pin(B, n, cout, dev)
             pin2 = _next_pin(B, n, cout, dev)
-            if (pin1 is not None or GATE_REC is not None) and not bits:
+            if (pin1 is not None or gate_debug.rec is not None) and not bits:
                 raise RuntimeError("gate instrumentation needs layer widths that are multiples of 32")
             L.cin, L.cout, L.bits, L.skip = cin, cout, bits, (k >= 4) and (cin == cout)
             L.pinned1, L.pinned2 = pin1 is not None, pin2 is not None
@@ -2160,10 +2126,10 @@ class InrHeadX3Function(torch.autograd.Function):
             if k >= 3:
                 torgb_fwd_x3(L.oP, rgbp[2 * (k - 3)], rgbp[2 * (k - 3) + 1], rgb.view(B * n, 3), accumulate=not first_rgb)
                 first_rgb = False
-        if GATE_REC is not None:
+        if gate_debug.rec is not None:
             for L in layers:
-                GATE_REC.append(L.gate1)
-                GATE_REC.append(L.gate2)
+                gate_debug.rec.append(L.gate1)
+                gate_debug.rec.append(L.gate2)
         if nblocks <= 3:
             rgb.zero_()
         # kept for backward: every layer's input / a1 / output planes, both gates and the prepped weights
@@ -2251,7 +2217,7 @@ class InrHeadX3Function(torch.autograd.Function):
         for i, k in enumerate(range(nblocks - 1, -1, -1)):
             (dW2, ds2), (dW1, ds1) = res[2 * i], res[2 * i + 1]
             grads_blocks[k] = (dW1, ds1, dW2, ds2)
-        return (None, None, None, dx0) + tuple(g for gb in grads_blocks for g in gb) + tuple(grads_rgb)
+        return _head_grads(dx0, grads_blocks, grads_rgb)
 
 
 class TailPorts:

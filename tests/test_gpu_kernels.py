@@ -470,6 +470,40 @@ def test_modfc_prep_batch_forward_backward(shapes, B_):
     assert all(torch.equal(a, b) and torch.equal(c, e) for (a, c), (b, e) in zip(res_c, res_c2))
 
 
+def test_modfc_prep_single_entries_match_batch():
+    """The single-job entries (cips_modfc_prep_x3, cips_modfc_prep_bwd) always run the scalar 32-column kernels with a
+    one-job table.  Where out_dim % 4 != 0 the batch entries take the same kernels, so the two must agree bit for bit;
+    at (64, 96) the batch entries take the 16-byte forms, and the single entries are held to the fp64 autograd reference
+    of the modulate / demodulate rule instead."""
+    from cips3d_amd import ops
+    g = torch.Generator().manual_seed(15)
+    d = dev()
+    B_ = 3
+    for i, o in [(40, 30), (36, 50), (64, 96)]:
+        W = torch.randn(i, o, generator=g).requires_grad_(True)
+        s = (torch.randn(B_, i, generator=g) * 0.5).requires_grad_(True)
+        up = torch.randn(B_, i, o, generator=g)
+        Wd, sd, upd = W.detach().to(d), s.detach().to(d), up.to(d)
+        wbP, wbtP, dm_d = ops.modfc_prep_x3(Wd, sd)
+        dW, ds = ops.modfc_prep_bwd(Wd, sd, dm_d, upd)
+        if o % 4:
+            (wbB, wbtB, dmB), = ops.modfc_prep_x3_batch([(Wd, sd)])
+            assert torch.equal(dm_d, dmB)
+            assert torch.equal(wbP.hi, wbB.hi) and torch.equal(wbP.lo, wbB.lo)
+            assert torch.equal(wbtP.hi, wbtB.hi) and torch.equal(wbtP.lo, wbtB.lo)
+            (dWB, dsB), = ops.modfc_prep_bwd_batch([(Wd, sd, dmB, upd)])
+            assert torch.equal(dW, dWB) and torch.equal(ds, dsB)
+        else:
+            w = W.double().unsqueeze(0) * (s.double().unsqueeze(-1) + 1)
+            dm = torch.rsqrt(w.pow(2).sum([1]) + 1e-8)
+            wb = w * dm.unsqueeze(1)
+            (wb * up.double()).sum().backward()
+            assert max_rel(dm_d, dm.detach().float()) < 1e-5
+            assert rel_err(wbP.float(), wb.detach().float()) < 2e-5
+            assert rel_err(wbtP.float(), wb.detach().float().transpose(1, 2)) < 2e-5
+            assert rel_err(dW, W.grad) < 1e-4 and rel_err(ds, s.grad) < 1e-4
+
+
 def _planes(x):
     hi = x.bfloat16()
     lo = (x - hi.float()).bfloat16()
