@@ -202,6 +202,8 @@ SIGNATURES = {
     "cips_modfc_max_jobs": (i32, []),
     "cips_modfc_prep_x3_batch": (i32, [C.POINTER(ModfcPrepJob), i32, i32, C.c_float, vp]),
     "cips_modfc_prep_bwd_batch": (i32, [C.POINTER(ModfcBwdJob), i32, i32, vp]),
+    "cips_modfc_prep_x3_batch_form": (i32, [C.POINTER(ModfcPrepJob), i32, i32]),
+    "cips_modfc_prep_bwd_batch_form": (i32, [C.POINTER(ModfcBwdJob), i32, i32]),
     "cips_modfc_prep_bwd_batch_cores": (i32, [C.POINTER(ModfcBwdJob), i32, i32, vp]),
     "cips_cores_colsum_parts": (i32, []),
     "cips_opt_chunk": (i32, []),

@@ -427,6 +427,15 @@ struct BwdJobs {
   int in_dim[MAXJOBS], out_dim[MAXJOBS];
 };
 
+// The planes of the FLOAT32 value v: hi = bf16(v), lo = bf16(v - hi).  Where v is a product a * b, hipcc contracts the
+// remainder into fma(a, b, -hi), taken from the unrounded product: lo then keeps bits below v's last place (at in_dim = 1,
+// Wb = +-1, all of lo is such bits) and (hi, lo) is the split of no float32 at all.  Not here.
+__device__ __forceinline__ void split_f32(float v, unsigned short& h, unsigned short& l) {
+#pragma clang fp contract(off)
+  h = f2bf(v);
+  l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+}
+
 // ---- scalar batch forms ---------------------------------------------------------------------------------------
 // out[b][n] = WITH_G ? c_n = sum_k G_kn u_kn : demod = rsqrt(sum_k u_kn^2 + eps);  grid (out/32, B, jobs),
 // 256 threads = 32 columns x 8 k-groups, combined in group order through LDS
@@ -474,8 +483,7 @@ __global__ __launch_bounds__(256) void modfc_planes_batch_kernel(PrepJobs J, int
     unsigned short h = 0, l = 0;
     if (k < in_dim && n < out_dim) {
       const float v = W[(long long)k * out_dim + n] * (s[(long long)b * in_dim + k] + 1.f) * demod[(long long)b * out_dim + n];
-      h = f2bf(v);
-      l = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+      split_f32(v, h, l);
       wbh[base + (long long)k * out_dim + n] = h;
       wbl[base + (long long)k * out_dim + n] = l;
     }
@@ -566,10 +574,7 @@ __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, i
         const float sc = s[(long long)b * in_dim + k] + 1.f;
         const float v[4] = {w.x * sc * dm.x, w.y * sc * dm.y, w.z * sc * dm.z, w.w * sc * dm.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h[j] = f2bf(v[j]);
-          l[j] = f2bf(v[j] - __uint_as_float(((unsigned)h[j]) << 16));
-        }
+        for (int j = 0; j < 4; ++j) split_f32(v[j], h[j], l[j]);
         const long long o = base + (long long)k * out_dim + n;
         *reinterpret_cast<uint2*>(wbh + o) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
         *reinterpret_cast<uint2*>(wbl + o) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
@@ -866,31 +871,38 @@ struct JobDims {
   }
 };
 
-int fill_prep_jobs(const cips_modfc_prep_job* jobs, int njobs, int B, PrepJobs& J, ColJobs& Cj, JobDims& D) {
+// the dimensions of a job list, validated: all that the form queries read, and the first step of every table fill
+template <class Job>
+int job_dims(const Job* jobs, int njobs, int B, JobDims& D) {
   if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
   for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].in_dim <= 0 || jobs[i].out_dim <= 0) return (int)hipErrorInvalidValue;
+    D.add(jobs[i].in_dim, jobs[i].out_dim);
+  }
+  return (int)hipSuccess;
+}
+
+int fill_prep_jobs(const cips_modfc_prep_job* jobs, int njobs, int B, PrepJobs& J, ColJobs& Cj, JobDims& D) {
+  if (const int rc = job_dims(jobs, njobs, B, D)) return rc;
+  for (int i = 0; i < njobs; ++i) {
     const cips_modfc_prep_job& j = jobs[i];
-    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
     J.W[i] = Cj.W[i] = j.weight; J.s[i] = Cj.s[i] = j.s; J.demod[i] = Cj.out[i] = j.demod;
     J.wbh[i] = (unsigned short*)j.wb_hi; J.wbl[i] = (unsigned short*)j.wb_lo;
     J.wth[i] = (unsigned short*)j.wbt_hi; J.wtl[i] = (unsigned short*)j.wbt_lo;
     J.in_dim[i] = Cj.in_dim[i] = j.in_dim; J.out_dim[i] = Cj.out_dim[i] = j.out_dim;
-    D.add(j.in_dim, j.out_dim);
   }
   return (int)hipSuccess;
 }
 
 // need_out4: an out_dim that is no multiple of 4 is refused (the co-resident kernels have no scalar form)
 int fill_bwd_jobs(const cips_modfc_bwd_job* jobs, int njobs, int B, bool need_out4, BwdJobs& J, ColJobs& Cj, JobDims& D) {
-  if (!jobs || njobs <= 0 || njobs > MAXJOBS || B <= 0) return (int)hipErrorInvalidValue;
+  if (const int rc = job_dims(jobs, njobs, B, D)) return rc;
   for (int i = 0; i < njobs; ++i) {
     const cips_modfc_bwd_job& j = jobs[i];
-    if (j.in_dim <= 0 || j.out_dim <= 0) return (int)hipErrorInvalidValue;
     if (need_out4 && j.out_dim % 4) return (int)hipErrorNotSupported;
     J.W[i] = Cj.W[i] = j.weight; J.s[i] = Cj.s[i] = j.s; J.demod[i] = j.demod; J.G[i] = Cj.G[i] = j.gwb;
     J.cbuf[i] = Cj.out[i] = j.cbuf; J.dW[i] = j.dweight; J.ds[i] = j.ds;
     J.in_dim[i] = Cj.in_dim[i] = j.in_dim; J.out_dim[i] = Cj.out_dim[i] = j.out_dim;
-    D.add(j.in_dim, j.out_dim);
   }
   return (int)hipSuccess;
 }
@@ -1096,17 +1108,34 @@ extern "C" int cips_torgb_bwd_x_x3(const float* drgb, const float* w, const void
 
 extern "C" int cips_modfc_max_jobs(void) { return MAXJOBS; }
 
+// ---- the rule that selects the batch forms: the queries of cips3d_hip.h, and what the two batch entries switch on ------
+extern "C" int cips_modfc_prep_x3_batch_form(const cips_modfc_prep_job* jobs, int njobs, int B) {
+  JobDims D;
+  if (const int rc = job_dims(jobs, njobs, B, D)) return -rc;
+  return (D.out4 ? CIPS_MODFC_PREP_COLSUM16 : 0)                      // 16-byte lanes in the column reductions
+         | (D.out4 && D.in8 ? CIPS_MODFC_PREP_TILES64 : 0);           // 64 x 64 tiles with vector accesses
+}
+
+extern "C" int cips_modfc_prep_bwd_batch_form(const cips_modfc_bwd_job* jobs, int njobs, int B) {
+  JobDims D;
+  if (const int rc = job_dims(jobs, njobs, B, D)) return -rc;
+  if (!(D.out4 && B <= 64 && D.max_out <= 1024)) return CIPS_MODFC_BWD_SCALAR;
+  return D.max_out <= 512 ? CIPS_MODFC_BWD_FUSED2 : CIPS_MODFC_BWD_FUSED4;
+}
+
 extern "C" int cips_modfc_prep_x3_batch(const cips_modfc_prep_job* jobs, int njobs, int B, float eps, cips_stream_t stream) {
+  const int form = cips_modfc_prep_x3_batch_form(jobs, njobs, B);
+  if (form < 0) return -form;
   PrepJobs J = {};
   ColJobs Cj = {};
   JobDims D;
   if (const int rc = fill_prep_jobs(jobs, njobs, B, J, Cj, D)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (D.out4)                                    // 16-byte lanes in the column reductions
+  if (form & CIPS_MODFC_PREP_COLSUM16)
     hipLaunchKernelGGL(modfc_colsum4_batch_kernel<false>, dim3((D.max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, eps);
   else
     hipLaunchKernelGGL(modfc_colsum_batch_kernel<false>, dim3((D.max_out + 31) / 32, B, njobs), dim3(256), 0, st, Cj, eps);
-  if (D.out4 && D.in8)                           // 64 x 64 tiles with vector accesses when every job's shape allows
+  if (form & CIPS_MODFC_PREP_TILES64)
     hipLaunchKernelGGL(modfc_planes_batch64_kernel, dim3((D.max_out + 63) / 64, (D.max_in + 63) / 64, B * njobs), dim3(256), 0, st, J, B);
   else
     hipLaunchKernelGGL(modfc_planes_batch_kernel, dim3((D.max_out + 31) / 32, (D.max_in + 31) / 32, B * njobs), dim3(256), 0, st, J, B);
@@ -1114,15 +1143,17 @@ extern "C" int cips_modfc_prep_x3_batch(const cips_modfc_prep_job* jobs, int njo
 }
 
 extern "C" int cips_modfc_prep_bwd_batch(const cips_modfc_bwd_job* jobs, int njobs, int B, cips_stream_t stream) {
+  const int form = cips_modfc_prep_bwd_batch_form(jobs, njobs, B);
+  if (form < 0) return -form;
   BwdJobs J = {};
   ColJobs Cj = {};
   JobDims D;
   if (const int rc = fill_bwd_jobs(jobs, njobs, B, false, J, Cj, D)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!(D.out4 && B <= 64 && D.max_out <= 1024)) return launch_bwd_scalar(J, Cj, D, njobs, B, st);
+  if (form == CIPS_MODFC_BWD_SCALAR) return launch_bwd_scalar(J, Cj, D, njobs, B, st);
   // two reads of G instead of three (see modfc_prep_bwd_ws_batch_kernel)
   hipLaunchKernelGGL(modfc_colsum4_batch_kernel<true>, dim3((D.max_out + 63) / 64, B, njobs), dim3(256), 0, st, Cj, B, 0.f);
-  if (D.max_out <= 512)
+  if (form == CIPS_MODFC_BWD_FUSED2)
     hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<2>, dim3((D.max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);
   else
     hipLaunchKernelGGL(modfc_prep_bwd_ws_batch_kernel<4>, dim3((D.max_in + 3) / 4, njobs), dim3(256), 0, st, J, B);

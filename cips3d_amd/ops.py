@@ -1892,6 +1892,29 @@ def modfc_prep_x3_batch(layers, eps=1e-8):
     return out
 
 
+def _modfc_form(entry, job_type, shapes, B):
+    jobs = (job_type * max(len(shapes), 1))()
+    for j, (in_dim, out_dim) in zip(jobs, shapes):
+        j.in_dim, j.out_dim = in_dim, out_dim
+    code = getattr(_lib.load(), entry)(jobs, len(shapes), B)
+    if code < 0:
+        raise ValueError(f"{entry[:-5]} refuses these jobs (hipError {-code})")
+    return code
+
+
+def modfc_prep_x3_batch_form(shapes, B):
+    """which kernels one call of cips_modfc_prep_x3_batch runs for layers of these (in_dim, out_dim) shapes (at most
+    cips_modfc_max_jobs() of them: one chunk of modfc_prep_x3_batch), host only: bit 0 (CIPS_MODFC_PREP_COLSUM16) 16-byte
+    column sums, bit 1 (CIPS_MODFC_PREP_TILES64) 64 x 64 plane tiles; ValueError for jobs the entry point refuses"""
+    return _modfc_form("cips_modfc_prep_x3_batch_form", ModfcPrepJob, shapes, B)
+
+
+def modfc_prep_bwd_batch_form(shapes, B):
+    """the same for cips_modfc_prep_bwd_batch: 0 the scalar three-pass kernels, 2 / 4 the fused dW / ds pass of 2 / 4
+    chunks of 256 columns (CIPS_MODFC_BWD_*)"""
+    return _modfc_form("cips_modfc_prep_bwd_batch_form", ModfcBwdJob, shapes, B)
+
+
 def modfc_prep_bwd_batch(layers, cores=False):
     """layers: list of (W, s, demod, gwb) -> list of (dW, ds), all layers in three launches.  cores=True: the co-resident
     form (no LDS, <= 40 VGPRs: runs beside the fused SIREN backward when issued on a side stream; B <= 64, out % 4 == 0)."""

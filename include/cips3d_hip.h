@@ -702,6 +702,21 @@ typedef struct cips_modfc_bwd_job {
 int cips_modfc_max_jobs(void);
 int cips_modfc_prep_x3_batch(const cips_modfc_prep_job* jobs, int njobs, int B, float eps, cips_stream_t stream);
 int cips_modfc_prep_bwd_batch(const cips_modfc_bwd_job* jobs, int njobs, int B, cips_stream_t stream);
+/* Which kernels the two batch entries run for a job list (host only; the entry points switch on these very functions, so
+ * the rule exists once).  Only the jobs' in_dim / out_dim are read, no pointer of a job is dereferenced.  Negative: minus
+ * the hipError the entry point returns for these arguments.  Every form computes the same values up to the summation order;
+ * the queries let a test say which kernels a shape reached. */
+enum {
+  CIPS_MODFC_PREP_COLSUM16 = 1,        /* bit 0: 16-byte column sums (every out_dim % 4 == 0), else the 32-column scalar sums */
+  CIPS_MODFC_PREP_TILES64 = 2          /* bit 1: 64 x 64 plane tiles (also every in_dim % 8 == 0), else 32 x 32 tiles */
+};
+enum {
+  CIPS_MODFC_BWD_SCALAR = 0,           /* three passes over G (c, dW, ds): every shape */
+  CIPS_MODFC_BWD_FUSED2 = 2,           /* 16-byte column sums + ONE dW / ds pass of 2 chunks of 256 columns: every */
+  CIPS_MODFC_BWD_FUSED4 = 4            /*   out_dim % 4 == 0, B <= 64, largest out_dim <= 512; 4 chunks: <= 1024 */
+};
+int cips_modfc_prep_x3_batch_form(const cips_modfc_prep_job* jobs, int njobs, int B);
+int cips_modfc_prep_bwd_batch_form(const cips_modfc_bwd_job* jobs, int njobs, int B);
 /* Co-resident form of cips_modfc_prep_bwd_batch (same results up to the summation order): kernels without LDS and with
  * <= 40 VGPRs, which get wave slots BESIDE a kernel that owns the whole LDS (the fused SIREN backward) instead of waiting
  * for it — for a caller that runs this tail on a side stream.  cbuf must hold cips_cores_colsum_parts() planes of (B, out).

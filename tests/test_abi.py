@@ -283,3 +283,71 @@ def test_upfirdn2d_form_of_the_conv_branch_blur_and_of_other_kernels():
     assert _form(9, 9, 3, 2, (2, 2, 2, 2)) == "generic" and _form(9, 9, 3, 2, (2, 2, 2, 2), k=(5, 3)) == "generic"
     from cips3d_amd import _lib
     assert _lib.load().cips_upfirdn2d_form(16, 16, 1, 4, 4, 1, 1, 2, 1, 1, 1, 1, 1) == 1     # down_x != down_y
+
+
+# --------------------------------------------------------------------------------------
+# cips_modfc_prep_x3_batch_form / cips_modfc_prep_bwd_batch_form: the dispatch rule of the two batch entries of the INR head's
+# modulate / demodulate prep, the very functions the entry points switch on
+# --------------------------------------------------------------------------------------
+def test_modfc_batch_form_codes_agree_with_the_header():
+    txt = open(os.path.join(ROOT, "include", "cips3d_hip.h")).read()
+    prep = {n: int(v) for n, v in re.findall(r"CIPS_MODFC_PREP_([A-Z0-9_]+) = (\d+)", txt)}
+    bwd = {n: int(v) for n, v in re.findall(r"CIPS_MODFC_BWD_([A-Z0-9_]+) = (\d+)", txt)}
+    assert prep == {"COLSUM16": 1, "TILES64": 2} and bwd == {"SCALAR": 0, "FUSED2": 2, "FUSED4": 4}
+
+
+def test_modfc_batch_forms_follow_the_rule():
+    """every out_dim % 4 == 0 -> 16-byte column sums; also every in_dim % 8 == 0 -> 64 x 64 tiles; backward: the fused pass
+    for every out_dim % 4 == 0, B <= 64 and the largest out_dim <= 512 (2 chunks) or <= 1024 (4 chunks).  The rule is over
+    the whole job list: one job that breaks a condition moves every job of the call."""
+    from cips3d_amd import ops
+    pf, bf = ops.modfc_prep_x3_batch_form, ops.modfc_prep_bwd_batch_form
+    assert pf([(512, 512)], 4) == 3 and pf([(8, 4)], 1) == 3 and pf([(72, 1028)], 2) == 3        # no limit on out_dim or B here
+    assert pf([(512, 512)], 65) == 3 and pf([(32, 512), (512, 512), (512, 512)] * 8, 4) == 3     # 24 jobs: the head's 18 and more
+    assert pf([(36, 520)], 3) == 1 and pf([(36, 520), (8, 4)], 3) == 1 and pf([(4, 8), (8, 4)], 2) == 1   # an in_dim % 8 != 0
+    assert pf([(64, 96), (40, 30)], 3) == 0 and pf([(33, 33)], 2) == 0 and pf([(40, 3)], 3) == 0
+    assert pf([(8, 6)], 2) == 0                                       # in_dim % 8 == 0 alone selects nothing: bit 1 never without bit 0
+    assert bf([(512, 512)], 4) == 2 and bf([(5, 4)], 1) == 2 and bf([(32, 512), (512, 512)], 64) == 2
+    assert bf([(8, 516)], 2) == 4 and bf([(8, 516), (8, 1024)], 2) == 4 and bf([(128, 1024)], 64) == 4
+    assert bf([(8, 1028)], 2) == 0 and bf([(8, 4), (8, 1028)], 2) == 0                           # largest out_dim above 1024
+    assert bf([(16, 64)], 64) == 2 and bf([(16, 64)], 65) == 0                                   # lane b keeps image b: B <= 64
+    assert bf([(64, 96), (40, 30)], 3) == 0 and bf([(1, 7)], 1) == 0                             # an out_dim % 4 != 0
+    assert bf([(7, 8)], 2) == 2                                                                  # in_dim does not matter here
+
+
+def test_modfc_batch_forms_refuse_what_the_entries_refuse():
+    """no launch is reached: the queries never launch, and the entry points return before they do"""
+    import ctypes
+    from cips3d_amd import _lib, ops
+    lib = _lib.load()
+    INVALID = 1
+    mx = lib.cips_modfc_max_jobs()
+    assert mx == 24
+    for form, entry, job_type, wrapper in [
+            (lib.cips_modfc_prep_x3_batch_form, lambda j, n, B: lib.cips_modfc_prep_x3_batch(j, n, B, 1e-8, None), _lib.ModfcPrepJob,
+             ops.modfc_prep_x3_batch_form),
+            (lib.cips_modfc_prep_bwd_batch_form, lambda j, n, B: lib.cips_modfc_prep_bwd_batch(j, n, B, None), _lib.ModfcBwdJob,
+             ops.modfc_prep_bwd_batch_form)]:
+        jobs = (job_type * (mx + 1))()
+        for j in jobs:
+            j.in_dim, j.out_dim = 8, 4            # every pointer stays NULL: the query reads none of them
+        assert form(jobs, mx, 2) >= 0 and form(jobs, 1, 1) >= 0
+        for n, B in [(0, 2), (-1, 2), (mx + 1, 2), (1, 0), (1, -3)]:
+            assert form(jobs, n, B) == -INVALID and entry(jobs, n, B) == INVALID, (n, B)
+        assert form(None, 1, 2) == -INVALID and entry(None, 1, 2) == INVALID
+        for bad in [(0, 4), (8, 0), (-8, 4)]:
+            jobs[1].in_dim, jobs[1].out_dim = bad
+            assert form(jobs, 2, 2) == -INVALID and entry(jobs, 2, 2) == INVALID, bad
+            assert form(jobs, 1, 2) >= 0                              # ... a job past njobs is not read
+        with pytest.raises(ValueError):
+            wrapper([(8, 4), (0, 4)], 2)
+        with pytest.raises(ValueError):
+            wrapper([(8, 4)] * (mx + 1), 2)
+        with pytest.raises(ValueError):
+            wrapper([], 2)
+    # the co-resident entry keeps its own refusals (it has one form)
+    jobs = (_lib.ModfcBwdJob * 1)()
+    jobs[0].in_dim, jobs[0].out_dim = 16, 64
+    assert lib.cips_modfc_prep_bwd_batch_cores(jobs, 1, 65, None) == 801
+    jobs[0].out_dim = 30
+    assert lib.cips_modfc_prep_bwd_batch_cores(jobs, 1, 2, None) == 801

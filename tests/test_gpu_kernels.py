@@ -438,6 +438,10 @@ def test_modfc_prep_batch_forward_backward(shapes, B_):
     every out_dim is a multiple of 4 (B <= 64, out_dim <= 1024), the scalar three-pass kernels otherwise — both against
     torch autograd of the modulate / demodulate rule (exp/comm/models/mod_conv_fc.py:19-120)."""
     from cips3d_amd import ops
+    # the forms these four batches reach (ops.modfc_prep_x3_batch_form / modfc_prep_bwd_batch_form, by hand from the rule):
+    # 16-byte sums with 32 x 32 tiles (in 36) and 4 chunks | everything 16-byte, 2 chunks | all scalar | B 70: scalar backward
+    want = {5: (1, 4), 64: (3, 2), 3: (0, 0), 70: (3, 0)}[B_]
+    assert (ops.modfc_prep_x3_batch_form(shapes, B_), ops.modfc_prep_bwd_batch_form(shapes, B_)) == want
     g = torch.Generator().manual_seed(14)
     d = dev()
     Ws = [torch.randn(i, o, generator=g).requires_grad_(True) for i, o in shapes]
