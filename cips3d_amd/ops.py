@@ -696,10 +696,10 @@ def _siren_backward_staged(t, dfeat, dsigma, B, P, points, f32):
                                       _p(dac.hi), _p(dac.lo), _p(red), B, P, _stream()), "cips_siren_bwd_data")
     R = red.view(B, rows // B, 868).sum(1)          # (B, 868) deterministic reduction of partial rows
 
-    def contract(A, Bm, M, N, batch):
-        """(batch, M, N) = A^T @ Bm per chunk of BP / batch rows (split-K): A (BP, M), Bm (BP, N) row-major, i.e. K-major;
+    def contract(A, Bm, M, N, batch, rows=BP):
+        """(batch, M, N) = A^T @ Bm per chunk of rows / batch rows (split-K): A (rows, M), Bm (rows, N) row-major, i.e. K-major;
         Planes on the bf16x3 K-major GEMM, fp32 tensors on the fp32 GEMM"""
-        Kc = BP // batch
+        Kc = rows // batch
         G = torch.empty(batch, M, N, device=dev)
         if isinstance(A, Planes):
             gemm_x3_km(A, Bm, M, N, Kc, M, N, batch, Kc * M, Kc * N, G)
@@ -708,10 +708,20 @@ def _siren_backward_staged(t, dfeat, dsigma, B, P, points, f32):
         return G
 
     sp = _split_k(P, 16)                             # per image: K = P
+    if not f32 and (P // sp) % 32:
+        # the bf16x3 K-major GEMM takes K in whole 32-row granules: a P off the granule contracts the staged planes on the fp32
+        # GEMM (any K), as the dwf line below does at every P
+        da2, h1, dac, h2 = da2.float(), h1.float(), dac.float(), h2.float()
     G1 = contract(da2, h1, 128, 128, B * sp).view(B, sp, 128, 128).sum(1)
     Gc = contract(dac, h2, 64, 128, B * sp).view(B, sp, 64, 128).sum(1)
-    # the 32x64 colour-linear gradient (no per-image scale) stays on the fp32 GEMM in both modes
-    dwf = contract(dfeat, hc if f32 else hc.float(), 32, 64, _split_k(BP, 1024)).sum(0)
+    # the 32x64 colour-linear gradient (no per-image scale) stays on the fp32 GEMM in both modes.  B * P off the 32-row granule:
+    # _split_k finds no split there, and all rows in ONE fp32 accumulation chain cost accuracy with its length (2 x 1029 points:
+    # 4.4 x the error of a blocked fp32 sum) — the whole granules are split as ever, the last rows (< 32) make one more term.
+    # (A count of granules without a divisor <= 1024, a prime one for instance, still leaves _split_k at 1 and one long chain.)
+    dfr, hcf, main = dfeat.view(BP, 32), hc if f32 else hc.float(), BP - BP % 32
+    dwf = contract(dfr, hcf, 32, 64, _split_k(main, 1024), main).sum(0) if main else 0
+    if main < BP:
+        dwf = dwf + contract(dfr[main:], hcf[main:], 32, 64, 1, BP - main)[0]
     # ---- assemble parameter / FiLM gradients (tiny tensors) ----
     g0, g1, gc = t["g0"], t["g1"], t["gc"]
     w0, b0, w1, b1, wc, bc = t["w0"], t["b0"], t["w1"], t["b1"], t["wc"], t["bc"]

@@ -90,7 +90,9 @@ def _siren_inputs(seed, b, P):
 @pytest.mark.parametrize("trig", [0, 1])
 @pytest.mark.parametrize("b,P", [(2, 32 * 7 + 5), (3, 4096 + 64)])
 def test_siren_forward(trig, b, P, monkeypatch):
-    """exact fp32 MFMA forward (CIPS_SIREN_FWD=f32)"""
+    """exact fp32 MFMA forward (CIPS_SIREN_FWD=f32) through the generator module, vs the fp32 CPU oracle.  The numerical anchor of
+    the SIREN kernels is tests/test_gpu_siren_fp64.py (fp64 truth, bars at the class of each form's arithmetic); this loose bar
+    ties the module's call path to the oracle."""
     from cips3d_amd import ops
     monkeypatch.setattr(ops, "SIREN_FWD_MODE", "f32")
     G, pts, style = _siren_inputs(3, b, P)
@@ -113,7 +115,8 @@ def test_siren_forward(trig, b, P, monkeypatch):
 
 @pytest.mark.parametrize("trig,b,P", [(1, 2, 2048 + 96), (0, 3, 128 * 7 + 5), (1, 1, 4096 * 3)])
 def test_siren_forward_x3(trig, b, P, monkeypatch):
-    """split-bf16 forward (default) vs the fp32 CPU oracle"""
+    """split-operand forward (default) through the generator module, vs the fp32 CPU oracle.  The numerical anchor is
+    tests/test_gpu_siren_fp64.py; this loose bar ties the module's call path to the oracle."""
     from cips3d_amd import ops
     monkeypatch.setattr(ops, "SIREN_FWD_MODE", "x3")
     G, pts, style = _siren_inputs(4, b, P)
@@ -147,7 +150,8 @@ def test_siren_forward_x3_sigma_is_fp32_class(scale_w, monkeypatch):
     error is measured against an fp64 evaluation next to the fp32 oracle's own: the product has to be in the oracle's class
     (<= 2x its rms distance from fp64 + 2e-7), where the bf16 planes of rounds 1-4 sat 5-10x above it.  scale_w rescales
     W1 / Wc / Wf and compensates in the FiLM gains' biases so that the function stays in range: the images must not depend on
-    the magnitude of the weights (fp16 has 5 exponent bits; the scale is chosen per matrix in-kernel)."""
+    the magnitude of the weights (fp16 has 5 exponent bits; the scale is chosen per matrix in-kernel).  The same rule, with a peak
+    bar, more regimes and the tail shapes, is held in tests/test_gpu_siren_fp64.py, the numerical anchor of these kernels."""
     from cips3d_amd import ops
     monkeypatch.setattr(ops, "SIREN_FWD_MODE", "x3")
     b, P = 2, 4096 * 2 + 160
@@ -194,7 +198,9 @@ def test_siren_backward(trig, mode, b, P, monkeypatch):
     """fused bf16x3 backward ("x3", default) and the staged data-pass + GEMM forms (split-bf16 "staged", all-fp32
     "staged_f32"), vs the fp32 CPU oracle's autograd.  P = 2240 = 2048 + 192: two data-pass chunks per image, the second
     ragged, and the staged contractions really split K (_split_k(2240, 16) == 14, _split_k(2 * 2240, 1024) == 140; at
-    P = 2144 the per-image split count is 1)."""
+    P = 2144 the per-image split count is 1).  The numerical anchor of every backward form is tests/test_gpu_siren_fp64.py
+    (each of the 16 gradients against fp64, at the class of the form's arithmetic); this loose bar ties the module's call path
+    and the FiLM linears behind it to the oracle."""
     from cips3d_amd import ops
     monkeypatch.setattr(ops, "SIREN_BWD_MODE", mode)
     G, pts, style = _siren_inputs(4, b, P)
