@@ -118,6 +118,8 @@ SIGNATURES = {
     "cips_siren_sigma_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, i32, vp]),
     "cips_siren_sigma_grad_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, i32, vp]),
     "cips_siren_sigma_grad_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, vp, i32, vp]),
+    "cips_siren_rgb_x3": (i32, [C.POINTER(SirenWeights), vp, vp, vp, i32, vp, vp, i32, i32, vp]),
+    "cips_siren_rgb_x3_grid": (i32, [C.POINTER(SirenWeights), C.POINTER(GridParams), vp, vp, i32, vp, vp, i32, vp]),
     "cips_siren_surface_x3": (i32, [C.POINTER(SirenWeights), C.POINTER(RayParams), f32, i32, vp, vp, vp, vp, vp, i32, vp]),
     "cips_mesh_scratch_bytes": (i64, [C.POINTER(GridParams), i32]),
     "cips_mesh_count": (i32, [C.POINTER(GridParams), vp, f32, i32, vp, i64, vp, vp]),

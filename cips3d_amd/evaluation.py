@@ -96,10 +96,13 @@ def density_lattice(N, cube_length, center):
     return tuple(idx * (cube_length / (N - 1)) + (c - cube_length / 2) for c in center)
 
 
-def save_ply(path, vertices, faces, normals=None):
+def save_ply(path, vertices, faces, normals=None, colors=None):
     """One triangle mesh (GeneratorNerfINR.extract_mesh, ops.mesh_from_volume) as a binary little-endian PLY file: vertices
-    (V, 3) as float x y z, normals (V, 3) as float nx ny nz when given, faces (T, 3) as `list uchar int vertex_indices`.
-    Tensors on any device or arrays.  (No .mrc writer: see DESIGN.md section 6.)"""
+    (V, 3) as float x y z, normals (V, 3) as float nx ny nz when given, colors (V, 3) in [-1, 1] (extract_mesh(colors=...)) as
+    uchar red green blue when given, faces (T, 3) as `list uchar int vertex_indices`.  Colours are quantised by image_to_u8's
+    rule for value_range (-1, 1), in fp32 with every step rounded on its own: clamp, (c + 1) * 0.5, * 255, + 0.5, clamp to
+    [0, 255], truncate.  Tensors on any device or arrays.  Without colors the file is what it was before colours existed, byte
+    for byte.  (No .mrc writer: see DESIGN.md section 6.)"""
     import numpy as np
 
     def host(t, dtype):
@@ -115,6 +118,19 @@ def save_ply(path, vertices, faces, normals=None):
             raise ValueError("save_ply: normals must have the vertices' shape")
         cols.append(n)
         props += ["property float nx", "property float ny", "property float nz"]
+    body = np.ascontiguousarray(np.concatenate(cols, 1))
+    if colors is not None:
+        c = host(colors, "<f4")
+        if c.shape != v.shape:
+            raise ValueError("save_ply: colors must have the vertices' shape")
+        one, half = np.float32(1.), np.float32(0.5)
+        q = (np.clip(c, -one, one) + one) * half
+        q = np.clip(q * np.float32(255.) + half, np.float32(0.), np.float32(255.)).astype("u1")
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+        packed = np.empty(len(v), dtype=[("f", "<f4", (body.shape[1],)), ("c", "u1", (3,))])      # one vertex, no padding
+        packed["f"] = body
+        packed["c"] = q
+        body = packed
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", *props, f"element face {len(f)}",
               "property list uchar int vertex_indices", "end_header"]
     rows = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
@@ -122,21 +138,27 @@ def save_ply(path, vertices, faces, normals=None):
     rows["i"] = f
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write(np.ascontiguousarray(np.concatenate(cols, 1)).tobytes())
+        fh.write(body.tobytes())
         fh.write(rows.tobytes())
 
 
 @torch.no_grad()
-def shade_surface(surface, light=(0., 0., 1.), ambient=0.2):
+def shade_surface(surface, light=(0., 0., 1.), ambient=0.2, albedo=False):
     """A picture of GeneratorNerfINR.surface's result for save_image / save_images: Lambert shading of the normals,
     ambient + (1 - ambient) * max(0, n . l) with l = light / |light| (world space), mapped to [-1, 1] and repeated over three
-    channels -> (b, 3, H, W); -1 (black) where mask == 0, the rays that cross no surface."""
+    channels -> (b, 3, H, W); -1 (black) where mask == 0, the rays that cross no surface.
+    albedo=True with surface.rgb present (GeneratorNerfINR.surface_colored): the Lambert factor multiplies the colour instead of white —
+    (rgb + 1) / 2 in [0, 1] times the factor, mapped back to [-1, 1]; the background stays -1.  Without .rgb, or by default,
+    the grey picture."""
     if surface.normals is None:
         raise ValueError("shade_surface needs normals (GeneratorNerfINR.surface(..., normals=True))")
     n = surface.normals
     l = torch.tensor(light, dtype=n.dtype, device=n.device)
     l = l / l.norm()
     lambert = (n * l.view(1, 3, 1, 1)).sum(1, keepdim=True).clamp(0., 1.)
+    if albedo and getattr(surface, "rgb", None) is not None:
+        shade = (surface.rgb.clamp(-1., 1.) + 1.) * 0.5 * (ambient + (1. - ambient) * lambert) * 2. - 1.
+        return torch.where(surface.mask == 0, torch.full_like(shade, -1.), shade.clamp(-1., 1.)).contiguous()
     shade = (ambient + (1. - ambient) * lambert) * 2. - 1.
     shade = torch.where(surface.mask == 0, torch.full_like(shade, -1.), shade.clamp(-1., 1.))
     return shade.expand(-1, 3, -1, -1).contiguous()

@@ -308,6 +308,33 @@ class NeRFNetwork(nn.Module):
         return self._density_call(style_dict, lambda *siren: ops.siren_sigma_grad_grid(gx, gy, gz, *siren),
                                   lambda styles: self._unfused_lattice(gx, gy, gz, styles, True))
 
+    def _unfused_color(self, points, style_dict, proj_w, proj_b, tanh):
+        """the colour entry points on tensor operations (other widths / depths) -> rgb (b,P,3), sigma (b,P)"""
+        feat, sigma = self._evaluate_unfused(points, style_dict)
+        y = F.linear(feat, proj_w, proj_b)
+        return (torch.tanh(y) if tanh else y), sigma
+
+    def color(self, points, style_dict, proj_w, proj_b, tanh=True):
+        """points (b,P,3) -> rgb (b,P,3) = [tanh](proj_w . feat + proj_b) of evaluate()'s 32 colour features, no gradient: the
+        point-colour HIP kernel for the shipped shape (ops.siren_rgb: the projection happens in the forward kernel's registers,
+        neither the features nor a second launch exist), tensor operations for other widths / depths.  proj_w (3,32), proj_b
+        (3): GeneratorNerfINR's auxiliary RGB layer, or any 32 -> 3 map.  Unlike the density family it needs the colour style."""
+        with torch.no_grad():
+            if not self.fused:
+                return self._unfused_color(points, style_dict, proj_w, proj_b, tanh)[0]
+            return ops.siren_rgb(points, proj_w, proj_b, *self._siren_args(style_dict), tanh=tanh)
+
+    def color_lattice(self, gx, gy, gz, style_dict, proj_w, proj_b, tanh=True, sigma=False):
+        """color() over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> rgb (b, nx, ny, nz, 3), with
+        sigma=True (rgb, sigma (b, nx, ny, nz)), sigma density_lattice()'s bit for bit; the fused kernel reads the coordinates
+        themselves, no points tensor is built"""
+        with torch.no_grad():
+            if self.fused:
+                return ops.siren_rgb_grid(gx, gy, gz, proj_w, proj_b, *self._siren_args(style_dict), tanh=tanh, sigma=sigma)
+            b, n = style_dict[f'{self.name_prefix}_w0'].shape[0], (len(gx), len(gy), len(gz))
+            rgb, sig = self._unfused_color(ops.lattice_points(gx, gy, gz, b), style_dict, proj_w, proj_b, tanh)
+            return (rgb.reshape(b, *n, 3), sig.reshape(b, *n)) if sigma else rgb.reshape(b, *n, 3)
+
     def surface_rays(self, style_dict, geom, xg, yg, zg, cam2world, level, refine):
         """The iso-surface sigma = level along the unjittered camera rays -> depth (b,n), hit (b,n) uint8, sigma (b,n), points
         (b,n,3), no gradient (the rule: ops.siren_surface).  The ray-cast HIP kernel for the shipped shape on the split-operand
@@ -1186,6 +1213,68 @@ class GeneratorNerfINR(nn.Module):
         density_grid's style handling and truncation, NeRFNetwork.density_gradient's kernel."""
         return self.siren.density_gradient(points, self._nerf_styles(self._density_styles(zs['z_nerf'], psi)))
 
+    # ---- the colour of the shape ----
+    # False: the styles of an 'aux' colour come from the NeRF mapping network alone (_density_styles).  generator_v1 sets it: its
+    # colour style nerf_rgb is a head of the INR mapping network, so both networks run for any colour
+    _color_style_from_inr = False
+    _COLOR_MODES = ('aux', 'head')
+
+    def _check_color_mode(self, who, mode, img_size, none_ok=False):
+        if not ((none_ok and mode is None) or mode in self._COLOR_MODES):
+            raise ValueError(f"GeneratorNerfINR.{who}: colours are {'None, ' if none_ok else ''}'aux' or 'head', got {mode!r}")
+        if mode == 'head' and img_size is None:
+            raise ValueError(f"GeneratorNerfINR.{who}: 'head' colours need img_size (it selects the depth of the INR head)")
+        if mode == 'head' and img_size < 32:
+            raise ValueError(f"GeneratorNerfINR.{who}: 'head' colours need img_size >= 32 (block \"32\" is the first of the INR "
+                             f"head with a ToRGB layer: a shallower head has no colour), got {img_size}")
+
+    def _color_styles(self, zs, psi, mode):
+        """zs -> the styles of a colour query.  'aux': the density entry points' (_density_styles: only the NeRF mapping network,
+        for psi < 1 an average of its own over 10 000 draws) unless _color_style_from_inr; 'head', or that flag: forward()'s —
+        both mapping networks, joined, for psi < 1 truncated towards generate_avg_frequencies' average (which it stores)"""
+        if mode == 'head' or self._color_style_from_inr:
+            return self._nerf_styles(self._truncate(self.mapping_network(**zs), psi))
+        return self._nerf_styles(self._density_styles(zs['z_nerf'], psi))
+
+    def _colors_at(self, points, style_dict, mode, img_size):
+        """rgb (b,P,3) in [-1, 1] at world-space points (b,P,3) for styles of _color_styles: 'aux' the point-colour kernel with
+        the auxiliary RGB layer's Linear (its Tanh is the kernel's), 'head' the SIREN's features as pixels through the INR head"""
+        if mode == 'aux':
+            return self.siren.color(points, style_dict, self.aux_to_rbg[0].weight, self.aux_to_rbg[0].bias, tanh=True)
+        feat, _ = self.siren.evaluate(points, style_dict)
+        return self.inr_net(feat, style_dict, img_size=img_size)
+
+    @torch.no_grad()
+    def point_colors(self, zs, points, psi=1.0, mode='aux', img_size=None):
+        """The colour of the generator's radiance field at arbitrary world-space points (b,P,3) -> (b,P,3) fp32 in [-1, 1], no
+        grad_fn.
+          'aux'   tanh(W_a f(x) + b_a) with the SIREN's 32 colour features f and aux_to_rbg's Linear, from the point-colour
+                  kernel (NeRFNetwork.color).  The auxiliary image is tanh(W_a sum_k w_k f_k + b_a); the map is affine and under
+                  last_back a ray's weights sum to one, so that image is the volume rendering of this per-point field.  Only
+                  the NeRF mapping network runs (generator_v1: both, its colour style comes from the INR one); psi < 1
+                  truncates as density_grid does, with the same draws.
+          'head'  the features of the points as (b,P,32) "pixels" through the CIPS head with the styles of zs['z_inr'], for
+                  checkpoints trained without the auxiliary image.  img_size is required: it selects the head's depth (forward()
+                  runs all nine blocks, img_size=1024) and must be at least 32, the first block with a ToRGB layer.  Both mapping networks run; psi < 1 truncates both towards
+                  generate_avg_frequencies' average, as forward() does, with its draws.  Any P."""
+        self._gpu_only('point_colors')
+        self._check_color_mode('point_colors', mode, img_size)
+        return self._colors_at(points, self._color_styles(zs, psi, mode), mode, img_size)
+
+    @torch.no_grad()
+    def color_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, return_sigma=False):
+        """The 'aux' point colour (point_colors) on density_grid's N^3 lattice -> (b, N, N, N, 3) fp32 in [-1, 1]; with
+        return_sigma=True -> (rgb, sigma (b, N, N, N)), sigma density_grid's bit for bit from the same launch.  The lattice
+        kernel reads the three coordinate arrays: no points tensor and no (b, N^3, 32) feature tensor exist.  Auxiliary colours
+        only: the INR head over 16.7 M points per image is out of scope (colour a mesh's vertices with extract_mesh(colors=
+        'head') or point_colors instead).  Styles, truncation and RNG draws: density_grid's (generator_v1: forward()'s)."""
+        from .evaluation import density_lattice
+        self._gpu_only('color_grid')
+        style_dict = self._color_styles(zs, psi, 'aux')
+        gx, gy, gz = (g.to(zs['z_nerf'].device) for g in density_lattice(resolution, cube_length, center))
+        return self.siren.color_lattice(gx, gy, gz, style_dict, self.aux_to_rbg[0].weight, self.aux_to_rbg[0].bias, tanh=True,
+                                        sigma=return_sigma)
+
     @torch.no_grad()
     def geometry(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                  h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, clamp_mode='relu', white_back=False,
@@ -1243,16 +1332,52 @@ class GeneratorNerfINR(nn.Module):
         `level` has no default (as in extract_mesh, whose mesh this is a view of).  Only the NeRF mapping network runs.  Random
         numbers: as geometry() — the draws and the camera are draw_randoms / camera_setup on the RenderSettings of a
         non-hierarchical forward() with nerf_noise = 0, so a seed gives the camera of the image it renders and the generators
-        are left where forward() leaves them; the jitter is drawn and not used."""
-        device = self._gpu_only('surface')
+        are left where forward() leaves them; the jitter is drawn and not used.  surface_colored() is this call with the colour
+        of the surface points next to it."""
+        return self._surface('surface', None, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
+                             v_mean, psi, sample_dist, camera_pos, camera_lookup, up_vector, refine, normals, rand_override)
+
+    @torch.no_grad()
+    def surface_colored(self, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean=math.pi * 0.5,
+                        v_mean=math.pi * 0.5, psi=1, sample_dist=None, camera_pos=None, camera_lookup=None, up_vector=None,
+                        refine=8, normals=True, rand_override=None, colors='aux'):
+        """surface() with the colour of the surface: its arguments and `colors` ('aux' or 'head'; None is surface() itself) ->
+        surface()'s SimpleNamespace and
+          rgb     (b,3,H,W)  point_colors' colour of that mode at `points` (for 'head' the INR head at depth img_size, which
+                             must be at least 32), exactly -1 where mask == 0; evaluation.shade_surface(albedo=True) shades it
+        An entry point of its own because surface()'s signature is part of the public contract (it is listed parameter by
+        parameter in tests/test_render_settings_cpu.py).  Random numbers and styles: 'aux' makes surface()'s draws, runs only the
+        NeRF mapping network and returns surface()'s other fields bit for bit.  'head' — and 'aux' on generator_v1, whose colour
+        style is a head of the INR mapping network — takes forward()'s styles instead: both mapping networks run, and psi < 1
+        draws the 10 000 latents as generate_avg_frequencies does (storing its average) and truncates the NeRF and the INR
+        styles alike, before the draws of the camera; the other fields are then those of the truncated shape forward() renders
+        (for psi = 1: surface()'s)."""
+        return self._surface('surface_colored', colors, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
+                             h_mean, v_mean, psi, sample_dist, camera_pos, camera_lookup, up_vector, refine, normals, rand_override)
+
+    def _surface(self, who, colors, zs, level, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, psi,
+                 sample_dist, camera_pos, camera_lookup, up_vector, refine, normals, rand_override):
+        """surface() (colors None) and surface_colored(): the settings, the styles and the camera in forward()'s order, the ray
+        cast, the normals and, when asked for, the colours at the surface points"""
+        device = self._gpu_only(who)
+        self._check_color_mode(who, colors, img_size, none_ok=True)
         s, b, H = RenderSettings.of(locals(), hierarchical_sample=False, nerf_noise=0.), zs['z_nerf'].shape[0], img_size
-        nerf_styles, _, _, cam2world, pitch_yaw = self._density_camera(s, zs, psi, device)
+        if colors is None:
+            nerf_styles, _, _, cam2world, pitch_yaw = self._density_camera(s, zs, psi, device)
+        else:
+            nerf_styles = self._color_styles(zs, psi, colors)
+            d = draw_randoms(s, b, device)
+            _, cam2world, pitch_yaw = camera_setup(s, d.theta, d.phi, b, device)
         xg, yg, zg = ops.pixel_grids(H, H, num_steps, ray_start, ray_end, device)
         depth, hit, sigma, points = self.siren.surface_rays(nerf_styles, ops.RayGeom(b, H, H, num_steps, _zc(fov)), xg, yg, zg,
                                                             cam2world, level, refine)
         nrm = _unit_normals(self.siren.density_gradient(points, nerf_styles)[1], hit) if normals else None
-        return SimpleNamespace(depth=_maps(depth, b, H), mask=_maps(hit, b, H), points=_maps(points, b, H),
-                               sigma=_maps(sigma, b, H), normals=_maps(nrm, b, H) if normals else None, pitch_yaw=pitch_yaw)
+        out = SimpleNamespace(depth=_maps(depth, b, H), mask=_maps(hit, b, H), points=_maps(points, b, H),
+                              sigma=_maps(sigma, b, H), normals=_maps(nrm, b, H) if normals else None, pitch_yaw=pitch_yaw)
+        if colors is not None:
+            rgb = self._colors_at(points, nerf_styles, colors, img_size)
+            out.rgb = _maps(torch.where(hit.unsqueeze(-1) != 0, rgb, rgb.new_full((), -1.)), b, H)
+        return out
 
     @torch.no_grad()
     def density_grid(self, zs, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, return_gradient=False):
@@ -1276,28 +1401,44 @@ class GeneratorNerfINR(nn.Module):
         return self.siren.density_lattice(gx, gy, gz, self._nerf_styles(style_dict))
 
     @torch.no_grad()
-    def extract_mesh(self, zs, level, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, normals=True):
+    def extract_mesh(self, zs, level, resolution=256, cube_length=0.3, center=(0., 0., 0.), psi=1.0, normals=True, colors=None,
+                     img_size=None):
         """The surface sigma = level of density_grid's volume as one indexed triangle mesh per image -> a list of
         SimpleNamespace(vertices (V, 3) fp32, faces (T, 3) int32, normals (V, 3) fp32 or None), all on the GPU; the volume never
         leaves it (ops.mesh_from_volume: marching tetrahedra, one host synchronisation for the mesh sizes).  `level` has no
         default: the right iso-value depends on the checkpoint.  The volume is density_grid's for the same arguments — same
         styles, truncation and RNG draws (psi < 1 draws the 10 000 latents once).  Triangles are wound so that their geometric
         normal points towards lower density; `normals` are -grad sigma / |grad sigma| at the vertices from
-        NeRFNetwork.density_gradient with that image's styles, exact zeros where the gradient is zero (as in geometry)."""
+        NeRFNetwork.density_gradient with that image's styles, exact zeros where the gradient is zero (as in geometry).
+        colors: None, 'aux' or 'head' — each mesh also gets .colors (V, 3) fp32 in [-1, 1], point_colors' colour of that mode at
+        its vertices with that image's latents ((0, 3) for an empty mesh; 'head' needs img_size, see point_colors;
+        evaluation.save_ply writes them).  With colors=None the result and the RNG draws are unchanged, and there is no .colors.
+        'aux' changes neither geometry nor draws (generator_v1 excepted: its colour style needs the INR mapping network, so
+        there, as with 'head' everywhere, the styles are forward()'s — both mapping networks, and psi < 1 draws and truncates as
+        forward() does, the shape's styles included)."""
         from .evaluation import density_lattice
         device = zs['z_nerf'].device
-        nerf_styles = self._nerf_styles(self._density_styles(zs['z_nerf'], psi))
+        self._check_color_mode('extract_mesh', colors, img_size, none_ok=True)
+        if colors is None:
+            nerf_styles = self._nerf_styles(self._density_styles(zs['z_nerf'], psi))
+        else:
+            nerf_styles = self._color_styles(zs, psi, colors)
         gx, gy, gz = (g.to(device) for g in density_lattice(resolution, cube_length, center))
         sigma = self.siren.density_lattice(gx, gy, gz, nerf_styles)
         meshes = []
         for b, (vertices, faces) in enumerate(ops.mesh_from_volume(sigma.contiguous(), gx, gy, gz, level)):
             n = None
+            styles_b = {name: style[b:b + 1] for name, style in nerf_styles.items()}
             if normals:
                 n = torch.zeros_like(vertices)
                 if vertices.shape[0]:
-                    styles_b = {name: style[b:b + 1] for name, style in nerf_styles.items()}
                     n = _unit_normals(self.siren.density_gradient(vertices.unsqueeze(0), styles_b)[1][0])
-            meshes.append(SimpleNamespace(vertices=vertices, faces=faces, normals=n))
+            mesh = SimpleNamespace(vertices=vertices, faces=faces, normals=n)
+            if colors is not None:
+                mesh.colors = torch.zeros_like(vertices)
+                if vertices.shape[0]:
+                    mesh.colors = self._colors_at(vertices.unsqueeze(0), styles_b, colors, img_size)[0]
+            meshes.append(mesh)
         return meshes
 
     def forward_camera_pos_and_lookup(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,

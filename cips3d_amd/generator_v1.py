@@ -51,6 +51,10 @@ class GeneratorNerfINR(generator.GeneratorNerfINR):
         self.module_name_list.append('aux_to_rbg')
         self.filters = nn.Identity()
 
+    # the colour entry points (point_colors, color_grid, extract_mesh with colors, surface_colored): nerf_rgb, which every colour of the
+    # SIREN depends on, leaves the INR mapping chain here, so an 'aux' colour too runs both mapping networks on forward()'s styles
+    _color_style_from_inr = True
+
     def _map_inr(self, z_inr):
         """generator_v1.py:1808-1818: style_dict['nerf_rgb'] = nerf_rgb_mapping(<INR mapping output>), on the grouped-linear
         kernel (the 10 000 latents of generate_avg_frequencies take the Linear itself, like the mapping network's layers)"""

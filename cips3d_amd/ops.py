@@ -352,6 +352,65 @@ def siren_sigma_grad_grid(gx, gy, gz, *siren):
     return sigma, grad
 
 
+def _proj_prep(who, proj_w, proj_b):
+    """the 32 -> 3 projection of the colour entry points, detached, contiguous and checked"""
+    proj_w, proj_b = _c(proj_w.detach()), _c(proj_b.detach())
+    _chk(proj_w, proj_b)
+    if tuple(proj_w.shape) != (3, 32) or tuple(proj_b.shape) != (3,):
+        raise ValueError(f"{who} takes proj_w (3, 32) and proj_b (3,), got {tuple(proj_w.shape)} and {tuple(proj_b.shape)}")
+    return proj_w, proj_b
+
+
+def _rgb_composed(t, points, proj_w, proj_b, tanh):
+    """the colour entry points on the exact-fp32 forward (SIREN_FWD_MODE "f32": that kernel has no colour form): its features
+    through an fp32 linear -> rgb (B, P, 3), sigma (B, P)"""
+    B, P, _ = points.shape
+    feat = torch.empty(B, P, 32, device=points.device)
+    sigma = torch.empty(B, P, device=points.device)
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_fwd(C.byref(sw), _p(points), _p(feat), _p(sigma), B, P, _stream()), "cips_siren_fwd")
+    y = torch.nn.functional.linear(feat, proj_w, proj_b)
+    return (torch.tanh(y) if tanh else y), sigma
+
+
+@torch.no_grad()
+def siren_rgb(points, proj_w, proj_b, *siren, tanh=True, sigma=False):
+    """rgb (B,P,3) = [tanh](proj_w . feat + proj_b) of SirenFunction's features at points (B,P,3), projected inside the kernel
+    (cips_siren_rgb_x3: 12 B per point written instead of 132, no (B,P,32) tensor and no second launch; the summation order:
+    include/cips3d_hip.h); with sigma=True -> (rgb, sigma (B,P)), sigma the forward kernel's bit for bit.  proj_w (3,32),
+    proj_b (3): the generator's auxiliary RGB layer, or any 32 -> 3 map.  A plain function: inputs are detached, no gradient
+    flows.  With SIREN_FWD_MODE "f32" the exact-fp32 forward runs and its features go through an fp32 linear."""
+    t, points, (B, P) = _sigma_prep(points, siren)
+    proj_w, proj_b = _proj_prep("siren_rgb", proj_w, proj_b)
+    if SIREN_FWD_MODE != "x3":
+        rgb, sig = _rgb_composed(t, points, proj_w, proj_b, tanh)
+        return (rgb, sig) if sigma else rgb
+    rgb = torch.empty(B, P, 3, device=points.device)
+    sig = torch.empty(B, P, device=points.device) if sigma else None
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_rgb_x3(C.byref(sw), _p(points), _p(proj_w), _p(proj_b), int(bool(tanh)), _p(rgb), _p(sig), B, P,
+                                        _stream()), "cips_siren_rgb_x3")
+    return (rgb, sig) if sigma else rgb
+
+
+@torch.no_grad()
+def siren_rgb_grid(gx, gy, gz, proj_w, proj_b, *siren, tanh=True, sigma=False):
+    """siren_rgb over the lattice (gx[i], gy[j], gz[k]) of three 1-D coordinate tensors -> rgb (B, nx, ny, nz, 3), with
+    sigma=True (rgb, sigma (B, nx, ny, nz)) (cips_siren_rgb_x3_grid: the kernel reads the coordinates, no points tensor exists).
+    The points form's values bit for bit.  With SIREN_FWD_MODE "f32" the points are materialised for the exact-fp32 forward."""
+    t, (gx, gy, gz), gp, shape = _sigma_grid_prep("siren_rgb_grid", gx, gy, gz, siren)
+    proj_w, proj_b = _proj_prep("siren_rgb_grid", proj_w, proj_b)
+    if SIREN_FWD_MODE != "x3":
+        rgb, sig = _rgb_composed(t, lattice_points(gx, gy, gz, shape[0]).contiguous(), proj_w, proj_b, tanh)
+        return (rgb.view(*shape, 3), sig.view(shape)) if sigma else rgb.view(*shape, 3)
+    rgb = torch.empty(*shape, 3, device=gx.device)
+    sig = torch.empty(shape, device=gx.device) if sigma else None
+    sw = _siren_struct(t)
+    check(_lib.load().cips_siren_rgb_x3_grid(C.byref(sw), C.byref(gp), _p(proj_w), _p(proj_b), int(bool(tanh)), _p(rgb), _p(sig),
+                                             shape[0], _stream()), "cips_siren_rgb_x3_grid")
+    return (rgb, sig) if sigma else rgb
+
+
 def siren_surface(level, refine, geom, xg, yg, zg, cam2world, *siren, trace=False):
     """The iso-surface sigma = level as the camera rays of (geom = (B, H, W, S, zc), pixel grids, cam2world) see it
     (cips_siren_surface_x3: one launch, about S + refine + 1 sigma evaluations per ray at most, no (B, n, S, 3) points and no

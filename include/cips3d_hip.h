@@ -174,6 +174,25 @@ int cips_siren_sigma_grad_x3(const cips_siren_weights* w, const float* points, f
 int cips_siren_sigma_grad_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, float* sigma /* may be NULL */,
                                   float* grad, int B, cips_stream_t stream);
 
+/* The colour of a point: the 32 colour features of cips_siren_fwd_x3 projected to three channels inside the kernel, so that
+ * neither the (B,P,32) features nor a second launch exist — 12 B per point written (16 with sigma) instead of 132.  With
+ * feat (B,P,32) and sigma (B,P) what cips_siren_fwd_x3 writes for the same w and points, bit for bit, channel c = (r&3) + 8(r>>2) + 4h
+ * for h = 0, 1 and r = 0..15:
+ *   s_h[j] = fmaf(W[j][c(15,h)], feat[c(15,h)], ... fmaf(W[j][c(0,h)], feat[c(0,h)], 0.f))      sixteen fmaf, r ascending, from zero
+ *   y[j]   = (s_0[j] + s_1[j]) + b[j]                                                           j = 0, 1, 2
+ *   rgb[j] = tanh_out ? tanhf(y[j]) : y[j]
+ * proj_w (3,32) row-major and proj_b (3) are device memory (the generator's auxiliary RGB layer, or any 32 -> 3 map); rgb (B,P,3)
+ * fp32 row-major; sigma (B,P) or NULL (not written).  Every element of rgb (and sigma) is written, nothing behind the last.
+ * trig_mode as for cips_siren_fwd_x3, both bits.  A NULL w / points / proj_w / proj_b / rgb, B <= 0, B > 65535 or P <= 0 returns
+ * hipErrorInvalidValue before any HIP call. */
+int cips_siren_rgb_x3(const cips_siren_weights* w, const float* points, const float* proj_w, const float* proj_b, int tanh_out,
+                      float* rgb, float* sigma /* may be NULL */, int B, int P, cips_stream_t stream);
+/* the same over the lattice of cips_grid_params (point p = (i*ny + j)*nz + k is (gx[i], gy[j], gz[k]), read by the kernel, which does
+ * index arithmetic only): rgb (B, nx, ny, nz, 3), sigma (B, nx, ny, nz) or NULL; the points form's values bit for bit.  Also
+ * refused: a NULL grid or coordinate array, a non-positive size, nx*ny*nz > INT_MAX. */
+int cips_siren_rgb_x3_grid(const cips_siren_weights* w, const cips_grid_params* grid, const float* proj_w, const float* proj_b,
+                           int tanh_out, float* rgb, float* sigma /* may be NULL */, int B, cips_stream_t stream);
+
 /* Ray casting of the iso-surface sigma = level: per camera ray of `rays` (n = H*W rays per image; rays->jitter and rays->zvals
  * must be NULL, the walk is on the unjittered grid zg[0..S-1]) the depth of the first crossing, a hit mask, the surface point and
  * the density there.  The point at depth t is camera origin + world ray direction * t (the zvals form of cips_ray_params: the
