@@ -14,9 +14,11 @@
 //     stages under the epilogue, and the epilogue needs no workgroup barrier;
 //   * the epilogue itself is about half the instructions: all tiles are interior (the entry point refuses other shapes),
 //     uniform base pointers + one 32-bit lane offset per tensor, LeakyReLU + gate bit in 4 instructions per element
-//     (v_cmp / v_cndmask / v_addc carry trick), gate application as bfe_i32 + bfi, half-sub-tiles (16 rows) ping-pong
-//     through the scratch so the LDS round trip of one half hides behind the arithmetic of the other, and the gate
-//     bit plane is written as one dword per four lanes.
+//     (v_cmp / v_cndmask / v_addc carry trick), gate application as bfe_i32 + bfi, steps of 8 rows x 64 columns ping-pong
+//     through the scratch so the LDS round trip of one step hides behind the arithmetic of the other; eight adjacent
+//     lanes move a whole 128-byte line of a plane row (stores and the residual / addend loads: a mixed read + write
+//     stream of 64-byte pieces runs at 4.85 TB/s, of whole lines at 5.59, profiles/r6_head_gemm_epilogue_experiments.txt),
+//     and the gate bit plane is written as one dword per four lanes.
 // Accumulation order and epilogue arithmetic are those of the wide kernel: results are bit-identical to it.
 //
 // Restrictions (else hipErrorNotSupported and the caller falls back to gemm_bf16x3_wide): M, N multiples of 256,
@@ -35,7 +37,7 @@ constexpr int BM = 256, BN = 256, BK = 32, ROWB = 64;
 constexpr int OFF_AHI = 0, OFF_ALO = BM * ROWB, OFF_BHI = 2 * BM * ROWB, OFF_BLO = OFF_BHI + BN * ROWB;
 constexpr int STAGE = OFF_BLO + BN * ROWB;      // 65536
 constexpr int SCR_OFF = 2 * STAGE;              // the epilogue scratch starts behind the two stages
-constexpr int SCR_WAVE = 4096;                  // per wave: two fp32 [16][32] halves (ping-pong)
+constexpr int SCR_WAVE = 4096;                  // per wave: two fp32 [8][64] halves (ping-pong)
 constexpr int SMEM_BYTES = SCR_OFF + 8 * SCR_WAVE;
 static_assert(SMEM_BYTES == 163840, "the kernel owns the whole LDS of the CU");
 static_assert(OFF_ALO == X3_PLANE_BYTES && OFF_BHI == 2 * X3_PLANE_BYTES && OFF_BLO == 3 * X3_PLANE_BYTES && ROWB == 64, "stage layout of gemm_x3_common.h");
@@ -54,8 +56,8 @@ struct VArgs {
 // (no gate input) apply the LeakyReLU and write the gate bit plane, backward flavours (gate input) do neither; only
 // C_unmasked (the skip gradient of the add flavour) stays a run-time switch.  !FAST: every switch of the descriptor.
 // RGBF: ToRGB forward folded in (descriptor fields torgb_w / torgb_part): per row and 128-column block the three partial
-// dot products of the final values with the ToRGB weights, accumulated over the wave's four column sub-blocks in
-// registers, reduced over the four lanes of a row with two DPP adds and stored as one float4 per row.
+// dot products of the final values with the ToRGB weights, accumulated over the wave's four column sub-blocks as four
+// chains per row (handed between lanes by DPP), combined with two DPP adds and stored as one float4 per row.
 // ADDP: the addend (HAS_ADD) arrives as the split planes of a gated tensor plus the bit plane of that gate (descriptor fields
 // addp_*): value = (hi + lo) * (bit ? 1 : addp_gain), same bytes in as the fp32 addend, and no C_unmasked copy is needed by
 // the next layer.
@@ -165,19 +167,32 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       u32x4 v = {__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(e)};
       st16(ubase, off, v);
     };
-    const int h_rr = lane >> 2, q2 = lane & 3;
-    const unsigned eC = (unsigned)((wm * 64 + h_rr) * d.ldc + wn * 128 + q2 * 8);         // lane element offsets in the tile
-    const unsigned eP = (unsigned)((wm * 64 + h_rr) * d.ldp + wn * 128 + q2 * 8);
-    // half-sub-tile hs = 0..15: column block jj = hs>>2, row block si = (hs>>1)&1, half h = hs&1 (16 rows)
-    // (RGBF: the other nesting — row set (si, h) = hs>>2 outermost, column block jj = hs&3 innermost — so that a row's ToRGB
-    // sums are complete after four consecutive steps and only one set of three accumulators is live)
-    // half-sub-tile hs = (row set hs >> 2, column block hs & 3): the column block runs innermost, so the four 64-byte
-    // pieces of a row's 256 output bytes are stored back to back and leave L2 as whole lines (measured against the
-    // column-block-outermost order on the C2 shape: plain 232 -> 210 us, res 280 -> 266, gate 236 -> 220, add 363 -> 351)
-    auto JJ = [](int hs) -> int { return hs & 3; };
-    auto RS = [](int hs) -> int { return hs >> 2; };
-    auto uoffC = [&](int hs) -> long long { return (long long)(((RS(hs) >> 1) * 32 + (RS(hs) & 1) * 16)) * d.ldc + JJ(hs) * 32; };
-    auto uoffP = [&](int hs) -> long long { return (long long)(((RS(hs) >> 1) * 32 + (RS(hs) & 1) * 16)) * d.ldp + JJ(hs) * 32; };
+    // an epilogue step is 8 rows x 64 columns of the wave's 64 x 128 block: lane = (row h_rr, 8-column chunk c8), so the
+    // eight lanes of a row move one whole 128-byte line of each bf16 plane per instruction (stores, residual and addend loads)
+    // and the row's 8 bytes of a gate bit plane; q2 = the lane's place in its quad (the bit plane moves as one dword per quad).
+    // Lane group j = lane >> 3 takes row 0,1,5,4,2,3,7,6 of the step: a ds_read_b128 serves lanes in groups of 16 that hold
+    // halves of the lane groups (0,1,2,3) or (4,5,6,7), and this order puts the pairs that meet on the same 16-byte chunks,
+    // (0,3), (1,2), (4,7), (5,6), on opposite sides of row 4, which is all the scratch image's swizzle looks at (below)
+    // They are derived inside the last k-tile (its second k-step, where one fragment set is dead), in front of the first
+    // input requests: held across the main loop they put the <1,1,0,!FAST> instantiation 8 bytes into scratch.
+    int c8, q2, h_rr;
+    unsigned eC, eP;                                                                       // lane element offsets in the tile
+    auto epi_lanes = [&]() {
+      int l = lane;
+      asm volatile("" : "+v"(l));
+      c8 = l & 7; q2 = l & 3;
+      h_rr = ((l >> 2) & 4) | ((l >> 4) & 2) | (((l >> 3) ^ (l >> 4)) & 1);
+      eC = (unsigned)((wm * 64 + h_rr) * d.ldc + wn * 128 + c8 * 8);
+      eP = (unsigned)((wm * 64 + h_rr) * d.ldp + wn * 128 + c8 * 8);
+    };
+    // step hs = (row set hs >> 1: rows 8 (hs >> 1) .. + 8, column half hs & 1): the column half runs innermost, so the two
+    // 128-byte lines of a row's 256 output bytes are stored back to back (column-innermost against column-outermost order,
+    // measured on the C2 shape with 64-byte pieces: plain 232 -> 210 us, res 280 -> 266, gate 236 -> 220, add 363 -> 351),
+    // and a row's ToRGB sums (RGBF) are complete after two consecutive steps: one set of three accumulators is live
+    auto CP = [](int hs) -> int { return hs & 1; };
+    auto RS = [](int hs) -> int { return hs >> 1; };
+    auto uoffC = [&](int hs) -> long long { return (long long)(RS(hs) * 8) * d.ldc + CP(hs) * 64; };
+    auto uoffP = [&](int hs) -> long long { return (long long)(RS(hs) * 8) * d.ldp + CP(hs) * 64; };
     struct Pre { float4 add[(HAS_ADD && !ADDP) ? 2 : 1]; float gg[HAS_ADD ? 3 : 1]; unsigned mask, amask; uint4 rh, rl; };      // rh / rl: residual planes (HAS_RES) or the planes addend (ADDP)
     const bool has_rgb = HAS_ADD && d.rgb_g != nullptr;
     auto prefetch = [&](int hs, Pre& p) {
@@ -195,7 +210,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
           p.add[1] = *reinterpret_cast<const float4*>(q + eC * 4u + 16);
         }
         if (has_rgb) {
-          const int row = m0 + wm * 64 + (RS(hs) >> 1) * 32 + (RS(hs) & 1) * 16 + h_rr;
+          const int row = m0 + wm * 64 + RS(hs) * 8 + h_rr;
           const float* gp = d.rgb_g + ((long long)bz * d.M + row) * 3;
           p.gg[0] = gp[0]; p.gg[1] = gp[1]; p.gg[2] = gp[2];
         }
@@ -212,7 +227,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       }
     };
     constexpr bool HAS_IN = HAS_ADD || HAS_MASK || HAS_RES;
-    constexpr int NPF = (HAS_ADD || RGBF) ? 3 : 4;        // ring of epilogue-input slots; slot hs % NPF is refilled NPF-1 half-sub-tiles ahead
+    constexpr int NPF = (HAS_ADD || RGBF) ? 3 : 4;        // ring of epilogue-input slots; slot hs % NPF is refilled NPF-1 steps ahead
     Pre pre[NPF];
 
     // ---- one k-tile.  MODE 0: steady state (fragments of the next k-tile + DMA of k-tile kt+2); 1: next-to-last
@@ -235,6 +250,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       // k-step b
       Src nsrc;
       if constexpr (MODE == 2) {
+        epi_lanes();
         if (have_next) {
           int tm2, tn2, bz2;
           decode(tnext, tm2, tn2, bz2);
@@ -279,6 +295,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       asm volatile("" : "+v"(ac0), "+v"(ac1), "+v"(bc0), "+v"(bc1), "+v"(an), "+v"(bn));
       Src nsrc;
       if constexpr (MODE == 2) {
+        epi_lanes();
         if (have_next) {
           int tm2, tn2, bz2;
           decode(tnext, tm2, tn2, bz2);
@@ -344,16 +361,21 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     const bool do_cu = (FAST && !HAS_ADD) ? false : (d.C_unmasked != nullptr);
     younger = (has_rgb || !(do_p || do_c)) ? 0 : 24;
     const unsigned sw = sbase + SCR_OFF + uw * SCR_WAVE;
-    // scratch image of a half: fp32 [16][32], the 16-byte chunk index of row R XORed with (R>>2)&1: the MFMA layout's
-    // writes (lane = column) and the row-contiguous 16-byte reads are both conflict-free
-    const unsigned wb = sw + (4 * hf) * 128 + ((((l31 >> 2) ^ hf)) << 4) + (l31 & 3) * 4;
-    const unsigned rsw = (h_rr >> 2) & 1;
-    const unsigned rb0 = sw + h_rr * 128 + (((2 * q2) ^ rsw) << 4), rb1 = sw + h_rr * 128 + (((2 * q2 + 1) ^ rsw) << 4);
-    auto put = [&](auto HS_) {                // accumulators of half-sub-tile hs -> scratch half hs & 1
-      constexpr int hs = decltype(HS_)::value, jj = hs & 3, rsx = hs >> 2, si = rsx >> 1, h = rsx & 1;
+    // scratch image of a step: fp32 [8][64] (rows of 256 bytes = all 64 banks), the 16-byte chunk index of row R XORed
+    // with R>>2.  Writes (MFMA layout: a ds_write_b32 puts 32 consecutive columns of rows r and r + 4, one row per
+    // 32-lane group, the XOR permutes chunks inside the group's 128 bytes) and reads (ds_read_b128: a 16-lane group holds
+    // the 8-column chunks 0-3 of two rows and 4-7 of two rows, every lane the same half of its 32 bytes; each pair lies
+    // on opposite sides of row 4, so the XOR sends it to opposite halves) are both conflict-free
+    const unsigned wb = sw + (4 * hf) * 256 + (l31 ^ (4 * hf)) * 4;
+    const unsigned rsw = h_rr >> 2;
+    const unsigned rb0 = sw + h_rr * 256 + (((2 * c8) ^ rsw) << 4), rb1 = sw + h_rr * 256 + (((2 * c8 + 1) ^ rsw) << 4);
+    auto put = [&](auto HS_) {                // accumulators of step hs -> scratch half hs & 1
+      constexpr int hs = decltype(HS_)::value, cp = hs & 1, rsx = hs >> 1, si = rsx >> 2, g = rsx & 3;
 #pragma unroll
-      for (int r = 0; r < 8; ++r)
-        LDS_W32(wb + (hs & 1) * 2048 + ((r & 3) + 8 * (r >> 2)) * 128) = acc[si][jj][8 * h + r];
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)           // accumulator register 4 g + r: tile row 8 g + 4 hf + r, column lane & 31
+          LDS_W32(wb + (hs & 1) * 2048 + r * 256 + c * 128) = acc[si][2 * cp + c][4 * g + r];
     };
     float rw[3][8];                           // rgb_w columns of the current column block
     float tacc[3] = {0.f, 0.f, 0.f};          // RGBF: the current row set's ToRGB sums
@@ -387,7 +409,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         }
         if (has_rgb) {                                       // rank-3 term: + g[row][0..2] . rgb_w[0..2][col..col+8]
           {
-            const int col = n0 + wn * 128 + (hs & 3) * 32 + q2 * 8;
+            const int col = n0 + wn * 128 + (hs & 1) * 64 + c8 * 8;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
               const float4 w0 = *reinterpret_cast<const float4*>(d.rgb_w + (long long)c * d.N + col);
@@ -434,7 +456,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         for (int e = 0; e < 8; ++e) bits |= (y[e] > 0.f ? 1u : 0u) << e;
       }
       if (do_bits) {
-        // the quad's four bytes as one dword, stored by its first lane
+        // a lane's 8 columns are one byte of the bit plane; the quad's four bytes as one dword, stored by its first lane
+        // (the two dwords of a row's 64 columns are adjacent in lanes and in memory)
         unsigned v = bits << (8 * q2);
         v |= (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
         v |= (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);     // quad_perm [2,3,0,1]
@@ -452,18 +475,27 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         }
       }
       if constexpr (RGBF) {
-        constexpr int jj = hs & 3, rs = hs >> 2;             // column sub-block (innermost), row set (si, h)
-        const int col = n0 + wn * 128 + jj * 32 + q2 * 8;
+        // The sums keep the order of the 16 x 32 steps this epilogue used to take: per row, four chains (q = 0..3) of 32
+        // FMAs over the columns 32 jj + 8 q + e (jj = 0..3, then e = 0..7), combined as (t0 + t1) + (t2 + t3).  Here chain q
+        // alternates between the lanes c8 = q (column blocks jj = 0, 2) and c8 = q + 4 (jj = 1, 3): every lane runs the
+        // step's eight FMAs twice, first on the carry of lanes 0-3, then on what lanes 0-3 hand to lanes 4-7 (row_shr:4);
+        // after the first column half lanes 4-7 hand the chain back (row_shl:4), after the second they hold t0..t3 as a quad.
+        constexpr int cp = hs & 1, rs = hs >> 1;             // column half (innermost), row set
+        const int col = n0 + wn * 128 + cp * 64 + c8 * 8;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float4 w0 = *reinterpret_cast<const float4*>(d.torgb_w + (long long)c * d.N + col);
           const float4 w1 = *reinterpret_cast<const float4*>(d.torgb_w + (long long)c * d.N + col + 4);
-          float t = (jj == 0) ? 0.f : tacc[c];
+          float t = (cp == 0) ? 0.f : tacc[c];
           t = fmaf(y[0], w0.x, t); t = fmaf(y[1], w0.y, t); t = fmaf(y[2], w0.z, t); t = fmaf(y[3], w0.w, t);
           t = fmaf(y[4], w1.x, t); t = fmaf(y[5], w1.y, t); t = fmaf(y[6], w1.z, t); t = fmaf(y[7], w1.w, t);
+          t = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x114, 0xF, 0xF, true));      // row_shr:4
+          t = fmaf(y[0], w0.x, t); t = fmaf(y[1], w0.y, t); t = fmaf(y[2], w0.z, t); t = fmaf(y[3], w0.w, t);
+          t = fmaf(y[4], w1.x, t); t = fmaf(y[5], w1.y, t); t = fmaf(y[6], w1.z, t); t = fmaf(y[7], w1.w, t);
+          if constexpr (cp == 0) t = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x104, 0xF, 0xF, true));      // row_shl:4
           tacc[c] = t;
         }
-        if constexpr (jj == 3) {
+        if constexpr (cp == 1) {
           float v[3];
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
@@ -472,8 +504,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
             t += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x4E, 0xF, 0xF, true));
             v[c] = t;
           }
-          if (q2 == 0) {
-            const long long row = (long long)bz * d.M + m0 + wm * 64 + (rs >> 1) * 32 + (rs & 1) * 16 + h_rr;
+          if (c8 == 4) {
+            const long long row = (long long)bz * d.M + m0 + wm * 64 + rs * 8 + h_rr;
             float* q = d.torgb_part + ((long long)(tn * 2 + wn) * d.batch * d.M + row) * 4;
             *reinterpret_cast<float4*>(q) = make_float4(v[0], v[1], v[2], 0.f);
           }
