@@ -213,6 +213,8 @@ SIGNATURES = {
     "cips_pyramid_loss_scratch": (i64, [i32, i32, i32, i32, i32]),
     "cips_pyramid_loss_fwd": (i32, [vp, vp, vp, C.POINTER(C.c_double), i32, i32, C.c_double, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "cips_pyramid_loss_bwd": (i32, [vp, vp, vp, i32, i64, vp]),
+    "cips_reproject_fwd": (i32, [vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cips_reproject_bwd": (i32, [vp, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cips_camera_pose": (i32, [vp, vp, i32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
     "cips_grouped_linear_max_jobs": (i32, []),
     "cips_grouped_linear_fwd": (i32, [C.POINTER(GlinJob), i32, i32, vp]),

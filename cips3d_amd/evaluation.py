@@ -9,6 +9,7 @@ import copy
 import ctypes as C
 import math
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -247,3 +248,83 @@ def render_views(G, styles, yaws, pitches=None, **render_kw):
               sample_dist='gaussian')
     kw.update(render_kw)
     return [G.forward_styles(styles, h_mean=yaw, v_mean=pitch, **kw)[0] for yaw, pitch in zip(yaws, pitches)]
+
+
+def relative_pose(tgt_cam2world, src_cam2world):
+    """Two cam2world batches (b,4,4) or (b,3,4), as the namespaces of GeneratorNerfINR.render() / geometry() / surface() carry
+    them -> tgt2src (b,3,4) fp32 = [R_s^T R_t | R_s^T (t_t - t_s)]: the rigid transform that takes a point of the target
+    camera's space to the source camera's, what ops.reproject wants.  Composed in fp64 on the matrices' device with plain torch
+    ops and rounded to fp32 once: t_t - t_s is the difference of two camera positions of norm ~1, the one cancellation in the
+    reprojection chain, and it must not happen in fp32.  No gradient (the camera gets none from ops.reproject either) and no
+    host synchronisation."""
+    for name, m in (("tgt_cam2world", tgt_cam2world), ("src_cam2world", src_cam2world)):
+        if m.dim() != 3 or m.shape[1] not in (3, 4) or m.shape[2] != 4:
+            raise ValueError(f"relative_pose: {name} (b,4,4) or (b,3,4) expected, got {tuple(m.shape)}")
+    if tgt_cam2world.shape[0] != src_cam2world.shape[0]:
+        raise ValueError(f"relative_pose: {tgt_cam2world.shape[0]} target cameras but {src_cam2world.shape[0]} source cameras")
+    with torch.no_grad():
+        t, s = tgt_cam2world.detach().double(), src_cam2world.detach().double()
+        RsT = s[:, :3, :3].transpose(1, 2)
+        rot = RsT @ t[:, :3, :3]
+        trans = RsT @ (t[:, :3, 3:] - s[:, :3, 3:])
+        return torch.cat([rot, trans], 2).float().contiguous()
+
+
+def warp_view(src, tgt, fov, src_fov=None, occ_tol=None):
+    """What view `src` predicts for view `tgt`: src.imgs seen from tgt's camera through tgt.depth.  src and tgt are two
+    namespaces of GeneratorNerfINR.render() / render_styles() (imgs, depth, cam2world; without return_aux_img, so that imgs and
+    depth have one batch size); fov: the field of view tgt was rendered with, src_fov (default fov) that of src.
+    -> SimpleNamespace(imgs (b,3,Ht,Wt), mask (b,1,Ht,Wt) uint8, uv (b,2,Ht,Wt)): ops.reproject's out, mask and uv.
+    occ_tol (in units of depth): a target pixel whose point lies more than occ_tol behind src.depth, sampled where it lands, is
+    marked occluded (mask 2) and left black; one sample spacing of the renders, (ray_end - ray_start) / (num_steps - 1), is what
+    view_consistency uses.  None: no occlusion test — the namespaces do not say what a sensible tolerance is — and every pixel
+    that lands in src's frame counts as visible.
+    Differentiable through src.imgs and tgt.depth (so through everything the two renders depend on); not through the mask, the
+    cameras or src.depth."""
+    from . import ops
+    from .generator import _zc
+    pose = relative_pose(tgt.cam2world, src.cam2world)
+    src_depth = None if occ_tol is None else src.depth
+    imgs, mask, uv = ops.reproject(src.imgs, tgt.depth, pose, _zc(fov), _zc(fov if src_fov is None else src_fov),
+                                   src_depth=src_depth, occ_tol=occ_tol, return_uv=True)
+    return SimpleNamespace(imgs=imgs, mask=mask, uv=uv)
+
+
+@torch.no_grad()
+def view_consistency(G, styles, yaw_a, yaw_b, pitch_a=math.pi * 0.5, pitch_b=math.pi * 0.5, occ_tol=None, **render_kw):
+    """Multi-view consistency of the styles of cips3d_amd.projection.project (or of G.styles): view A (yaw_a, pitch_a) and view
+    B (yaw_b, pitch_b) are rendered with G.render_styles, B is warped into A's camera through A's depth (warp_view, occlusion
+    tested against B's depth) and compared with A where A's pixels are visible in B.  render_kw: render_styles' arguments with
+    render_views' defaults (img_size is required).  The two renders make the same random draws (the generator's state is
+    rewound between them and left where one render leaves it), so that what differs between them is the camera.
+    occ_tol: default one sample spacing, (ray_end - ray_start) / (num_steps - 1).
+    -> SimpleNamespace of
+      error    (b,)  mean over the visible pixels and the channels of |a.imgs - warped|; NaN for an image with no visible pixel
+      coverage (b,)  the share of A's pixels with mask == 1
+      warped (b,3,H,W), mask (b,1,H,W) uint8   warp_view's imgs and mask
+      a, b           the two render_styles namespaces
+    A 3D-consistent generator renders one surface from both cameras and keeps the error at the level of its view-dependent
+    effects and of the bilinear resampling; the number says nothing about image quality.
+    A ray of A that meets no density at all has opacity 0 and depth 0: it has no point to reproject and counts as not covered
+    (mask 0), also when A and B are the same view.  last_back=True gives every ray a depth.
+    The tensors of a and b are detached (the NeRF path of a trainable generator records a graph under no_grad too)."""
+    kw = dict(fov=12, ray_start=0.88, ray_end=1.12, num_steps=24, h_stddev=0., v_stddev=0., hierarchical_sample=False,
+              sample_dist='gaussian')
+    kw.update(render_kw)
+    if occ_tol is None:
+        occ_tol = (kw['ray_end'] - kw['ray_start']) / (kw['num_steps'] - 1)
+    dev = next(G.parameters()).device
+    state = torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None
+    a = G.render_styles(styles, h_mean=float(yaw_a), v_mean=float(pitch_a), **kw)
+    if state is not None:
+        torch.cuda.set_rng_state(state, dev)
+    b = G.render_styles(styles, h_mean=float(yaw_b), v_mean=float(pitch_b), **kw)
+    for ns in (a, b):
+        ns.imgs, ns.depth, ns.opacity = ns.imgs.detach(), ns.depth.detach(), ns.opacity.detach()
+    w = warp_view(b, a, kw['fov'], occ_tol=occ_tol)
+    vis = (w.mask == 1)
+    n = vis.sum(dim=(1, 2, 3)).double()
+    diff = ((a.imgs - w.imgs).abs() * vis).double().sum(dim=(1, 2, 3))
+    error = (diff / (n * a.imgs.shape[1])).float()               # 0 / 0 = NaN: no visible pixel
+    coverage = (n / vis[0].numel()).float()
+    return SimpleNamespace(error=error, coverage=coverage, warped=w.imgs, mask=w.mask, a=a, b=b)

@@ -1033,7 +1033,8 @@ class GeneratorNerfINR(nn.Module):
         """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path:
         draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_stage) -> head (_head), or
         the last two per pixel subset (_part_grad).  -> imgs, pitch_yaw; with `geo` (render(): whole images in one shot)
-        -> SimpleNamespace(imgs, depth, opacity, pitch_yaw), the same launches plus the opacity store of the NeRF path."""
+        -> SimpleNamespace(imgs, depth, opacity, pitch_yaw, cam2world), the same launches plus the opacity store of the NeRF
+        path; cam2world is camera_setup's matrix of this call."""
         device = next(self.parameters()).device
         b = list(style_dict.values())[0].shape[0]
         if not s.part and not s.staged and self.nerf_grad and torch.is_grad_enabled():
@@ -1062,7 +1063,7 @@ class GeneratorNerfINR(nn.Module):
         if not geo:
             return imgs, pitch_yaw
         depth, opacity = (t.view(b, 1, s.img_size, s.img_size) for t in (depth, opacity))
-        return SimpleNamespace(imgs=imgs, depth=depth, opacity=opacity, pitch_yaw=pitch_yaw)
+        return SimpleNamespace(imgs=imgs, depth=depth, opacity=opacity, pitch_yaw=pitch_yaw, cam2world=cam2world)
 
     def forward(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,
                 h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, psi=1, sample_dist=None, lock_view_dependence=False,
@@ -1084,6 +1085,8 @@ class GeneratorNerfINR(nn.Module):
                              last weight); for nerf_noise = 0 it is geometry().depth bit for bit
           opacity (b,1,H,W)  sum_k w_k, taken BEFORE the last_back top-up (the reference's weights_sum, the soft foreground
                              matte): under last_back it is not the constant 1
+          cam2world (b,4,4)  the camera matrix camera_setup returned for this call (b rows with return_aux_img too): what
+                             relates this view to another one (evaluation.relative_pose, warp_view)
         depth and opacity carry a grad_fn whenever the NeRF path runs with gradients, as in the reference, where fancy_integration
         returns them as autograd tensors: a depth-supervised inversion, a silhouette loss or a geometric regulariser reaches
         the SIREN weights, the NeRF mapping network, zs['z_nerf'] and a camera that requires grad (camera_pos, camera_lookup,
@@ -1193,7 +1196,7 @@ class GeneratorNerfINR(nn.Module):
                       h_mean=math.pi * 0.5, v_mean=math.pi * 0.5, sample_dist=None, clamp_mode='relu', nerf_noise=0.,
                       white_back=False, last_back=False, return_aux_img=False, camera_pos=None, camera_lookup=None,
                       up_vector=None, rand_override=None, grad_points=None, forward_points=None):
-        """render() from a style dictionary (forward_styles' `styles`): -> SimpleNamespace(imgs, depth, opacity, pitch_yaw),
+        """render() from a style dictionary (forward_styles' `styles`): -> SimpleNamespace(imgs, depth, opacity, pitch_yaw, cam2world),
         what render(zs, psi=psi, ...) returns for styles(zs, psi).  Whole images in one shot only, as render()."""
         self._whole_images_only('render_styles', 'forward_styles', grad_points, forward_points)
         return self._render_styles(self._check_styles(styles, "render_styles"), RenderSettings.of(locals()), geo=True)
@@ -1286,6 +1289,7 @@ class GeneratorNerfINR(nn.Module):
           sigma   (b,1,H,W)  the density at those points
           normals (b,3,H,W)  -grad sigma / |grad sigma| there (ops.siren_sigma_grad); exact zeros where the gradient is zero
           pitch_yaw (b,2)
+          cam2world (b,4,4)  the camera matrix camera_setup returned for this call
         Only the NeRF mapping network runs: neither the INR mapping network nor the head.
         Random numbers: the draws and the camera are draw_randoms / camera_setup on the RenderSettings of those calls, so a
         seed gives the geometry of the image it renders, and the generator is left in the state forward() leaves it in — with
@@ -1302,7 +1306,7 @@ class GeneratorNerfINR(nn.Module):
         sigma, grad = self.siren.density_gradient(points, nerf_styles)
         normals = _unit_normals(grad)
         return SimpleNamespace(depth=_maps(depth, b, H), points=_maps(points, b, H), sigma=_maps(sigma, b, H),
-                               normals=_maps(normals, b, H), pitch_yaw=pitch_yaw)
+                               normals=_maps(normals, b, H), pitch_yaw=pitch_yaw, cam2world=cam2world)
 
     def _density_camera(self, s, zs, psi, device):
         """what geometry() and surface() start from, in the order forward() consumes the generator in: the NeRF styles of the
@@ -1329,6 +1333,7 @@ class GeneratorNerfINR(nn.Module):
           normals (b,3,H,W)  -grad sigma / |grad sigma| at the points (NeRFNetwork.density_gradient); exact zeros where
                              mask == 0 or the gradient is zero; None with normals=False
           pitch_yaw (b,2)
+          cam2world (b,4,4)  the camera matrix camera_setup returned for this call
         `level` has no default (as in extract_mesh, whose mesh this is a view of).  Only the NeRF mapping network runs.  Random
         numbers: as geometry() — the draws and the camera are draw_randoms / camera_setup on the RenderSettings of a
         non-hierarchical forward() with nerf_noise = 0, so a seed gives the camera of the image it renders and the generators
@@ -1373,7 +1378,8 @@ class GeneratorNerfINR(nn.Module):
                                                             cam2world, level, refine)
         nrm = _unit_normals(self.siren.density_gradient(points, nerf_styles)[1], hit) if normals else None
         out = SimpleNamespace(depth=_maps(depth, b, H), mask=_maps(hit, b, H), points=_maps(points, b, H),
-                              sigma=_maps(sigma, b, H), normals=_maps(nrm, b, H) if normals else None, pitch_yaw=pitch_yaw)
+                              sigma=_maps(sigma, b, H), normals=_maps(nrm, b, H) if normals else None, pitch_yaw=pitch_yaw,
+                              cam2world=cam2world)
         if colors is not None:
             rgb = self._colors_at(points, nerf_styles, colors, img_size)
             out.rgb = _maps(torch.where(hit.unsqueeze(-1) != 0, rgb, rgb.new_full((), -1.)), b, H)

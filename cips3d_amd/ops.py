@@ -2623,3 +2623,86 @@ def pyramid_loss(pred, target, weight=None, level_weights=(1.,), kind="mse", eps
     weight = weight.detach().contiguous() if weight is not None else None
     _chk(target, weight)
     return PyramidLossFunction.apply(pred.contiguous(), target, weight, level_weights, FIT_LOSS_KINDS.index(kind), float(eps))
+
+
+# --------------------------------------------------------------------------------------
+# View reprojection (csrc/reproject.hip): a source view seen through a target view's depth
+# --------------------------------------------------------------------------------------
+class ReprojectFunction(torch.autograd.Function):
+    """(src, tgt_depth, tgt2src, src_depth or None) -> out, mask, uv or None: cips_reproject_fwd, one launch.  mask and uv are
+    not differentiable.  The backward is cips_reproject_bwd on the stored mask: d tgt_depth always (a gather, reproducible);
+    d src only where src needs a gradient — its buffer is zeroed and summed with fp32 atomic adds, the one result whose last
+    bits can differ from call to call; without it neither the memset nor the adds run."""
+
+    @staticmethod
+    def forward(ctx, src, tgt_depth, tgt2src, src_depth, zc_tgt, zc_src, occ_tol, return_uv):
+        lib = _lib.load()
+        B, Cc, Hs, Ws = src.shape
+        Ht, Wt = tgt_depth.shape[2:]
+        out = torch.empty(B, Cc, Ht, Wt, device=src.device)
+        mask = torch.empty(B, 1, Ht, Wt, dtype=torch.uint8, device=src.device)
+        uv = torch.empty(B, 2, Ht, Wt, device=src.device) if return_uv else None
+        check(lib.cips_reproject_fwd(_p(src), _p(src_depth), _p(tgt_depth), _p(tgt2src), zc_tgt, zc_src, occ_tol, _p(out),
+                                     _p(mask), _p(uv), B, Cc, Hs, Ws, Ht, Wt, _stream()), "cips_reproject_fwd")
+        ctx.save_for_backward(src, tgt_depth, tgt2src, mask)
+        ctx.zc = (zc_tgt, zc_src)
+        ctx.mark_non_differentiable(mask)
+        if uv is not None:
+            ctx.mark_non_differentiable(uv)
+        return out, mask, uv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, dmask, duv):
+        src, tgt_depth, tgt2src, mask = ctx.saved_tensors
+        B, Cc, Hs, Ws = src.shape
+        Ht, Wt = tgt_depth.shape[2:]
+        dout = _c(dout)
+        d_src = torch.empty_like(src) if ctx.needs_input_grad[0] else None          # zeroed by the entry point
+        d_depth = torch.empty_like(tgt_depth) if ctx.needs_input_grad[1] else None
+        check(_lib.load().cips_reproject_bwd(_p(dout), _p(src), _p(tgt_depth), _p(tgt2src), _p(mask), ctx.zc[0], ctx.zc[1],
+                                             _p(d_src), _p(d_depth), B, Cc, Hs, Ws, Ht, Wt, _stream()), "cips_reproject_bwd")
+        return d_src, d_depth, None, None, None, None, None, None
+
+
+def reproject(src, tgt_depth, tgt2src, zc_tgt, zc_src=None, src_depth=None, occ_tol=None, return_uv=False):
+    """The source view `src` as the target view's pixels see it -> (out, mask) or, with return_uv, (out, mask, uv).
+    src (b,C,Hs,Ws); tgt_depth (b,1,Ht,Wt), the target's depth along the normalised ray (render().depth, geometry().depth);
+    tgt2src (b,3,4), a rigid transform from target-camera to source-camera space (evaluation.relative_pose); zc_tgt, zc_src
+    (default zc_tgt): the two cameras' image-plane constants, generator._zc(fov); src_depth (b,1,Hs,Ws) with occ_tol >= 0: the
+    occlusion test — a pixel whose point lies more than occ_tol behind the source's own depth there is occluded.
+      out  (b,C,Ht,Wt)        the bilinear sample of src where mask == 1, exact zeros elsewhere
+      mask (b,1,Ht,Wt) uint8  1 visible, 0 not in the source's frame (or no valid depth), 2 in frame but occluded
+      uv   (b,2,Ht,Wt)        the source pixel coordinates (column u, row v) every target pixel lands on, NaN where mask == 0
+    The definition, step by step: include/cips3d_hip.h (cips_reproject_fwd).  Differentiable with respect to src and tgt_depth
+    where mask == 1, zero elsewhere; nothing flows through mask, uv, src_depth, tgt2src or the plane constants, and there is no
+    double backward.  out, mask, uv and the gradient of tgt_depth are bit-reproducible; the gradient of src is a sum of fp32
+    atomic adds, whose last bits can differ from call to call (it is not computed when src needs no gradient)."""
+    if src.dim() != 4 or src.numel() == 0 or src.shape[2] < 2 or src.shape[3] < 2:
+        raise ValueError(f"reproject: src (b,C,Hs,Ws) with Hs, Ws >= 2 expected, got {tuple(src.shape)}")
+    b, Cc, Hs, Ws = src.shape
+    if tgt_depth.dim() != 4 or tgt_depth.shape[1] != 1 or tgt_depth.shape[2] < 2 or tgt_depth.shape[3] < 2:
+        raise ValueError(f"reproject: tgt_depth (b,1,Ht,Wt) with Ht, Wt >= 2 expected, got {tuple(tgt_depth.shape)}")
+    if tgt_depth.shape[0] != b or tuple(tgt2src.shape) != (b, 3, 4):
+        raise ValueError(f"reproject: batch {b} of src needs tgt_depth ({b},1,Ht,Wt) and tgt2src ({b},3,4), got "
+                         f"{tuple(tgt_depth.shape)} and {tuple(tgt2src.shape)}")
+    if src_depth is not None and tuple(src_depth.shape) != (b, 1, Hs, Ws):
+        raise ValueError(f"reproject: src_depth ({b},1,{Hs},{Ws}) expected, got {tuple(src_depth.shape)}")
+    if src_depth is not None and occ_tol is None:
+        raise ValueError("reproject: src_depth needs an occ_tol (>= 0, in units of depth)")
+    zc_tgt = float(zc_tgt)
+    zc_src = zc_tgt if zc_src is None else float(zc_src)
+    occ_tol = 0. if occ_tol is None else float(occ_tol)
+    if not (math.isfinite(zc_tgt) and math.isfinite(zc_src) and zc_tgt != 0 and zc_src != 0):
+        raise ValueError(f"reproject: zc_tgt and zc_src must be finite and non-zero, got {zc_tgt} and {zc_src}")
+    if not (math.isfinite(occ_tol) and occ_tol >= 0):
+        raise ValueError(f"reproject: occ_tol must be finite and >= 0, got {occ_tol}")
+    for t in (src, tgt_depth, tgt2src, src_depth):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise ValueError("reproject needs fp32 tensors on the GPU (no CPU fallback)")
+    tgt2src = tgt2src.detach().contiguous()
+    src_depth = src_depth.detach().contiguous() if src_depth is not None else None
+    src, tgt_depth = src.contiguous(), tgt_depth.contiguous()
+    _chk(src, tgt_depth, tgt2src, src_depth)
+    out, mask, uv = ReprojectFunction.apply(src, tgt_depth, tgt2src, src_depth, zc_tgt, zc_src, occ_tol, bool(return_uv))
+    return (out, mask, uv) if return_uv else (out, mask)

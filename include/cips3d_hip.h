@@ -980,6 +980,43 @@ int cips_pyramid_loss_fwd(const float* pred, const float* target, const float* w
 int cips_pyramid_loss_bwd(const float* grad, const float* upstream, float* out, int B, long long per_image,
                           cips_stream_t stream);
 
+/* ------------------------------------------------------------------ */
+/* View reprojection (csrc/reproject.hip): what the pixels of a TARGET view see of a SOURCE view, through the target's depth.
+ * src (B,C,Hs,Ws), tgt_depth (B,1,Ht,Wt), src_depth (B,1,Hs,Ws) or NULL, tgt2src (B,3,4), all fp32 contiguous on the device.
+ * tgt_depth: distance along the normalised ray (the renderer's depth).  tgt2src = [R | t]: a rigid transform from target-camera
+ * to source-camera space.  zc_tgt, zc_src: camera-space z of the two image planes (negative: the cameras look along -z).
+ * Camera (csrc/raygen.h): pixel (row i, col j) of an H x W image has x = -1 + 2j/(W-1), y = 1 - 2i/(H-1) and the direction
+ * d = (x, y, zc) / |(x, y, zc)|.  For every target pixel:
+ *   1. q = d * tgt_depth                                   2. q' = R q + t
+ *   3. x' = q'_x zc_src / q'_z,  y' = q'_y zc_src / q'_z    4. u = (x'+1)/2 (Ws-1),  v = (1-y')/2 (Hs-1)
+ *   5. in frame: tgt_depth finite and > 0;  q'_z zc_src > 0 (in front of the source camera);  -1/256 <= u <= Ws-1+1/256 and
+ *      the same for v against Hs.  Then u, v are clamped to [0, Ws-1], [0, Hs-1].  (The 1/256 px of slack gives an identity
+ *      warp full coverage when its last column rounds an ulp past the border.)
+ *   6. bilinear sample over all C channels with u0 = min(floor(u), Ws-2), v0 = min(floor(v), Hs-2) and the weights u - u0, v - v0
+ *   7. with src_depth: ds = the same sample of src_depth; visible iff |q'| <= ds + occ_tol is true (a NaN in ds: occluded)
+ * Steps 1-5 and 7 run in fp64 on the fp32 inputs, (u, v) is rounded to fp32 once; step 6 is fp32.
+ *   out  (B,C,Ht,Wt)        the sample where mask == 1, exact zeros elsewhere
+ *   mask (B,1,Ht,Wt) uint8  1 visible, 0 not in frame, 2 in frame but occluded (never without src_depth)
+ *   uv   (B,2,Ht,Wt) / NULL the clamped (u, v): the correspondence field; NaN where mask == 0
+ * One launch; every output is bit-reproducible.
+ * cips_reproject_bwd, where mask == 1 (the forward's mask is READ: no branch is decided again) and zero elsewhere:
+ *   d_src / NULL        (B,C,Hs,Ws)  the transposed bilinear weights times dout.  Zeroed here (hipMemsetAsync on the stream), then
+ *                       summed with no-return fp32 atomic adds: the ONLY output whose last bits depend on arrival order and can
+ *                       differ from call to call.  NULL: neither the memset nor the adds run.
+ *   d_tgt_depth / NULL  (B,1,Ht,Wt)  sum_c dout_c (d out_c/du du/ddepth + d out_c/dv dv/ddepth), with e = R d:
+ *                       du/ddepth = (Ws-1)/2 zc_src (e_x q'_z - q'_x e_z) / q'_z^2,  dv/ddepth = -(Hs-1)/2 zc_src (e_y q'_z - q'_y e_z) / q'_z^2,
+ *                       and the slopes of the bilinear cell; zero through a coordinate that the clamp of step 5 holds.  A gather:
+ *                       plain stores, bit-reproducible.
+ * No gradient goes through the mask, src_depth, tgt2src or the plane constants.  One launch (none when both outputs are NULL).
+ * Invalid arguments (a required NULL pointer, B or C < 1, any of Hs, Ws, Ht, Wt < 2, a zero or non-finite zc, src_depth with a
+ * negative or non-finite occ_tol, a plane of 2^31 pixels or more, B > 65535) return hipErrorInvalidValue before any HIP call. */
+int cips_reproject_fwd(const float* src, const float* src_depth, const float* tgt_depth, const float* tgt2src, float zc_tgt,
+                       float zc_src, float occ_tol, float* out, unsigned char* mask, float* uv, int B, int C, int Hs, int Ws,
+                       int Ht, int Wt, cips_stream_t stream);
+int cips_reproject_bwd(const float* dout, const float* src, const float* tgt_depth, const float* tgt2src,
+                       const unsigned char* mask, float zc_tgt, float zc_src, float* d_src, float* d_tgt_depth, int B, int C,
+                       int Hs, int Ws, int Ht, int Wt, cips_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
