@@ -270,6 +270,80 @@ def relative_pose(tgt_cam2world, src_cam2world):
         return torch.cat([rot, trans], 2).float().contiguous()
 
 
+def world2cam(cam2world):
+    """cam2world (b,4,4) or (b,3,4), a rigid camera matrix -> its inverse [R^T | -R^T t] (b,3,4) fp32, what ops.rasterize wants:
+    composed in fp64 on the matrices' device and rounded to fp32 once, as relative_pose is.  No gradient, no host
+    synchronisation."""
+    if cam2world.dim() != 3 or cam2world.shape[1] not in (3, 4) or cam2world.shape[2] != 4:
+        raise ValueError(f"world2cam: cam2world (b,4,4) or (b,3,4) expected, got {tuple(cam2world.shape)}")
+    with torch.no_grad():
+        m = cam2world.detach().double()
+        rt = m[:, :3, :3].transpose(1, 2)
+        return torch.cat([rt, -(rt @ m[:, :3, 3:])], 2).float().contiguous()
+
+
+def orbit_cameras(yaws, pitches=None, radius=1.0, lookat=(0., 0., 0.), device='cuda'):
+    """Cameras on a sphere around `lookat`, looking at it -> cam2world (b,4,4) fp32 on `device`: camera b sits at yaw yaws[b]
+    and pitch pitches[b] (default pi / 2, the equator) at distance `radius`, built from camera_origin_from_angles and
+    create_cam2world_matrix — for lookat = 0 and radius = 1 the camera that forward(h_mean=yaw, v_mean=pitch, h_stddev=0,
+    v_stddev=0) and render_views use for those angles."""
+    from .generator import _normalize, camera_origin_from_angles, create_cam2world_matrix
+    yaws = [float(y) for y in yaws]
+    pitches = [math.pi * 0.5] * len(yaws) if pitches is None else [float(p) for p in pitches]
+    if len(pitches) != len(yaws):
+        raise ValueError(f"orbit_cameras: {len(yaws)} yaws but {len(pitches)} pitches")
+    theta = torch.tensor(yaws, dtype=torch.float32, device=device).view(-1, 1)
+    phi = torch.tensor(pitches, dtype=torch.float32, device=device).view(-1, 1)
+    offset, _ = camera_origin_from_angles(theta, phi, float(radius))
+    origin = offset + torch.tensor([float(c) for c in lookat], dtype=torch.float32, device=device)
+    return create_cam2world_matrix(_normalize(-offset), origin)
+
+
+@torch.no_grad()
+def render_mesh(mesh, cam2world, fov, img_size, near=1e-4, far=float('inf'), cull=None):
+    """One triangle mesh seen from b cameras, without the network: ops.rasterize and ops.raster_interpolate.  mesh: anything
+    with .vertices (V,3) fp32 and .faces (T,3) int32 on the GPU and optionally .normals, .colors (V,3) — an element of
+    GeneratorNerfINR.extract_mesh's list, or a mesh loaded from elsewhere; cam2world (b,4,4) (orbit_cameras, or the cam2world
+    of a render()/surface() namespace); fov in degrees; img_size: H = W.  -> SimpleNamespace in surface()'s layout:
+      depth   (b,1,H,W)  distance along the unit ray, `far` on the background
+      mask    (b,1,H,W)  uint8, 1 where a triangle was hit, 0 elsewhere
+      points  (b,3,H,W)  the interpolated vertices (zeros on the background)
+      normals (b,3,H,W)  mesh.normals interpolated and renormalised where the mesh has them, otherwise the geometric normal of
+                         the triangle hit, (v1-v0) x (v2-v0) normalised; exact zeros on the background
+      rgb     (b,3,H,W)  only if the mesh has .colors: interpolated, -1 on the background
+      face (b,H,W) int32, bary (b,H,W,3), cam2world
+    so that shade_surface and save_image take it as they take surface()'s result.  near, far, cull: ops.rasterize's.  A view
+    costs a pass over the triangles and the pixels; extract once, render as many views as wanted.  Forward only."""
+    from . import ops
+    from .generator import _zc
+    vertices, faces = mesh.vertices, mesh.faces
+    H = int(img_size)
+    face, bary, depth, mask = ops.rasterize(vertices, faces, world2cam(cam2world), _zc(fov), H, H, near=near, far=far, cull=cull)
+    hit = mask.unsqueeze(1) != 0
+    out = SimpleNamespace(depth=depth.unsqueeze(1), mask=mask.unsqueeze(1), face=face, bary=bary, cam2world=cam2world,
+                          points=ops.raster_interpolate(face, bary, faces, vertices))
+    vn = getattr(mesh, "normals", None)
+    if vn is not None:
+        n = ops.raster_interpolate(face, bary, faces, vn)
+        norm = n.norm(dim=1, keepdim=True)
+        out.normals = torch.where(hit & (norm > 0), n / norm, torch.zeros_like(n))
+    else:
+        if vertices.shape[0] and faces.shape[0]:
+            # (T, 3 corners, 3); an index outside the mesh is clamped for the gather: the rasteriser never hits such a triangle
+            tri = vertices[faces.long().clamp(0, vertices.shape[0] - 1)]
+            fn = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=-1)
+            norm = fn.norm(dim=-1, keepdim=True)
+            fn = torch.where(norm > 0, fn / norm, torch.zeros_like(fn))
+            picked = fn[face.clamp_min(0).long()]
+        else:
+            picked = torch.zeros(*face.shape, 3, device=face.device)
+        out.normals = torch.where(hit, picked.permute(0, 3, 1, 2), torch.zeros((), device=face.device)).contiguous()
+    colors = getattr(mesh, "colors", None)
+    if colors is not None:
+        out.rgb = ops.raster_interpolate(face, bary, faces, colors, fill=-1.)
+    return out
+
+
 def warp_view(src, tgt, fov, src_fov=None, occ_tol=None):
     """What view `src` predicts for view `tgt`: src.imgs seen from tgt's camera through tgt.depth.  src and tgt are two
     namespaces of GeneratorNerfINR.render() / render_styles() (imgs, depth, cam2world; without return_aux_img, so that imgs and

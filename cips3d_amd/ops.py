@@ -2706,3 +2706,99 @@ def reproject(src, tgt_depth, tgt2src, zc_tgt, zc_src=None, src_depth=None, occ_
     _chk(src, tgt_depth, tgt2src, src_depth)
     out, mask, uv = ReprojectFunction.apply(src, tgt_depth, tgt2src, src_depth, zc_tgt, zc_src, occ_tol, bool(return_uv))
     return (out, mask, uv) if return_uv else (out, mask)
+
+
+# --------------------------------------------------------------------------------------
+# Mesh rasterisation (csrc/raster.hip): an indexed triangle mesh seen through the camera of the ray set-up
+# --------------------------------------------------------------------------------------
+RASTER_CULL = {None: 0, 'back': 1}
+
+
+def _raster_tensor(who, t, name, dtype, shape):
+    """one argument of the rasteriser: dtype and shape as the entry points want them (shape: None matches any size)"""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{who}: {name} must be a {str(dtype).replace('torch.', '')} tensor")
+    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        raise ValueError(f"{who}: {name} {tuple('*' if s is None else s for s in shape)} expected, got {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+def _raster_on_gpu(who, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
+    _chk(*tensors)
+
+
+def rasterize(vertices, faces, world2cam, zc, H, W, near=1e-4, far=float('inf'), cull=None):
+    """One indexed triangle mesh seen from b cameras -> (face, bary, depth, mask): per pixel the first triangle the pixel's
+    ray hits and where.  vertices (V,3) fp32, faces (T,3) int32, world2cam (b,3,4) fp32 = [R | t], the inverse of cam2world
+    (evaluation.world2cam composes it in fp64), zc = generator._zc(fov) < 0, H, W >= 2; the camera is the one of the ray set-up
+    (pixel_grids' xg, yg).
+      face  (b,H,W) int32    the winning triangle, -1 where the ray meets none
+      bary  (b,H,W,3)        its perspective-correct barycentrics (raster_interpolate takes them), zeros for none
+      depth (b,H,W)          the distance along the unit ray — surface().depth's and render().depth's quantity; `far` for none
+      mask  (b,H,W) uint8    1 / 0
+    near: a triangle with a vertex closer than that (or behind the camera) is dropped whole, there is no clipping.  cull:
+    None or 'back' (drop triangles whose geometric normal points away from the camera; extract_mesh winds towards lower
+    density).  The rule, decision by decision: include/cips3d_hip.h (cips_raster_fwd).  Forward only: nothing here has a
+    gradient.  Every output is bit-reproducible, whatever the order of the triangles; no host synchronisation."""
+    who = "rasterize"
+    if cull not in RASTER_CULL:
+        raise ValueError(f"{who}: cull must be None or 'back', got {cull!r}")
+    H, W, zc, near, far = int(H), int(W), float(zc), float(near), float(far)
+    if H < 2 or W < 2:
+        raise ValueError(f"{who}: H, W >= 2 expected, got {H} x {W}")
+    if not (math.isfinite(zc) and zc < 0):
+        raise ValueError(f"{who}: zc must be finite and negative, got {zc}")
+    if not (math.isfinite(near) and near > 0):
+        raise ValueError(f"{who}: near must be finite and positive, got {near}")
+    if math.isnan(far):
+        raise ValueError(f"{who}: far must not be NaN")
+    vertices = _raster_tensor(who, vertices, "vertices", torch.float32, (None, 3))
+    faces = _raster_tensor(who, faces, "faces", torch.int32, (None, 3))
+    world2cam = _raster_tensor(who, world2cam, "world2cam", torch.float32, (None, 3, 4))
+    B, V, T = world2cam.shape[0], vertices.shape[0], faces.shape[0]
+    if max(B * H * W, B * V, B * T) > 0x7fffffff:
+        raise ValueError(f"{who}: b*H*W, b*V and b*T must fit in int32, got b = {B}, H x W = {H} x {W}, V = {V}, T = {T}")
+    _raster_on_gpu(who, vertices, faces, world2cam)
+    dev = vertices.device
+    xg, yg, _ = pixel_grids(W, H, 2, 0., 1., dev)
+    face = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    bary = torch.empty(B, H, W, 3, device=dev)
+    depth = torch.empty(B, H, W, device=dev)
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    if B == 0:
+        return face, bary, depth, mask
+    # scratch: written by the entry point before it is read
+    screen = torch.empty(max(B * V, 1), 4, device=dev)
+    keys = torch.empty(B * H * W, dtype=torch.int64, device=dev)
+    big = torch.empty(max(B * T, 1) + 1, dtype=torch.int32, device=dev)           # the list, then its counter
+    check(_lib.load().cips_raster_fwd(_p(vertices) if V else None, _p(faces) if T else None, _p(world2cam), _p(xg), _p(yg), zc,
+                                      near, far, RASTER_CULL[cull], _p(screen), _p(keys), _p(big), _p(big[-1:]), B * T, _p(face),
+                                      _p(bary), _p(depth), _p(mask), B, V, T, H, W, _stream()), "cips_raster_fwd")
+    return face, bary, depth, mask
+
+
+def raster_interpolate(face, bary, faces, attr, fill=0.):
+    """A per-vertex attribute attr (V,C) fp32 over rasterize's (face (b,H,W) int32, bary (b,H,W,3)) and the mesh's faces (T,3)
+    int32 -> (b,C,H,W): sum_i bary_i * attr[faces[face][i]] where a triangle was hit, `fill` elsewhere.  Any C >= 1.  Forward
+    only, bit-reproducible, no host synchronisation."""
+    who = "raster_interpolate"
+    face = _raster_tensor(who, face, "face", torch.int32, (None, None, None))
+    B, H, W = face.shape
+    bary = _raster_tensor(who, bary, "bary", torch.float32, (B, H, W, 3))
+    faces = _raster_tensor(who, faces, "faces", torch.int32, (None, 3))
+    attr = _raster_tensor(who, attr, "attr", torch.float32, (None, None))
+    V, Cc = attr.shape
+    if Cc < 1:
+        raise ValueError(f"{who}: attr (V,C) with C >= 1 expected, got {tuple(attr.shape)}")
+    if H < 2 or W < 2 or B * H * W > 0x7fffffff:
+        raise ValueError(f"{who}: face (b,H,W) with H, W >= 2 and b*H*W within int32 expected, got {tuple(face.shape)}")
+    _raster_on_gpu(who, face, bary, faces, attr)
+    out = torch.empty(B, Cc, H, W, device=face.device)
+    if B == 0:
+        return out
+    T = faces.shape[0]
+    check(_lib.load().cips_raster_interp(_p(face), _p(bary), _p(faces) if T else None, _p(attr) if V else None, float(fill), _p(out),
+                                         B, H, W, T, V, Cc, _stream()), "cips_raster_interp")
+    return out

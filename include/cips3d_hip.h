@@ -1017,6 +1017,43 @@ int cips_reproject_bwd(const float* dout, const float* src, const float* tgt_dep
                        const unsigned char* mask, float zc_tgt, float zc_src, float* d_src, float* d_tgt_depth, int B, int C,
                        int Hs, int Ws, int Ht, int Wt, cips_stream_t stream);
 
+/* ------------------------------------------------------------------ */
+/* Mesh rasterisation (csrc/raster.hip), forward only: which triangle of an indexed mesh does the ray of pixel (r, c) hit first,
+ * and at what distance along the unit ray direction — the question cips_siren_surface_x3 answers for a level set.
+ * vertices (V,3) fp32, faces (T,3) int32, world2cam (B,3,4) fp32 = [R | t] (the inverse of cam2world), xg (W) = linspace(-1, 1, W)
+ * and yg (H) = linspace(1, -1, H) (the grids of the ray set-up: read, not computed), zc < 0 the image-plane constant.
+ * Per camera b and vertex i (computed once and stored in `screen`, so a shared vertex has one set of bits):
+ *   q = R v + t;   u = (q.x zc / q.z + 1) (W-1)/2,  v = (1 - q.y zc / q.z) (H-1)/2   (pixel (r, c) has its centre at (u, v) = (c, r))
+ *   valid iff q is finite and -q.z >= near
+ * A triangle is dropped whole, never clipped, if a vertex index is outside [0, V), a vertex is invalid, its screen area is zero
+ * or not finite, or cull == 1 and it faces away from the camera (front-facing: the geometric normal (v1-v0) x (v2-v0) points
+ * towards the camera; with extract_mesh's winding that is the side of lower density).
+ * Coverage: the value of edge {i, j} is ONE fp32 expression with the lower vertex index first,
+ *   e = (u_hi - u_lo)(r - v_lo) - (v_hi - v_lo)(c - u_lo),
+ * negated for the triangle that runs from hi to lo; pixel (r, c) is covered iff all three values have the triangle's orientation
+ * sign or are zero (inclusive on every edge).  Two triangles that share an edge evaluate the same bits: no cracks.
+ * Depth: with E_i the edge value opposite vertex i, w_i = E_i / q_i.z:  z = sum E / sum w,  lambda_i = w_i / sum w (the
+ * perspective-correct barycentrics) and depth = (z / zc) sqrt(xg[c]^2 + yg[r]^2 + zc^2), the quantity of the renderer's depth maps.
+ * A fragment whose depth is not positive and finite is dropped.
+ * Winner: the smallest 64-bit key (bits of depth as fp32) << 32 | face index (64-bit atomicMin into `keys`): equal depths go to
+ * the lower face index, and every output is the same bits on every call whatever order the triangles arrive in.
+ *   face (B,H,W) int32, -1 for none;  bary (B,H,W,3) lambda, zeros for none;  depth (B,H,W), far for none;  mask (B,H,W) uint8 1 / 0
+ * Scratch, provided by the caller and written before it is read: screen (B,V) records of 16 bytes (16-byte aligned), keys
+ * (B,H,W) of 8 bytes, big_list of big_cap >= B*T ints and big_count, one int: a triangle whose clamped bounding box holds more
+ * than 256 pixels is appended to the list and rasterised by workgroups in a further launch.
+ * Launches: memset of keys (and of big_count), vertex, face, large-triangle, resolve kernel; with V == 0 or T == 0 the memset of
+ * keys and the resolve kernel only (the background); with B == 0 none.
+ * cips_raster_interp: out[b, ch, r, c] = sum_i lambda_i attr[faces[face][i], ch] for a per-vertex attribute attr (V,C), `fill`
+ * where face < 0 (or where it names no face or vertex of the mesh); out (B,C,H,W) channel-major.  One launch.
+ * Invalid arguments (a required NULL pointer; H or W < 2; B, V or T < 0; near <= 0 or not finite; zc >= 0 or not finite; a NaN
+ * far; cull not 0 or 1; B*H*W, B*V or B*T beyond int32; big_cap < B*T; C < 1) return hipErrorInvalidValue before any HIP call. */
+int cips_raster_fwd(const float* vertices, const int* faces, const float* world2cam, const float* xg, const float* yg, float zc,
+                    float near_, float far_, int cull, void* screen, unsigned long long* keys, int* big_list, int* big_count,
+                    long long big_cap, int* face, float* bary, float* depth, unsigned char* mask, int B, int V, int T, int H,
+                    int W, cips_stream_t stream);
+int cips_raster_interp(const int* face, const float* bary, const int* faces, const float* attr, float fill, float* out, int B,
+                       int H, int W, int T, int V, int C, cips_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
