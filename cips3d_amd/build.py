@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libcips3d_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "gemm_bf16x3_wide.hip", "gemm_bf16x3_v3.hip", "gemm_bf16x3_km_wide.hip", "siren.hip", "siren_bwd_x3.hip", "siren_fwd_x3.hip", "siren_bwd_points_x3.hip", "siren_surface_x3.hip", "siren_color_x3.hip", "mesh.hip", "render.hip", "modfc.hip", "disc_ops.hip", "optim.hip", "fit_loss.hip", "reproject.hip", "raster.hip", "small_ops.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "gemm_bf16x3_wide.hip", "gemm_bf16x3_v3.hip", "gemm_bf16x3_km_wide.hip", "siren.hip", "siren_bwd_x3.hip", "siren_fwd_x3.hip", "siren_bwd_points_x3.hip", "siren_surface_x3.hip", "siren_color_x3.hip", "mesh.hip", "render.hip", "modfc.hip", "disc_ops.hip", "optim.hip", "fit_loss.hip", "reproject.hip", "raster.hip", "volume.hip", "small_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 # per-source extras.  siren_bwd_x3.hip: the m-major layers of siren_bwd_x4_kernel unroll 32 items x (3 MFMAs + 3 epilogue slots);

@@ -344,6 +344,29 @@ def render_mesh(mesh, cam2world, fov, img_size, near=1e-4, far=float('inf'), cul
     return out
 
 
+@torch.no_grad()
+def render_volume(volume, cam2world, fov, img_size, ray_start, ray_end, num_steps, clamp_mode='relu', last_back=False,
+                  white_back=False, skip=True):
+    """A baked volume seen from b cameras, without the network: ops.render_volume.  volume: anything with .rgbs (Bv,nx,ny,nz,4),
+    .occupancy, .lo and .hi — GeneratorNerfINR.bake's namespace, Bv = 1 (a turntable of one volume) or b; cam2world (b,4,4)
+    (orbit_cameras, or the cam2world of a render() namespace); fov in degrees; img_size: H = W; ray_start, ray_end, num_steps:
+    the depths linspace(ray_start, ray_end, num_steps) of forward() before jitter; clamp_mode, last_back, white_back:
+    forward()'s; skip: the empty-space skip (same bits either way; 'relu' only, pass skip=False with 'softplus').
+    -> SimpleNamespace in render()'s layout:
+      imgs    (b,3,H,W)  the composited colours ('aux' colours for a volume of bake): soft and view-consistent
+      depth   (b,1,H,W)  the expected depth sum w z
+      opacity (b,1,H,W)  sum w, the matte
+      cam2world
+    so that save_image and warp_view take it as they take render()'s result.  Forward only."""
+    from . import ops
+    from .generator import _zc
+    H = int(img_size)
+    rgb, depth, opacity = ops.render_volume(volume.rgbs, volume.occupancy, volume.lo, volume.hi, cam2world, _zc(fov), H, H,
+                                            ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, clamp_mode=clamp_mode,
+                                            last_back=last_back, white_back=white_back, skip=skip)
+    return SimpleNamespace(imgs=rgb, depth=depth, opacity=opacity, cam2world=cam2world)
+
+
 def warp_view(src, tgt, fov, src_fov=None, occ_tol=None):
     """What view `src` predicts for view `tgt`: src.imgs seen from tgt's camera through tgt.depth.  src and tgt are two
     namespaces of GeneratorNerfINR.render() / render_styles() (imgs, depth, cam2world; without return_aux_img, so that imgs and

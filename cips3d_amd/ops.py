@@ -2802,3 +2802,112 @@ def raster_interpolate(face, bary, faces, attr, fill=0.):
     check(_lib.load().cips_raster_interp(_p(face), _p(bary), _p(faces) if T else None, _p(attr) if V else None, float(fill), _p(out),
                                          B, H, W, T, V, Cc, _stream()), "cips_raster_interp")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# Baked radiance volumes (csrc/volume.hip): sigma and colour on a lattice, volume-rendered without the network
+# --------------------------------------------------------------------------------------
+VOLUME_BRICK = 8          # cells per axis of one occupancy brick
+
+
+def _volume_box(who, lo, hi):
+    try:
+        lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: lo and hi must be three numbers each") from None
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"{who}: lo and hi must be three numbers each, got {len(lo)} and {len(hi)}")
+    if not all(math.isfinite(v) for v in lo + hi) or not all(h > l for l, h in zip(lo, hi)):
+        raise ValueError(f"{who}: a finite box with hi > lo on every axis expected, got lo = {lo}, hi = {hi}")
+    return (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+
+
+def bake_volume(sigma, rgb):
+    """sigma (Bv,nx,ny,nz) and rgb (Bv,nx,ny,nz,3), fp32 on the GPU (density_grid's and color_grid's layout) -> (packed, occ):
+      packed (Bv,nx,ny,nz,4)  r, g, b, sigma per node, bits copied: one 16-byte record, what render_volume gathers
+      occ    (Bv, ceil((nx-1)/8), ceil((ny-1)/8), ceil((nz-1)/8))  per brick of 8 x 8 x 8 cells the maximum of sigma over every
+             node a trilinear lookup inside the brick can read (nodes 8I .. min(8I+8, nx-1) per axis): render_volume's
+             empty-space skip reads it.  Exact.
+    The volume is taken to be finite.  The rule: include/cips3d_hip.h (cips_volume_bake).  No host synchronisation."""
+    who = "bake_volume"
+    sigma = _raster_tensor(who, sigma, "sigma", torch.float32, (None, None, None, None))
+    Bv, nx, ny, nz = sigma.shape
+    rgb = _raster_tensor(who, rgb, "rgb", torch.float32, (Bv, nx, ny, nz, 3))
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
+        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
+    _raster_on_gpu(who, sigma, rgb)
+    dev = sigma.device
+    packed = torch.empty(Bv, nx, ny, nz, 4, device=dev)
+    occ = torch.empty(Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz)), device=dev)
+    if Bv:
+        check(_lib.load().cips_volume_bake(_p(sigma), _p(rgb), _p(packed), _p(occ), Bv, nx, ny, nz, _stream()), "cips_volume_bake")
+    return packed, occ
+
+
+def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=None, ray_end=None, num_steps=None,
+                  clamp_mode='relu', last_back=False, white_back=False, skip=True):
+    """A baked volume seen from b cameras -> (rgb (b,3,H,W), depth (b,1,H,W), opacity (b,1,H,W)): trilinear samples of
+    bake_volume's packed (Bv,nx,ny,nz,4) along the rays of the ray set-up, composited by forward()'s rule without noise.
+    occ: bake_volume's brick occupancy (may be None with skip=False); lo, hi: three numbers each, the box of the lattice (node i
+    of axis a at lo[a] + i (hi[a] - lo[a]) / (n_a - 1)); cam2world (b,4,4) fp32; zc = generator._zc(fov) < 0; H, W >= 2.  The
+    sample depths are zg (S,) fp32 on the GPU, or linspace(ray_start, ray_end, num_steps) — pixel_grids', the depths forward()
+    uses before jitter; S >= 2.  Bv is 1 (every camera sees the one volume) or b.  A sample outside the box contributes nothing.
+    clamp_mode 'relu' or 'softplus', last_back, white_back: forward()'s.  opacity is sum w before last_back's top-up.
+    skip (relu only; with 'softplus' skip=True is refused, there is no empty space): samples in bricks with occ <= 0 are not
+    fetched; the outputs are the same bits with and without.  The rule: include/cips3d_hip.h (cips_volume_render).  Forward
+    only, bit-reproducible, no host synchronisation."""
+    who = "render_volume"
+    if clamp_mode not in ('relu', 'softplus'):
+        raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
+    skip = bool(skip)
+    if skip and clamp_mode == 'softplus':
+        raise ValueError(f"{who}: skip=True needs clamp_mode='relu' (softplus(sigma) > 0 everywhere: nothing is empty)")
+    H, W, zc = int(H), int(W), float(zc)
+    if H < 2 or W < 2:
+        raise ValueError(f"{who}: H, W >= 2 expected, got {H} x {W}")
+    if not (math.isfinite(zc) and zc < 0):
+        raise ValueError(f"{who}: zc must be finite and negative, got {zc}")
+    lo_c, hi_c = _volume_box(who, lo, hi)
+    packed = _raster_tensor(who, packed, "packed", torch.float32, (None, None, None, None, 4))
+    Bv, nx, ny, nz = packed.shape[:4]
+    cam2world = _raster_tensor(who, cam2world, "cam2world", torch.float32, (None, 4, 4))
+    b = cam2world.shape[0]
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
+        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
+    if Bv != 1 and Bv != b:
+        raise ValueError(f"{who}: one volume or one per camera expected, got {Bv} volumes and {b} cameras")
+    if zg is None:
+        if ray_start is None or ray_end is None or num_steps is None:
+            raise ValueError(f"{who}: give zg, or ray_start, ray_end and num_steps")
+        if int(num_steps) < 2:
+            raise ValueError(f"{who}: num_steps >= 2 expected, got {num_steps}")
+        if not packed.is_cuda:
+            raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
+        zg = pixel_grids(W, H, int(num_steps), ray_start, ray_end, packed.device)[2]
+    zg = _raster_tensor(who, zg, "zg", torch.float32, (None,))
+    S = zg.shape[0]
+    if S < 2:
+        raise ValueError(f"{who}: at least 2 sample depths expected, got {S}")
+    if b * H * W > 0x7fffffff or H * W * S > 0x7fffffff:
+        raise ValueError(f"{who}: b*H*W and H*W*S must fit in int32, got b = {b}, H x W = {H} x {W}, S = {S}")
+    tensors = [packed, cam2world, zg]
+    if occ is not None or skip:
+        if occ is None:
+            raise ValueError(f"{who}: skip=True needs occ")
+        occ = _raster_tensor(who, occ, "occ", torch.float32, (Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz))))
+        tensors.append(occ)
+    _raster_on_gpu(who, *tensors)
+    if packed.data_ptr() % 16:
+        raise ValueError(f"{who}: packed must be 16-byte aligned")
+    dev = packed.device
+    rgb = torch.empty(b, 3, H, W, device=dev)
+    depth = torch.empty(b, 1, H, W, device=dev)
+    opacity = torch.empty(b, 1, H, W, device=dev)
+    if b == 0:
+        return rgb, depth, opacity
+    xg, yg, _ = pixel_grids(W, H, 2, 0., 1., dev)
+    flags = (1 if last_back else 0) | (2 if white_back else 0) | (4 if skip else 0)
+    check(_lib.load().cips_volume_render(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc,
+                                         0 if clamp_mode == 'relu' else 1, flags, _p(rgb), _p(depth), _p(opacity), b, Bv, nx, ny,
+                                         nz, H, W, S, _stream()), "cips_volume_render")
+    return rgb, depth, opacity

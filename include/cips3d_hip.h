@@ -1054,6 +1054,43 @@ int cips_raster_fwd(const float* vertices, const int* faces, const float* world2
 int cips_raster_interp(const int* face, const float* bary, const int* faces, const float* attr, float fill, float* out, int B,
                        int H, int W, int T, int V, int C, cips_stream_t stream);
 
+/* ------------------------------------------------------------------ */
+/* Baked radiance volumes (csrc/volume.hip), forward only: sigma and colour on a lattice, volume-rendered from any camera of the
+ * ray set-up with the network out of the loop.
+ *
+ * cips_volume_bake: sigma (Bv,nx,ny,nz) and rgb (Bv,nx,ny,nz,3) -> packed (Bv,nx,ny,nz,4) = r, g, b, sigma: one 16-byte record
+ * per node (packed is 16-byte aligned), the two z-neighbours of a corner pair are one 32-byte access.  Bits are copied, nothing
+ * is computed.  occ (Bv, ceil((nx-1)/8), ceil((ny-1)/8), ceil((nz-1)/8)): entry (I, J, K) is the maximum of sigma over the nodes
+ * 8I .. min(8I+8, nx-1) (same per axis; the shared face included): every node a trilinear lookup in a cell of that brick of
+ * 8 x 8 x 8 cells can read.  A maximum is exact.  The volume is taken to be finite (fmaxf drops a NaN).  Two launches.
+ *
+ * cips_volume_render: one ray per lane, lanes mapped to pixels in 8 x 8 tiles.  The ray of pixel (r, c) and its depths
+ * z_s = zg[s] are those of gen_point (csrc/raygen.h: its ray_dir once per ray, its ray_point per sample) with xg (W), yg (H), zg (S), zc and cam2world (b,4,4): no jitter, no
+ * resampled depths.  lo, hi: HOST arrays of three floats, the box of the lattice: node i of axis a sits at
+ * lo[a] + i (hi[a] - lo[a]) / (n_a - 1).  With inv_h[a] = fp32(n_a - 1) / (hi[a] - lo[a]) (fp32, on the host) a sample x has
+ *   u_a = (x_a - lo[a]) * inv_h[a];   inside iff 0 <= u_a <= n_a - 1 on all three axes;   cell i_a = min(floor(u_a), n_a - 2),
+ *   t_a = u_a - i_a, and the four channels are interpolated by nested lerps  p + t (q - p): along z, then y, then x.
+ * A sample outside has sigma = 0 and colour 0.  Compositing is cips_composite_fwd's rule without noise:
+ *   delta_s = z_{s+1} - z_s, the last one 1e10;  alpha = 1 - expf(-delta clamp(sigma)),  clamp_mode 0 relu, 1 softplus;
+ *   w_s = alpha_s fp32(T_s),  T_{s+1} = T_s (1 - alpha_s + 1e-10f) kept in double;  opacity = sum w (before any top-up);
+ *   flags bit 0 (last_back): the last sample's weight gains 1 - sum w;  rgb = sum w c,  depth = sum w z;
+ *   flags bit 1 (white_back): rgb += 1 - sum w.  Sums run in sample order in fp32.
+ * flags bit 2 (skip), relu only: a sample whose brick has occ <= 0 is not fetched.  Exact: every corner <= 0 makes every nested
+ * lerp <= 0 (each rounding is monotone and 0 is representable), so relu gives 0, alpha = 0, w = 0 and T is multiplied by
+ * fp32(1 + 1e-10) = 1: the outputs are the same bits with the bit set or clear.  Under last_back the last sample is fetched
+ * whenever it is inside (its colour takes the top-up).  With clamp_mode 1 the bit is IGNORED here (treated as clear):
+ * softplus(sigma) > 0 everywhere; ops.render_volume refuses the combination.  No early ray termination (it changes bits).
+ *   rgb (b,3,H,W), depth (b,1,H,W), opacity (b,1,H,W);  Bv is 1 (every camera sees volume 0) or b.
+ * Invalid arguments return hipErrorInvalidValue before any HIP call: a NULL pointer (occ may be NULL only with the skip bit
+ * clear); n_a < 2; H, W or S < 2; b or Bv < 0, Bv not in {1, b} (render); lo / hi not finite or hi <= lo; zc >= 0, NaN or -inf;
+ * clamp_mode not 0 or 1; flags outside 0..7; packed not 16-byte aligned; nx*ny*nz, b*H*W or H*W*S beyond int32.
+ * b == 0 (render) or Bv == 0 (bake) returns 0 and launches nothing. */
+int cips_volume_bake(const float* sigma, const float* rgb, void* packed, float* occ, int Bv, int nx, int ny, int nz,
+                     cips_stream_t stream);
+int cips_volume_render(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg, const float* yg,
+                       const float* zg, const float* cam2world, float zc, int clamp_mode, int flags, float* rgb, float* depth,
+                       float* opacity, int b, int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
