@@ -1,6 +1,6 @@
 // volume.hip — baked radiance volumes for gfx950: pack sigma and colour on a lattice into 16-byte nodes with a brick occupancy,
 // and volume-render the result from any camera of raygen.h with the network out of the loop.  The rule, decision by decision,
-// is in include/cips3d_hip.h (cips_volume_bake, cips_volume_render).
+// is in include/cips3d_hip.h (cips_volume_bake, cips_volume_render, cips_volume_render_bwd).
 //
 //   volume_pack_kernel    one thread per node: r, g, b, sigma leave as ONE 16-byte record (bits copied, nothing computed).
 //   volume_occ_kernel     one wave per brick of 8 x 8 x 8 cells: the maximum of sigma over its 9 x 9 x 9 nodes (fewer at the
@@ -10,6 +10,10 @@
 //                         brick's occupancy, eight 16-byte loads (four pairs of z-neighbours, 32 contiguous bytes each), seven
 //                         vector lerps, the composite step.  No LDS, no cross-lane traffic: the kernel waits on gathers, not
 //                         on arithmetic.
+//   volume_render_bwd_kernel  the gradient with respect to the nodes: the same lane marches the same ray, stores one 16-byte
+//                         record per sample, walks the records backwards (composite_bwd_kernel<true>'s reverse scan) and adds
+//                         into the eight nodes of every live sample with fp32 atomic adds.  volume_occ_kernel with stride 4
+//                         rebuilds the occupancy of a packed volume whose nodes have moved (cips_volume_occupancy).
 //
 // The skip and the fetch run through the same code in the same kernel, and so do Bv = 1 and Bv = b: a fetched sample has the
 // same bits whichever way it was reached.  Every float -> int conversion follows the inside test (0 <= u <= n - 1, false for a
@@ -27,6 +31,7 @@ struct PackArgs {
   const float* sigma; const float* rgb; f32x4* packed; float* occ;
   long long total;                       // Bv * nx * ny * nz
   int Bv, nx, ny, nz, bx, by, bz;
+  int stride;                            // floats between two nodes' sigma (volume_occ_kernel)
 };
 
 __global__ __launch_bounds__(256) void volume_pack_kernel(PackArgs a) {
@@ -43,11 +48,12 @@ __global__ __launch_bounds__(64) void volume_occ_kernel(PackArgs a) {
   const int I = br / (a.by * a.bz), rem = br - I * (a.by * a.bz), J = rem / a.bz, K = rem - J * a.bz;
   const int i0 = I << BRICK_SHIFT, j0 = J << BRICK_SHIFT, k0 = K << BRICK_SHIFT;
   const int ni = min(i0 + 8, a.nx - 1) - i0 + 1, nj = min(j0 + 8, a.ny - 1) - j0 + 1, nk = min(k0 + 8, a.nz - 1) - k0 + 1;
-  const float* s = a.sigma + (size_t)vb * a.nx * a.ny * a.nz;
+  // sigma of node n at sigma[n * stride]: stride 1 for a plain sigma tensor, 4 (from channel 3 on) for a packed volume
+  const float* s = a.sigma + (size_t)vb * a.nx * a.ny * a.nz * a.stride;
   float m = -INFINITY;
   for (int t = threadIdx.x; t < ni * nj * nk; t += 64) {
     const int di = t / (nj * nk), r2 = t - di * (nj * nk), dj = r2 / nk, dk = r2 - dj * nk;
-    m = fmaxf(m, s[((size_t)(i0 + di) * a.ny + (j0 + dj)) * a.nz + (k0 + dk)]);
+    m = fmaxf(m, s[(((size_t)(i0 + di) * a.ny + (j0 + dj)) * a.nz + (k0 + dk)) * a.stride]);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
@@ -72,6 +78,39 @@ __device__ __forceinline__ float vol_clamp(float x, int mode) {
 
 __device__ __forceinline__ f32x4 vol_lerp(f32x4 p, f32x4 q, float t) { return p + t * (q - p); }
 
+// Where a sample lands: the inside test, the cell and the three weights, in this one place for the forward and the backward (the
+// backward must find exactly the cell the forward did).  false outside the box, and for a NaN.
+struct VolCell { int i, j, k; float tx, ty, tz; };
+
+__device__ __forceinline__ bool vol_locate(const VolArgs& a, float wx, float wy, float wz, VolCell& c) {
+  const float ux = (wx - a.lo[0]) * a.inv_h[0], uy = (wy - a.lo[1]) * a.inv_h[1], uz = (wz - a.lo[2]) * a.inv_h[2];
+  const bool inside = ux >= 0.f && ux <= a.umax[0] && uy >= 0.f && uy <= a.umax[1] && uz >= 0.f && uz <= a.umax[2];
+  if (inside) {
+    c.i = min((int)ux, a.nx - 2); c.j = min((int)uy, a.ny - 2); c.k = min((int)uz, a.nz - 2);
+    c.tx = ux - (float)c.i; c.ty = uy - (float)c.j; c.tz = uz - (float)c.k;
+  }
+  return inside;
+}
+
+// Is sample s at this world point fetched, and from which cell?  occ: the image's occupancy with the skip on, else NULL.
+__device__ __forceinline__ bool vol_sample_cell(const VolArgs& a, const float* occ, bool last_back, int s, float wx, float wy,
+                                                float wz, VolCell& c) {
+  if (!vol_locate(a, wx, wy, wz, c)) return false;
+  if (occ && !(last_back && s == a.S - 1))
+    return !(occ[((size_t)(c.i >> BRICK_SHIFT) * a.by + (c.j >> BRICK_SHIFT)) * a.bz + (c.k >> BRICK_SHIFT)] <= 0.f);
+  return true;
+}
+
+__device__ __forceinline__ f32x4 vol_fetch(const VolArgs& a, const f32x4* vol, const VolCell& c) {
+  const size_t sy = (size_t)a.nz, sx = (size_t)a.ny * a.nz;
+  const f32x4* p = vol + ((size_t)c.i * a.ny + c.j) * a.nz + c.k;
+  const f32x4 c000 = p[0], c001 = p[1], c010 = p[sy], c011 = p[sy + 1];
+  const f32x4 c100 = p[sx], c101 = p[sx + 1], c110 = p[sx + sy], c111 = p[sx + sy + 1];
+  const f32x4 c00 = vol_lerp(c000, c001, c.tz), c01 = vol_lerp(c010, c011, c.tz);
+  const f32x4 c10 = vol_lerp(c100, c101, c.tz), c11 = vol_lerp(c110, c111, c.tz);
+  return vol_lerp(vol_lerp(c00, c01, c.ty), vol_lerp(c10, c11, c.ty), c.tx);
+}
+
 __global__ __launch_bounds__(256) void volume_render_kernel(VolArgs a) {
   const int img = blockIdx.x / a.blocks_per_image;
   const int tile = (blockIdx.x - img * a.blocks_per_image) * 4 + (threadIdx.x >> 6);
@@ -85,7 +124,6 @@ __global__ __launch_bounds__(256) void volume_render_kernel(VolArgs a) {
   const bool skip = (a.flags & 4) && a.clamp_mode == 0;
   const bool last_back = a.flags & 1;
   const float* occ = skip ? a.occ + (a.Bv == 1 ? 0 : (size_t)img * a.bricks) : nullptr;
-  const size_t sy = (size_t)a.nz, sx = (size_t)a.ny * a.nz;
 
   float cr = 0.f, cg = 0.f, cb = 0.f, depth = 0.f, wsum = 0.f, zlast = 0.f;
   f32x4 vlast = {0.f, 0.f, 0.f, 0.f};
@@ -96,24 +134,9 @@ __global__ __launch_bounds__(256) void volume_render_kernel(VolArgs a) {
   for (int s = 0; s < S; ++s) {
     float wx, wy, wz, z;
     ray_point(a.g, M, dir, a.g.zg[s], 0.f, false, wx, wy, wz, z);
-    const float ux = (wx - a.lo[0]) * a.inv_h[0], uy = (wy - a.lo[1]) * a.inv_h[1], uz = (wz - a.lo[2]) * a.inv_h[2];
-    const bool inside = ux >= 0.f && ux <= a.umax[0] && uy >= 0.f && uy <= a.umax[1] && uz >= 0.f && uz <= a.umax[2];
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (inside) {
-      const int i = min((int)ux, a.nx - 2), j = min((int)uy, a.ny - 2), k = min((int)uz, a.nz - 2);
-      bool fetch = true;
-      if (skip && !(last_back && s == S - 1))
-        fetch = !(occ[((size_t)(i >> BRICK_SHIFT) * a.by + (j >> BRICK_SHIFT)) * a.bz + (k >> BRICK_SHIFT)] <= 0.f);
-      if (fetch) {
-        const float tx_ = ux - (float)i, ty_ = uy - (float)j, tz_ = uz - (float)k;
-        const f32x4* p = vol + ((size_t)i * a.ny + j) * a.nz + k;
-        const f32x4 c000 = p[0], c001 = p[1], c010 = p[sy], c011 = p[sy + 1];
-        const f32x4 c100 = p[sx], c101 = p[sx + 1], c110 = p[sx + sy], c111 = p[sx + sy + 1];
-        const f32x4 c00 = vol_lerp(c000, c001, tz_), c01 = vol_lerp(c010, c011, tz_);
-        const f32x4 c10 = vol_lerp(c100, c101, tz_), c11 = vol_lerp(c110, c111, tz_);
-        v = vol_lerp(vol_lerp(c00, c01, ty_), vol_lerp(c10, c11, ty_), tx_);
-      }
-    }
+    VolCell cell;
+    if (vol_sample_cell(a, occ, last_back, s, wx, wy, wz, cell)) v = vol_fetch(a, vol, cell);
     const float delta = (s + 1 < S) ? (a.g.zg[s + 1] - z) : 1e10f;
     const float alpha = 1.f - expf(-delta * vol_clamp(v.w, a.clamp_mode));
     const float w = alpha * (float)T;
@@ -139,6 +162,144 @@ __global__ __launch_bounds__(256) void volume_render_kernel(VolArgs a) {
   a.opacity[pix] = wsum;                  // neither adjustment above changed it
 }
 
+// d clamp / d x: clamp_density_grad of render.hip
+__device__ __forceinline__ float vol_clamp_grad(float x, int mode) {
+  if (mode == 1) return (x > 20.f) ? 1.f : 1.f / (1.f + expf(-x));
+  return x > 0.f ? 1.f : 0.f;
+}
+
+__device__ __forceinline__ float sel4(int c, float v0, float v1, float v2, float v3) {
+  return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : v3;
+}
+
+struct VolBwdArgs {
+  VolArgs f;                              // the forward's arguments (its three outputs unused)
+  const float *drgb, *ddepth, *dopacity;  // the last two may be NULL (zeros)
+  float* dpacked;                         // zeroed by the entry point
+  f32x4* rec;                             // S * threads records (alpha, fp32(T), s, x), sample-major
+  size_t threads;                         // grid * 256
+};
+
+// The backward of volume_render_kernel with respect to the nodes: the same lane marches the same ray forward once, storing one
+// 16-byte record per sample (sample-major by the thread's linear id: a wave stores 1 KiB contiguous), then walks the records
+// backwards with composite_bwd_kernel<true>'s reverse scan (no division) and adds omega * (w G, dx) to the eight nodes of every
+// live sample.  The reverse pass gathers nothing from the volume: it recomputes the cell and t through the forward's helpers.
+// A thread reads back only its own stores, so there is no fence.
+//   QUAD = false: every lane adds its own four dwords per corner — per wave-instruction 64 dwords in up to 64 nodes.
+//   QUAD = true:  the four lanes of a quad transpose their 4 x 4 values among themselves first (three shuffles), so that in
+//                 instruction r the quad covers the 16 contiguous bytes of the node of its lane r: the same number of atomic
+//                 instructions, 16-byte segments.  Lanes off the image stay for the shuffles; they march and add nothing.
+template <bool QUAD>
+__global__ __launch_bounds__(256) void volume_render_bwd_kernel(VolBwdArgs q) {
+  const VolArgs& a = q.f;
+  const int img = blockIdx.x / a.blocks_per_image;
+  const int tile = (blockIdx.x - img * a.blocks_per_image) * 4 + (threadIdx.x >> 6);
+  if (tile >= a.tiles) return;            // the whole wave
+  const int lane = threadIdx.x & 63;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int r = ty * 8 + (lane >> 3), c = tx * 8 + (lane & 7);
+  const bool on = r < a.H && c < a.W;
+  if (!QUAD && !on) return;
+  const int ray = on ? r * a.W + c : 0, S = a.S;
+  const bool skip = (a.flags & 4) && a.clamp_mode == 0;
+  const bool last_back = a.flags & 1;
+  const float* occ = skip ? a.occ + (a.Bv == 1 ? 0 : (size_t)img * a.bricks) : nullptr;
+  f32x4* rec = q.rec + ((size_t)blockIdx.x * 256 + threadIdx.x);
+  const RayDir dir = ray_dir(a.g, ray);
+  const float* M = a.g.c2w + (size_t)img * 16;
+
+  float Gr = 0.f, Gg = 0.f, Gb = 0.f, gd = 0.f, wsum = 0.f, s_off = 0.f;
+  if (on) {
+    const f32x4* vol = a.vol + (a.Bv == 1 ? 0 : (size_t)img * a.nodes);
+    const size_t plane = (size_t)a.H * a.W, pix = (size_t)img * plane + ray;
+    const float* gp = q.drgb + (size_t)img * 3 * plane + ray;
+    Gr = gp[0]; Gg = gp[plane]; Gb = gp[2 * plane];
+    gd = q.ddepth ? q.ddepth[pix] : 0.f;
+    const float go = q.dopacity ? q.dopacity[pix] : 0.f;
+    double T = 1.0;
+    float slast = 0.f;
+    for (int s = 0; s < S; ++s) {         // the forward's march, expression by expression
+      float wx, wy, wz, z;
+      ray_point(a.g, M, dir, a.g.zg[s], 0.f, false, wx, wy, wz, z);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      VolCell cell;
+      if (vol_sample_cell(a, occ, last_back, s, wx, wy, wz, cell)) v = vol_fetch(a, vol, cell);
+      const float delta = (s + 1 < S) ? (a.g.zg[s + 1] - z) : 1e10f;
+      const float alpha = 1.f - expf(-delta * vol_clamp(v.w, a.clamp_mode));
+      const float Tf = (float)T;
+      wsum += alpha * Tf;
+      T *= (double)(1.f - alpha + 1e-10f);
+      slast = fmaf(gd, z, Gr * v.x + Gg * v.y + Gb * v.z);
+      const f32x4 rc = {alpha, Tf, slast, v.w};
+      rec[(size_t)s * q.threads] = rc;
+    }
+    s_off = (last_back ? slast : 0.f) + ((a.flags & 2) ? (Gr + Gg + Gb) : 0.f) - go;
+  }
+
+  float* dvol = q.dpacked + (a.Bv == 1 ? 0 : (size_t)img * a.nodes * 4);
+  const int sy = a.nz, sx = a.ny * a.nz;  // nx * ny * nz fits in int
+  float Q = 0.f;
+  for (int k = S - 1; k >= 0; --k) {
+    bool live = false;
+    f32x4 g = {0.f, 0.f, 0.f, 0.f};
+    VolCell cell = {0, 0, 0, 0.f, 0.f, 0.f};
+    if (on) {
+      float wx, wy, wz, z;
+      ray_point(a.g, M, dir, a.g.zg[k], 0.f, false, wx, wy, wz, z);
+      const bool fetched = vol_sample_cell(a, occ, last_back, k, wx, wy, wz, cell);
+      const f32x4 rc = rec[(size_t)k * q.threads];
+      const float alpha = rc.x, Tk = rc.y, s = rc.z - s_off, x = rc.w;
+      float w = alpha * Tk;
+      if (last_back && k == S - 1) w += 1.f - wsum;         // the colour of the last sample sees the topped-up weight
+      const float dalpha = Tk * (s - Q);
+      Q = fmaf(alpha, s, (1.f - alpha + 1e-10f) * Q);
+      const float delta = (k + 1 < S) ? (a.g.zg[k + 1] - z) : 1e10f;
+      const float dx = dalpha * (delta * expf(-delta * vol_clamp(x, a.clamp_mode))) * vol_clamp_grad(x, a.clamp_mode);
+      // live: a sample the forward fetched whose colour weight or sigma gradient is not zero (a NaN is not zero)
+      live = fetched && ((w != 0.f) || (dx != 0.f));
+      g.x = w * Gr; g.y = w * Gg; g.z = w * Gb; g.w = dx;
+    }
+    if (QUAD) {
+      if (__ballot(live) == 0) continue;                    // wave-uniform
+    } else if (!live) {
+      continue;
+    }
+    const int base = (cell.i * a.ny + cell.j) * a.nz + cell.k;
+    if (!QUAD) {
+#pragma unroll
+      for (int corner = 0; corner < 8; ++corner) {
+        const int di = corner >> 2, dj = (corner >> 1) & 1, dk = corner & 1;
+        const float om = ((di ? cell.tx : 1.f - cell.tx) * (dj ? cell.ty : 1.f - cell.ty)) * (dk ? cell.tz : 1.f - cell.tz);
+        float* p = dvol + (size_t)(base + di * sx + dj * sy + dk) * 4;
+        atomicAdd(p, om * g.x); atomicAdd(p + 1, om * g.y); atomicAdd(p + 2, om * g.z); atomicAdd(p + 3, om * g.w);
+      }
+    } else {
+      const int qc = lane & 3, q0 = lane & ~3;
+      const int mine = live ? base : -1;
+      const int n0 = __shfl(mine, q0), n1 = __shfl(mine, q0 + 1), n2 = __shfl(mine, q0 + 2), n3 = __shfl(mine, q0 + 3);
+#pragma unroll
+      for (int corner = 0; corner < 8; ++corner) {
+        const int di = corner >> 2, dj = (corner >> 1) & 1, dk = corner & 1;
+        const float om = ((di ? cell.tx : 1.f - cell.tx) * (dj ? cell.ty : 1.f - cell.ty)) * (dk ? cell.tz : 1.f - cell.tz);
+        const float v0 = om * g.x, v1 = om * g.y, v2 = om * g.z, v3 = om * g.w;
+        // a 4 x 4 transpose inside the quad.  A_j = v[(qc + j) & 3]; B_j = A_j of quad lane (qc - j) & 3 = that lane's v[qc];
+        // the value of quad lane r for this lane's channel qc is B[(qc - r) & 3].
+        const float A0 = sel4(qc, v0, v1, v2, v3), A1 = sel4(qc, v1, v2, v3, v0);
+        const float A2 = sel4(qc, v2, v3, v0, v1), A3 = sel4(qc, v3, v0, v1, v2);
+        const float B0 = A0, B1 = __shfl(A1, q0 + ((qc + 3) & 3)), B2 = __shfl(A2, q0 + ((qc + 2) & 3));
+        const float B3 = __shfl(A3, q0 + ((qc + 1) & 3));
+        const float t0 = sel4(qc, B0, B1, B2, B3), t1 = sel4(qc, B3, B0, B1, B2);
+        const float t2 = sel4(qc, B2, B3, B0, B1), t3 = sel4(qc, B1, B2, B3, B0);
+        const int off = di * sx + dj * sy + dk;
+        if (n0 >= 0) atomicAdd(dvol + (size_t)(n0 + off) * 4 + qc, t0);
+        if (n1 >= 0) atomicAdd(dvol + (size_t)(n1 + off) * 4 + qc, t1);
+        if (n2 >= 0) atomicAdd(dvol + (size_t)(n2 + off) * 4 + qc, t2);
+        if (n3 >= 0) atomicAdd(dvol + (size_t)(n3 + off) * 4 + qc, t3);
+      }
+    }
+  }
+}
+
 bool lattice_ok(int nx, int ny, int nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && (long long)nx * ny * nz <= 0x7fffffffLL;
 }
@@ -153,7 +314,7 @@ extern "C" int cips_volume_bake(const float* sigma, const float* rgb, void* pack
   if (!sigma || !rgb || !packed || !occ) return (int)hipErrorInvalidValue;
   if ((uintptr_t)packed & 15) return (int)hipErrorInvalidValue;
   PackArgs a = {};
-  a.sigma = sigma; a.rgb = rgb; a.packed = (f32x4*)packed; a.occ = occ;
+  a.sigma = sigma; a.rgb = rgb; a.packed = (f32x4*)packed; a.occ = occ; a.stride = 1;
   a.Bv = Bv; a.nx = nx; a.ny = ny; a.nz = nz; a.bx = bricks_of(nx); a.by = bricks_of(ny); a.bz = bricks_of(nz);
   a.total = (long long)Bv * nx * ny * nz;
   const long long pack_blocks = (a.total + 255) / 256, occ_blocks = (long long)Bv * a.bx * a.by * a.bz;
@@ -165,20 +326,21 @@ extern "C" int cips_volume_bake(const float* sigma, const float* rgb, void* pack
   return CIPS_CHECK_LAUNCH();
 }
 
-extern "C" int cips_volume_render(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
-                                  const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode, int flags,
-                                  float* rgb, float* depth, float* opacity, int b, int Bv, int nx, int ny, int nz, int H, int W,
-                                  int S, cips_stream_t stream) {
+namespace {
+
+// The checks and the launch geometry that cips_volume_render and cips_volume_render_bwd share (everything but their own
+// pointers): hipErrorInvalidValue, or 0 with `a` filled.  Host arithmetic only.
+int vol_render_args(VolArgs& a, const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                    const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode, int flags, int b, int Bv,
+                    int nx, int ny, int nz, int H, int W, int S) {
   if (b < 0 || Bv < 0 || !lattice_ok(nx, ny, nz) || H < 2 || W < 2 || S < 2) return (int)hipErrorInvalidValue;
   if (Bv != 1 && Bv != b) return (int)hipErrorInvalidValue;
   if ((long long)b * H * W > 0x7fffffffLL || (long long)H * W * S > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   if (clamp_mode != 0 && clamp_mode != 1) return (int)hipErrorInvalidValue;
-  if (flags < 0 || flags > 7) return (int)hipErrorInvalidValue;
-  if (!packed || !lo || !hi || !xg || !yg || !zg || !cam2world || !rgb || !depth || !opacity) return (int)hipErrorInvalidValue;
+  if (!packed || !lo || !hi || !xg || !yg || !zg || !cam2world) return (int)hipErrorInvalidValue;
   if ((flags & 4) && !occ) return (int)hipErrorInvalidValue;
   if ((uintptr_t)packed & 15) return (int)hipErrorInvalidValue;
   if (std::isnan(zc) || std::isinf(zc) || !(zc < 0.f)) return (int)hipErrorInvalidValue;
-  VolArgs a = {};
   const int n[3] = {nx, ny, nz};
   for (int k = 0; k < 3; ++k) {
     if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !(hi[k] > lo[k])) return (int)hipErrorInvalidValue;
@@ -187,18 +349,78 @@ extern "C" int cips_volume_render(const void* packed, const float* occ, const fl
     a.inv_h[k] = a.umax[k] / (hi[k] - lo[k]);
     if (!std::isfinite(a.inv_h[k]) || !(a.inv_h[k] > 0.f)) return (int)hipErrorInvalidValue;
   }
-  if (b == 0) return 0;
   a.vol = (const f32x4*)packed; a.occ = occ;
   a.g.xg = xg; a.g.yg = yg; a.g.zg = zg; a.g.c2w = cam2world; a.g.jitter = nullptr; a.g.zvals = nullptr; a.g.zc = zc;
   a.g.W = W; a.g.n = W * H; a.g.S = S;
-  a.rgb = rgb; a.depth = depth; a.opacity = opacity;
   a.b = b; a.Bv = Bv; a.nx = nx; a.ny = ny; a.nz = nz; a.by = bricks_of(ny); a.bz = bricks_of(nz);
-  a.H = H; a.W = W; a.S = S; a.clamp_mode = clamp_mode; a.flags = flags;
+  a.H = H; a.W = W; a.S = S; a.clamp_mode = clamp_mode; a.flags = flags & 7;
   a.nodes = (long long)nx * ny * nz; a.bricks = (long long)bricks_of(nx) * a.by * a.bz;
   a.tiles_x = (W + 7) >> 3;
   a.tiles = a.tiles_x * ((H + 7) >> 3);                  // <= H * W
-  a.blocks_per_image = (a.tiles + 3) >> 2;
-  const long long grid = (long long)b * a.blocks_per_image;          // <= b * H * W
+  a.blocks_per_image = (a.tiles + 3) >> 2;               // grid = b * blocks_per_image <= b * H * W
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cips_volume_render(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                                  const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode, int flags,
+                                  float* rgb, float* depth, float* opacity, int b, int Bv, int nx, int ny, int nz, int H, int W,
+                                  int S, cips_stream_t stream) {
+  if (flags < 0 || flags > 7 || !rgb || !depth || !opacity) return (int)hipErrorInvalidValue;
+  VolArgs a = {};
+  const int bad = vol_render_args(a, packed, occ, lo, hi, xg, yg, zg, cam2world, zc, clamp_mode, flags, b, Bv, nx, ny, nz, H, W, S);
+  if (bad) return bad;
+  if (b == 0) return 0;
+  a.rgb = rgb; a.depth = depth; a.opacity = opacity;
+  const long long grid = (long long)b * a.blocks_per_image;
   hipLaunchKernelGGL(volume_render_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" long long cips_volume_render_bwd_scratch(int b, int H, int W, int S) {
+  if (b < 0 || H < 2 || W < 2 || S < 2) return -1;
+  if ((long long)b * H * W > 0x7fffffffLL || (long long)H * W * S > 0x7fffffffLL) return -1;
+  const long long tiles = (long long)((W + 7) >> 3) * ((H + 7) >> 3);
+  return (long long)S * (b * ((tiles + 3) >> 2) * 256) * 16;
+}
+
+extern "C" int cips_volume_render_bwd(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                                      const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode,
+                                      int flags, const float* drgb, const float* ddepth, const float* dopacity, void* dpacked,
+                                      void* scratch, int b, int Bv, int nx, int ny, int nz, int H, int W, int S,
+                                      cips_stream_t stream) {
+  if (flags < 0 || flags > 15 || !drgb || !dpacked || !scratch) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)dpacked & 15) || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+  VolBwdArgs q = {};
+  const int bad = vol_render_args(q.f, packed, occ, lo, hi, xg, yg, zg, cam2world, zc, clamp_mode, flags, b, Bv, nx, ny, nz, H, W,
+                                  S);
+  if (bad) return bad;
+  if (Bv == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(dpacked, 0, (size_t)Bv * q.f.nodes * 16, st);
+  if (e != hipSuccess) return (int)e;
+  if (b == 0) return 0;
+  q.drgb = drgb; q.ddepth = ddepth; q.dopacity = dopacity; q.dpacked = (float*)dpacked; q.rec = (f32x4*)scratch;
+  const long long grid = (long long)b * q.f.blocks_per_image;
+  q.threads = (size_t)grid * 256;
+  if (flags & 8)
+    hipLaunchKernelGGL(volume_render_bwd_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, q);
+  else
+    hipLaunchKernelGGL(volume_render_bwd_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, q);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_volume_occupancy(const void* packed, float* occ, int Bv, int nx, int ny, int nz, cips_stream_t stream) {
+  if (Bv < 0 || !lattice_ok(nx, ny, nz)) return (int)hipErrorInvalidValue;
+  if (!packed || !occ) return (int)hipErrorInvalidValue;
+  if ((uintptr_t)packed & 15) return (int)hipErrorInvalidValue;
+  PackArgs a = {};
+  a.sigma = (const float*)packed + 3; a.occ = occ; a.stride = 4;
+  a.Bv = Bv; a.nx = nx; a.ny = ny; a.nz = nz; a.bx = bricks_of(nx); a.by = bricks_of(ny); a.bz = bricks_of(nz);
+  const long long occ_blocks = (long long)Bv * a.bx * a.by * a.bz;
+  if (occ_blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (Bv == 0) return 0;
+  hipLaunchKernelGGL(volume_occ_kernel, dim3((unsigned)occ_blocks), dim3(64), 0, (hipStream_t)stream, a);
   return CIPS_CHECK_LAUNCH();
 }

@@ -5,6 +5,7 @@ exp/cips3d/scripts/train.py:87-170 (`save_images`: the sample grids written with
 (`cips_image_to_u8`, bit-exact torchvision arithmetic); JPEG encoding is PIL on the host, as torchvision does it.
 FID itself (torch-fidelity's Inception network, eval_fid.py:36-50) is outside this repository: the submodule is not
 vendored in the reference, so parity is stated on the pixels that reach it."""
+import contextlib
 import copy
 import ctypes as C
 import math
@@ -344,9 +345,8 @@ def render_mesh(mesh, cam2world, fov, img_size, near=1e-4, far=float('inf'), cul
     return out
 
 
-@torch.no_grad()
 def render_volume(volume, cam2world, fov, img_size, ray_start, ray_end, num_steps, clamp_mode='relu', last_back=False,
-                  white_back=False, skip=True):
+                  white_back=False, skip=True, grad=False):
     """A baked volume seen from b cameras, without the network: ops.render_volume.  volume: anything with .rgbs (Bv,nx,ny,nz,4),
     .occupancy, .lo and .hi — GeneratorNerfINR.bake's namespace, Bv = 1 (a turntable of one volume) or b; cam2world (b,4,4)
     (orbit_cameras, or the cam2world of a render() namespace); fov in degrees; img_size: H = W; ray_start, ray_end, num_steps:
@@ -357,14 +357,100 @@ def render_volume(volume, cam2world, fov, img_size, ray_start, ray_end, num_step
       depth   (b,1,H,W)  the expected depth sum w z
       opacity (b,1,H,W)  sum w, the matte
       cam2world
-    so that save_image and warp_view take it as they take render()'s result.  Forward only."""
+    so that save_image and warp_view take it as they take render()'s result.  grad=False (the default) runs under no_grad;
+    grad=True runs with autograd as the caller has it: where volume.rgbs requires a gradient, imgs, depth and opacity are
+    differentiable with respect to it (the nodes only, not the cameras: ops.render_volume), and volume.occupancy must be the
+    occupancy of volume.rgbs as it stands (ops.volume_occupancy)."""
     from . import ops
     from .generator import _zc
     H = int(img_size)
-    rgb, depth, opacity = ops.render_volume(volume.rgbs, volume.occupancy, volume.lo, volume.hi, cam2world, _zc(fov), H, H,
-                                            ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, clamp_mode=clamp_mode,
-                                            last_back=last_back, white_back=white_back, skip=skip)
+    with contextlib.nullcontext() if grad else torch.no_grad():
+        rgb, depth, opacity = ops.render_volume(volume.rgbs, volume.occupancy, volume.lo, volume.hi, cam2world, _zc(fov), H, H,
+                                                ray_start=ray_start, ray_end=ray_end, num_steps=num_steps, clamp_mode=clamp_mode,
+                                                last_back=last_back, white_back=white_back, skip=skip)
     return SimpleNamespace(imgs=rgb, depth=depth, opacity=opacity, cam2world=cam2world)
+
+
+def fit_volume(volume, targets, cam2world, fov, ray_start, ray_end, num_steps, *, steps, lr, clamp_mode='relu', last_back=False,
+               white_back=False, level_weights=(1.,), kind='mse', target_depth=None, target_opacity=None, depth_weight=0.,
+               opacity_weight=0.):
+    """Fit the nodes of a baked volume to images: a copy of volume.rgbs (Bv,nx,ny,nz,4) — colours and sigma — is optimised so
+    that render_volume from cam2world (b,4,4) gives targets (b,3,H,H).  Bv = 1: one volume seen from b views; Bv = b: one volume
+    per view.  fov, ray_start, ray_end, num_steps, clamp_mode, last_back, white_back: render_volume's.
+    Per step: ops.render_volume with autograd -> loss (b,) = ops.pyramid_loss(imgs, targets, None, level_weights, kind)
+    + depth_weight * MSE(depth, target_depth (b,1,H,H)) + opacity_weight * MSE(opacity, target_opacity (b,1,H,H)) (a term runs
+    where its weight is > 0; it then needs its target) -> backward to the nodes -> FusedClipAdamEMA without clip or EMA, as
+    projection.project uses it.  Under 'relu' the occupancy is refreshed from the moving sigma (ops.volume_occupancy) before
+    every forward, so the empty-space skip stays exact; under 'softplus' there is no skip.  steps and lr have no defaults: the
+    right values depend on the volume's scale (sigma of a baked generator is in the tens to hundreds, colours in [-1, 1]; one
+    learning rate serves both).  The loop never synchronises with the host.
+    -> SimpleNamespace like GeneratorNerfINR.bake's: rgbs (the fitted nodes), occupancy (of the fitted nodes), lo, hi, resolution
+    (volume's, None if it has none), and losses (steps, b) on the device: the loss of every image BEFORE each step.
+    The input volume is not modified."""
+    from . import ops
+    from .generator import _zc
+    from .optim import FusedClipAdamEMA
+    who = "fit_volume"
+    steps = int(steps)
+    lr, depth_weight, opacity_weight = float(lr), float(depth_weight), float(opacity_weight)
+    if steps < 1:
+        raise ValueError(f"{who}: steps >= 1 expected, got {steps}")
+    if not (math.isfinite(lr) and lr > 0):
+        raise ValueError(f"{who}: lr must be finite and positive, got {lr}")
+    if clamp_mode not in ('relu', 'softplus'):
+        raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
+    for name, wt, tgt in (("depth", depth_weight, target_depth), ("opacity", opacity_weight, target_opacity)):
+        if not (math.isfinite(wt) and wt >= 0):
+            raise ValueError(f"{who}: {name}_weight must be finite and >= 0, got {wt}")
+        if wt > 0 and tgt is None:
+            raise ValueError(f"{who}: {name}_weight > 0 needs target_{name}")
+    rgbs = volume.rgbs
+    if not torch.is_tensor(rgbs) or rgbs.dtype != torch.float32 or rgbs.dim() != 5 or rgbs.shape[-1] != 4:
+        raise ValueError(f"{who}: volume.rgbs (Bv,nx,ny,nz,4) fp32 expected")
+    if not torch.is_tensor(targets) or targets.dtype != torch.float32 or targets.dim() != 4 or targets.shape[1] != 3 \
+            or targets.shape[2] != targets.shape[3] or targets.shape[0] == 0:
+        raise ValueError(f"{who}: targets (b,3,H,H) fp32 expected, got {tuple(targets.shape) if torch.is_tensor(targets) else targets!r}")
+    b, H = targets.shape[0], targets.shape[2]
+    if not torch.is_tensor(cam2world) or tuple(cam2world.shape) != (b, 4, 4):
+        raise ValueError(f"{who}: cam2world ({b},4,4) expected for {b} targets")
+    Bv = rgbs.shape[0]
+    if Bv != 1 and Bv != b:
+        raise ValueError(f"{who}: one volume or one per view expected, got {Bv} volumes and {b} targets")
+    for name, tgt in (("depth", target_depth), ("opacity", target_opacity)):
+        if tgt is not None and (not torch.is_tensor(tgt) or tgt.dtype != torch.float32 or tuple(tgt.shape) != (b, 1, H, H)):
+            raise ValueError(f"{who}: target_{name} ({b},1,{H},{H}) fp32 expected")
+    if not (rgbs.is_cuda and targets.is_cuda and cam2world.is_cuda):
+        raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
+    use_depth, use_opacity = depth_weight > 0, opacity_weight > 0
+    targets = targets.detach().contiguous()
+    target_depth = target_depth.detach().contiguous() if use_depth else None
+    target_opacity = target_opacity.detach().contiguous() if use_opacity else None
+    cam2world = cam2world.detach().contiguous()
+    zc, skip, dev = _zc(fov), clamp_mode == 'relu', rgbs.device
+    nodes = rgbs.detach().clone(memory_format=torch.contiguous_format).requires_grad_(True)
+    nodes.grad = torch.zeros_like(nodes)                 # one buffer for every step: autograd adds into it in place
+    opt = FusedClipAdamEMA([nodes], lr=lr, betas=(0.9, 0.999))
+    losses = torch.zeros(steps, b, device=dev)
+    ones = torch.ones(b, device=dev)
+    zg = ops.pixel_grids(H, H, int(num_steps), ray_start, ray_end, dev)[2]
+    for i in range(steps):
+        with torch.no_grad():
+            nodes.grad.zero_()
+            occ = ops.volume_occupancy(nodes) if skip else None
+        with torch.enable_grad():
+            rgb, depth, opacity = ops.render_volume(nodes, occ, volume.lo, volume.hi, cam2world, zc, H, H, zg=zg,
+                                                    clamp_mode=clamp_mode, last_back=last_back, white_back=white_back, skip=skip)
+            loss = ops.pyramid_loss(rgb, targets, None, level_weights, kind)
+            if use_depth:
+                loss = loss + ops.pyramid_loss(depth, target_depth, None, (1.,), "mse") * depth_weight
+            if use_opacity:
+                loss = loss + ops.pyramid_loss(opacity, target_opacity, None, (1.,), "mse") * opacity_weight
+        losses[i].copy_(loss.detach())
+        torch.autograd.backward(loss, ones)
+        opt.step()
+    fitted = nodes.detach()
+    return SimpleNamespace(rgbs=fitted, occupancy=ops.volume_occupancy(fitted), lo=volume.lo, hi=volume.hi,
+                           resolution=getattr(volume, "resolution", None), losses=losses)
 
 
 def warp_view(src, tgt, fov, src_fov=None, occ_tol=None):

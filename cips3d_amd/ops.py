@@ -2844,6 +2844,72 @@ def bake_volume(sigma, rgb):
     return packed, occ
 
 
+def volume_occupancy(packed):
+    """bake_volume's occ for a packed volume (Bv,nx,ny,nz,4) whose nodes have moved: the brick maxima of packed[..., 3], the same
+    bits bake_volume returns for the same sigma (one launch, sigma read in place).  fit_volume refreshes the occupancy with it
+    before every forward, so that render_volume's skip stays exact while sigma moves.  No gradient, no host synchronisation."""
+    who = "volume_occupancy"
+    packed = _raster_tensor(who, packed, "packed", torch.float32, (None, None, None, None, 4))
+    Bv, nx, ny, nz = packed.shape[:4]
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
+        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
+    _raster_on_gpu(who, packed)
+    if packed.data_ptr() % 16:
+        raise ValueError(f"{who}: packed must be 16-byte aligned")
+    occ = torch.empty(Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz)), device=packed.device)
+    if Bv:
+        check(_lib.load().cips_volume_occupancy(_p(packed), _p(occ), Bv, nx, ny, nz, _stream()), "cips_volume_occupancy")
+    return occ
+
+
+def _volume_render_launch(packed, occ, lo_c, hi_c, xg, yg, zg, cam2world, zc, clamp, flags, H, W):
+    b, dev = cam2world.shape[0], packed.device
+    Bv, nx, ny, nz = packed.shape[:4]
+    rgb = torch.empty(b, 3, H, W, device=dev)
+    depth = torch.empty(b, 1, H, W, device=dev)
+    opacity = torch.empty(b, 1, H, W, device=dev)
+    check(_lib.load().cips_volume_render(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc, clamp, flags,
+                                         _p(rgb), _p(depth), _p(opacity), b, Bv, nx, ny, nz, H, W, zg.shape[0], _stream()),
+          "cips_volume_render")
+    return rgb, depth, opacity
+
+
+VOLUME_SCATTER_PER_LANE = False      # scripts/bench_volume_backward.py measures both shapes of the backward's atomic adds
+
+
+class VolumeRenderFunction(torch.autograd.Function):
+    """packed -> rgb, depth, opacity: cips_volume_render, the launch render_volume makes without autograd; the backward is
+    cips_volume_render_bwd on the saved volume, occupancy, cameras and depths.  An output nothing was computed from arrives
+    as None and is passed as NULL.  Only packed has a gradient."""
+
+    @staticmethod
+    def forward(ctx, packed, occ, cam2world, zg, xg, yg, lo_c, hi_c, zc, clamp, flags, H, W):
+        out = _volume_render_launch(packed, occ, lo_c, hi_c, xg, yg, zg, cam2world, zc, clamp, flags, H, W)
+        ctx.save_for_backward(packed, occ, cam2world, zg, xg, yg)
+        ctx.consts = (lo_c, hi_c, zc, clamp, flags, H, W)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, drgb, ddepth, dopacity):
+        packed, occ, cam2world, zg, xg, yg = ctx.saved_tensors
+        lo_c, hi_c, zc, clamp, flags, H, W = ctx.consts
+        lib = _lib.load()
+        b, S = cam2world.shape[0], zg.shape[0]
+        Bv, nx, ny, nz = packed.shape[:4]
+        drgb, ddepth, dopacity = _c(drgb), _c(ddepth), _c(dopacity)
+        if drgb is None:
+            drgb = torch.zeros(b, 3, H, W, device=packed.device)
+        dpacked = torch.empty_like(packed)                                          # zeroed by the entry point
+        scratch = torch.empty(max(lib.cips_volume_render_bwd_scratch(b, H, W, S) // 4, 4), device=packed.device)
+        check(lib.cips_volume_render_bwd(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc, clamp,
+                                         flags | (8 if VOLUME_SCATTER_PER_LANE else 0), _p(drgb), _p(ddepth), _p(dopacity),
+                                         _p(dpacked), _p(scratch), b, Bv, nx, ny, nz, H, W, S, _stream()),
+              "cips_volume_render_bwd")
+        return (dpacked,) + (None,) * 12
+
+
 def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=None, ray_end=None, num_steps=None,
                   clamp_mode='relu', last_back=False, white_back=False, skip=True):
     """A baked volume seen from b cameras -> (rgb (b,3,H,W), depth (b,1,H,W), opacity (b,1,H,W)): trilinear samples of
@@ -2854,9 +2920,16 @@ def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=N
     uses before jitter; S >= 2.  Bv is 1 (every camera sees the one volume) or b.  A sample outside the box contributes nothing.
     clamp_mode 'relu' or 'softplus', last_back, white_back: forward()'s.  opacity is sum w before last_back's top-up.
     skip (relu only; with 'softplus' skip=True is refused, there is no empty space): samples in bricks with occ <= 0 are not
-    fetched; the outputs are the same bits with and without.  The rule: include/cips3d_hip.h (cips_volume_render).  Forward
-    only, bit-reproducible, no host synchronisation."""
+    fetched; the outputs are the same bits with and without.  The rule: include/cips3d_hip.h (cips_volume_render).  The forward
+    is bit-reproducible, with or without autograd; no host synchronisation.
+    Gradients: when autograd is on and packed requires a gradient, the three outputs are differentiable with respect to packed
+    (the nodes: colours and sigma), and to nothing else: cam2world, zg, lo and hi get none, occ is read as given (it must be the
+    occupancy of packed's sigma: volume_occupancy), and there is no double backward.  With Bv = 1 all b cameras add into the
+    one volume.  The gradient is a sum of fp32 atomic adds (cips_volume_render_bwd), whose last bits can differ from call to
+    call, like reproject's source gradient.  Otherwise this is the forward launch alone, the same bits."""
     who = "render_volume"
+    want_grad = torch.is_grad_enabled() and torch.is_tensor(packed) and packed.requires_grad
+    packed_in = packed
     if clamp_mode not in ('relu', 'softplus'):
         raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
     skip = bool(skip)
@@ -2900,14 +2973,11 @@ def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=N
     if packed.data_ptr() % 16:
         raise ValueError(f"{who}: packed must be 16-byte aligned")
     dev = packed.device
-    rgb = torch.empty(b, 3, H, W, device=dev)
-    depth = torch.empty(b, 1, H, W, device=dev)
-    opacity = torch.empty(b, 1, H, W, device=dev)
     if b == 0:
-        return rgb, depth, opacity
+        return torch.empty(b, 3, H, W, device=dev), torch.empty(b, 1, H, W, device=dev), torch.empty(b, 1, H, W, device=dev)
     xg, yg, _ = pixel_grids(W, H, 2, 0., 1., dev)
     flags = (1 if last_back else 0) | (2 if white_back else 0) | (4 if skip else 0)
-    check(_lib.load().cips_volume_render(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc,
-                                         0 if clamp_mode == 'relu' else 1, flags, _p(rgb), _p(depth), _p(opacity), b, Bv, nx, ny,
-                                         nz, H, W, S, _stream()), "cips_volume_render")
-    return rgb, depth, opacity
+    clamp = 0 if clamp_mode == 'relu' else 1
+    if want_grad:
+        return VolumeRenderFunction.apply(packed_in.contiguous(), occ, cam2world, zg, xg, yg, lo_c, hi_c, zc, clamp, flags, H, W)
+    return _volume_render_launch(packed, occ, lo_c, hi_c, xg, yg, zg, cam2world, zc, clamp, flags, H, W)

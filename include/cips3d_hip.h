@@ -1055,8 +1055,8 @@ int cips_raster_interp(const int* face, const float* bary, const int* faces, con
                        int H, int W, int T, int V, int C, cips_stream_t stream);
 
 /* ------------------------------------------------------------------ */
-/* Baked radiance volumes (csrc/volume.hip), forward only: sigma and colour on a lattice, volume-rendered from any camera of the
- * ray set-up with the network out of the loop.
+/* Baked radiance volumes (csrc/volume.hip): sigma and colour on a lattice, volume-rendered from any camera of the ray set-up
+ * with the network out of the loop, and the gradient of that render with respect to the nodes.
  *
  * cips_volume_bake: sigma (Bv,nx,ny,nz) and rgb (Bv,nx,ny,nz,3) -> packed (Bv,nx,ny,nz,4) = r, g, b, sigma: one 16-byte record
  * per node (packed is 16-byte aligned), the two z-neighbours of a corner pair are one 32-byte access.  Bits are copied, nothing
@@ -1090,6 +1090,45 @@ int cips_volume_bake(const float* sigma, const float* rgb, void* packed, float* 
 int cips_volume_render(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg, const float* yg,
                        const float* zg, const float* cam2world, float zc, int clamp_mode, int flags, float* rgb, float* depth,
                        float* opacity, int b, int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
+
+/* cips_volume_render_bwd: the gradient of cips_volume_render's three outputs with respect to the NODES, dpacked (Bv,nx,ny,nz,4)
+ * fp32 in packed's layout (r, g, b, sigma per node), so that an optimiser can step a packed volume in place.  Nothing flows to
+ * the cameras, zg or the box.  Arguments: the forward's, with drgb (b,3,H,W), ddepth (b,1,H,W) and dopacity (b,1,H,W) in place
+ * of the outputs; ddepth and dopacity may each be NULL, meaning zeros.
+ *   Per ray, every forward quantity by the forward's own expressions (the same device functions locate the cell, T in double and
+ * rounded to fp32 per prefix): x_k the interpolated sigma, c_k the interpolated colour, both 0 for a sample that is outside the
+ * box or skipped.  With G = drgb at the pixel, gd = ddepth, go = dopacity, gsum = G_r + G_g + G_b:
+ *     s_k = G . c_k + gd z_k;      s_off = [last_back] s_{S-1} + [white_back] gsum - go;      Q = 0;
+ *     for k = S-1 .. 0:   s' = s_k - s_off;   dalpha = T_k (s' - Q);   Q = alpha_k s' + (1 - alpha_k + 1e-10f) Q;
+ *                         dx_k = dalpha * delta_k expf(-delta_k dens_k) * clamp'(x_k);
+ *                         w_k = alpha_k T_k (+ 1 - sum w for k = S-1 under last_back);   dc_k = w_k G.
+ * clamp' is 1 for x > 0 else 0 (relu), and 1 for x > 20 else 1 / (1 + expf(-x)) (softplus): cips_composite_bwd_geo's reverse scan
+ * with the colour in place of the 32 features; opacity is sum w BEFORE the top-up, so go stays out of s_{S-1}.  No division.
+ *   The scatter: a fetched sample adds omega (dc_k, dx_k) to each of its cell's eight nodes, omega the product over the axes of
+ * t_a or 1 - t_a with the forward's t_a, by fp32 atomic adds: the last bits of dpacked can differ from call to call.  A sample
+ * with w_k == 0 and dx_k == 0 adds nothing (under relu: all empty space and every clamped sample; the last sample under
+ * last_back keeps its colour row through the top-up).  The skip bit has the forward's meaning: a skipped sample has x = 0,
+ * c = 0 and receives nothing, which is exact for the same reason as in the forward; dpacked is the same set of non-zero nodes
+ * with the bit set or clear.
+ *   flags: the forward's bits 0..2, and bit 3 for the shape of the atomic adds, which changes nothing but their order: clear,
+ * the four lanes of a quad exchange their values so that each atomic instruction covers whole 16-byte nodes; set, every lane
+ * adds its own four dwords (kept for scripts/bench_volume_backward.py, which measures the two).
+ *   scratch: cips_volume_render_bwd_scratch(b, H, W, S) bytes = S * threads * 16 with threads = 256 b ceil(tiles / 4),
+ * tiles = ceil(W / 8) ceil(H / 8): one 16-byte record (alpha, T, s, x) per sample and thread, written by the thread's forward march
+ * and read back by the same thread; -1 for sizes the entry point refuses.  Contents need not be initialised.
+ *   dpacked is zeroed on the stream by the entry point, then one launch.  One ray per lane in 8 x 8 tiles as the forward, no LDS.
+ * Invalid arguments return hipErrorInvalidValue before any HIP call: everything the forward refuses (flags outside 0..15 here),
+ * a NULL drgb, dpacked or scratch, dpacked or scratch not 16-byte aligned.  Bv == 0 returns 0; b == 0 zeroes dpacked only.
+ *
+ * cips_volume_occupancy: bake's occ from a PACKED volume (sigma read at stride 4 by the kernel bake uses), for a volume whose
+ * nodes have moved: the same bits as cips_volume_bake gives for the same sigma.  Refuses NULLs, a packed that is not 16-byte
+ * aligned, n_a < 2, nx*ny*nz beyond int32, Bv < 0 with hipErrorInvalidValue before any HIP call; Bv == 0 returns 0. */
+long long cips_volume_render_bwd_scratch(int b, int H, int W, int S);
+int cips_volume_render_bwd(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                           const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode, int flags,
+                           const float* drgb, const float* ddepth, const float* dopacity, void* dpacked, void* scratch, int b,
+                           int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
+int cips_volume_occupancy(const void* packed, float* occ, int Bv, int nx, int ny, int nz, cips_stream_t stream);
 
 #ifdef __cplusplus
 }
