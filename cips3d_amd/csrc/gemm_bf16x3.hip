@@ -812,6 +812,7 @@ static int gemm_nt(const cips_gemm_x3_desc* d, cips_stream_t stream) {
   }
   if (d->torgb_w) return (int)hipErrorNotSupported;       // only the v3 kernel folds ToRGB in: never drop it silently
   if (d->addp_hi) return (int)hipErrorNotSupported;       // ... and only it takes the addend as gated planes
+  if (d->b_kmajor) return (int)hipErrorNotSupported;      // ... or reads B k-major: the kernels below would read [N][ldb]
   if (!X1 && x3_wants_256(d)) {
     const int rc = cips_gemm_bf16x3_wide(d, stream);
     if (rc != (int)hipErrorNotSupported) return rc;
@@ -845,6 +846,7 @@ static int x3_on_v3(const cips_gemm_x3_desc* d, bool x1) {
 }
 extern "C" int cips_gemm_bf16x3_fuses_torgb(const cips_gemm_x3_desc* d) { return (d && d->torgb_w) ? x3_on_v3(d, false) : 0; }
 extern "C" int cips_gemm_bf16x3_takes_addp(const cips_gemm_x3_desc* d) { return (d && d->addp_hi) ? x3_on_v3(d, false) : 0; }
+extern "C" int cips_gemm_bf16x3_takes_bkmajor(const cips_gemm_x3_desc* d) { return (d && d->b_kmajor) ? x3_on_v3(d, false) : 0; }
 extern "C" int cips_gemm_bf16_fuses_torgb(const cips_gemm_x3_desc* d) { return (d && d->torgb_w) ? x3_on_v3(d, true) : 0; }
 extern "C" int cips_gemm_bf16_takes_addp(const cips_gemm_x3_desc* d) { return (d && d->addp_hi) ? x3_on_v3(d, true) : 0; }
 
@@ -853,8 +855,9 @@ static int gemm_km(const cips_gemm_x3_desc* d, cips_stream_t stream) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || !d->C) return (int)hipErrorInvalidValue;
   if ((d->K & 31) || (d->M & 7) || (d->N & 7) || (d->lda & 7) || (d->ldb & 7) || (d->strideA & 7) || (d->strideB & 7))
     return (int)hipErrorInvalidValue;
-  if (d->P_hi || d->T_hi || d->mask || d->add || d->addp_hi || d->rgb_g || d->C_unmasked || d->mask_out || d->res_hi || d->act)
-    return (int)hipErrorNotSupported;            // the K-major form has the plain fp32 epilogue only
+  if (d->P_hi || d->T_hi || d->mask || d->add || d->addp_hi || d->rgb_g || d->C_unmasked || d->mask_out || d->res_hi || d->act ||
+      d->b_kmajor)
+    return (int)hipErrorNotSupported;            // the K-major form has the plain fp32 epilogue only (b_kmajor belongs to the NT entry)
   // square-ish outputs filling the chip with 256x256 tiles: the wide kernel (a single problem is a group of one);
   // descriptor field `kernel`: 1 never, 2 / 3 whenever the shape allows
   if (d->kernel < 0 || d->kernel > 3) return (int)hipErrorInvalidValue;

@@ -516,7 +516,7 @@ static int km_grouped(const cips_gemm_x3_desc* descs, int ngroups, cips_stream_t
     if (e.M != d->M || e.N != d->N || e.K != d->K || e.batch != d->batch || e.lda != d->lda || e.ldb != d->ldb ||
         e.ldc != d->ldc || e.strideA != d->strideA || e.strideB != d->strideB || e.strideC != d->strideC)
       return (int)hipErrorNotSupported;
-    if (e.P_hi || e.T_hi || e.mask || e.add || e.rgb_g || e.C_unmasked || e.mask_out || e.res_hi || e.act)
+    if (e.P_hi || e.T_hi || e.mask || e.add || e.rgb_g || e.C_unmasked || e.mask_out || e.res_hi || e.act || e.b_kmajor)
       return (int)hipErrorNotSupported;
     g.A_hi[i] = e.A_hi; g.A_lo[i] = e.A_lo; g.B_hi[i] = e.B_hi; g.B_lo[i] = e.B_lo; g.C[i] = e.C;
   }

@@ -22,7 +22,9 @@
 // Accumulation order and epilogue arithmetic are those of the wide kernel: results are bit-identical to it.
 //
 // Restrictions (else hipErrorNotSupported and the caller falls back to gemm_bf16x3_wide): M, N multiples of 256,
-// K a multiple of 64, no transposed planes, gate planes as bit planes, 16-byte aligned rows of every tensor.
+// K a multiple of 64, no transposed planes, gate planes as bit planes, 16-byte aligned rows of every tensor.  B planes [K][ldb]
+// (b_kmajor, the BKM instantiations below): the backward's epilogues only, 3-pass only — and no fallback, the entry point
+// refuses what this kernel does not take.
 #include "gemm_x3_common.h"
 #include "../../include/cips3d_hip.h"
 #include <utility>
@@ -32,8 +34,11 @@ namespace {
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef short short4v __attribute__((ext_vector_type(4)));
+typedef short short8v __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 256, BN = 256, BK = 32, ROWB = 64;
+constexpr int KROW = 512;                       // BKM: bytes per k-row of the B image (256 bf16)
 constexpr int OFF_AHI = 0, OFF_ALO = BM * ROWB, OFF_BHI = 2 * BM * ROWB, OFF_BLO = OFF_BHI + BN * ROWB;
 constexpr int STAGE = OFF_BLO + BN * ROWB;      // 65536
 constexpr int SCR_OFF = 2 * STAGE;              // the epilogue scratch starts behind the two stages
@@ -50,6 +55,7 @@ struct VArgs {
 #define LDS_B128(a) (*((__attribute__((address_space(3))) const bf16x8*)(uintptr_t)(a)))
 #define LDS_F4(a) (*((__attribute__((address_space(3))) const f32x4*)(uintptr_t)(a)))
 #define LDS_W32(a) (*((__attribute__((address_space(3))) float*)(uintptr_t)(a)))
+#define LDS_TR(a) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(uintptr_t)(a))
 #define SB() __builtin_amdgcn_sched_barrier(0)
 
 // FAST: the epilogue shapes of the training step, decided at compile time — planes out, no fp32 C; forward flavours
@@ -64,8 +70,17 @@ struct VArgs {
 // X1: the single-pass form (cips_gemm_bf16: sum_k a_hi b_hi, lo operand planes never addressed) — stage contents, fragment
 // numbering and the k-tile schedule x1_ktile are described in gemm_x3_common.h; tile walk, DMA pieces and epilogue are
 // the ones below.  K is a multiple of 128 (an even number of 64-deep k-tiles, at least two).
-template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool RGBF = false, bool ADDP = false, bool X1 = false>
+// BKM: the B planes are row-major [K][ldb] (descriptor field b_kmajor: the head's dX GEMMs on the forward's wbt planes).  The
+// B half of a stage is then the K-major image of gemm_bf16x3_km_wide.hip — 32 k-rows of 512 bytes per plane, 32-byte column
+// pairs XOR-swizzled by 2 (k & 3) in the DMA source address, pieces of 2 k-rows x 512 bytes at the same LDS places as the NT
+// pieces — and a B fragment is two ds_read_b64_tr_b16 (k-rows kb and kb + 4) into the registers of the one ds_read_b128:
+// same values in the same lanes, same MFMA order, bit-identical results; the A half, the barrier, the DMA slots and the
+// epilogue are untouched.  The four 32-column tiles of the wave's B block meet the swizzle in address bits 6-7, so each has
+// a lane base of its own (bq[4], in place of the NT form's two); k-step 1 is an immediate (+ 16 k-rows) and the stage flips
+// by one add per base and k-tile.  3-pass only.
+template <bool HAS_ADD, bool HAS_MASK, bool HAS_RES, bool FAST, bool RGBF = false, bool ADDP = false, bool X1 = false, bool BKM = false>
 __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
+  static_assert(!(BKM && X1), "the single-pass form reads B contraction-contiguous only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const cips_gemm_x3_desc& d = g.d;
   const int tid = threadIdx.x;
@@ -94,8 +109,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       sr.Blo = sr.Bhi + 32;
     } else {
       sr.Alo = (const u16*)d.A_lo + (long long)bz * d.strideA + (long long)tm * BM * d.lda;
-      sr.Bhi = (const u16*)d.B_hi + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
-      sr.Blo = (const u16*)d.B_lo + (long long)bz * d.strideB + (long long)tn * BN * d.ldb;
+      const long long bt = BKM ? (long long)tn * BN : (long long)tn * BN * d.ldb;       // the tile's columns / rows of B
+      sr.Bhi = (const u16*)d.B_hi + (long long)bz * d.strideB + bt;
+      sr.Blo = (const u16*)d.B_lo + (long long)bz * d.strideB + bt;
     }
     const int drow = lane >> 2, dslot = lane & 3;
 #pragma unroll
@@ -103,7 +119,15 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       const int row = (uw + 8 * p) * 16 + drow;
       const int kcsw = dslot ^ ((row >> 2) & 3);
       sr.offA[p] = (unsigned)(row * d.lda + kcsw * 8) * 2u;
-      sr.offB[p] = (unsigned)(row * d.ldb + kcsw * 8) * 2u;
+      if constexpr (BKM) {
+        // piece idx = uw + 8 p: k-rows 2 idx + (lane >> 5), 16-byte chunk lane & 31 of the row; the LDS place c16 holds the
+        // columns of chunk 2 pr + (c16 & 1), pr = (c16 >> 1) ^ 2 (k & 3), k & 3 = 2 (uw & 1) + (lane >> 5) for both p
+        const int lh = lane >> 5, c16 = lane & 31;
+        const int pr = (c16 >> 1) ^ (2 * (2 * (uw & 1) + lh));
+        sr.offB[p] = (unsigned)(lh * d.ldb + (pr * 2 + (c16 & 1)) * 8) * 2u;
+      } else {
+        sr.offB[p] = (unsigned)(row * d.ldb + kcsw * 8) * 2u;
+      }
     }
   };
   // piece pc = 0..7 of the k-tile starting at contraction index k0, into the stage at LDS byte offset `st`
@@ -112,6 +136,11 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     const unsigned la = sbase + st + (unsigned)((uw + 8 * pp) * 16 * ROWB);
     if (which == 0) lds_dma16(sr.Ahi + k0, sr.offA[pp], la + OFF_AHI);
     else if (which == 1) lds_dma16(sr.Alo + k0, sr.offA[pp], la + OFF_ALO);
+    else if constexpr (BKM) {
+      const long long krow = (long long)(k0 + 2 * (uw + 8 * pp)) * d.ldb;      // the piece's first k-row (uniform)
+      if (which == 2) lds_dma16(sr.Bhi + krow, sr.offB[pp], la + OFF_BHI);
+      else lds_dma16(sr.Blo + krow, sr.offB[pp], la + OFF_BLO);
+    }
     else if (which == 2) lds_dma16(sr.Bhi + k0, sr.offB[pp], la + OFF_BHI);
     else lds_dma16(sr.Blo + k0, sr.offB[pp], la + OFF_BLO);
   };
@@ -155,6 +184,34 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
     const int csw = (l31 >> 2) & 3;
     const unsigned fa0 = sbase + (wm * 64 + l31) * ROWB + ((hf ^ csw) << 4), fa1 = sbase + (wm * 64 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
     const unsigned fb0 = sbase + (wn * 128 + l31) * ROWB + ((hf ^ csw) << 4), fb1 = sbase + (wn * 128 + l31) * ROWB + (((2 + hf) ^ csw) << 4);
+
+    // BKM, transpose reads of the B image: lane = column 16 (lane>>4 & 1) + 4 (lane & 3) .. + 4 of the 32-column tile, k-row
+    // kb = 8 hf + (lane>>2 & 3) (+ 4 for the second read, + 16 for k-step 1: kb & 3 is the same for all four), 32-byte pair
+    // (col >> 4) ^ 2 (kb & 3).  bq[j]: tile j of the stage whose k-step 0 is read next (stage 0 here; ktile flips it)
+    unsigned bq[4] = {0, 0, 0, 0};
+    if constexpr (BKM) {
+      const int s16 = lane & 15, mhalf = (lane >> 4) & 1;
+      const int kb = 8 * hf + (s16 >> 2);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = wn * 128 + j * 32 + 16 * mhalf + 4 * (s16 & 3);
+        bq[j] = sbase + kb * KROW + (((col >> 4) ^ (2 * (kb & 3))) << 5) + (col & 15) * 2;
+      }
+    }
+    auto frag_tr = [&](unsigned a) -> bf16x8 {
+      const short4v x = LDS_TR(a), y = LDS_TR(a + 4 * KROW);
+      const short8v v = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
+      return __builtin_bit_cast(bf16x8, v);
+    };
+    // fragment q of the 3-pass k-step: A (and the NT B) from the lane base of its operand, the BKM B from bq + KOFF
+    auto rdq = [&](auto Q_, unsigned abase, unsigned bbase, auto KOFF_) -> bf16x8 {
+      constexpr int q = decltype(Q_)::value;
+      if constexpr (x3_frag_is_a(q)) return LDS_B128(abase + x3_frag_off_nt(q));
+      else if constexpr (BKM) return frag_tr(bq[x3_frag_tile(q)] + x3_frag_plane(q) + decltype(KOFF_)::value);
+      else return LDS_B128(bbase + x3_frag_off_nt(q));
+    };
+    constexpr std::integral_constant<int, 0> KS0{};
+    constexpr std::integral_constant<int, 16 * KROW> KS1{};
 
     bf16x8 F0[12], F1[12];        // the 3-pass schedule's two fragment sets
     bf16x8 G[2][6];               // the single-pass schedule's
@@ -236,14 +293,19 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       constexpr int MODE = decltype(MODE_)::value;
       const unsigned cur = (unsigned)(kt & 1) * STAGE, nxt = STAGE - cur;
       unsigned a1 = fa1 + cur, b1 = fb1 + cur, a0n = fa0 + nxt, b0n = fb0 + nxt;
-      asm volatile("" : "+v"(a1), "+v"(b1), "+v"(a0n), "+v"(b0n));
+      if constexpr (BKM) asm volatile("" : "+v"(a1), "+v"(a0n));
+      else asm volatile("" : "+v"(a1), "+v"(b1), "+v"(a0n), "+v"(b0n));
       // k-step a: MFMAs on set 0, the twelve reads of k-step b into set 1 (one per two MFMAs)
       static_for(std::make_integer_sequence<int, 24>{}, [&](auto M_) {
         constexpr int m = decltype(M_)::value;
         acc[(m >> 2) & 1][m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F0[x3_mfma_a(m)], F0[x3_mfma_b(m)], acc[(m >> 2) & 1][m & 3], 0, 0, 0);
         if constexpr ((m & 1) == 0) {
           constexpr int q = m >> 1;
-          F1[q] = LDS_B128((x3_frag_is_a(q) ? a1 : b1) + x3_frag_off_nt(q));
+          F1[q] = rdq(std::integral_constant<int, q>{}, a1, b1, KS1);
+        }
+        if constexpr (BKM && m == 23) {       // the last B read of stage `cur` is issued: the bases move to stage `nxt`
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bq[j] += nxt - cur;
         }
         SB();
       });
@@ -271,8 +333,8 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
         if constexpr (MODE <= 1) {
           if constexpr (m >= 5 && m <= 15 && (m & 1) == 1) {
             constexpr int q = m - 5;
-            F0[q] = LDS_B128((x3_frag_is_a(q) ? a0n : b0n) + x3_frag_off_nt(q));
-            F0[q + 1] = LDS_B128((x3_frag_is_a(q + 1) ? a0n : b0n) + x3_frag_off_nt(q + 1));
+            F0[q] = rdq(std::integral_constant<int, q>{}, a0n, b0n, KS0);
+            F0[q + 1] = rdq(std::integral_constant<int, q + 1>{}, a0n, b0n, KS0);
           }
         }
         if constexpr (MODE == 2) {
@@ -344,8 +406,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
       ktile1(std::integral_constant<int, 1>{}, nk - 2);
       ktile1(std::integral_constant<int, 2>{}, nk - 1);
     } else {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) F0[q] = LDS_B128((x3_frag_is_a(q) ? fa0 : fb0) + x3_frag_off_nt(q));
+      static_for(std::make_integer_sequence<int, 12>{}, [&](auto Q_) { F0[decltype(Q_)::value] = rdq(Q_, fa0, fb0, KS0); });
       SB();
       for (int kt = 0; kt < nk - 2; ++kt) ktile(std::integral_constant<int, 0>{}, kt);
       ktile(std::integral_constant<int, 1>{}, nk - 2);
@@ -536,19 +597,27 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(VArgs g) {
 
 }  // namespace
 
-template <bool X1, bool A, bool Mk, bool R, bool FAST, bool RGBF = false, bool ADDP = false>
+template <bool X1, bool A, bool Mk, bool R, bool FAST, bool RGBF = false, bool ADDP = false, bool BKM = false>
 static void launch_v3f(const VArgs& g, int grid, hipStream_t stream) {
   static bool attr = false;
   CIPS_PER_DEVICE(attr, false);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1, BKM>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
+  hipLaunchKernelGGL((gemm_bf16x3_v3_kernel<A, Mk, R, FAST, RGBF, ADDP, X1, BKM>), dim3(grid), dim3(512), SMEM_BYTES, stream, g);
 }
 template <bool X1, bool A, bool Mk, bool R>
 static void launch_v3(const VArgs& g, int grid, hipStream_t stream) {
   const cips_gemm_x3_desc& d = g.d;
+  if constexpr (!X1 && !R) {
+    if (d.b_kmajor) {      // the three forms v3_accepts admits: the backward's dX flavours
+      if constexpr (A) launch_v3f<X1, true, true, false, true, false, true, true>(g, grid, stream);             // planes addend (+ rgb term) + gate
+      else if constexpr (Mk) launch_v3f<X1, false, true, false, true, false, false, true>(g, grid, stream);    // gate bits in, planes out
+      else launch_v3f<X1, false, false, false, false, false, false, true>(g, grid, stream);                    // plain: fp32 C and / or planes
+      return;
+    }
+  }
   // the training step's epilogues take the compile-time form
   const bool fwd = !Mk && d.act == 1 && d.mask_out != nullptr, bwd = Mk && d.act == 0 && d.mask_out == nullptr;
   const bool fast = d.P_hi != nullptr && d.C == nullptr && (fwd || bwd) && (A || d.C_unmasked == nullptr);
@@ -584,6 +653,12 @@ static int v3_accepts(const cips_gemm_x3_desc* d, bool x1 = false) {
   if (d->torgb_w) {      // fused ToRGB: the forward flavours' compile-time epilogue only
     if (!d->torgb_part || a || m || !(d->act == 1 && d->mask_out && d->P_hi && !d->C && !d->C_unmasked)) return (int)hipErrorNotSupported;
     if ((d->N & 127) || ((uintptr_t)d->torgb_part & 15) || ((uintptr_t)d->torgb_w & 15)) return (int)hipErrorNotSupported;
+  }
+  if (d->b_kmajor) {     // B planes [K][ldb]: 3-pass, the instantiations of launch_v3 — no activation, no gate output, no residual, and
+    if (d->b_kmajor != 1 || x1 || d->ldb < d->N || r || d->torgb_w || d->act || d->mask_out) return (int)hipErrorNotSupported;
+    if (m) {             // with a gate input the compile-time epilogue: planes out, no fp32 C; the addend as planes or none
+      if (d->add || !d->P_hi || d->C || (!a && d->C_unmasked)) return (int)hipErrorNotSupported;
+    }
   }
   return 0;
 }

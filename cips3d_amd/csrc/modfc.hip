@@ -484,8 +484,10 @@ __global__ __launch_bounds__(256) void modfc_planes_batch_kernel(PrepJobs J, int
     if (k < in_dim && n < out_dim) {
       const float v = W[(long long)k * out_dim + n] * (s[(long long)b * in_dim + k] + 1.f) * demod[(long long)b * out_dim + n];
       split_f32(v, h, l);
-      wbh[base + (long long)k * out_dim + n] = h;
-      wbl[base + (long long)k * out_dim + n] = l;
+      if (wbh) {                                 // NULL (with wbl): this job keeps the transposed orientation only
+        wbh[base + (long long)k * out_dim + n] = h;
+        wbl[base + (long long)k * out_dim + n] = l;
+      }
     }
     th[kk][tx] = h; tl[kk][tx] = l;
   }
@@ -547,6 +549,8 @@ __global__ __launch_bounds__(256) void modfc_prep_bwd_s_batch_kernel(BwdJobs J, 
 // The planes in 64 x 64 tiles: float4 reads of W along n, 8-byte plane stores along n straight from registers,
 // 16-byte stores of the transposed planes along k through LDS (the 32 x 32 form above writes 64-byte segments of 2-byte
 // elements: 3.4 TB/s on the 1.2 GB of per-sample weight planes of a C2 step).  Needs out_dim % 4 == 0, in_dim % 8 == 0.
+// A job without wb planes (the head's 512 x 512 layers: their dX GEMMs read wbt k-major) writes the transposed planes only,
+// half the bytes.
 __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, int B) {
   __shared__ __attribute__((aligned(16))) unsigned short th[64][72], tl[64][72];      // [n local][k local]
   const int job = blockIdx.z / B, b = blockIdx.z % B;
@@ -575,9 +579,11 @@ __global__ __launch_bounds__(256) void modfc_planes_batch64_kernel(PrepJobs J, i
         const float v[4] = {w.x * sc * dm.x, w.y * sc * dm.y, w.z * sc * dm.z, w.w * sc * dm.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) split_f32(v[j], h[j], l[j]);
-        const long long o = base + (long long)k * out_dim + n;
-        *reinterpret_cast<uint2*>(wbh + o) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
-        *reinterpret_cast<uint2*>(wbl + o) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
+        if (wbh) {                               // NULL (with wbl): this job keeps the transposed orientation only
+          const long long o = base + (long long)k * out_dim + n;
+          *reinterpret_cast<uint2*>(wbh + o) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
+          *reinterpret_cast<uint2*>(wbl + o) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
+        }
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) { th[4 * col4 + j][kl] = h[j]; tl[4 * col4 + j][kl] = l[j]; }
@@ -886,6 +892,7 @@ int fill_prep_jobs(const cips_modfc_prep_job* jobs, int njobs, int B, PrepJobs& 
   if (const int rc = job_dims(jobs, njobs, B, D)) return rc;
   for (int i = 0; i < njobs; ++i) {
     const cips_modfc_prep_job& j = jobs[i];
+    if ((j.wb_hi == nullptr) != (j.wb_lo == nullptr)) return (int)hipErrorInvalidValue;      // both planes of wb, or neither
     J.W[i] = Cj.W[i] = j.weight; J.s[i] = Cj.s[i] = j.s; J.demod[i] = Cj.out[i] = j.demod;
     J.wbh[i] = (unsigned short*)j.wb_hi; J.wbl[i] = (unsigned short*)j.wb_lo;
     J.wth[i] = (unsigned short*)j.wbt_hi; J.wtl[i] = (unsigned short*)j.wbt_lo;

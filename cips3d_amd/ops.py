@@ -1618,8 +1618,9 @@ def _x3_operands(d, A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C):
 
 def _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C=None, P=None, T=None, ldt=0, strideT=0,
              mask_out=None, add=None, rgb_g=None, rgb_w=None, C_unmasked=None, mask=None, act=0, res=None, gate_bits=0,
-             torgb=None, addp=None):
+             torgb=None, addp=None, b_kmajor=0):
     d = _x3_operands(GemmX3Desc(), A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, C)
+    d.b_kmajor = b_kmajor          # 1: Bm is stored (batch, K, ldb), row-major over the contraction index (cips3d_hip.h)
     d.P_hi, d.P_lo = (_p(P.hi), _p(P.lo)) if P is not None else (None, None)
     d.ldp, d.strideP = N, M * N
     d.T_hi, d.T_lo = (_p(T.hi), _p(T.lo)) if T is not None else (None, None)
@@ -1657,8 +1658,40 @@ def gemm_x3_takes_addp(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single
     return bool(_x3_entry(single, "_takes_addp")[1](C.byref(d)))
 
 
+# The head's dX GEMMs (dL/dx = g . Wb^T) read the forward's weight planes wbt (B, out, in) as a k-major B operand
+# (descriptor field b_kmajor) wherever the library's 256x256-tile kernel takes that form, and the prep then writes no wb
+# (B, in, out) planes for the layer: half the bytes of the HBM-bound prep.  False: both orientations, wb as the B operand —
+# the former path, kept as the other side of the parity test (tests/test_gpu_head_bkmajor.py: rgb and every gradient equal).
+HEAD_DX_BKMAJOR = True
+_BKMAJOR_OK = {}
+
+
+def gemm_x3_takes_bkmajor(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi):
+    """True when the library runs this descriptor with B read k-major (Bm (batch, K, ldb); 3-pass entry, 256x256-tile kernel)"""
+    d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, b_kmajor=1, **epi)
+    return bool(_lib.load().cips_gemm_bf16x3_takes_bkmajor(C.byref(d)))
+
+
+def _dx_bkmajor_ok(n, cin, cout, nb, dev, single, form):
+    """does the dX GEMM of a (cin, cout) layer over n pixels of nb images take the layer's wbt planes (nb, cout, cin) as its
+    k-major B operand?  form: its epilogue — "gate" (gate bit plane in, planes out), "addp" (+ the planes addend), "c"
+    (plain fp32 output), None (a form the k-major kernel has not: the fp32 addend or copy, bf16 gate planes).  Asked like
+    _addp_shape_ok: once per shape, with stand-in pointers; the single-pass family has no k-major form."""
+    if not HEAD_DX_BKMAJOR or single or form is None:
+        return False
+    key = (n, cin, cout, nb, dev.index, X3_KERNEL, form)
+    ok = _BKMAJOR_OK.get(key)
+    if ok is None:
+        gq = Planes.empty(1, 8, 8, device=dev)
+        epi = {"gate": dict(P=gq, mask=gq.hi, gate_bits=1), "addp": dict(P=gq, mask=gq.hi, gate_bits=1, addp=(gq, gq.hi)),
+               "c": dict(C=gq.hi)}[form]
+        ok = _BKMAJOR_OK[key] = gemm_x3_takes_bkmajor(gq, gq, n, cin, cout, cout, cin, nb, n * cout, cout * cin, **epi)
+    return ok
+
+
 def gemm_x3(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, single=False, **epi):
     """C[b][m][n] = epi(sum_k A[b][m][k] * B[b][n][k]); A, B, P, T, res: Planes; row-major aux use ld = N.
+    b_kmajor=1: B is stored (batch, K, ldb) instead (refused unless gemm_x3_takes_bkmajor says yes).
     single: sum_k A_hi * B_hi only (cips_gemm_bf16; here and in the functions below)"""
     name, fn = _x3_entry(single)
     d = _x3_desc(A, Bm, M, N, K, lda, ldb, batch, strideA, strideB, **epi)
@@ -1923,27 +1956,28 @@ def conv2d_x3_wgrad(dyP, xP, B, Cin, H, W, O, kh, kw, stride, pad, scale=1.0, nc
     return dw
 
 
-def _modfc_prep_x3_out(W, B):
-    """what one layer's split-plane prep writes: wb Planes (B,in,out), wbt Planes (B,out,in), demod (B,out)"""
+def _modfc_prep_x3_out(W, B, want_wb=True):
+    """what one layer's split-plane prep writes: wb Planes (B,in,out) — None when not wanted —, wbt Planes (B,out,in),
+    demod (B,out)"""
     in_dim, out_dim = W.shape
-    return (Planes.empty(B, in_dim, out_dim, device=W.device), Planes.empty(B, out_dim, in_dim, device=W.device),
-            torch.empty(B, out_dim, device=W.device))
+    return (Planes.empty(B, in_dim, out_dim, device=W.device) if want_wb else None,
+            Planes.empty(B, out_dim, in_dim, device=W.device), torch.empty(B, out_dim, device=W.device))
 
 
-def modfc_prep_x3(W, s, eps=1e-8):
+def modfc_prep_x3(W, s, eps=1e-8, want_wb=True):
     """one layer through the single-job entry: the scalar kernels whatever the shape"""
     lib = _lib.load()
     in_dim, out_dim = W.shape
     B = s.shape[0]
-    wb, wbt, demod = _modfc_prep_x3_out(W, B)
-    check(lib.cips_modfc_prep_x3(_p(W), _p(s), _p(wb.hi), _p(wb.lo), _p(wbt.hi), _p(wbt.lo), _p(demod), B, in_dim,
-                                 out_dim, eps, _stream()), "cips_modfc_prep_x3")
+    wb, wbt, demod = _modfc_prep_x3_out(W, B, want_wb)
+    check(lib.cips_modfc_prep_x3(_p(W), _p(s), _p(wb.hi) if wb else None, _p(wb.lo) if wb else None, _p(wbt.hi), _p(wbt.lo),
+                                 _p(demod), B, in_dim, out_dim, eps, _stream()), "cips_modfc_prep_x3")
     return wb, wbt, demod
 
 
-def modfc_prep_x3_batch(layers, eps=1e-8):
+def modfc_prep_x3_batch(layers, eps=1e-8, want_wb=None):
     """layers: list of (W (in,out), s (B,in)) -> list of (wb Planes (B,in,out), wbt Planes (B,out,in), demod (B,out)),
-    all layers in two launches."""
+    all layers in two launches.  want_wb: one flag per layer, False = no wb planes for it (None in its place)."""
     lib = _lib.load()
     mx = lib.cips_modfc_max_jobs()
     out = []
@@ -1951,10 +1985,11 @@ def modfc_prep_x3_batch(layers, eps=1e-8):
         chunk = layers[c0:c0 + mx]
         jobs = (ModfcPrepJob * len(chunk))()
         B = chunk[0][1].shape[0]
-        for j, (W, s) in zip(jobs, chunk):
-            wb, wbt, demod = _modfc_prep_x3_out(W, B)
+        for i, (j, (W, s)) in enumerate(zip(jobs, chunk)):
+            wb, wbt, demod = _modfc_prep_x3_out(W, B, want_wb is None or want_wb[c0 + i])
             j.weight, j.s, j.demod = _p(W), _p(s), _p(demod)
-            j.wb_hi, j.wb_lo, j.wbt_hi, j.wbt_lo = _p(wb.hi), _p(wb.lo), _p(wbt.hi), _p(wbt.lo)
+            j.wb_hi, j.wb_lo = (_p(wb.hi), _p(wb.lo)) if wb is not None else (None, None)
+            j.wbt_hi, j.wbt_lo = _p(wbt.hi), _p(wbt.lo)
             j.in_dim, j.out_dim = W.shape
             out.append((wb, wbt, demod))
         check(lib.cips_modfc_prep_x3_batch(jobs, len(chunk), B, eps, _stream()), "cips_modfc_prep_x3_batch")
@@ -2071,7 +2106,38 @@ class _HeadLayer:
     written by the forward's epilogues unless pinned), else the bf16 sign form: a1's own hi plane, and the output's hi
     plane or, behind a skip connection, a copy of a2's sign the forward writes."""
     __slots__ = ("cin", "cout", "skip", "bits", "pinned1", "pinned2", "xP", "a1P", "gate1", "oP", "gate2", "wb1", "d1", "wb2",
-                 "d2")
+                 "d2", "wbt1", "wbt2")      # per modulated layer one of wb / wbt is kept, the other None (_head_dx_kmajor)
+
+
+def _head_addp(layers, bits, n, nb, dev, single):
+    """the backward recovers the skip gradient from the previous layer's gated planes (no fp32 copy): every layer has
+    bit-plane gates and the 256x256-tile kernel takes the planes addend at the skip layers' shapes"""
+    fam = {"single": True} if single else {}       # the default mode asks exactly as before
+    return all(bits) and all(_addp_shape_ok(n, L.cin, L.cout, nb, dev, **fam) for L in layers[1:] if L.skip)
+
+
+def _head_dx_kmajor(layers, n, nb, dev, single, train):
+    """per block (dX through W1, dX through W2): True where the backward's dX GEMM reads the forward's wbt planes k-major, so
+    that the prep writes no wb planes for the layer.  Decided from the epilogue the backward will launch (the rules of
+    InrHeadX3Function.backward, below) and the library's query.  Without `train` nothing is kept and no backward follows:
+    the plan is the one of the training step at the same shapes."""
+    bits = [L.bits if train else L.cout % 32 == 0 for L in layers]
+    addp = _head_addp(layers, bits, n, nb, dev, single)
+    plan = []
+    for k, L in enumerate(layers):
+        if k == 0:
+            form1 = "c"
+        elif not bits[k - 1]:
+            form1 = None
+        elif L.skip:
+            form1 = "addp" if addp else None
+        elif k - 1 >= 3:
+            form1 = None                                # the rgb term without an addend: no 256x256-tile form at all
+        else:
+            form1 = "gate" if addp or not layers[k - 1].skip else None
+        plan.append((_dx_bkmajor_ok(n, L.cin, L.cout, nb, dev, single, form1),
+                     _dx_bkmajor_ok(n, L.cout, L.cout, nb, dev, single, "gate" if bits[k] else None)))
+    return plan
 
 
 def _pixel_split(n, ksp, more):
@@ -2156,23 +2222,29 @@ class InrHeadX3Function(torch.autograd.Function):
         train = grad_mode and any(ctx.needs_input_grad)       # no-grad / inference: nothing kept
         x0P, _ = split_planes(x0, want_t=False)
         rgb = torch.empty(B, n, 3, device=dev)
-        # modulate / demodulate / split every layer's weights up front, in one batch
-        prepped = modfc_prep_x3_batch([(W, s_) for (W1, s1, W2, s2) in blocks for (W, s_) in ((W1, s1), (W2, s2))])
         dbg = gate_debug.active                                     # gate instrumentation (tests): bit planes always
-        # every buffer is allocated here, before the first GEMM
         layers = []
-        xP = x0P
         for k, (W1, s1, W2, s2) in enumerate(blocks):
             L = _HeadLayer()
-            cin, cout = W1.shape
+            L.cin, L.cout = W1.shape
+            L.skip = (k >= 4) and (L.cin == L.cout)
             # LeakyReLU gates as bit planes (1 bit per activation, written by the forward GEMMs' epilogues) instead of bf16
             # planes: 2.5 GB less HBM traffic per C2 step (layer widths that are not multiples of 32 keep the bf16 form)
-            bits = (train or dbg) and cout % 32 == 0
+            L.bits = (train or dbg) and L.cout % 32 == 0
+            layers.append(L)
+        # modulate / demodulate / split every layer's weights up front, in one batch: the planes wbt (B, out, in) of the
+        # forward GEMMs, and wb (B, in, out) only for the layers whose dX GEMM does not read wbt k-major
+        kmajor = _head_dx_kmajor(layers, n, B, dev, sp, train)
+        prepped = modfc_prep_x3_batch([(W, s_) for (W1, s1, W2, s2) in blocks for (W, s_) in ((W1, s1), (W2, s2))],
+                                      want_wb=[not f for pair in kmajor for f in pair])
+        # every buffer is allocated here, before the first GEMM
+        xP = x0P
+        for k, L in enumerate(layers):
+            cin, cout, bits = L.cin, L.cout, L.bits
             pin1 = _next_pin(B, n, cout, dev)
             pin2 = _next_pin(B, n, cout, dev)
             if (pin1 is not None or gate_debug.rec is not None) and not bits:
                 raise RuntimeError("gate instrumentation needs layer widths that are multiples of 32")
-            L.cin, L.cout, L.bits, L.skip = cin, cout, bits, (k >= 4) and (cin == cout)
             L.pinned1, L.pinned2 = pin1 is not None, pin2 is not None
             L.xP = xP
             L.a1P = Planes.empty(B, n, cout, device=dev)
@@ -2186,9 +2258,10 @@ class InrHeadX3Function(torch.autograd.Function):
                 L.gate2 = torch.empty(B, n, cout, device=dev, dtype=BF) if train else None
             else:
                 L.gate2 = L.oP.hi
-            L.wb1, _, L.d1 = prepped[2 * k]
-            L.wb2, _, L.d2 = prepped[2 * k + 1]
-            layers.append(L)
+            # the dX operand of each modulated layer: wb, or (wb None) the forward's own wbt planes
+            L.wb1, wbt1, L.d1 = prepped[2 * k]
+            L.wb2, wbt2, L.d2 = prepped[2 * k + 1]
+            L.wbt1, L.wbt2 = (wbt1 if L.wb1 is None else None), (wbt2 if L.wb2 is None else None)
             xP = L.oP
         first_rgb = True
         for k, L in enumerate(layers):
@@ -2251,7 +2324,7 @@ class InrHeadX3Function(torch.autograd.Function):
         # the skip gradient D (un-gated) is either kept as an fp32 copy next to the gated planes every GEMM writes
         # for its successors, or — when every layer has bit-plane gates and the 256x256-tile kernel takes the shapes —
         # recovered from those planes by the consumer: no copy written, same bytes read
-        addp = all(L.bits for L in layers) and all(_addp_shape_ok(n, L.cin, L.cout, B, dev, **fam) for L in layers[1:] if L.skip)
+        addp = _head_addp(layers, [L.bits for L in layers], n, B, dev, sp)
         k, L = nblocks - 1, layers[-1]
         Dout = None
         if k >= 3 and L.bits and width % 8 == 0:
@@ -2281,16 +2354,20 @@ class InrHeadX3Function(torch.autograd.Function):
             gP_in = gP              # D_{k+1} gated by a2_k's gate: the planes form of the skip gradient
             # ---- mod2: gradient through the gate of a1 ----
             g1P = Planes.empty(B, n, cout, device=dev)
-            gemm_x3(gP, L.wb2, n, cout, cout, cout, cout, B, n * cout, cout * cout, P=g1P, mask=L.gate1,
-                    gate_bits=1 if L.bits else 0, single=sp)
+            # the weights as the B operand of a dX GEMM: wb (in, out) = [N][K], or the forward's wbt (out, in) = [K][N] read k-major
+            w2 = (L.wb2, cout) if L.wb2 is not None else (L.wbt2, cout)
+            w1 = (L.wb1, cout) if L.wb1 is not None else (L.wbt1, cin)
+            km2, km1 = {"b_kmajor": 1} if L.wb2 is None else {}, {"b_kmajor": 1} if L.wb1 is None else {}
+            gemm_x3(gP, w2[0], n, cout, cout, cout, w2[1], B, n * cout, cout * cout, P=g1P, mask=L.gate1,
+                    gate_bits=1 if L.bits else 0, single=sp, **km2)
             _head_wgrad(L, gP, g1P, *gwb[k], n, **fam)
             if k == 0:
-                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, C=dx0, single=sp)
+                gemm_x3(g1P, w1[0], n, cin, cout, cout, w1[1], B, n * cout, cin * cout, C=dx0, single=sp, **km1)
             else:
                 prev = layers[k - 1]
                 newD = torch.empty(B, n, cin, device=dev) if prev.skip and not addp else None
                 gP = Planes.empty(B, n, cin, device=dev)
-                gemm_x3(g1P, L.wb1, n, cin, cout, cout, cout, B, n * cout, cin * cout, P=gP,
+                gemm_x3(g1P, w1[0], n, cin, cout, cout, w1[1], B, n * cout, cin * cout, P=gP, **km1,
                         add=Dout if L.skip and not addp else None, addp=(gP_in, L.gate2) if L.skip and addp else None,
                         rgb_g=drgb2 if k - 1 >= 3 else None, rgb_w=rgbp[2 * (k - 1 - 3)] if k - 1 >= 3 else None,
                         C_unmasked=newD, mask=prev.gate2, gate_bits=1 if prev.bits else 0, single=sp)

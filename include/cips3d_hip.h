@@ -556,9 +556,20 @@ typedef struct cips_gemm_x3_desc {
    * whenever a kernel takes the shape; 3 = like 2 but never the v3 schedule.  1-3 serve the parity tests of each kernel.
    * The K-major entry points read it the same way (1: never the 256x256-tile kernel, 2 / 3: whenever the shape allows). */
   int kernel;
+  /* Orientation of the B planes.  0: [N][ldb], contraction-contiguous, as stated at the top.  1: row-major [K][ldb] with
+   * ldb >= N, ldb % 8 == 0, batch stride strideB (0 = shared) — the product is still C = A . B over K.  The head's dX GEMMs
+   * pass the forward's weight planes wbt (B, out, in) this way instead of a transposed copy: the kernel stages the B tile as
+   * k-rows and builds its MFMA fragments with LDS transpose reads, same MFMA order, bit-identical results.  Only the
+   * 256x256-tile v3 kernel of cips_gemm_bf16x3 implements it, for the epilogues of the backward: gate bit plane in / planes
+   * out (without or with the planes addend addp_*, rgb term included), and the plain fp32 C.  Every other descriptor with
+   * b_kmajor = 1 — another shape, kernel = 1 or 3, another epilogue, the single-pass and K-major entry points — returns
+   * hipErrorNotSupported and writes nothing; cips_gemm_bf16x3_takes_bkmajor tells beforehand. */
+  int b_kmajor;
 } cips_gemm_x3_desc;
 
 int cips_gemm_bf16x3(const cips_gemm_x3_desc* d, cips_stream_t stream);
+/* 1 when cips_gemm_bf16x3 would run this descriptor with its B planes read k-major (b_kmajor = 1; v3 kernel only) */
+int cips_gemm_bf16x3_takes_bkmajor(const cips_gemm_x3_desc* d);
 /* 1 when cips_gemm_bf16x3 would run this descriptor on the v3 kernel (the only one with the fused ToRGB partials) */
 int cips_gemm_bf16x3_fuses_torgb(const cips_gemm_x3_desc* d);
 /* 1 when cips_gemm_bf16x3 would take this descriptor's planes addend (addp_*; v3 kernel only) */
@@ -695,7 +706,7 @@ int cips_split_planes(const float* x, void* p_hi, void* p_lo, void* t_hi, void* 
  * demod (B,out) = rsqrt(sum_in (W*(s+1))^2 + eps). */
 int cips_modfc_prep(const float* weight, const float* s, float* wb, float* wbt, float* demod,
                     int B, int in_dim, int out_dim, float eps, cips_stream_t stream);
-/* same, writing the bf16x3 operand planes: wb [in][out] and wbt [out][in], hi/lo each. */
+/* same, writing the bf16x3 operand planes: wb [in][out] and wbt [out][in], hi/lo each (wb_hi == wb_lo == NULL: wbt only). */
 int cips_modfc_prep_x3(const float* weight, const float* s, void* wb_hi, void* wb_lo, void* wbt_hi,
                        void* wbt_lo, float* demod, int B, int in_dim, int out_dim, float eps,
                        cips_stream_t stream);
@@ -709,7 +720,9 @@ int cips_modfc_prep_bwd(const float* weight, const float* s, const float* demod,
  * per-layer contracts as cips_modfc_prep_x3 / cips_modfc_prep_bwd, one shared batch size B. */
 typedef struct cips_modfc_prep_job {
   const float* weight; const float* s;        /* (in,out), (B,in) */
-  void *wb_hi, *wb_lo, *wbt_hi, *wbt_lo;      /* (B,in,out) and (B,out,in) bf16 planes */
+  void *wb_hi, *wb_lo, *wbt_hi, *wbt_lo;      /* (B,in,out) and (B,out,in) bf16 planes.  wb_hi == wb_lo == NULL: that
+                                               * orientation is not written (wbt and demod are what they are with it);
+                                               * exactly one of the pair NULL is hipErrorInvalidValue */
   float* demod;                               /* (B,out) */
   int in_dim, out_dim;
 } cips_modfc_prep_job;
