@@ -223,6 +223,8 @@ SIGNATURES = {
     "cips_volume_render_bwd_scratch": (i64, [i32] * 4),
     "cips_volume_render_bwd": (i32, [vp] * 8 + [f32, i32, i32] + [vp] * 5 + [i32] * 8 + [vp]),
     "cips_volume_occupancy": (i32, [vp, vp] + [i32] * 4 + [vp]),
+    "cips_volume_render_bwd_cam_scratch": (i64, [i32] * 4),
+    "cips_volume_render_bwd_cam": (i32, [vp] * 8 + [f32, i32, i32] + [vp] * 5 + [i32] * 8 + [vp]),
     "cips_camera_pose": (i32, [vp, vp, i32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
     "cips_grouped_linear_max_jobs": (i32, []),
     "cips_grouped_linear_fwd": (i32, [C.POINTER(GlinJob), i32, i32, vp]),

@@ -300,6 +300,134 @@ __global__ __launch_bounds__(256) void volume_render_bwd_kernel(VolBwdArgs q) {
   }
 }
 
+// d v / d t_a (a = x, y, z) of vol_fetch's interpolant, from the same eight corners through the same addressing: the difference
+// of the cell's two bilinear faces along axis a, which is exact for the trilinear rule.
+struct VolSlope { f32x4 x, y, z; };
+
+__device__ __forceinline__ VolSlope vol_fetch_slope(const VolArgs& a, const f32x4* vol, const VolCell& c) {
+  const size_t sy = (size_t)a.nz, sx = (size_t)a.ny * a.nz;
+  const f32x4* p = vol + ((size_t)c.i * a.ny + c.j) * a.nz + c.k;
+  const f32x4 c000 = p[0], c001 = p[1], c010 = p[sy], c011 = p[sy + 1];
+  const f32x4 c100 = p[sx], c101 = p[sx + 1], c110 = p[sx + sy], c111 = p[sx + sy + 1];
+  const f32x4 c00 = vol_lerp(c000, c001, c.tz), c01 = vol_lerp(c010, c011, c.tz);
+  const f32x4 c10 = vol_lerp(c100, c101, c.tz), c11 = vol_lerp(c110, c111, c.tz);
+  VolSlope g;
+  g.x = vol_lerp(c10, c11, c.ty) - vol_lerp(c00, c01, c.ty);
+  g.y = vol_lerp(c01 - c00, c11 - c10, c.tx);
+  g.z = vol_lerp(vol_lerp(c001 - c000, c011 - c010, c.ty), vol_lerp(c101 - c100, c111 - c110, c.ty), c.tx);
+  return g;
+}
+
+struct VolCamArgs {
+  VolArgs f;                              // the forward's arguments (its three outputs unused)
+  const float *drgb, *ddepth, *dopacity;  // the last two may be NULL (zeros)
+  float* dcam;                            // (b,4,4), fully written by volume_cam_finish_kernel
+  f32x4* rec;                             // S * threads records (alpha, fp32(T), s, x), sample-major
+  float* part;                            // b * tiles * 12 floats: one 3 x 4 block per tile, behind the records
+  size_t threads;                         // grid * 256
+};
+
+// The backward of volume_render_kernel with respect to cam2world.  The march and the reverse scan are volume_render_bwd_kernel's,
+// expression by expression; where that kernel scatters omega (w G, dx) into eight nodes, this one gathers the eight nodes again
+// (live samples only) and forms dp = w (G . grad c) + dx grad sigma, then A = sum dp and B = sum z dp per ray.  With
+// world = R (dir z) + t:  d R[a][c] = B_a dir_c,  d t_a = A_a.  The wave adds its 64 rays' twelve products by a butterfly of
+// shuffles (a fixed order) and lane 0 stores them: no atomics, the same bits on every call.  Lanes off the image stay for the
+// shuffles with zeros.
+__global__ __launch_bounds__(256) void volume_render_bwd_cam_kernel(VolCamArgs q) {
+  const VolArgs& a = q.f;
+  const int img = blockIdx.x / a.blocks_per_image;
+  const int tile = (blockIdx.x - img * a.blocks_per_image) * 4 + (threadIdx.x >> 6);
+  if (tile >= a.tiles) return;            // the whole wave
+  const int lane = threadIdx.x & 63;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int r = ty * 8 + (lane >> 3), c = tx * 8 + (lane & 7);
+  const bool on = r < a.H && c < a.W;
+  const int ray = on ? r * a.W + c : 0, S = a.S;
+  const RayDir dir = ray_dir(a.g, ray);
+  float Ax = 0.f, Ay = 0.f, Az = 0.f, Bx = 0.f, By = 0.f, Bz = 0.f;
+  if (on) {
+    const bool skip = (a.flags & 4) && a.clamp_mode == 0;
+    const bool last_back = a.flags & 1;
+    const float* occ = skip ? a.occ + (a.Bv == 1 ? 0 : (size_t)img * a.bricks) : nullptr;
+    f32x4* rec = q.rec + ((size_t)blockIdx.x * 256 + threadIdx.x);
+    const float* M = a.g.c2w + (size_t)img * 16;
+    const f32x4* vol = a.vol + (a.Bv == 1 ? 0 : (size_t)img * a.nodes);
+    const size_t plane = (size_t)a.H * a.W, pix = (size_t)img * plane + ray;
+    const float* gp = q.drgb + (size_t)img * 3 * plane + ray;
+    const float Gr = gp[0], Gg = gp[plane], Gb = gp[2 * plane];
+    const float gd = q.ddepth ? q.ddepth[pix] : 0.f;
+    const float go = q.dopacity ? q.dopacity[pix] : 0.f;
+    double T = 1.0;
+    float wsum = 0.f, slast = 0.f;
+    for (int s = 0; s < S; ++s) {         // the forward's march, expression by expression
+      float wx, wy, wz, z;
+      ray_point(a.g, M, dir, a.g.zg[s], 0.f, false, wx, wy, wz, z);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      VolCell cell;
+      if (vol_sample_cell(a, occ, last_back, s, wx, wy, wz, cell)) v = vol_fetch(a, vol, cell);
+      const float delta = (s + 1 < S) ? (a.g.zg[s + 1] - z) : 1e10f;
+      const float alpha = 1.f - expf(-delta * vol_clamp(v.w, a.clamp_mode));
+      const float Tf = (float)T;
+      wsum += alpha * Tf;
+      T *= (double)(1.f - alpha + 1e-10f);
+      slast = fmaf(gd, z, Gr * v.x + Gg * v.y + Gb * v.z);
+      const f32x4 rc = {alpha, Tf, slast, v.w};
+      rec[(size_t)s * q.threads] = rc;
+    }
+    const float s_off = (last_back ? slast : 0.f) + ((a.flags & 2) ? (Gr + Gg + Gb) : 0.f) - go;
+
+    float Q = 0.f;
+    for (int k = S - 1; k >= 0; --k) {
+      float wx, wy, wz, z;
+      ray_point(a.g, M, dir, a.g.zg[k], 0.f, false, wx, wy, wz, z);
+      VolCell cell;
+      const bool fetched = vol_sample_cell(a, occ, last_back, k, wx, wy, wz, cell);
+      const f32x4 rc = rec[(size_t)k * q.threads];
+      const float alpha = rc.x, Tk = rc.y, s = rc.z - s_off, x = rc.w;
+      float w = alpha * Tk;
+      if (last_back && k == S - 1) w += 1.f - wsum;           // the colour of the last sample sees the topped-up weight
+      const float dalpha = Tk * (s - Q);
+      Q = fmaf(alpha, s, (1.f - alpha + 1e-10f) * Q);
+      const float delta = (k + 1 < S) ? (a.g.zg[k + 1] - z) : 1e10f;
+      const float dx = dalpha * (delta * expf(-delta * vol_clamp(x, a.clamp_mode))) * vol_clamp_grad(x, a.clamp_mode);
+      // live: volume_render_bwd_kernel's rule.  A skipped sample and a fetched one that is not live add nothing either way.
+      if (!(fetched && ((w != 0.f) || (dx != 0.f)))) continue;
+      const VolSlope g = vol_fetch_slope(a, vol, cell);
+      const float px = a.inv_h[0] * fmaf(dx, g.x.w, w * (Gr * g.x.x + Gg * g.x.y + Gb * g.x.z));
+      const float py = a.inv_h[1] * fmaf(dx, g.y.w, w * (Gr * g.y.x + Gg * g.y.y + Gb * g.y.z));
+      const float pz = a.inv_h[2] * fmaf(dx, g.z.w, w * (Gr * g.z.x + Gg * g.z.y + Gb * g.z.z));
+      Ax += px; Ay += py; Az += pz;
+      Bx = fmaf(z, px, Bx); By = fmaf(z, py, By); Bz = fmaf(z, pz, Bz);
+    }
+  }
+  // rows a = x, y, z of d cam2world: (B_a dir_x, B_a dir_y, B_a dir_z, A_a)
+  float m[12] = {Bx * dir.dx, Bx * dir.dy, Bx * dir.dz, Ax, By * dir.dx, By * dir.dy, By * dir.dz, Ay,
+                 Bz * dir.dx, Bz * dir.dy, Bz * dir.dz, Az};
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m[j] += __shfl_xor(m[j], off, 64);
+  }
+  if (lane == 0) {
+    float* o = q.part + ((size_t)img * a.tiles + tile) * 12;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) o[j] = m[j];
+  }
+}
+
+// One block of 12 waves per image: wave j adds entry j of the image's tiles, lane l the tiles l, l + 64, ... in order, then the
+// same butterfly.  Writes the image's whole 4 x 4 matrix, row 3 as zeros.
+__global__ __launch_bounds__(768) void volume_cam_finish_kernel(const float* part, float* dcam, int tiles) {
+  const int img = blockIdx.x, j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* p = part + (size_t)img * tiles * 12 + j;
+  float acc = 0.f;
+  for (int t = lane; t < tiles; t += 64) acc += p[(size_t)t * 12];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) dcam[(size_t)img * 16 + j] = acc;
+  if (j == 0 && lane < 4) dcam[(size_t)img * 16 + 12 + lane] = 0.f;
+}
+
 bool lattice_ok(int nx, int ny, int nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && (long long)nx * ny * nz <= 0x7fffffffLL;
 }
@@ -408,6 +536,39 @@ extern "C" int cips_volume_render_bwd(const void* packed, const float* occ, cons
     hipLaunchKernelGGL(volume_render_bwd_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, q);
   else
     hipLaunchKernelGGL(volume_render_bwd_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, q);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" long long cips_volume_render_bwd_cam_scratch(int b, int H, int W, int S) {
+  if (b < 0 || H < 2 || W < 2 || S < 2) return -1;
+  if ((long long)b * H * W > 0x7fffffffLL || (long long)H * W * S > 0x7fffffffLL) return -1;
+  const long long tiles = (long long)((W + 7) >> 3) * ((H + 7) >> 3);           // <= H * W
+  const long long threads = b * ((tiles + 3) >> 2) * 256;                        // <= 256 b H W < 2^39
+  const long long part = b * tiles * 48;                                         // < 2^37
+  if (threads > (0x7fffffffffffffffLL - part) / 16 / S) return -1;               // S * threads * 16 + part would overflow
+  return (long long)S * threads * 16 + part;
+}
+
+extern "C" int cips_volume_render_bwd_cam(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                                          const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode,
+                                          int flags, const float* drgb, const float* ddepth, const float* dopacity,
+                                          float* dcam2world, void* scratch, int b, int Bv, int nx, int ny, int nz, int H, int W,
+                                          int S, cips_stream_t stream) {
+  if (flags < 0 || flags > 7 || !drgb || !dcam2world || !scratch) return (int)hipErrorInvalidValue;
+  if ((uintptr_t)scratch & 15) return (int)hipErrorInvalidValue;
+  VolCamArgs q = {};
+  const int bad = vol_render_args(q.f, packed, occ, lo, hi, xg, yg, zg, cam2world, zc, clamp_mode, flags, b, Bv, nx, ny, nz, H, W,
+                                  S);
+  if (bad) return bad;
+  if (cips_volume_render_bwd_cam_scratch(b, H, W, S) < 0) return (int)hipErrorInvalidValue;
+  if (b == 0) return 0;
+  const long long grid = (long long)b * q.f.blocks_per_image;
+  q.threads = (size_t)grid * 256;
+  q.drgb = drgb; q.ddepth = ddepth; q.dopacity = dopacity; q.dcam = dcam2world;
+  q.rec = (f32x4*)scratch; q.part = (float*)(q.rec + (size_t)S * q.threads);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(volume_render_bwd_cam_kernel, dim3((unsigned)grid), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(volume_cam_finish_kernel, dim3((unsigned)b), dim3(768), 0, st, (const float*)q.part, dcam2world, q.f.tiles);
   return CIPS_CHECK_LAUNCH();
 }
 

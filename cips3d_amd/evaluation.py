@@ -358,9 +358,10 @@ def render_volume(volume, cam2world, fov, img_size, ray_start, ray_end, num_step
       opacity (b,1,H,W)  sum w, the matte
       cam2world
     so that save_image and warp_view take it as they take render()'s result.  grad=False (the default) runs under no_grad;
-    grad=True runs with autograd as the caller has it: where volume.rgbs requires a gradient, imgs, depth and opacity are
-    differentiable with respect to it (the nodes only, not the cameras: ops.render_volume), and volume.occupancy must be the
-    occupancy of volume.rgbs as it stands (ops.volume_occupancy)."""
+    grad=True runs with autograd as the caller has it: where volume.rgbs or cam2world requires a gradient, imgs, depth and
+    opacity are differentiable with respect to it (the nodes and the cameras: ops.render_volume; a cam2world built from leaf
+    angles keeps its graph, fit_cameras does that), and volume.occupancy must be the occupancy of volume.rgbs as it stands
+    (ops.volume_occupancy)."""
     from . import ops
     from .generator import _zc
     H = int(img_size)
@@ -451,6 +452,106 @@ def fit_volume(volume, targets, cam2world, fov, ray_start, ray_end, num_steps, *
     fitted = nodes.detach()
     return SimpleNamespace(rgbs=fitted, occupancy=ops.volume_occupancy(fitted), lo=volume.lo, hi=volume.hi,
                            resolution=getattr(volume, "resolution", None), losses=losses)
+
+
+def fit_cameras(volume, targets, fov, ray_start, ray_end, num_steps, *, yaws, pitches, radius=1.0, lookat=(0., 0., 0.), steps, lr,
+                fit_radius=False, target_depth=None, target_mask=None, depth_weight=0., mask_weight=0., clamp_mode='relu',
+                last_back=False, white_back=False, level_weights=(1.,), kind='mse', lr_decay_every=100, lr_gamma=0.75):
+    """Fit one camera per view to images of a FROZEN baked volume: yaw and pitch (and, with fit_radius, the distance) of b
+    cameras on spheres around `lookat` are optimised so that render_volume gives targets (b,3,H,H).  yaws, pitches: b numbers
+    each, the start; radius: a number or b numbers.  volume.rgbs is (1,nx,ny,nz,4) (every view sees it) or (b,...).
+    Per step: cam2world = create_cam2world_matrix(-offset, offset + lookat) with offset = camera_origin_from_angles(yaw, pitch,
+    radius), the construction of orbit_cameras, kept in autograd (the first iterate is orbit_cameras(yaws, pitches, radius,
+    lookat)) -> ops.render_volume -> loss (b,) = ops.pyramid_loss(imgs, targets, None, level_weights, kind)
+    + depth_weight * MSE(depth, target_depth (b,1,H,H)) + mask_weight * MSE(opacity, target_mask (b,1,H,H)) (a term runs where
+    its weight is > 0; it then needs its target) -> backward through cips_volume_render_bwd_cam to the angles ->
+    FusedClipAdamEMA without clip or EMA at lr_at(step, lr, lr_decay_every, lr_gamma): the optimiser and schedule of
+    projection.project(fit_camera=True).  The network is not in the loop, the nodes get no gradient and the loop never
+    synchronises with the host.  steps and lr have no defaults.  The gradient is that of a piecewise-trilinear field: it sees
+    what one sample spacing sees, so a start further off than the picture's features are wide can stall.
+    -> SimpleNamespace(yaws (b,), pitches (b,), radius (b,), cam2world (b,4,4) of the fitted angles, losses (steps, b) on the
+    device: the loss of every view BEFORE each step)."""
+    from . import ops
+    from .generator import _normalize, _zc, camera_origin_from_angles, create_cam2world_matrix
+    from .optim import FusedClipAdamEMA
+    from .projection import lr_at
+    who = "fit_cameras"
+    steps = int(steps)
+    lr, depth_weight, mask_weight = float(lr), float(depth_weight), float(mask_weight)
+    if steps < 1:
+        raise ValueError(f"{who}: steps >= 1 expected, got {steps}")
+    if not (math.isfinite(lr) and lr > 0):
+        raise ValueError(f"{who}: lr must be finite and positive, got {lr}")
+    if clamp_mode not in ('relu', 'softplus'):
+        raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
+    for name, wt, tgt in (("depth", depth_weight, target_depth), ("mask", mask_weight, target_mask)):
+        if not (math.isfinite(wt) and wt >= 0):
+            raise ValueError(f"{who}: {name}_weight must be finite and >= 0, got {wt}")
+        if wt > 0 and tgt is None:
+            raise ValueError(f"{who}: {name}_weight > 0 needs target_{name}")
+    rgbs = volume.rgbs
+    if not torch.is_tensor(rgbs) or rgbs.dtype != torch.float32 or rgbs.dim() != 5 or rgbs.shape[-1] != 4:
+        raise ValueError(f"{who}: volume.rgbs (Bv,nx,ny,nz,4) fp32 expected")
+    if not torch.is_tensor(targets) or targets.dtype != torch.float32 or targets.dim() != 4 or targets.shape[1] != 3 \
+            or targets.shape[2] != targets.shape[3] or targets.shape[0] == 0:
+        raise ValueError(f"{who}: targets (b,3,H,H) fp32 expected, got {tuple(targets.shape) if torch.is_tensor(targets) else targets!r}")
+    b, H = targets.shape[0], targets.shape[2]
+    if rgbs.shape[0] != 1 and rgbs.shape[0] != b:
+        raise ValueError(f"{who}: one volume or one per view expected, got {rgbs.shape[0]} volumes and {b} targets")
+    for name, tgt in (("depth", target_depth), ("mask", target_mask)):
+        if tgt is not None and (not torch.is_tensor(tgt) or tgt.dtype != torch.float32 or tuple(tgt.shape) != (b, 1, H, H)):
+            raise ValueError(f"{who}: target_{name} ({b},1,{H},{H}) fp32 expected")
+    try:
+        yaws, pitches = [float(v) for v in yaws], [float(v) for v in pitches]
+        radius = [float(v) for v in radius] if isinstance(radius, (tuple, list)) else [float(radius)] * b
+        lookat = [float(v) for v in lookat]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: yaws, pitches, radius and lookat must be numbers") from None
+    if len(yaws) != b or len(pitches) != b or len(radius) != b or len(lookat) != 3:
+        raise ValueError(f"{who}: {b} yaws, pitches (and radii) and a lookat of 3 numbers expected for {b} targets")
+    if not all(math.isfinite(v) for v in yaws + pitches + radius + lookat) or not all(r > 0 for r in radius):
+        raise ValueError(f"{who}: finite angles and lookat and a positive radius expected")
+    if not (rgbs.is_cuda and targets.is_cuda):
+        raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
+    use_depth, use_mask = depth_weight > 0, mask_weight > 0
+    dev = rgbs.device
+    targets = targets.detach().contiguous()
+    target_depth = target_depth.detach().contiguous() if use_depth else None
+    target_mask = target_mask.detach().contiguous() if use_mask else None
+    nodes, occ = rgbs.detach().contiguous(), volume.occupancy
+    zc, skip = _zc(fov), clamp_mode == 'relu'
+    column = lambda v: torch.tensor(v, dtype=torch.float32, device=dev).view(b, 1)
+    theta, phi, rad = column(yaws).requires_grad_(True), column(pitches).requires_grad_(True), column(radius)
+    centre = torch.tensor(lookat, dtype=torch.float32, device=dev)
+    leaves = [theta, phi] + ([rad.requires_grad_(True)] if fit_radius else [])
+
+    def cameras():
+        offset, _ = camera_origin_from_angles(theta, phi, rad)
+        return create_cam2world_matrix(_normalize(-offset), offset + centre)
+
+    opt = FusedClipAdamEMA(leaves, lr=lr, betas=(0.9, 0.999))
+    losses = torch.zeros(steps, b, device=dev)
+    ones = torch.ones(b, device=dev)
+    zg = ops.pixel_grids(H, H, int(num_steps), ray_start, ray_end, dev)[2]
+    for i in range(steps):
+        for p in leaves:
+            p.grad = None
+        with torch.enable_grad():
+            rgb, depth, opacity = ops.render_volume(nodes, occ if skip else None, volume.lo, volume.hi, cameras(), zc, H, H, zg=zg,
+                                                    clamp_mode=clamp_mode, last_back=last_back, white_back=white_back, skip=skip)
+            loss = ops.pyramid_loss(rgb, targets, None, level_weights, kind)
+            if use_depth:
+                loss = loss + ops.pyramid_loss(depth, target_depth, None, (1.,), "mse") * depth_weight
+            if use_mask:
+                loss = loss + ops.pyramid_loss(opacity, target_mask, None, (1.,), "mse") * mask_weight
+        losses[i].copy_(loss.detach())
+        torch.autograd.backward(loss, ones)
+        opt.lr = lr_at(i, lr, lr_decay_every, lr_gamma)
+        opt.step()
+    with torch.no_grad():
+        cam2world = cameras()
+    return SimpleNamespace(yaws=theta.detach().view(b), pitches=phi.detach().view(b), radius=rad.detach().view(b),
+                           cam2world=cam2world, losses=losses)
 
 
 def warp_view(src, tgt, fov, src_fov=None, occ_tol=None):

@@ -2955,9 +2955,10 @@ VOLUME_SCATTER_PER_LANE = False      # scripts/bench_volume_backward.py measures
 
 
 class VolumeRenderFunction(torch.autograd.Function):
-    """packed -> rgb, depth, opacity: cips_volume_render, the launch render_volume makes without autograd; the backward is
-    cips_volume_render_bwd on the saved volume, occupancy, cameras and depths.  An output nothing was computed from arrives
-    as None and is passed as NULL.  Only packed has a gradient."""
+    """packed, cam2world -> rgb, depth, opacity: cips_volume_render, the launch render_volume makes without autograd; the
+    backward is cips_volume_render_bwd (the nodes) and / or cips_volume_render_bwd_cam (the cameras) on the saved volume,
+    occupancy, cameras and depths: only what needs_input_grad asks for is launched.  An output nothing was computed from
+    arrives as None and is passed as NULL.  Only packed and cam2world have a gradient."""
 
     @staticmethod
     def forward(ctx, packed, occ, cam2world, zg, xg, yg, lo_c, hi_c, zc, clamp, flags, H, W):
@@ -2978,13 +2979,22 @@ class VolumeRenderFunction(torch.autograd.Function):
         drgb, ddepth, dopacity = _c(drgb), _c(ddepth), _c(dopacity)
         if drgb is None:
             drgb = torch.zeros(b, 3, H, W, device=packed.device)
-        dpacked = torch.empty_like(packed)                                          # zeroed by the entry point
-        scratch = torch.empty(max(lib.cips_volume_render_bwd_scratch(b, H, W, S) // 4, 4), device=packed.device)
-        check(lib.cips_volume_render_bwd(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc, clamp,
-                                         flags | (8 if VOLUME_SCATTER_PER_LANE else 0), _p(drgb), _p(ddepth), _p(dopacity),
-                                         _p(dpacked), _p(scratch), b, Bv, nx, ny, nz, H, W, S, _stream()),
-              "cips_volume_render_bwd")
-        return (dpacked,) + (None,) * 12
+        dpacked = dcam = None
+        if ctx.needs_input_grad[0]:
+            dpacked = torch.empty_like(packed)                                      # zeroed by the entry point
+            scratch = torch.empty(max(lib.cips_volume_render_bwd_scratch(b, H, W, S) // 4, 4), device=packed.device)
+            check(lib.cips_volume_render_bwd(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc, clamp,
+                                             flags | (8 if VOLUME_SCATTER_PER_LANE else 0), _p(drgb), _p(ddepth), _p(dopacity),
+                                             _p(dpacked), _p(scratch), b, Bv, nx, ny, nz, H, W, S, _stream()),
+                  "cips_volume_render_bwd")
+        if ctx.needs_input_grad[2]:
+            dcam = torch.empty_like(cam2world)                                      # fully written: no memset, no atomics
+            scratch = torch.empty(max(lib.cips_volume_render_bwd_cam_scratch(b, H, W, S) // 4, 4), device=packed.device)
+            check(lib.cips_volume_render_bwd_cam(_p(packed), _p(occ), lo_c, hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world), zc,
+                                                 clamp, flags, _p(drgb), _p(ddepth), _p(dopacity), _p(dcam), _p(scratch), b, Bv,
+                                                 nx, ny, nz, H, W, S, _stream()),
+                  "cips_volume_render_bwd_cam")
+        return (dpacked, None, dcam) + (None,) * 10
 
 
 def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=None, ray_end=None, num_steps=None,
@@ -2999,14 +3009,20 @@ def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=N
     skip (relu only; with 'softplus' skip=True is refused, there is no empty space): samples in bricks with occ <= 0 are not
     fetched; the outputs are the same bits with and without.  The rule: include/cips3d_hip.h (cips_volume_render).  The forward
     is bit-reproducible, with or without autograd; no host synchronisation.
-    Gradients: when autograd is on and packed requires a gradient, the three outputs are differentiable with respect to packed
-    (the nodes: colours and sigma), and to nothing else: cam2world, zg, lo and hi get none, occ is read as given (it must be the
-    occupancy of packed's sigma: volume_occupancy), and there is no double backward.  With Bv = 1 all b cameras add into the
-    one volume.  The gradient is a sum of fp32 atomic adds (cips_volume_render_bwd), whose last bits can differ from call to
-    call, like reproject's source gradient.  Otherwise this is the forward launch alone, the same bits."""
+    Gradients: when autograd is on and packed or cam2world requires a gradient, the three outputs are differentiable with
+    respect to whichever of the two asks (each on its own: the backward launches only what is asked for), and to nothing else:
+    zg, lo, hi and zc get none (the sample depths are constants), occ is read as given (it must be the occupancy of packed's
+    sigma: volume_occupancy), and there is no double backward.
+      packed (the nodes: colours and sigma): with Bv = 1 all b cameras add into the one volume.  A sum of fp32 atomic adds
+    (cips_volume_render_bwd), whose last bits can differ from call to call, like reproject's source gradient.
+      cam2world (b,4,4): rows 0..2 receive sum_rays [B dir^T | A] with A = sum_k dp_k, B = sum_k z_k dp_k and dp_k the gradient
+    with respect to the sample's world position (the slope of the trilinear interpolant in the sample's cell); row 3 is zero.
+    No atomics and no memset (cips_volume_render_bwd_cam): the same bits on every call, with skip on or off, and for a camera
+    alone or in a batch.  The slope jumps at cell faces and, under relu, where sigma crosses 0.
+    Without a gradient request this is the forward launch alone, the same bits."""
     who = "render_volume"
-    want_grad = torch.is_grad_enabled() and torch.is_tensor(packed) and packed.requires_grad
-    packed_in = packed
+    want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (packed, cam2world))
+    packed_in, cam_in = packed, cam2world
     if clamp_mode not in ('relu', 'softplus'):
         raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
     skip = bool(skip)
@@ -3056,5 +3072,6 @@ def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=N
     flags = (1 if last_back else 0) | (2 if white_back else 0) | (4 if skip else 0)
     clamp = 0 if clamp_mode == 'relu' else 1
     if want_grad:
-        return VolumeRenderFunction.apply(packed_in.contiguous(), occ, cam2world, zg, xg, yg, lo_c, hi_c, zc, clamp, flags, H, W)
+        return VolumeRenderFunction.apply(packed_in.contiguous(), occ, cam_in.contiguous(), zg, xg, yg, lo_c, hi_c, zc, clamp,
+                                          flags, H, W)
     return _volume_render_launch(packed, occ, lo_c, hi_c, xg, yg, zg, cam2world, zc, clamp, flags, H, W)

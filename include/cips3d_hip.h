@@ -1069,7 +1069,7 @@ int cips_raster_interp(const int* face, const float* bary, const int* faces, con
 
 /* ------------------------------------------------------------------ */
 /* Baked radiance volumes (csrc/volume.hip): sigma and colour on a lattice, volume-rendered from any camera of the ray set-up
- * with the network out of the loop, and the gradient of that render with respect to the nodes.
+ * with the network out of the loop, and the gradients of that render with respect to the nodes and to the cameras.
  *
  * cips_volume_bake: sigma (Bv,nx,ny,nz) and rgb (Bv,nx,ny,nz,3) -> packed (Bv,nx,ny,nz,4) = r, g, b, sigma: one 16-byte record
  * per node (packed is 16-byte aligned), the two z-neighbours of a corner pair are one 32-byte access.  Bits are copied, nothing
@@ -1142,6 +1142,35 @@ int cips_volume_render_bwd(const void* packed, const float* occ, const float* lo
                            const float* drgb, const float* ddepth, const float* dopacity, void* dpacked, void* scratch, int b,
                            int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
 int cips_volume_occupancy(const void* packed, float* occ, int Bv, int nx, int ny, int nz, cips_stream_t stream);
+
+/* cips_volume_render_bwd_cam: the gradient of cips_volume_render's three outputs with respect to the CAMERAS, dcam2world (b,4,4)
+ * fp32.  Arguments: cips_volume_render_bwd's, with dcam2world in place of dpacked.  Nothing flows to the nodes, zg or the box.
+ *   The sample depths z_k are constants, as everywhere in this library, so ddepth and dopacity reach the camera only through
+ * dx_k.  Per ray the march and the reverse scan are cips_volume_render_bwd's, with its w_k (top-up included), dx_k and live rule.
+ * A live sample in cell (i, j, k) with weights t gathers the forward's eight corners again and forms the slope of the
+ * interpolant v(t) = (c, sigma): dv/dt_a is the difference of the cell's two bilinear faces along axis a (exact for the
+ * trilinear rule), and dv/dx_a = inv_h[a] dv/dt_a.  Then
+ *     dp_k = w_k (G . grad c_k) + dx_k grad sigma_k;      A = sum_k dp_k;      B = sum_k z_k dp_k      (sample order S-1 .. 0)
+ * and, with world = R (dir z_k) + t and dir the unit direction of ray_dir:
+ *     dcam2world[:3,:3] = sum over rays of B dir^T;     dcam2world[:3,3] = sum over rays of A;     row 3 = 0
+ * (cips_rays_bwd_cam's convention, without a per-point tensor).  A sample outside the box, skipped or not live adds nothing.
+ *   No atomics.  One ray per lane in 8 x 8 tiles as the forward; the wave adds its rays' twelve products by a butterfly of
+ * shuffles and stores one 12-float partial per tile; a second launch (one block per image) adds an image's tiles, lane l the
+ * tiles l, l + 64, ... in order, then the same butterfly, and writes all 16 entries.  Hence the SAME BITS on every call; the
+ * same bits with the skip bit set or clear (a skipped sample and a fetched sample that is not live both add nothing, and the
+ * scan of the live ones does not see the difference: alpha = 0 leaves Q as it is); and the same bits for camera i of a Bv = 1
+ * call as for that camera alone.  The interpolant is continuous but its slope is not: a sample within rounding of a cell face
+ * may take the neighbouring cell's slope, and a sigma within rounding of 0 under relu either side of relu'.
+ *   scratch: cips_volume_render_bwd_cam_scratch(b, H, W, S) bytes = the records of cips_volume_render_bwd_scratch followed by
+ * 48 b tiles bytes of partials; -1 for sizes the entry point refuses, among them a size beyond int64.  16-byte aligned,
+ * contents need not be initialised.  Two launches, no LDS.
+ * Invalid arguments return hipErrorInvalidValue before any HIP call: everything the forward refuses (flags outside 0..7), a
+ * NULL drgb, dcam2world or scratch, a scratch that is not 16-byte aligned or whose size overflows.  b == 0 returns 0. */
+long long cips_volume_render_bwd_cam_scratch(int b, int H, int W, int S);
+int cips_volume_render_bwd_cam(const void* packed, const float* occ, const float* lo, const float* hi, const float* xg,
+                               const float* yg, const float* zg, const float* cam2world, float zc, int clamp_mode, int flags,
+                               const float* drgb, const float* ddepth, const float* dopacity, float* dcam2world, void* scratch,
+                               int b, int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
 
 #ifdef __cplusplus
 }
