@@ -225,6 +225,9 @@ SIGNATURES = {
     "cips_volume_occupancy": (i32, [vp, vp] + [i32] * 4 + [vp]),
     "cips_volume_render_bwd_cam_scratch": (i64, [i32] * 4),
     "cips_volume_render_bwd_cam": (i32, [vp] * 8 + [f32, i32, i32] + [vp] * 5 + [i32] * 8 + [vp]),
+    "cips_feature_volume_bake": (i32, [vp] * 4 + [i32] * 4 + [vp]),
+    "cips_feature_volume_bake_slab": (i32, [vp] * 4 + [i32] * 6 + [vp]),
+    "cips_feature_volume_render": (i32, [vp] * 9 + [f32, i32, i32] + [vp] * 3 + [i32] * 8 + [vp]),
     "cips_camera_pose": (i32, [vp, vp, i32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
     "cips_grouped_linear_max_jobs": (i32, []),
     "cips_grouped_linear_fwd": (i32, [C.POINTER(GlinJob), i32, i32, vp]),

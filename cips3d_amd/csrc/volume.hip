@@ -585,3 +585,174 @@ extern "C" int cips_volume_occupancy(const void* packed, float* occ, int Bv, int
   hipLaunchKernelGGL(volume_occ_kernel, dim3((unsigned)occ_blocks), dim3(64), 0, (hipStream_t)stream, a);
   return CIPS_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Baked FEATURE volumes: the 32 colour features of the SIREN on the lattice instead of a colour, composited per ray into the
+// (b, H W, 32) rows the INR head takes.  The rule is cips_volume_render's with 32 channels in place of 3 (include/cips3d_hip.h,
+// cips_feature_volume_render); everything a sample's place and weight depend on runs through the helpers above.
+//
+//   feature_pack_kernel    one thread per node and channel group: 16 bytes of a (node, 32) row leave as one record of the
+//                          group's plane (bits copied).  Reads are contiguous; a wave's writes are 8 runs of 128 bytes.
+//   feature_render_kernel  volume_render_kernel's lane and tile mapping.  Per sample: the eight 4-byte sigma nodes, seven lerps,
+//                          the composite step; only a sample whose weight is not zero gathers its eight groups (8 x vol_fetch:
+//                          64 16-byte loads) and adds them into 32 accumulators.  No LDS, no scratch, no atomics.
+namespace {
+
+struct FeatPackArgs {
+  const f32x4* rows; f32x4* planes;
+  long long total;                       // Bv * sx * ny * nz * 8 records
+  long long slab, nodes;                 // sx * ny * nz and nx * ny * nz
+  long long first;                       // x0 * ny * nz: the slab's first node
+};
+
+__global__ __launch_bounds__(256) void feature_pack_kernel(FeatPackArgs a) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= a.total) return;
+  const long long node = id >> 3, v = node / a.slab, n = node - v * a.slab;
+  const int g = (int)(id & 7);
+  a.planes[(v * 8 + g) * a.nodes + a.first + n] = a.rows[id];
+}
+
+struct FeatArgs {
+  VolArgs f;                             // vol = planes; its rgb pointer is unused
+  const float* sigma;
+  f32x4* fea;
+};
+
+__device__ __forceinline__ float lerp1(float p, float q, float t) { return p + t * (q - p); }
+
+// vol_fetch for the one channel of a plain (nx, ny, nz) tensor: the same corners in the same order
+__device__ __forceinline__ float sigma_fetch(const VolArgs& a, const float* sig, const VolCell& c) {
+  const size_t sy = (size_t)a.nz, sx = (size_t)a.ny * a.nz;
+  const float* p = sig + ((size_t)c.i * a.ny + c.j) * a.nz + c.k;
+  const float c000 = p[0], c001 = p[1], c010 = p[sy], c011 = p[sy + 1];
+  const float c100 = p[sx], c101 = p[sx + 1], c110 = p[sx + sy], c111 = p[sx + sy + 1];
+  const float c00 = lerp1(c000, c001, c.tz), c01 = lerp1(c010, c011, c.tz);
+  const float c10 = lerp1(c100, c101, c.tz), c11 = lerp1(c110, c111, c.tz);
+  return lerp1(lerp1(c00, c01, c.ty), lerp1(c10, c11, c.ty), c.tx);
+}
+
+__device__ __forceinline__ f32x4 fma4(float w, f32x4 v, f32x4 c) {
+  f32x4 r;
+  r.x = fmaf(w, v.x, c.x); r.y = fmaf(w, v.y, c.y); r.z = fmaf(w, v.z, c.z); r.w = fmaf(w, v.w, c.w);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void feature_render_kernel(FeatArgs q) {
+  const VolArgs& a = q.f;
+  const int img = blockIdx.x / a.blocks_per_image;
+  const int tile = (blockIdx.x - img * a.blocks_per_image) * 4 + (threadIdx.x >> 6);
+  if (tile >= a.tiles) return;
+  const int lane = threadIdx.x & 63;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int r = ty * 8 + (lane >> 3), c = tx * 8 + (lane & 7);
+  if (r >= a.H || c >= a.W) return;
+  const int ray = r * a.W + c, S = a.S;
+  const f32x4* planes = a.vol + (a.Bv == 1 ? 0 : (size_t)img * 8 * a.nodes);
+  const float* sig = q.sigma + (a.Bv == 1 ? 0 : (size_t)img * a.nodes);
+  const bool skip = (a.flags & 4) && a.clamp_mode == 0;
+  const bool last_back = a.flags & 1;
+  const float* occ = skip ? a.occ + (a.Bv == 1 ? 0 : (size_t)img * a.bricks) : nullptr;
+
+  f32x4 acc[8];
+#pragma unroll
+  for (int g = 0; g < 8; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float depth = 0.f, wsum = 0.f, zlast = 0.f, wlast = 0.f;
+  bool last_in = false;                   // under last_back: the last sample lies inside, its features take the top-up
+  VolCell clast = {0, 0, 0, 0.f, 0.f, 0.f};
+  double T = 1.0;
+  const RayDir dir = ray_dir(a.g, ray);
+  const float* M = a.g.c2w + (size_t)img * 16;
+  for (int s = 0; s < S; ++s) {           // volume_render_kernel's march, expression by expression
+    float wx, wy, wz, z;
+    ray_point(a.g, M, dir, a.g.zg[s], 0.f, false, wx, wy, wz, z);
+    float x = 0.f;
+    VolCell cell;
+    const bool fetched = vol_sample_cell(a, occ, last_back, s, wx, wy, wz, cell);
+    if (fetched) x = sigma_fetch(a, sig, cell);
+    const float delta = (s + 1 < S) ? (a.g.zg[s + 1] - z) : 1e10f;
+    const float alpha = 1.f - expf(-delta * vol_clamp(x, a.clamp_mode));
+    const float Tf = (float)T;
+    const float w = alpha * Tf;
+    T *= (double)(1.f - alpha + 1e-10f);
+    depth = fmaf(w, z, depth);
+    // opacity takes alpha T through one fused multiply-add, which is what volume_render_kernel's `wsum += w` compiles to (the
+    // product is contracted into the sum): written out here so that the two kernels agree bit for bit whatever the compiler does
+    // with this one; tests/test_gpu_feature_volume.py holds them to each other
+    wsum = fmaf(alpha, Tf, wsum);
+    zlast = z;
+    if (last_back && s == S - 1) {        // resolved behind the loop, where 1 - sum w is known
+      last_in = fetched; wlast = w; clast = cell;
+    } else if (fetched && w != 0.f) {     // fmaf(0, f, c) == c for finite f: a zero weight needs no features
+#pragma unroll
+      for (int g = 0; g < 8; ++g) acc[g] = fma4(w, vol_fetch(a, planes + (size_t)g * a.nodes, cell), acc[g]);
+    }
+  }
+  const float extra = 1.f - wsum;
+  if (last_back) {                        // the last weight gains 1 - sum w: two fmafs per channel, as volume_render_kernel
+    if (last_in && (wlast != 0.f || extra != 0.f)) {
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        const f32x4 v = vol_fetch(a, planes + (size_t)g * a.nodes, clast);
+        acc[g] = fma4(extra, v, fma4(wlast, v, acc[g]));
+      }
+    }
+    depth = fmaf(extra, zlast, depth);
+  }
+  if (a.flags & 2) {                      // white_back, every channel
+#pragma unroll
+    for (int g = 0; g < 8; ++g) acc[g] += extra;
+  }
+  const size_t pix = (size_t)img * a.H * a.W + ray;
+  f32x4* o = q.fea + pix * 8;             // the lane's 128 contiguous bytes
+#pragma unroll
+  for (int g = 0; g < 8; ++g) o[g] = acc[g];
+  a.depth[pix] = depth;
+  a.opacity[pix] = wsum;
+}
+
+}  // namespace
+
+extern "C" int cips_feature_volume_bake_slab(const float* sigma, const float* feat_rows, void* planes, float* occ, int Bv, int nx,
+                                             int ny, int nz, int x0, int sx, cips_stream_t stream) {
+  if (Bv < 0 || !lattice_ok(nx, ny, nz)) return (int)hipErrorInvalidValue;
+  if (x0 < 0 || sx < 1 || x0 > nx - sx) return (int)hipErrorInvalidValue;
+  if (!sigma || !feat_rows || !planes || !occ) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)planes & 15) || ((uintptr_t)feat_rows & 15)) return (int)hipErrorInvalidValue;
+  FeatPackArgs p = {};
+  p.rows = (const f32x4*)feat_rows; p.planes = (f32x4*)planes;
+  p.slab = (long long)sx * ny * nz; p.nodes = (long long)nx * ny * nz; p.first = (long long)x0 * ny * nz;
+  if (Bv > 0 && p.slab > 0x7fffffffLL * 32 / Bv) return (int)hipErrorInvalidValue;            // the pack grid, beyond int32
+  p.total = (long long)Bv * p.slab * 8;
+  PackArgs a = {};
+  a.sigma = sigma; a.occ = occ; a.stride = 1;
+  a.Bv = Bv; a.nx = nx; a.ny = ny; a.nz = nz; a.bx = bricks_of(nx); a.by = bricks_of(ny); a.bz = bricks_of(nz);
+  const long long pack_blocks = (p.total + 255) / 256, occ_blocks = (long long)Bv * a.bx * a.by * a.bz;
+  if (pack_blocks > 0x7fffffffLL || occ_blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (Bv == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(feature_pack_kernel, dim3((unsigned)pack_blocks), dim3(256), 0, st, p);
+  if (x0 + sx == nx) hipLaunchKernelGGL(volume_occ_kernel, dim3((unsigned)occ_blocks), dim3(64), 0, st, a);
+  return CIPS_CHECK_LAUNCH();
+}
+
+extern "C" int cips_feature_volume_bake(const float* sigma, const float* feat_rows, void* planes, float* occ, int Bv, int nx,
+                                        int ny, int nz, cips_stream_t stream) {
+  return cips_feature_volume_bake_slab(sigma, feat_rows, planes, occ, Bv, nx, ny, nz, 0, nx, stream);
+}
+
+extern "C" int cips_feature_volume_render(const float* sigma, const void* planes, const float* occ, const float* lo, const float* hi,
+                                          const float* xg, const float* yg, const float* zg, const float* cam2world, float zc,
+                                          int clamp_mode, int flags, float* fea, float* depth, float* opacity, int b, int Bv, int nx,
+                                          int ny, int nz, int H, int W, int S, cips_stream_t stream) {
+  if (flags < 0 || flags > 7 || !sigma || !fea || !depth || !opacity) return (int)hipErrorInvalidValue;
+  if ((uintptr_t)fea & 15) return (int)hipErrorInvalidValue;
+  FeatArgs q = {};
+  const int bad = vol_render_args(q.f, planes, occ, lo, hi, xg, yg, zg, cam2world, zc, clamp_mode, flags, b, Bv, nx, ny, nz, H, W, S);
+  if (bad) return bad;
+  if (b == 0) return 0;
+  q.sigma = sigma; q.fea = (f32x4*)fea; q.f.depth = depth; q.f.opacity = opacity;
+  const long long grid = (long long)b * q.f.blocks_per_image;
+  hipLaunchKernelGGL(feature_render_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, q);
+  return CIPS_CHECK_LAUNCH();
+}

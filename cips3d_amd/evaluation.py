@@ -372,6 +372,40 @@ def render_volume(volume, cam2world, fov, img_size, ray_start, ray_end, num_step
     return SimpleNamespace(imgs=rgb, depth=depth, opacity=opacity, cam2world=cam2world)
 
 
+@torch.no_grad()
+def render_feature_volume(G, volume, cam2world, fov, img_size, ray_start, ray_end, num_steps, clamp_mode='relu', last_back=False,
+                          white_back=False, skip=True, return_aux_img=False):
+    """A baked feature volume seen from b cameras: forward()'s picture without the SIREN.  ops.render_feature_volume composites
+    the 32 features per ray, then the generator's own tail runs on them — G._head (the INR head WITHOUT img_size, as forward()
+    calls it, and the auxiliary layer with its tanh) and G._images (G.filters): the code _render runs behind its NeRF stage.
+    G: the generator the volume was baked from; volume: GeneratorNerfINR.bake_features' namespace (.sigma, .features,
+    .occupancy, .lo, .hi, .styles), one volume for all b cameras (its styles are expanded to b) or one per camera; the other
+    arguments: render_volume's.  -> SimpleNamespace in render()'s layout:
+      imgs     (b,3,H,W)   the INR image
+      aux      (b,3,H,W)   the auxiliary image, only with return_aux_img
+      depth    (b,1,H,W)   the expected depth sum w z
+      opacity  (b,1,H,W)   sum w, the matte
+      features (b,H*W,32)  the composited features the head ran on
+      cam2world
+    so that save_image and warp_view take it as they take render()'s result.  A view costs a gather-and-composite pass and
+    one head pass over H W pixels, where forward() costs H W num_steps SIREN evaluations.  No gradient; GPU only."""
+    from . import ops
+    from .generator import _zc
+    H = int(img_size)
+    fea, depth, opacity = ops.render_feature_volume(volume.sigma, volume.features, volume.occupancy, volume.lo, volume.hi,
+                                                    cam2world, _zc(fov), H, H, ray_start=ray_start, ray_end=ray_end,
+                                                    num_steps=num_steps, clamp_mode=clamp_mode, last_back=last_back,
+                                                    white_back=white_back, skip=skip)
+    b = fea.shape[0]
+    styles = {name: (t.expand(b, -1).contiguous() if t.shape[0] == 1 and b != 1 else t) for name, t in volume.styles.items()}
+    rows, aux_rows = G._head(SimpleNamespace(return_aux_img=bool(return_aux_img)), fea, styles, False)
+    inr_img, aux_img = G._images(rows, aux_rows, b, H)
+    out = SimpleNamespace(imgs=inr_img.contiguous(), depth=depth, opacity=opacity, features=fea, cam2world=cam2world)
+    if return_aux_img:
+        out.aux = aux_img.contiguous()
+    return out
+
+
 def fit_volume(volume, targets, cam2world, fov, ray_start, ray_end, num_steps, *, steps, lr, clamp_mode='relu', last_back=False,
                white_back=False, level_weights=(1.,), kind='mse', target_depth=None, target_opacity=None, depth_weight=0.,
                opacity_weight=0.):

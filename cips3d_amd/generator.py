@@ -1029,6 +1029,12 @@ class GeneratorNerfINR(nn.Module):
 
         return scatter(inr_g, inr_r), scatter(aux_g, aux_r) if s.return_aux_img else None
 
+    def _images(self, inr_rows, aux_rows, b, H):
+        """_head's pixel rows (b, H*H, 3) -> images (b,3,H,H): the INR one through self.filters, the auxiliary one (or None) as
+        it is; views, made contiguous by the caller.  _render's tail, shared with evaluation.render_feature_volume."""
+        inr_img = self.filters(inr_rows.view(b, H, H, 3).permute(0, 3, 1, 2))
+        return inr_img, aux_rows.view(b, H, H, 3).permute(0, 3, 1, 2) if aux_rows is not None else None
+
     def _render(self, style_dict, s, geo=False):
         """whole_grad_forward / part_grad_forward + points_forward (generator.py:1378-1657, 1659-1762) on the HIP path:
         draws (draw_randoms) -> camera (camera_setup) -> NeRF features (_ray_geometry, _nerf_stage) -> head (_head), or
@@ -1053,10 +1059,8 @@ class GeneratorNerfINR(nn.Module):
         else:
             fea, depth, opacity = self._nerf_stage(s, g, nerf_styles, d.noise_c, d.u, d.noise_f, self.nerf_grad, geo=geo)
             inr_img, aux_img = self._head(s, fea, style_dict, self.nerf_grad)
-        inr_img = inr_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
-        inr_img = self.filters(inr_img)
+        inr_img, aux_img = self._images(inr_img, aux_img, b, s.img_size)
         if s.return_aux_img:
-            aux_img = aux_img.view(b, s.img_size, s.img_size, 3).permute(0, 3, 1, 2)
             imgs, pitch_yaw = torch.cat([inr_img, aux_img]), torch.cat([pitch_yaw, pitch_yaw])
         else:
             imgs = inr_img.contiguous()
@@ -1297,6 +1301,48 @@ class GeneratorNerfINR(nn.Module):
         grids = density_lattice(resolution, cube_length, center)
         return SimpleNamespace(rgbs=packed, occupancy=occ, lo=tuple(float(g[0]) for g in grids),
                                hi=tuple(float(g[-1]) for g in grids), resolution=int(resolution))
+
+    @torch.no_grad()
+    def bake_features(self, zs, resolution=64, cube_length=0.3, center=(0., 0., 0.), psi=1.0, slab=None):
+        """The SIREN's 32 colour features and sigma of zs baked onto density_grid's N^3 lattice, for
+        evaluation.render_feature_volume, which composites them per ray and runs the INR head on the result: forward()'s
+        picture (not the auxiliary one bake() holds) with the SIREN out of the loop -> SimpleNamespace
+          sigma      (b, N, N, N)        the density per node
+          features   (b, 8, N, N, N, 4)  channel-group-major planes: features[:, g, i, j, k] holds channels 4g .. 4g+3 of node
+                                         (i, j, k) (ops.bake_feature_volume's layout)
+          occupancy  (b, ceil((N-1)/8),) * 3  the brick maxima of sigma, bake()'s
+          lo, hi     three floats each, bake()'s box
+          resolution N
+          styles     the full style dictionary the volume was baked with, NeRF and INR keys (b rows each): the renderer needs
+                     no zs
+        Styles: forward()'s — both mapping networks, joined; psi < 1 truncates both towards generate_avg_frequencies' average
+        with its draws (_color_styles(zs, psi, 'head')).  density_grid's default style path is another one (_density_styles:
+        the NeRF mapping network alone, for psi < 1 an average of its own), so for psi < 1 sigma is not density_grid(zs)'s; it
+        is NeRFNetwork.density_lattice's on the same lattice with volume.styles, bit for bit, and for psi = 1 density_grid's.
+        The lattice is evaluated by NeRFNetwork.evaluate a slab of x-planes at a time and packed slab by slab, so that the
+        (b, slab N^2, 32) temporary stays bounded: `slab` x-planes per pass, by default as many as keep it under 256 MB.  The
+        result does not depend on it.  A volume costs 132 N^3 bytes per image: 34.6 MB at N = 64, 277 MB at N = 128.
+        No gradient; GPU only."""
+        from . import ops
+        from .evaluation import density_lattice
+        device = self._gpu_only('bake_features')
+        N = int(resolution)
+        style_dict = self._color_styles(zs, psi, 'head')
+        b = zs['z_nerf'].shape[0]
+        grids = density_lattice(N, cube_length, center)
+        gx, gy, gz = (g.to(device) for g in grids)
+        if slab is None:
+            slab = max(1, (256 << 20) // max(1, b * N * N * 128))
+        slab = int(slab)
+        if slab < 1:
+            raise ValueError(f"GeneratorNerfINR.bake_features: slab must be at least 1 x-plane, got {slab}")
+        sigma, planes, occ = ops.feature_volume_buffers(b, N, N, N, device)
+        for x0 in range(0, N, slab):
+            feat, sig = self.siren.evaluate(ops.lattice_points(gx[x0:x0 + slab], gy, gz, b).contiguous(), style_dict)
+            sigma[:, x0:x0 + slab] = sig.view(b, -1, N, N)
+            ops._bake_feature_slab(sigma, feat.contiguous(), planes, occ, x0)
+        return SimpleNamespace(sigma=sigma, features=planes, occupancy=occ, lo=tuple(float(g[0]) for g in grids),
+                               hi=tuple(float(g[-1]) for g in grids), resolution=N, styles=dict(style_dict))
 
     @torch.no_grad()
     def geometry(self, zs, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, hierarchical_sample,

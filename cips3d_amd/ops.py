@@ -11,6 +11,7 @@ import math
 import os
 import weakref
 from collections import namedtuple
+from types import SimpleNamespace
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -2997,6 +2998,60 @@ class VolumeRenderFunction(torch.autograd.Function):
         return (dpacked, None, dcam) + (None,) * 10
 
 
+def _volume_render_args(who, volume, aligned, occ, lo, hi, cam2world, zc, H, W, zg, ray_start, ray_end, num_steps, clamp_mode, last_back,
+                        white_back, skip):
+    """The checks and refusals render_volume and render_feature_volume share, in one order.  volume(who) checks the caller's
+    own node tensors and returns them as a list, the one that fixes the lattice (Bv, nx, ny, nz, ...) and must be 16-byte
+    aligned LAST (`aligned` is its name in that message).  -> SimpleNamespace(volume,
+    occ, cam2world, zg, lo_c, hi_c, zc, H, W, b, S, clamp, flags), every tensor detached, contiguous and on the GPU."""
+    if clamp_mode not in ('relu', 'softplus'):
+        raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
+    skip = bool(skip)
+    if skip and clamp_mode == 'softplus':
+        raise ValueError(f"{who}: skip=True needs clamp_mode='relu' (softplus(sigma) > 0 everywhere: nothing is empty)")
+    H, W, zc = int(H), int(W), float(zc)
+    if H < 2 or W < 2:
+        raise ValueError(f"{who}: H, W >= 2 expected, got {H} x {W}")
+    if not (math.isfinite(zc) and zc < 0):
+        raise ValueError(f"{who}: zc must be finite and negative, got {zc}")
+    lo_c, hi_c = _volume_box(who, lo, hi)
+    nodes = volume(who)
+    main = nodes[-1]
+    Bv, (nx, ny, nz) = main.shape[0], main.shape[-4:-1]
+    cam2world = _raster_tensor(who, cam2world, "cam2world", torch.float32, (None, 4, 4))
+    b = cam2world.shape[0]
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
+        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
+    if Bv != 1 and Bv != b:
+        raise ValueError(f"{who}: one volume or one per camera expected, got {Bv} volumes and {b} cameras")
+    if zg is None:
+        if ray_start is None or ray_end is None or num_steps is None:
+            raise ValueError(f"{who}: give zg, or ray_start, ray_end and num_steps")
+        if int(num_steps) < 2:
+            raise ValueError(f"{who}: num_steps >= 2 expected, got {num_steps}")
+        if not main.is_cuda:
+            raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
+        zg = pixel_grids(W, H, int(num_steps), ray_start, ray_end, main.device)[2]
+    zg = _raster_tensor(who, zg, "zg", torch.float32, (None,))
+    S = zg.shape[0]
+    if S < 2:
+        raise ValueError(f"{who}: at least 2 sample depths expected, got {S}")
+    if b * H * W > 0x7fffffff or H * W * S > 0x7fffffff:
+        raise ValueError(f"{who}: b*H*W and H*W*S must fit in int32, got b = {b}, H x W = {H} x {W}, S = {S}")
+    tensors = list(nodes) + [cam2world, zg]
+    if occ is not None or skip:
+        if occ is None:
+            raise ValueError(f"{who}: skip=True needs occ")
+        occ = _raster_tensor(who, occ, "occ", torch.float32, (Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz))))
+        tensors.append(occ)
+    _raster_on_gpu(who, *tensors)
+    if main.data_ptr() % 16:
+        raise ValueError(f"{who}: {aligned} must be 16-byte aligned")
+    return SimpleNamespace(volume=nodes, occ=occ, cam2world=cam2world, zg=zg, lo_c=lo_c, hi_c=hi_c, zc=zc, H=H, W=W, b=b, S=S,
+                           clamp=0 if clamp_mode == 'relu' else 1,
+                           flags=(1 if last_back else 0) | (2 if white_back else 0) | (4 if skip else 0))
+
+
 def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=None, ray_end=None, num_steps=None,
                   clamp_mode='relu', last_back=False, white_back=False, skip=True):
     """A baked volume seen from b cameras -> (rgb (b,3,H,W), depth (b,1,H,W), opacity (b,1,H,W)): trilinear samples of
@@ -3020,58 +3075,109 @@ def render_volume(packed, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=N
     No atomics and no memset (cips_volume_render_bwd_cam): the same bits on every call, with skip on or off, and for a camera
     alone or in a batch.  The slope jumps at cell faces and, under relu, where sigma crosses 0.
     Without a gradient request this is the forward launch alone, the same bits."""
-    who = "render_volume"
     want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (packed, cam2world))
     packed_in, cam_in = packed, cam2world
-    if clamp_mode not in ('relu', 'softplus'):
-        raise ValueError(f"{who}: clamp_mode must be 'relu' or 'softplus', got {clamp_mode!r}")
-    skip = bool(skip)
-    if skip and clamp_mode == 'softplus':
-        raise ValueError(f"{who}: skip=True needs clamp_mode='relu' (softplus(sigma) > 0 everywhere: nothing is empty)")
-    H, W, zc = int(H), int(W), float(zc)
-    if H < 2 or W < 2:
-        raise ValueError(f"{who}: H, W >= 2 expected, got {H} x {W}")
-    if not (math.isfinite(zc) and zc < 0):
-        raise ValueError(f"{who}: zc must be finite and negative, got {zc}")
-    lo_c, hi_c = _volume_box(who, lo, hi)
-    packed = _raster_tensor(who, packed, "packed", torch.float32, (None, None, None, None, 4))
-    Bv, nx, ny, nz = packed.shape[:4]
-    cam2world = _raster_tensor(who, cam2world, "cam2world", torch.float32, (None, 4, 4))
-    b = cam2world.shape[0]
-    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
-        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
-    if Bv != 1 and Bv != b:
-        raise ValueError(f"{who}: one volume or one per camera expected, got {Bv} volumes and {b} cameras")
-    if zg is None:
-        if ray_start is None or ray_end is None or num_steps is None:
-            raise ValueError(f"{who}: give zg, or ray_start, ray_end and num_steps")
-        if int(num_steps) < 2:
-            raise ValueError(f"{who}: num_steps >= 2 expected, got {num_steps}")
-        if not packed.is_cuda:
-            raise ValueError(f"{who} needs tensors on the GPU (no CPU fallback)")
-        zg = pixel_grids(W, H, int(num_steps), ray_start, ray_end, packed.device)[2]
-    zg = _raster_tensor(who, zg, "zg", torch.float32, (None,))
-    S = zg.shape[0]
-    if S < 2:
-        raise ValueError(f"{who}: at least 2 sample depths expected, got {S}")
-    if b * H * W > 0x7fffffff or H * W * S > 0x7fffffff:
-        raise ValueError(f"{who}: b*H*W and H*W*S must fit in int32, got b = {b}, H x W = {H} x {W}, S = {S}")
-    tensors = [packed, cam2world, zg]
-    if occ is not None or skip:
-        if occ is None:
-            raise ValueError(f"{who}: skip=True needs occ")
-        occ = _raster_tensor(who, occ, "occ", torch.float32, (Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz))))
-        tensors.append(occ)
-    _raster_on_gpu(who, *tensors)
-    if packed.data_ptr() % 16:
-        raise ValueError(f"{who}: packed must be 16-byte aligned")
+    q = _volume_render_args("render_volume", lambda who: [_raster_tensor(who, packed, "packed", torch.float32, (None, None, None, None, 4))],
+                            "packed", occ, lo, hi, cam2world, zc, H, W, zg, ray_start, ray_end, num_steps, clamp_mode, last_back, white_back,
+                            skip)
+    (packed,), occ, cam2world, zg, H, W = q.volume, q.occ, q.cam2world, q.zg, q.H, q.W
     dev = packed.device
-    if b == 0:
-        return torch.empty(b, 3, H, W, device=dev), torch.empty(b, 1, H, W, device=dev), torch.empty(b, 1, H, W, device=dev)
+    if q.b == 0:
+        return torch.empty(0, 3, H, W, device=dev), torch.empty(0, 1, H, W, device=dev), torch.empty(0, 1, H, W, device=dev)
     xg, yg, _ = pixel_grids(W, H, 2, 0., 1., dev)
-    flags = (1 if last_back else 0) | (2 if white_back else 0) | (4 if skip else 0)
-    clamp = 0 if clamp_mode == 'relu' else 1
+    lo_c, hi_c, zc, clamp, flags = q.lo_c, q.hi_c, q.zc, q.clamp, q.flags
     if want_grad:
         return VolumeRenderFunction.apply(packed_in.contiguous(), occ, cam_in.contiguous(), zg, xg, yg, lo_c, hi_c, zc, clamp,
                                           flags, H, W)
     return _volume_render_launch(packed, occ, lo_c, hi_c, xg, yg, zg, cam2world, zc, clamp, flags, H, W)
+
+
+# --------------------------------------------------------------------------------------
+# Baked feature volumes (csrc/volume.hip): the SIREN's 32 colour features on the lattice, composited into the head's pixel rows
+# --------------------------------------------------------------------------------------
+FEATURE_GROUPS = 8        # planes of 4 channels: 32 features
+
+
+def _feature_lattice(who, sigma):
+    sigma = _raster_tensor(who, sigma, "sigma", torch.float32, (None, None, None, None))
+    nx, ny, nz = sigma.shape[1:]
+    if min(nx, ny, nz) < 2 or nx * ny * nz > 0x7fffffff:
+        raise ValueError(f"{who}: a lattice of at least 2 nodes per axis and at most 2^31 - 1 nodes expected, got {nx} x {ny} x {nz}")
+    return sigma
+
+
+def _bake_feature_slab(sigma, rows, planes, occ, x0):
+    """x-planes x0 .. of a feature volume: rows (Bv, sx*ny*nz, 32) -> planes[:, :, x0:x0+sx]; the slab that ends the lattice
+    writes occ from the whole sigma (cips_feature_volume_bake_slab).  GeneratorNerfINR.bake_features packs slab by slab."""
+    Bv, nx, ny, nz = sigma.shape
+    sx = rows.shape[1] // (ny * nz)
+    if Bv:
+        check(_lib.load().cips_feature_volume_bake_slab(_p(sigma), _p(rows), _p(planes), _p(occ), Bv, nx, ny, nz, x0, sx, _stream()),
+              "cips_feature_volume_bake_slab")
+
+
+def feature_volume_buffers(Bv, nx, ny, nz, device):
+    """the empty tensors of a feature volume -> sigma (Bv,nx,ny,nz), planes (Bv,8,nx,ny,nz,4), occ (Bv, bricks per axis)"""
+    return (torch.empty(Bv, nx, ny, nz, device=device), torch.empty(Bv, FEATURE_GROUPS, nx, ny, nz, 4, device=device),
+            torch.empty(Bv, *(-(-(n - 1) // VOLUME_BRICK) for n in (nx, ny, nz)), device=device))
+
+
+def bake_feature_volume(sigma, feat):
+    """sigma (Bv,nx,ny,nz) and feat (Bv,nx,ny,nz,32) or (Bv,nx*ny*nz,32) — NeRFNetwork.evaluate's rows on the lattice, x
+    outermost — fp32 on the GPU -> (planes, occ):
+      planes (Bv,8,nx,ny,nz,4)  channel-group-major: planes[v, g, i, j, k] holds channels 4g .. 4g+3 of node (i, j, k), bits
+             copied; every plane has bake_volume's packed layout, so one group's interpolation is the rgb renderer's gather
+      occ    bake_volume's brick occupancy of sigma, the same bits
+    sigma itself is the third tensor of the volume; render_feature_volume reads it as it is.  The volume is taken to be finite.
+    A volume costs 132 bytes per node with its sigma.  The rule: include/cips3d_hip.h (cips_feature_volume_bake).  No host
+    synchronisation, no gradient."""
+    who = "bake_feature_volume"
+    sigma = _feature_lattice(who, sigma)
+    Bv, nx, ny, nz = sigma.shape
+    if torch.is_tensor(feat) and feat.dim() == 5:
+        feat = _raster_tensor(who, feat, "feat", torch.float32, (Bv, nx, ny, nz, 4 * FEATURE_GROUPS))
+    else:
+        feat = _raster_tensor(who, feat, "feat", torch.float32, (Bv, nx * ny * nz, 4 * FEATURE_GROUPS))
+    _raster_on_gpu(who, sigma, feat)
+    if feat.data_ptr() % 16:
+        raise ValueError(f"{who}: feat must be 16-byte aligned")
+    _, planes, occ = feature_volume_buffers(Bv, nx, ny, nz, sigma.device)
+    _bake_feature_slab(sigma, feat.view(Bv, nx * ny * nz, 4 * FEATURE_GROUPS), planes, occ, 0)
+    return planes, occ
+
+
+def render_feature_volume(sigma, planes, occ, lo, hi, cam2world, zc, H, W, zg=None, ray_start=None, ray_end=None, num_steps=None,
+                          clamp_mode='relu', last_back=False, white_back=False, skip=True):
+    """A baked feature volume seen from b cameras -> (fea (b,H*W,32), depth (b,1,H,W), opacity (b,1,H,W)): what the NeRF stage of
+    forward() hands to the INR head, from trilinear samples of the lattice instead of the SIREN.  sigma (Bv,nx,ny,nz), planes
+    (Bv,8,nx,ny,nz,4) and occ: bake_feature_volume's; every other argument, every check and refusal: render_volume's (skip=True
+    with 'softplus' is refused).  The rule is render_volume's with 32 channels in place of 3, white_back adding 1 - sum w to every
+    channel (include/cips3d_hip.h, cips_feature_volume_render); a sample gathers its features only where its weight is not
+    zero, which changes no bit.  The outputs are the same bits on every call, with skip on or off.
+    Forward only: gradients are not built.  It runs as under no_grad — the outputs carry no grad_fn — and an input that requires
+    grad is refused.  No host synchronisation."""
+    who = "render_feature_volume"
+    for name, t in (("sigma", sigma), ("planes", planes), ("occ", occ), ("cam2world", cam2world), ("zg", zg)):
+        if torch.is_tensor(t) and t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad, but gradients are not built for feature volumes (forward only): "
+                             f"pass {name}.detach()")
+
+    def volume(who):
+        sig = _raster_tensor(who, sigma, "sigma", torch.float32, (None, None, None, None))
+        return [sig, _raster_tensor(who, planes, "planes", torch.float32, (sig.shape[0], FEATURE_GROUPS, *sig.shape[1:], 4))]
+
+    q = _volume_render_args(who, volume, "planes", occ, lo, hi, cam2world, zc, H, W, zg, ray_start, ray_end, num_steps, clamp_mode, last_back,
+                            white_back, skip)
+    (sigma, planes), occ, cam2world, zg, H, W, b, S = q.volume, q.occ, q.cam2world, q.zg, q.H, q.W, q.b, q.S
+    Bv, nx, ny, nz = sigma.shape
+    dev = planes.device
+    fea = torch.empty(b, H * W, 4 * FEATURE_GROUPS, device=dev)
+    depth = torch.empty(b, 1, H, W, device=dev)
+    opacity = torch.empty(b, 1, H, W, device=dev)
+    if b == 0:
+        return fea, depth, opacity
+    xg, yg, _ = pixel_grids(W, H, 2, 0., 1., dev)
+    check(_lib.load().cips_feature_volume_render(_p(sigma), _p(planes), _p(occ), q.lo_c, q.hi_c, _p(xg), _p(yg), _p(zg), _p(cam2world),
+                                                 q.zc, q.clamp, q.flags, _p(fea), _p(depth), _p(opacity), b, Bv, nx, ny, nz, H, W, S,
+                                                 _stream()), "cips_feature_volume_render")
+    return fea, depth, opacity

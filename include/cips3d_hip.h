@@ -1172,6 +1172,59 @@ int cips_volume_render_bwd_cam(const void* packed, const float* occ, const float
                                const float* drgb, const float* ddepth, const float* dopacity, float* dcam2world, void* scratch,
                                int b, int Bv, int nx, int ny, int nz, int H, int W, int S, cips_stream_t stream);
 
+/* Baked FEATURE volumes (csrc/volume.hip): the SIREN's 32 colour features on the lattice in place of a colour, composited per
+ * ray into the pixel rows the INR head takes, so that a view of a baked identity is forward()'s picture and costs a
+ * gather-and-composite pass plus one head pass.  Forward only: nothing here has a gradient.  A feature volume is
+ *   sigma  (Bv,nx,ny,nz) fp32;
+ *   planes (Bv,8,nx,ny,nz,4) fp32, 16-byte aligned: channel-group-major planes of 16-byte records, group g holding channels
+ *          4g .. 4g+3 of a node — every plane has cips_volume_bake's packed layout (z-neighbours 32 contiguous bytes apart);
+ *   occ    cips_volume_bake's brick maxima of sigma, same shape and bits.
+ * The volume is taken to be finite (sigma and features): the occupancy drops a NaN, and the weight skip below relies on
+ * 0 * f == 0.
+ *
+ * cips_feature_volume_bake: feat_rows (Bv, nx*ny*nz, 32), the layout NeRFNetwork.evaluate returns (16-byte aligned), is
+ * transposed into planes: planes[v][g][n] = feat_rows[v][n][4g .. 4g+3].  Bits are copied, nothing is computed.  occ is written
+ * by cips_volume_bake's occupancy kernel reading sigma at stride 1.  Two launches.
+ * cips_feature_volume_bake_slab: the same for the x-planes x0 .. x0+sx-1 only, so that a caller can evaluate the lattice a slab at
+ * a time: feat_rows is (Bv, sx*ny*nz, 32) and lands in planes[v][g][x0 .. x0+sx-1]; planes, sigma, occ, nx, ny, nz are the WHOLE
+ * volume's.  occ is written only by the call with x0 + sx == nx, from the whole sigma, which the caller has completed by then.
+ * cips_feature_volume_bake is the slab call with x0 = 0, sx = nx.
+ * Invalid arguments return hipErrorInvalidValue before any HIP call: a NULL pointer; n_a < 2; Bv < 0; nx*ny*nz beyond int32;
+ * planes or feat_rows not 16-byte aligned; a grid beyond int32 (Bv*sx*ny*nz/32 blocks); (slab) x0 < 0, sx < 1 or x0 + sx > nx.
+ * Bv == 0 returns 0 and launches nothing.
+ *
+ * cips_feature_volume_render: cips_volume_render's rule, word for word, with 32 channels in place of 3: the same ray_dir and
+ * ray_point for pixel (r, c) and depth zg[s]; the same inside test, cell and t_a from lo, hi and inv_h; sigma interpolated from
+ * `sigma` and every channel from its group's plane by the same nested lerps p + t (q - p) along z, then y, then x; a sample
+ * outside has sigma = 0 and features 0; the same delta, alpha, w_s = alpha_s fp32(T_s) with T in double; opacity = sum w before
+ * any top-up, accumulated as fmaf(alpha_s, fp32(T_s), opacity) — the form cips_volume_render's sum takes once compiled, written
+ * out here; flags bit 0 (last_back): the last sample's weight gains 1 - sum w (as a second fmaf per channel, after the sum,
+ * and on the depth); fea = sum w f, depth = sum w z, in sample order by fmaf; flags bit 1 (white_back): 1 - sum w is added to
+ * every one of the 32 channels, as cips_composite_fwd does for features; flags bit 2 (skip), relu only and IGNORED under
+ * clamp_mode 1 as there: a sample whose brick has occ <= 0 does not gather its sigma (exact for the reason given there), the last
+ * sample under last_back excepted.
+ *   The weight skip, always on: a sample gathers its eight feature groups only if its weight w_s is not zero (the last sample
+ * under last_back: if w_s or 1 - sum w is not zero).  fmaf(0, f, c) == c bit for bit for a finite f, so the skip is exact; it is
+ * finer than the brick skip (it also drops clamped samples in occupied bricks) and ends a ray's feature traffic once fp32(T)
+ * has reached 0.  Hence the same bits with the skip bit set or clear, on every call, and for camera i of a Bv = 1 call as for that
+ * camera alone; and with planes whose every group is a packed (r, g, b, x) volume and sigma that volume's, fea[..., 4g .. 4g+2]
+ * is cips_volume_render's rgb bit for bit.
+ *   Outputs: fea (b, H*W, 32) pixel-major, 16-byte aligned — each lane stores its 128 contiguous bytes; depth (b,1,H,W);
+ * opacity (b,1,H,W).  Bv is 1 (every camera sees volume 0) or b.  One ray per lane in 8 x 8 tiles, one launch, no LDS, no
+ * scratch memory, no atomics, no S-sized buffer.
+ * Invalid arguments return hipErrorInvalidValue before any HIP call: everything cips_volume_render refuses, with planes in
+ * packed's place — a NULL pointer (occ may be NULL only with the skip bit clear); n_a < 2; H, W or S < 2; b or Bv < 0, Bv not in
+ * {1, b}; lo / hi not finite or hi <= lo; zc >= 0, NaN or -inf; clamp_mode not 0 or 1; flags outside 0..7; planes or fea not
+ * 16-byte aligned; nx*ny*nz, b*H*W or H*W*S beyond int32.  b == 0 returns 0 and launches nothing. */
+int cips_feature_volume_bake(const float* sigma, const float* feat_rows, void* planes, float* occ, int Bv, int nx, int ny,
+                             int nz, cips_stream_t stream);
+int cips_feature_volume_bake_slab(const float* sigma, const float* feat_rows, void* planes, float* occ, int Bv, int nx, int ny,
+                                  int nz, int x0, int sx, cips_stream_t stream);
+int cips_feature_volume_render(const float* sigma, const void* planes, const float* occ, const float* lo, const float* hi,
+                               const float* xg, const float* yg, const float* zg, const float* cam2world, float zc,
+                               int clamp_mode, int flags, float* fea, float* depth, float* opacity, int b, int Bv, int nx, int ny,
+                               int nz, int H, int W, int S, cips_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
